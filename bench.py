@@ -11,7 +11,12 @@ one host thread, stream set and model replica per lane - a batch-1 clip cannot f
 waveforms of the step are gathered on rank 0 over RCCL (the path's only exchange step).  `--lanes 1` is the strictly sequential
 one-clip-at-a-time rate.  Clips are independent, so the work shards clip-per-GPU with no data-path collective besides that gather:
 weak scaling.  Weights are procedural (comfy-rvc_amd/synthetic.py) - no checkpoint is reachable offline - and compute is fp32
-(fp32 MFMA, or the bf16x3 split with fp32 accumulation).  Rank 0 prints ONE JSON line (metric/value/roofline/cpu_baseline ...).
+(fp32 MFMA, or the bf16x3 split with fp32 accumulation).  Rank 0 prints ONE JSON line (metric/value/ms_per_step ...).
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what the headline does not need: one clip alone
+on the GPU, the per-kernel roofline pass (with its rocprofv3 PMC child passes) and the CPU baseline.  `--dump-outputs DIR` writes the
+arrays the last timed step delivered (rank 0's clips) as DIR/*.npy; the synthesizer noise of a clip is drawn from a device generator
+seeded by the rank and the clip's place in its step, so the same arguments give the same inputs and comparable outputs on every run.
 
 `--dry-run` replaces the conversion with a stub (no HIP call at all) and exists to exercise the launcher, the process group, the
 per-step gather and the timing protocol on a box without GPUs (tests/test_parallel_gloo.py); its line says so in `data`.
@@ -210,8 +215,10 @@ def main():
                     help="40k_v2 = the configuration the metric is quoted on (BASELINE.json configs[2]); 48k_v2 = configs[3]'s model; uvr_48k_v2 = "
                          "configs[4]'s chain: MDX23C vocal split of a stereo 44.1 kHz clip (overlap 8) -> VC of the vocal stem with the 48k_v2 model; "
                          "rmvpe_60s = configs[1]: lib/rmvpe.RMVPE pitch extraction alone on 60 s clips (host audio in -> float64 f0 out)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure one clip alone, the per-kernel roofline and the CPU baseline (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the arrays of the last timed step as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no roofline pass")
     ap.add_argument("--no-traffic", action="store_true", help="do not run the two rocprofv3 --pmc child passes (roofline.traffic then comes from the committed file)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)      # the child of a --pmc pass: convert the clips, print nothing else
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: stub conversion; checks launcher / process group / gather / timing")
@@ -312,6 +319,8 @@ def main():
             lvc = VC(SYN_CFG[-1], cfg)
             lvc.model_rmvpe = RMVPE(rmvpe_sd, device=dev)
             lvc.noise_on_device = True          # the reference draws its noise with the compute device's generator as well
+            gen = torch.Generator(device=dev)   # ... here one per lane, re-seeded per clip: the same clip gets the same noise whichever lane runs it
+            clip_gen = lambda shape: torch.randn(shape, generator=gen, device=dev)
 
             mdx = None
             if chain:
@@ -324,6 +333,8 @@ def main():
 
             def convert(clip, i=0):
                 sr_in = 16000
+                gen.manual_seed(1_000_003 * (rank + 1) + i % n_clips)
+                lvc.noise_fn = clip_gen
                 if chain:      # UVR5Node.split -> vocal stem -> RVCNode.convert (reference custom_nodes/uvr.py:56-100, rvc_nodes.py:186-206)
                     clip, sr_in = demix_mdxv3(clip, mdx, dev, MDX23C_CONFIG, MDX23C_CONFIG["inference"]["num_overlap"])["Vocals"], 44100
                 out = vc_single(cpt=vcd["cpt"], net_g=vcd["net_g"], vc=lvc, hubert_model=hub, input_audio=(clip, sr_in), config=cfg, **params)
@@ -349,6 +360,8 @@ def main():
     def step():                            # single clip on lane 0, caller's thread and stream (warm-up, roofline pass)
         return lanes[0][0](audio)
 
+    last_step = []
+
     def run_steps(k):
         """k steps = k * CLIPS clips of this rank through the lanes (a free lane pulls the next clip while the previous step is gathered);
         the waveforms of a step are handed to ONE gather (the path's only exchange) in clip order."""
@@ -357,6 +370,7 @@ def main():
             wav = res.host if isinstance(res, Delivered) else res
             batch.append(res)
             if len(batch) == n_clips:
+                last_step[:] = [b.host if isinstance(b, Delivered) else b for b in batch]
                 if collective:   # every rank already holds ITS clips on the host (vc_single delivered them); rank 0 keeps the gathered copy in HBM
                     if isinstance(batch[0], Delivered):
                         cur = torch.cuda.current_stream()
@@ -389,19 +403,23 @@ def main():
         dt = float(t.item())
     delivered = args.seconds if pitch_only else wav.shape[0] / float(SYN_CFG[-1])       # audio seconds of one converted clip (pitch: of one analysed clip)
     value = delivered * n_clips * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step, "f0" if pitch_only else "wav")
 
-    # informational: one clip alone on the GPU (what a single ComfyUI graph execution sees), lane 0, a few untimed-for-the-headline passes
-    sync()
-    alone = []
-    for _ in range(1 if args.pmc_child else 9):
-        t1 = time.perf_counter()
-        step()
-        if use_gpu:
-            torch.cuda.synchronize()
-        alone.append(time.perf_counter() - t1)
-    alone_ms = sorted(alone)[len(alone) // 2] * 1e3          # median of 9
-    alone3_ms = None
-    if use_gpu and convert_mdx:            # the UVR node's setting for a single conversion: a clip's chunks over three streams (UVR5Node: load_mdx23c)
+    full = args.full and not args.pmc_child
+    # informational (--full): one clip alone on the GPU (what a single ComfyUI graph execution sees), lane 0, a few untimed-for-the-headline passes
+    alone_ms = alone3_ms = None
+    if full:
+        sync()
+        alone = []
+        for _ in range(9):
+            t1 = time.perf_counter()
+            step()
+            if use_gpu:
+                torch.cuda.synchronize()
+            alone.append(time.perf_counter() - t1)
+        alone_ms = sorted(alone)[len(alone) // 2] * 1e3          # median of 9
+    if full and use_gpu and convert_mdx:            # the UVR node's setting for a single conversion: a clip's chunks over three streams (UVR5Node: load_mdx23c)
         convert_mdx[0].set_streams(3)
         a3 = []
         for _ in range(6):
@@ -412,7 +430,7 @@ def main():
     sync()
 
     roofline, detail = None, None
-    if rank == 0 and use_gpu and not args.no_roofline and not args.pmc_child:
+    if rank == 0 and use_gpu and full and not args.no_roofline:
         live = None
         if world == 1 and not args.no_traffic and os.environ.get("RVC_BENCH_TRAFFIC", "1") != "0":
             live = pmc_traffic_live(args.variant, args.seconds)
@@ -420,7 +438,7 @@ def main():
         if roofline is not None and pitch_only:
             roofline["note"] = "conv kernels only; rvc::gru_scan_kernel (serial, latency-bound) is the largest single kernel of this variant"
     cpu = None
-    if rank == 0 and world == 1 and use_gpu and not args.no_cpu_baseline and not args.pmc_child:
+    if rank == 0 and world == 1 and use_gpu and full and not args.no_cpu_baseline:
         # the CPU baseline is "the reference's path on this box's host cores" (BASELINE.md section 4), not on the one NUMA node the rank was pinned
         # to for the GPU run: every thread of the process (torch's intra-op pool included) gets the original mask back for this leg
         if bound is not None and orig_affinity is not None:
@@ -449,9 +467,9 @@ def main():
                        "clips_per_step": world * n_clips, "clips_per_gpu_per_step": n_clips, "clips_in_flight_per_gpu": n_lanes,
                        "gathers_per_step": 1 if collective else 0,
                        "audio_seconds_delivered_per_clip": round(delivered, 3),
-                       "one_clip_alone_ms": round(alone_ms, 2), "one_clip_alone_xrt": round(delivered / alone_ms * 1e3, 1),
+                       **({"one_clip_alone_ms": round(alone_ms, 2), "one_clip_alone_xrt": round(delivered / alone_ms * 1e3, 1)} if alone_ms is not None else {}),
                        **({"one_clip_alone_ms_3_chunk_streams": round(alone3_ms, 2)} if alone3_ms is not None else {}),
-                       "weights": "procedural (comfy-rvc_amd/synthetic.py)", "noise": "device generator",
+                       "weights": "procedural (comfy-rvc_amd/synthetic.py)", "noise": "device generator, seeded per clip",
                        "parallelism": f"clip-per-GPU x{world} ({n_lanes} lanes each), one RCCL gather of the step's int16 waveforms"},
             "roofline": roofline, "cpu_baseline": cpu,
         }
@@ -474,6 +492,22 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 63_000_000      # (+ the .npy headers: under 64 MB in all)
+
+
+def dump_outputs(d, arrays, prefix):
+    """The arrays one timed step delivered, in clip order, as d/<prefix>_<clip>.npy: int16 waveforms as float32 (exact), f0 as float64.  Above
+    DUMP_BUDGET_BYTES in all, each array keeps the same share of its positions, a sorted sample seeded by the clip's number."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    outs = [np.asarray(a).astype(np.float64 if np.asarray(a).dtype == np.float64 else np.float32).reshape(-1) for a in arrays]
+    total = sum(a.nbytes for a in outs)
+    for i, a in enumerate(outs):
+        if total > DUMP_BUDGET_BYTES:
+            a = a[np.sort(np.random.default_rng(i).choice(a.size, max(1, a.size * DUMP_BUDGET_BYTES // total), replace=False))]
+        np.save(os.path.join(d, f"{prefix}_{i:02d}.npy"), a)
 
 
 KERNEL_DESC = {
