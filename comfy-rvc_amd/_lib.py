@@ -165,7 +165,6 @@ SIGNATURES = {
 EXPERIMENT_SIGNATURES = {
     "rvc_debug_conv_timing": (c_int, [P(C.c_uint64), c_int]),
     "rvc_debug_x3p_check": (c_int, []),
-    "rvc_debug_set_x3s_mode": (c_int, [c_int]),
     "rvc_debug_gemm_split_bench": (c_int, [c_void_p] + [c_int] * 8 + [P(c_float), c_int, c_int]),
 }
 

@@ -2,13 +2,9 @@
 // `sdpa`): out[h*64+d][q] = sum_k softmax_k(K_h[:,k] . Q_h[:,q]) * V[k][h*64+d] + bv, with Q already scaled.
 // One workgroup (4 waves) owns 64 queries of one head and walks the keys in tiles of 64 with an online softmax, so the
 // [heads][T][T] score matrix never exists in HBM (it was 123 MB written + 3 x 123 MB re-read per layer at 30 s).
-//   S tile  (64 keys x 64 queries) = K^T Q   : v_mfma_f32_32x32x2_f32, A = Ks[d][key], B = Qs[d][query]
-//   P tile  = exp(S - m_new) to LDS           : m, l are per query column = per lane of the 32x32 accumulator layout
-//   O tile  (64 d x 64 queries) += V^T P      : A = Vs[key][d], B = Ps[key][query]; O is rescaled by exp(m_old - m_new)
-// fp32 throughout (bitwise fp32 FMA chains in the MFMA units); keys beyond T are masked, query tails are not stored.
-// Measured at 12 heads, T = 1599: 195 us (the three-kernel path it replaces took 312 us); ablations: MFMAs 96 us, K/V tile loads
-// 25 us, exp 17 us, the rest scalar ds_read_b32 operand fetches at one wave per SIMD.  Next step: row-major Q / K and
-// channel-major V so that every operand fragment is one ds_read_b128 for four MFMA steps.
+//   S tile  (64 keys x 64 queries) = K^T Q,  P tile = exp(S - m_new) to LDS,  O tile (64 d x 64 queries) += V^T P, O rescaled by exp(m_old - m_new)
+// in the bf16x3 arithmetic below; keys beyond T are masked, query tails are not stored.  (The first version ran fp32 MFMAs: 195 us at 12 heads,
+// T = 1599, against 312 us for the three-kernel path it replaced.)
 #include "rvc_internal.h"
 
 namespace rvc {
@@ -34,158 +30,10 @@ void attention_timing_read(unsigned long long* out8, bool reset) {
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int kAD = 64;        // head dimension
-constexpr int kAP = 68;        // LDS row pitch (floats): 16-byte aligned rows, 4-bank shift per row -> conflict-free ds_read_b128
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// LDS tiles are stored with the MFMA reduction index contiguous:  Qs[query][d], Ks[key][d], Vs[d][key], Ps[query][key].
-// An MFMA step consumes the index pair (i, 32 + i) - lane half 0 takes i, half 1 takes 32 + i; any pairing is valid as long as A and
-// B agree - so each lane reads its 32 values of a row as eight ds_read_b128, one per four MFMA steps.
-__global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ Q, const float* __restrict__ K, long long ldqk,
-                                                        const float* __restrict__ V, long long ldv, const float* __restrict__ bv,
-                                                        float* __restrict__ out, long long ldo, int T) {
-  __shared__ __attribute__((aligned(16))) float Qs[64 * kAP], Ks[64 * kAP], Vs[kAD * kAP], Ps[64 * kAP];
-  __shared__ float red[2][2][64];          // [stat: max | sum][wm][query]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 31, lh = lane >> 5;
-  const int h = blockIdx.y, q0 = blockIdx.x * 64;
-  const float* Qh = Q + (long long)h * kAD * ldqk;
-  const float* Kh = K + (long long)h * kAD * ldqk;
-  const float* Vh = V + h * kAD;
-
-  // Q tile -> Qs[query][d]: a thread takes 4 consecutive d of one query (4 coalesced loads) and writes them as one 16-byte store
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int e = tid + 256 * s, j = e & 63, d0 = (e >> 6) * 4;
-    f32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (q0 + j < T) ? Qh[(long long)(d0 + i) * ldqk + q0 + j] : 0.f;
-    *reinterpret_cast<f32x4*>(Qs + j * kAP + d0) = v;
-  }
-  f32x4 kr[4], vr[4];
-  auto load_kv = [&](int k0) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int e = tid + 256 * s, j = e & 63, g4 = (e >> 6) * 4;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        kr[s][i] = (k0 + j < T) ? Kh[(long long)(g4 + i) * ldqk + k0 + j] : 0.f;            // K[d = g4 + i][key = j]
-        vr[s][i] = (k0 + g4 + i < T) ? Vh[(long long)(k0 + g4 + i) * ldv + j] : 0.f;        // V[key = g4 + i][d = j]
-      }
-    }
-  };
-  auto store_kv = [&]() {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int e = tid + 256 * s, j = e & 63, g4 = (e >> 6) * 4;
-      *reinterpret_cast<f32x4*>(Ks + j * kAP + g4) = kr[s];       // Ks[key j][d g4..]
-      *reinterpret_cast<f32x4*>(Vs + j * kAP + g4) = vr[s];       // Vs[d j][key g4..]
-    }
-  };
-
-  f32x16 o, o1;                             // two independent accumulation chains, summed at the end
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { o[r] = 0.f; o1[r] = 0.f; }
-  float m_run = -1.0e30f, l_run = 0.f;       // per query column wn*32 + li (identical in the lanes / waves that share a column)
-  const int ntiles = (T + 63) / 64;
-  const float* arow_s = Ks + (wm * 32 + li) * kAP + lh * 32;     // A of S: key row
-  const float* brow_s = Qs + (wn * 32 + li) * kAP + lh * 32;     // B of S: query row
-  const float* arow_o = Vs + (wm * 32 + li) * kAP + lh * 32;     // A of O: d row
-  const float* brow_o = Ps + (wn * 32 + li) * kAP + lh * 32;     // B of O: query row
-  const unsigned long long t_begin = ATICK();
-  load_kv(0);
-  for (int it = 0; it < ntiles; ++it) {
-    const int k0 = it * 64;
-    const unsigned long long t0 = ATICK();
-    lds_barrier();                          // previous tile's Ks / Vs / Ps reads are done
-    store_kv();
-    lds_barrier();
-    if (it + 1 < ntiles) load_kv(k0 + 64);
-    const unsigned long long t1 = ATICK();
-    ATACC(1, t1 - t0);
-    // ---- S = K^T Q for this wave's 32 keys x 32 queries
-    f32x16 sacc, sacc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; sacc1[r] = 0.f; }
-    {
-      f32x4 a[8], b[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) { a[c] = *reinterpret_cast<const f32x4*>(arow_s + 4 * c); b[c] = *reinterpret_cast<const f32x4*>(brow_s + 4 * c); }
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][0], b[c][0], sacc, 0, 0, 0);
-        sacc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][1], b[c][1], sacc1, 0, 0, 0);
-        sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][2], b[c][2], sacc, 0, 0, 0);
-        sacc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][3], b[c][3], sacc1, 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sacc[r] += sacc1[r];
-    const unsigned long long t2 = ATICK();
-    ATACC(2, t2 - t1);
-    // rows of sacc: key = k0 + wm*32 + (r&3) + 8(r>>2) + 4 lh; column: query wn*32 + li
-    if (k0 + 64 > T) {                        // only the last key tile has a masked tail
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = k0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (key >= T) sacc[r] = -1.0e30f;
-      }
-    }
-    float mx = -1.0e30f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    if (lh == 0) red[0][wm][wn * 32 + li] = mx;
-    lds_barrier();
-    const float m_tile = fmaxf(red[0][0][wn * 32 + li], red[0][1][wn * 32 + li]);
-    const float m_new = fmaxf(m_run, m_tile);
-    const float alpha = expf(m_run - m_new);
-    float ps = 0.f;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      f32x4 pv;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { pv[i] = expf(sacc[4 * g + i] - m_new); ps += pv[i]; }     // masked keys: exp(-1e30 - m) = 0
-      *reinterpret_cast<f32x4*>(Ps + (wn * 32 + li) * kAP + wm * 32 + 8 * g + 4 * lh) = pv;   // Ps[query][key .. key + 3]
-    }
-    ps += __shfl_xor(ps, 32);
-    if (lh == 0) red[1][wm][wn * 32 + li] = ps;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { o[r] *= alpha; o1[r] *= alpha; }
-    lds_barrier();
-    l_run = l_run * alpha + red[1][0][wn * 32 + li] + red[1][1][wn * 32 + li];
-    m_run = m_new;
-    const unsigned long long t3 = ATICK();
-    ATACC(3, t3 - t2);
-    // ---- O += V^T P : rows d = wm*32 + .., columns queries wn*32 + li
-    {
-      f32x4 a[8], b[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) { a[c] = *reinterpret_cast<const f32x4*>(arow_o + 4 * c); b[c] = *reinterpret_cast<const f32x4*>(brow_o + 4 * c); }
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        o = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][0], b[c][0], o, 0, 0, 0);
-        o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][1], b[c][1], o1, 0, 0, 0);
-        o = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][2], b[c][2], o, 0, 0, 0);
-        o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][3], b[c][3], o1, 0, 0, 0);
-      }
-    }
-    ATACC(4, ATICK() - t3);
-  }
-  ATACC(6, ATICK() - t_begin); ATACC(0, 1);
-  const int q = q0 + wn * 32 + li;
-  if (q < T) {
-    const float inv = 1.f / l_run;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int d = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      out[(long long)(h * kAD + d) * ldo + q] = (o[r] + o1[r]) * inv + (bv ? bv[h * kAD + d] : 0.f);
-    }
-  }
-}
-
-// ---- bf16x3 variant: Q, K, V and P are split into bf16 hi / lo while they are staged in LDS and both products run as
+// ---- bf16x3: Q, K, V and P are split into bf16 hi / lo while they are staged in LDS and both products run as
 // hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (the arithmetic of conv_x3.hip): a 32 x 32 x 64 block
 // costs 12 MFMAs of 8 passes instead of 32 fp32 MFMAs of 16.
 constexpr int kXP = 72;        // LDS row pitch in bf16 elements (144 B)
@@ -391,11 +239,8 @@ __global__ __launch_bounds__(256) void attention_x3_kernel(const float* __restri
 void attention_fused(hipStream_t s, const float* Q, const float* K, long long ldqk, const float* V, long long ldv, const float* bv,
                      float* out, long long ldo, int heads, int dhead, int T, unsigned char* out_img, long long img_tp) {
   RVC_REQUIRE(dhead == kAD, "fused attention is built for head dimension 64");
-  static const bool x3 = (exp_int("RVC_ATT_X3", 1) != 0);
   RVC_REQUIRE(out != nullptr || out_img != nullptr, "fused attention: no output");
-  RVC_REQUIRE(out_img == nullptr || x3, "the split-image output needs the bf16x3 attention kernel");
-  if (x3) { hipLaunchKernelGGL(attention_x3_kernel, dim3((T + 63) / 64, heads), dim3(256), 0, s, Q, K, ldqk, V, ldv, bv, out, ldo, T, out_img, img_tp, (int)kSplitMargin); return; }
-  hipLaunchKernelGGL(attention_kernel, dim3((T + 63) / 64, heads), dim3(256), 0, s, Q, K, ldqk, V, ldv, bv, out, ldo, T);
+  hipLaunchKernelGGL(attention_x3_kernel, dim3((T + 63) / 64, heads), dim3(256), 0, s, Q, K, ldqk, V, ldv, bv, out, ldo, T, out_img, img_tp, (int)kSplitMargin);
 }
 
 // ================================================================================================ key-split variant

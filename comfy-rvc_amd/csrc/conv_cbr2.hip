@@ -267,7 +267,7 @@ static void launch_cbr2(const Cbr2Args& a, hipStream_t s) {
 
 bool cbr2_small_eligible(const ConvLayer& c1, const ConvLayer& c2) {
   auto ok = [](const ConvLayer& L) { return L.mode == 2 && L.Wx_ != nullptr && L.ktaps == 9 && L.kh == 3 && L.kw == 3 && L.up2 == 0 && L.tconv_u == 0 && L.bd_ != nullptr; };
-  return conv_x3_enabled() && ok(c1) && ok(c2) && c1.Ci == c1.Co && c2.Ci == c2.Co && c1.Co == c2.Co && (c1.Co == 16 || c1.Co == 32);
+  return ok(c1) && ok(c2) && c1.Ci == c1.Co && c2.Ci == c2.Co && c1.Co == c2.Co && (c1.Co == 16 || c1.Co == 32);
 }
 
 // out = relu(c2(relu(c1(x)))) + x for a 16- or 32-channel ConvBlockRes; x, out fp32 [C][H W] (distinct buffers)
@@ -443,7 +443,7 @@ static void launch_conv3_small(const Conv3SmallArgs& a, hipStream_t s) {
 }
 
 bool conv3_small_eligible(const ConvLayer& L) {
-  return conv_x3_enabled() && L.mode == 2 && L.Wx_ != nullptr && L.ktaps == 9 && L.kh == 3 && L.kw == 3 && L.up2 == 0 && L.tconv_u == 0 && L.bd_ != nullptr &&
+  return L.mode == 2 && L.Wx_ != nullptr && L.ktaps == 9 && L.kh == 3 && L.kw == 3 && L.up2 == 0 && L.tconv_u == 0 && L.bd_ != nullptr &&
          ((L.Ci == 16 && L.Co <= 64) || (L.Ci == 32 && L.Co <= 32)) && L.CoPx >= 64;      // (32 inputs x 64 rows of weights do not fit the registers)
 }
 // Y[co] = act(conv3x3(x)[co] + b[co]) [+ R[co]] for co < split_row, Y2[co - split_row] = the same without residual for the rest; ReLU on the rows below relu_rows

@@ -155,7 +155,6 @@ void splitk_reduce_launch(const ConvArgsX& a, int S, int batch, hipStream_t s);
 
 // bf16x3 path: returns false when the layer / geometry is not eligible (caller falls back to the fp32 kernel)
 bool conv_x3_try(ConvArgsX& a, int batch, hipStream_t s, double flops, bool dry = false);
-bool conv_x3_enabled();
 // software-pipelined kernel for stride-1 1-D convolutions on 2 x 2-wave tiles (conv_x3p.hip); `a` as conv_x3_try prepared it
 bool conv_x3p_try(ConvArgsX& a, int AM, int AN, hipStream_t s, dim3& grid_out, bool dry);
 int conv_x3p_check_read();

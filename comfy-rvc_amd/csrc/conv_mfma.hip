@@ -929,9 +929,6 @@ static void run_conv(ConvArgsX a, int mode, int batch, hipStream_t s, double flo
   RVC_REQUIRE(a.act == ACT_NONE || a.act == ACT_LRELU || a.act == ACT_RELU, "in-kernel activations are identity / ReLU / leaky ReLU");
   RVC_REQUIRE(a.pre_act == ACT_NONE || a.pre_act == ACT_LRELU, "input activation must be identity or leaky ReLU");
   TileCfg t = choose_tile(a.Co, a.Tout, batch);
-  if (const char* f = RVC_EXP_STR("RVC_FORCE_TILE")) {   // experiments: "WM,WN,AM,AN"
-    int w[4]; if (sscanf(f, "%d,%d,%d,%d", &w[0], &w[1], &w[2], &w[3]) == 4 && (a.Co > 32 || w[0] == 1)) t = TileCfg{w[0], w[1], w[2], w[3]};
-  }
   size_t lds = 0;
   if (!setup_tile(a, mode, t, lds)) {
     // fall back to narrower tiles (fewer staged columns per row)

@@ -379,12 +379,10 @@ static void launch_rb3(const Rb3Args& a, bool acc, dim3 grid, size_t lds, hipStr
 // one-plane fp16 image, the fp16x2 pair arithmetic switched on, at least two rounds of tiles; false: not this kernel's (the caller runs the pairs one by one).
 bool conv_rb3_try(const ConvLayer* const* c1, const ConvLayer* const* c2, hipStream_t s, const float* X, long long ldX, int T, float* Y, long long ldY,
                   float pre_slope, float out_scale, int accumulate, bool dry, const float* nsrc, const float* nw, const float* nb) {
-  static const int on = exp_int("RVC_RB3", 1);
-  static const int on64 = exp_int("RVC_RB3_64", 1);             // the 64-channel stage's 3-tap ResBlock (otherwise three conv_x3pf_kernel launches in bf16x3)
-  if (!on || !conv_x3_enabled() || !conv_set_pair_arithmetic(-1)) return false;
+  if (!conv_set_pair_arithmetic(-1)) return false;
   const int k = c1[0]->k, C = c1[0]->Co;
-  static const int on64k7 = exp_int("RVC_RB3_64K7", 1);         // the 64-channel stage's 7-tap ResBlock (otherwise six conv_x3q_kernel launches with the intermediate images through HBM)
-  if (!((C == 32 && (k == 3 || k == 7 || k == 11)) || (C == 64 && k == 3 && on64) || (C == 64 && k == 7 && on64 && on64k7))) return false;
+  // (the 64-channel stage's 3- and 7-tap ResBlocks too: otherwise three conv_x3pf_kernel launches in bf16x3 / six conv_x3q_kernel launches with the images through HBM)
+  if (!((C == 32 && (k == 3 || k == 7 || k == 11)) || (C == 64 && (k == 3 || k == 7)))) return false;
   int dsum = 0;
   for (int i = 0; i < 3; ++i) {
     const ConvLayer& a = *c1[i]; const ConvLayer& b = *c2[i];

@@ -289,8 +289,7 @@ static void launch_rbh(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s)
 // a: the fused pair's arguments as conv_x3_pair_try prepared them, with Wx / Wx2 = the two layers' ONE-plane fp16 images (ConvLayer::Wh_).  32 channels,
 // 3 / 7 / 11 taps, a sequence of at least two rounds of tiles; false: not this kernel's (conv_x3pf_kernel takes the pair in bf16x3).
 bool conv_rbh_try(ConvArgsX& a, int T, hipStream_t s, dim3& grid_out, bool dry) {
-  static const int on = exp_int("RVC_RBH", 1);
-  if (!on || a.Ci != 32 || a.Co != 32 || !(a.ktaps == 3 || a.ktaps == 7 || a.ktaps == 11) || a.CoPx < 32) return false;
+  if (a.Ci != 32 || a.Co != 32 || !(a.ktaps == 3 || a.ktaps == 7 || a.ktaps == 11) || a.CoPx < 32) return false;
   const int BN = 512, NO = BN - (a.ktaps - 1);
   const int P = BN + (a.ktaps - 1) * a.dil;
   if (P > 576 || a.dil < 1) return false;

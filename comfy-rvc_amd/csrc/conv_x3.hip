@@ -479,11 +479,6 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : ((WM == 2 && WN ==
 }
 
 // ============================================================================ host side
-bool conv_x3_enabled() {
-  static const bool on = (exp_int("RVC_X3", 1) != 0);
-  return on;
-}
-
 template <int WM, int WN, int AM, int AN, bool FUSE = false, bool XSPLIT = false, bool YSPLIT = false>
 static void launch_x3(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s) {
   auto kern = conv_x3_kernel<WM, WN, AM, AN, FUSE, XSPLIT, YSPLIT>;
@@ -492,7 +487,7 @@ static void launch_x3(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s) 
 }
 
 bool conv_x3_try(ConvArgsX& a0, int batch, hipStream_t s, double flops, bool dry) {
-  if (!conv_x3_enabled() || !a0.Wx) return false;
+  if (!a0.Wx) return false;
   const bool xs = a0.Xs != nullptr;
   if ((xs || a0.Ys) && (a0.Wd > 0 || a0.stride != 1 || a0.ostride != 1 || (a0.Co & 31) || batch != 1)) return false;
   if (xs && a0.pre_act != ACT_NONE) return false;                     // the producer applied the activation
@@ -531,29 +526,17 @@ bool conv_x3_try(ConvArgsX& a0, int batch, hipStream_t s, double flops, bool dry
       // (k <= 3 at 128+ channels is HBM-bound: three 128 x 128 workgroups per CU beat two wide ones, C128 k3 238 -> 219 us)
       // (round 2, after the staging / epilogue changes and with split-resident inputs: the 64 x 256 tile at three workgroups per CU now
       // beats 64 x 512 at two - C64 k7 205 -> 187 us - and a split-input consumer with k <= 7 prefers 128 x 128: 333 -> 317 us)
-      static const int wide64 = exp_int("RVC_X3_WIDE64", 0);
-      // 8-wave workgroups (128 x 512 tile, one per CU): RVC_X3_W8 = minimum tap count that takes them (0 = never)
-      static const int w8_taps = exp_int("RVC_X3_W8", 0);
-      static const int w8_blk = exp_int("RVC_X3_W8_BLK", 400);
       static const int wide_xs7 = exp_int("RVC_X3_WIDE_XS7", 1);   // the wide tile also for a split-input consumer with k = 7 (persistent kernel: C128 k7 pair 399 -> 377 us; the per-tile kernel preferred 128 x 128 there)
       static const int wide_k3 = exp_int("RVC_X3_WIDE_K3", 2);      // the wide tile also for k = 3 (1: fp32 inputs, 2: split inputs too): on the pipelined kernel C128 k3 135 -> 129 us; not for the up-samplers (240 -> 250)
-      if (w8_taps > 0 && a.Co > 64 && a.ktaps >= w8_taps && blocks(128, 512) >= w8_blk) t = TileCfg{2, 4, 2, 4};
-      else
       if (a.Co > 64 && blocks(128, 256) >= wide_blk && (a.ktaps > 3 || (wide_k3 >= 1 && a.ostride == 1)) &&
           !(xs && a.ktaps <= 7 && !(a.ktaps <= 3 && wide_k3 >= 2) && !(a.ktaps == 7 && wide_xs7))) t = TileCfg{2, 2, 2, 4};
-      else if (wide64 && a.Co > 32 && a.Co <= 64 && blocks(64, 512) >= wide_blk) t = TileCfg{1, 4, 2, 4};
     }
-  }
-  if (const char* f = RVC_EXP_STR("RVC_FORCE_TILE")) {
-    int w[4]; if (sscanf(f, "%d,%d,%d,%d", &w[0], &w[1], &w[2], &w[3]) == 4 && (a.Co > 32 || w[0] == 1)) t = TileCfg{w[0], w[1], w[2], w[3]};
   }
   int id = tile_cfg_id(t);
   if (t.WM == 2 && t.WN == 2 && t.AM == 2 && t.AN == 4) id = 7;
-  if (t.WM == 1 && t.WN == 4 && t.AM == 2 && t.AN == 4) id = 8;
-  if (t.WM == 2 && t.WN == 4 && t.AM == 2 && t.AN == 4) id = 9;
   const int NW = t.WM * t.WN;
   if (id < 0) return false;
-  if ((xs || a0.Ys) && !(id == 3 || id == 4 || id == 7 || id == 8 || id == 9)) return false;   // tiles instantiated with the split-resident paths
+  if ((xs || a0.Ys) && !(id == 3 || id == 4 || id == 7)) return false;             // tiles instantiated with the split-resident paths
   if (xs && a0.Ys) return false;                                                    // (one side at a time)
   const int BM = t.WM * t.AM * 32, BN = t.WN * t.AN * 32;
   const long long nblk = (long long)((a.Tout + BN - 1) / BN) * ((a.Co + BM - 1) / BM);
@@ -601,11 +584,10 @@ bool conv_x3_try(ConvArgsX& a0, int batch, hipStream_t s, double flops, bool dry
   while (NC > 1 && (nchunk % NC != 0 || (!xs && (NC * 2 * a.ni + NW - 1) / NW > x3_slots(BN, NW)))) NC >>= 1;
   if (!xs && (NC * 2 * a.ni + NW - 1) / NW > x3_slots(BN, NW)) return false;
   // LDS budget per workgroup: 53 KiB = three workgroups per CU for the tiles whose registers allow it (<= 170 VGPRs), two for the
-  // 8-accumulator tiles.  Measured: occupancy matters more than stage length (one 156 KiB workgroup per CU with 3x longer stages:
+  // 8-accumulator tiles (four waves each: 8-wave workgroups with the CU's whole LDS were measured and not kept).  Measured: occupancy matters more than stage length (one 156 KiB workgroup per CU with 3x longer stages:
   // +32 % time; three 128x128 workgroups instead of two: -12 %).  X double-buffered when that still leaves >= 2 taps per stage.
   static const int budget_kb = exp_int("RVC_X3_LDS_KB", 53);
-  static const int budget8_kb = exp_int("RVC_X3_LDS8_KB", 156);   // 8-wave workgroups own the CU's LDS
-  const int budget = (NW == 8 ? budget8_kb : budget_kb) * 1024;
+  const int budget = budget_kb * 1024;
   // weight slabs: a ring of NS: the DMA of a slab is issued NS - 1 stages before its MFMAs, waited for with a counted vmcnt and published
   // with a barrier that does not drain the queue.  Measured: NS = 3 / 4 lose to NS = 2 (C128 k11 490 vs 433 us): the LDS they take
   // halves the taps per stage, and the per-stage costs (DMA issue, barrier) outweigh the ~400 cycles of DMA wait they would hide.
@@ -653,17 +635,13 @@ bool conv_x3_try(ConvArgsX& a0, int batch, hipStream_t s, double flops, bool dry
     switch (id) {
       case 3: launch_x3<2, 2, 2, 2, false, true>(a, grid, lds, s); break;
       case 4: launch_x3<2, 2, 1, 4, false, true>(a, grid, lds, s); break;
-      case 7: launch_x3<2, 2, 2, 4, false, true>(a, grid, lds, s); break;
-      case 9: launch_x3<2, 4, 2, 4, false, true>(a, grid, lds, s); break;
-      default: launch_x3<1, 4, 2, 4, false, true>(a, grid, lds, s); break;
+      default: launch_x3<2, 2, 2, 4, false, true>(a, grid, lds, s); break;
     }
   } else if (a.Ys) {
     switch (id) {
       case 3: launch_x3<2, 2, 2, 2, false, false, true>(a, grid, lds, s); break;
       case 4: launch_x3<2, 2, 1, 4, false, false, true>(a, grid, lds, s); break;
-      case 7: launch_x3<2, 2, 2, 4, false, false, true>(a, grid, lds, s); break;
-      case 9: launch_x3<2, 4, 2, 4, false, false, true>(a, grid, lds, s); break;
-      default: launch_x3<1, 4, 2, 4, false, false, true>(a, grid, lds, s); break;
+      default: launch_x3<2, 2, 2, 4, false, false, true>(a, grid, lds, s); break;
     }
   } else
   switch (id) {
@@ -674,8 +652,6 @@ bool conv_x3_try(ConvArgsX& a0, int batch, hipStream_t s, double flops, bool dry
     case 4: launch_x3<2, 2, 1, 4>(a, grid, lds, s); break;
     case 5: launch_x3<2, 2, 1, 2>(a, grid, lds, s); break;
     case 7: launch_x3<2, 2, 2, 4>(a, grid, lds, s); break;
-    case 8: launch_x3<1, 4, 2, 4>(a, grid, lds, s); break;
-    case 9: launch_x3<2, 4, 2, 4>(a, grid, lds, s); break;
     default: launch_x3<2, 2, 1, 1>(a, grid, lds, s); break;
   }
   if (S > 1) splitk_reduce_launch(a, S, 1, s);
@@ -689,18 +665,15 @@ bool conv_x3_try(ConvArgsX& a0, int batch, hipStream_t s, double flops, bool dry
 // dry_only: answers whether the pair would run in the fp16x2 arithmetic on the LDS-resident-weights kernel (nothing is launched)
 bool conv_x3_pair_try(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, const float* X, long long ldX, int T, float* Y, long long ldY,
                       const ConvEpilogue& e2, bool dry_only) {
-  static const bool on = (exp_int("RVC_PAIR", 1) != 0);
-  static const bool pair64 = (exp_int("RVC_PAIR64", 0) != 0);      // experiment: 64-channel stage (2 WGs per CU)
-  if (!on || !conv_x3_enabled() || !c1.Wx_ || !c2.Wx_) return false;
+  if (!c1.Wx_ || !c2.Wx_) return false;
   const int C = c1.Co, k = c1.k;
   if (c1.mode != 1 || c2.mode != 1 || c1.groups != 1 || c2.groups != 1 || c1.stride != 1 || c2.stride != 1 || c1.tconv_u || c2.tconv_u) return false;
   if (c1.Ci != C || c2.Ci != C || c2.Co != C || c2.k != k || c2.dil != 1 || (k & 1) == 0 || !(C == 32 || C == 64)) return false;
   if (c1.pad != (k - 1) / 2 * c1.dil || c2.pad != (k - 1) / 2) return false;                      // "same" convolutions
   if (e2.pre_act != ACT_LRELU || e2.act != ACT_NONE || e2.bias_override || e2.tout_limit || e2.R != X) return false;
   if ((double)C * (double)ldX * 4.0 >= 2147483648.0 || (double)C * (double)ldY * 4.0 >= 2147483648.0) return false;
-  static const int bn_env = exp_int("RVC_PAIR_BN", 256);
   const int BM = C;
-  const int BN = (C == 64 || bn_env == 128) ? 128 : 256;
+  const int BN = C == 64 ? 128 : 256;
   const int P2 = (k - 1) / 2, P1 = c1.pad;
   const int NO = BN - 2 * P2;
   if ((long long)(T + NO - 1) / NO < 512) return false;          // short sequences: the unfused path fills the chip better
@@ -741,17 +714,16 @@ bool conv_x3_pair_try(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, c
       conv_prof_end(tk, s, 2.0 * 2.0 * (double)C * C * k * T, 14 + (C == 32 ? 1 : 5), bytes, &a, (long long)gpf.x, 1 | (3 << 4));
       return true;
     }
-    if (C == 64 && !pair64) return false;
+    if (C == 64) return false;                                   // (the staged pair at 64 channels was measured and not kept)
   }
   const int P = BN + 2 * P1;                                      // staged input columns
   a.ni = (P + 63) / 64;
   const int nchunk = C / 16, NC = nchunk;                         // every channel of the tile resident: one chunk group
-  if ((NC * 2 * a.ni + 3) / 4 > (C == 64 ? 7 : 5)) return false;
+  if ((NC * 2 * a.ni + 3) / 4 > 5) return false;
   const int xbytes = (NC * 2 * P * 32 + 1023) & ~1023;
   // three workgroups per CU with single-tap stages beat two with 4-tap stages (k3 233 -> 196 us, k7 279 -> 233, k11 352 -> 308):
   // occupancy is what hides the per-stage latencies of this narrow tile
-  static const int budget_kb_env = exp_int("RVC_PAIR_LDS_KB", 53);
-  const int budget_kb = C == 64 ? 80 : budget_kb_env;
+  static const int budget_kb = exp_int("RVC_PAIR_LDS_KB", 53);
   const int per_tap = 2 * NC * 2 * BM * 32;
   int ktmax = (budget_kb * 1024 - xbytes) / per_tap;
   if (ktmax < 1) return false;
@@ -764,9 +736,7 @@ bool conv_x3_pair_try(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, c
   const size_t lds = (size_t)xbytes + (size_t)2 * NC * a.KT * 2 * BM * 32;
   dim3 grid((unsigned)((T + NO - 1) / NO), 1, 1);
   ProfTicket tk = conv_prof_begin(s);
-  if (C == 64) launch_x3<2, 2, 1, 2, true>(a, grid, lds, s);
-  else if (BN == 128) launch_x3<1, 4, 1, 1, true>(a, grid, lds, s);
-  else launch_x3<1, 4, 1, 2, true>(a, grid, lds, s);
+  launch_x3<1, 4, 1, 2, true>(a, grid, lds, s);                 // 32 channels, 256 columns
   // algorithmic traffic of the pair: x read (the residual is x itself: one tensor, counted once), y write (+ previous y when accumulating) + both weight sets
   const double bytes = 4.0 * ((double)C * T * (2.0 + (e2.accumulate ? 1.0 : 0.0)) + 2.0 * C * C * k);   // x ONCE (the residual is the same tensor), y [, previous y]
   conv_prof_end(tk, s, 2.0 * 2.0 * (double)C * C * k * T, 14 + 1, bytes, &a, (long long)grid.x, 1);

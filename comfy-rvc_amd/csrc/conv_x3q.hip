@@ -611,8 +611,6 @@ static void launch_x3q_r(const ConvArgsX& a, int R, int mode, dim3 grid, size_t 
 // measured on the GPU for the bf16 2-term variant).  Only the pair convolutions of a residual branch are offered this arithmetic: their errors
 // enter the stage tensor additively beside the exact skip path.  fp16 range: hi saturates at 65504 (round toward zero), |x| < 131008 stays finite.
 bool conv_x3q_try(ConvArgsX& a, int AM, int AN, hipStream_t s, dim3& grid_out, bool dry) {
-  static const int on = exp_int("RVC_X3Q", 1);
-  if (!on) return false;
   const bool xs = a.Xs != nullptr, ys = a.Ys != nullptr;
   if (a.Wd > 0 || (a.Ci & 15) || a.Ci < 48 || xs == ys || a.stride != 1 || a.ostride != 1 || a.orows != a.Co) return false;
   if (!(a.ktaps == 3 || a.ktaps == 7 || a.ktaps == 11)) return false;
@@ -633,14 +631,12 @@ bool conv_x3q_try(ConvArgsX& a, int AM, int AN, hipStream_t s, dim3& grid_out, b
   // C64 k7: ring of 4 at 54 528 B 279 us, ring of 3 251 us - so the budget is cut to whole 2-KiB granules)
   const size_t budget = (size_t)(160 * 1024 / per_cu) & ~(size_t)2047;
   const size_t fixed = (size_t)xbytes + (size_t)((a.Co * 4 + 255) & ~255) + (mode == 1 ? 4096 : 0);   // (mode 1: the epilogue's staging area)
-  static const int r_env = exp_int("RVC_X3Q_R", 0);
   const int rmin = (AM == 2 && AN == 4) ? 4 : 3;
   // image in, three taps: at most four slots - the input chunk's DMA (requested KT units before its first read) is covered by the wait for the
   // weight unit requested R - 2 units before, which must not be the older of the two (latent in rounds 4 - 5 with R = 5: the window was a whole chunk
   // of MFMAs wide and never observed; the shorter fp16x2 units of round 6 made the full-size repeat test differ)
   int R = (mode == 1 && a.ktaps == 3) ? 4 : 5;
   while (R > rmin && fixed + (size_t)R * wslot > budget) --R;
-  if (r_env >= rmin && r_env < R) R = r_env;
   const size_t lds = fixed + (size_t)R * wslot;
   if (lds > budget) return false;
   const long long ntiles = (long long)((a.Tout + BN - 1) / BN) * (a.Co / BM);

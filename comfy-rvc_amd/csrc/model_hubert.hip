@@ -127,9 +127,7 @@ static void hubert_graph(Hubert* H, hipStream_t s, Arena& A, const float* audio,
   const int T = Tc[7];
   // the positional convolution (k = 128, 16 groups) reads its input as a split-resident image through row offsets -64 .. +63: the margins
   // of that image are its zero padding, so it lives in a block of its own (first allocation, never aliased) that is zeroed per (layout, T)
-  static const bool x3s_on0 = (exp_int("RVC_X3S", 1) != 0);
-  static const bool pos_on = (exp_int("RVC_X3S_POS", 1) != 0);
-  const bool pos_s = x3s_on0 && pos_on && conv_x3_enabled() && conv_x3s_eligible(H->pos) && conv_x3s_eligible(H->proj);
+  const bool pos_s = conv_x3s_eligible(H->pos) && conv_x3s_eligible(H->proj);
   unsigned char* hpos_s = nullptr;
   if (pos_s) {
     const size_t img0 = A.off;
@@ -141,12 +139,10 @@ static void hubert_graph(Hubert* H, hipStream_t s, Arena& A, const float* audio,
     }
   }
   // ---- feature encoder
-  static const bool fuse0 = (exp_int("RVC_HUBERT_FUSE0", 1) != 0);
   // Layers 1 .. 6 (k = 3 / 2, stride 2, no padding) on the split-resident GEMM: every layer's output is written by its producer's epilogue as the bf16 hi / lo
   // image of the next one, DE-INTERLEAVED (even | odd positions), so that a stride-2 tap is a row offset and no layer converts its input per tile; the exact-erf
-  // GELU sits in the epilogue (the pipelined kernel ran it as a second pass over the tensor).  RVC_HUBERT_S2=0: the fp32 path on conv_x3p_kernel / conv_x3_kernel.
-  static const bool s2_on = (exp_int("RVC_HUBERT_S2", 1) != 0);
-  bool s2 = s2_on && fuse0 && conv_x3_enabled();
+  // GELU sits in the epilogue (the pipelined kernel ran it as a second pass over the tensor).  Without bf16x3 images: the fp32 path on conv_x3p_kernel / conv_x3_kernel.
+  bool s2 = true;
   for (int i = 1; i < 7 && s2; ++i) s2 = conv_x3s_s2_eligible(H->conv[i]) && Tc[i + 1] >= 1;
   float* feat = nullptr;
   if (s2) {
@@ -167,20 +163,11 @@ static void hubert_graph(Hubert* H, hipStream_t s, Arena& A, const float* audio,
       }
     }
   } else {
-  float* fr = fuse0 ? nullptr : A.alloc<float>((size_t)10 * Tc[1]);
   float* c0 = A.alloc<float>((size_t)512 * Tc[1]);
   float* c1 = A.alloc<float>((size_t)512 * Tc[2]);
-  double* c0part = fuse0 ? A.alloc<double>(hubert_conv0_scratch_doubles(512, Tc[1])) : nullptr;
-  float* c0stat = fuse0 ? A.alloc<float>(1024) : nullptr;
-  if (!dry) {
-    if (fuse0) {
-      hubert_conv0_gn_gelu(s, audio, L, H->w0.p, H->gn_g.p, H->gn_b.p, 512, Tc[1], 1e-5f, c0, Tc[1], c0part, c0stat);
-    } else {
-      frames(s, audio, fr, (int)L, 10, 5, 0, Tc[1], 0);
-      conv1d_run(H->conv[0], s, fr, Tc[1], Tc[1], c0, Tc[1], E0);
-      groupnorm_t_gelu(s, c0, H->gn_g.p, H->gn_b.p, 512, Tc[1], Tc[1], 1e-5f);
-    }
-  }
+  double* c0part = A.alloc<double>(hubert_conv0_scratch_doubles(512, Tc[1]));
+  float* c0stat = A.alloc<float>(1024);
+  if (!dry) hubert_conv0_gn_gelu(s, audio, L, H->w0.p, H->gn_g.p, H->gn_b.p, 512, Tc[1], 1e-5f, c0, Tc[1], c0part, c0stat);
   float* in = c0; float* outb = c1;
   for (int i = 1; i < 7; ++i) {
     if (!dry) { ConvEpilogue Eg; Eg.act = ACT_GELU; conv1d_run(H->conv[i], s, in, Tc[i], Tc[i], outb, Tc[i + 1], Eg); }
@@ -192,12 +179,11 @@ static void hubert_graph(Hubert* H, hipStream_t s, Arena& A, const float* audio,
   if (taps) tap(taps->conv_stack, feat, (size_t)512 * T);
   // Split-resident GEMM path (conv_x3s.hip): the activations that feed a k = 1 projection live as the bf16 hi / lo image the kernel stages,
   // written by their producers (LayerNorm, the attention's epilogue, FFN1's GELU epilogue); the fp32 copy is kept only where a residual or
-  // the attention reads it.  Needs the bf16x3 weight images (context precision 1 / 2); RVC_X3S=0 selects the fp32-input kernels.
-  static const bool x3s_on = (exp_int("RVC_X3S", 1) != 0);
+  // the attention reads it.  Needs the bf16x3 weight images (context precision 1 / 2); without them the fp32-input kernels run.
   int need = version == 1 ? 8 : 11;
   if (n_layers > 0) need = n_layers;
   RVC_REQUIRE(need <= (int)H->layers.size(), "not enough encoder layers loaded");
-  bool gs = x3s_on && conv_x3_enabled() && conv_x3s_eligible(H->proj) && (version != 1 || conv_x3s_eligible(H->final_proj));
+  bool gs = conv_x3s_eligible(H->proj) && (version != 1 || conv_x3s_eligible(H->final_proj));
   for (int l = 0; l < need && gs; ++l) {
     const HubLayer& Y = H->layers[l];
     gs = conv_x3s_eligible(Y.qk) && conv_x3s_eligible(Y.o) && conv_x3s_eligible(Y.ff1) && conv_x3s_eligible(Y.ff2);
@@ -226,43 +212,27 @@ static void hubert_graph(Hubert* H, hipStream_t s, Arena& A, const float* audio,
   }
   {
     const size_t mark = A.off;
-    // attention on split-resident operands (attention_dma.hip): q / k as one image, V^T by the swapped product; RVC_ATT_DMA=0: fp32 q / k / v
-    static const bool att_dma = (exp_int("RVC_ATT_DMA", 1) != 0);
-    const bool ad = gs && att_dma;
-    float* qk = ad ? nullptr : A.alloc<float>((size_t)2304 * T);
-    float* vr = ad ? nullptr : A.alloc<float>((size_t)T * 768);
-    unsigned char* qk_s = ad ? A.alloc<unsigned char>(split_image_bytes(1536, T)) : nullptr;
-    unsigned char* vt_s = ad ? A.alloc<unsigned char>(attention_vt_bytes(768, T)) : nullptr;
+    // attention on split-resident operands (attention_dma.hip): q / k as one image, V^T written by the same launch; without them fp32 q / k / v
+    float* qk = gs ? nullptr : A.alloc<float>((size_t)2304 * T);
+    float* vr = gs ? nullptr : A.alloc<float>((size_t)T * 768);
+    unsigned char* qk_s = gs ? A.alloc<unsigned char>(split_image_bytes(1536, T)) : nullptr;
+    unsigned char* vt_s = gs ? A.alloc<unsigned char>(attention_vt_bytes(768, T)) : nullptr;
     float* attn = gs ? nullptr : A.alloc<float>((size_t)768 * T);
     float* ff = gs ? nullptr : A.alloc<float>((size_t)3072 * T);
     unsigned char* attn_s = gs ? A.alloc<unsigned char>(split_image_bytes(768, T)) : nullptr;
     unsigned char* ff_s = gs ? A.alloc<unsigned char>(split_image_bytes(3072, T)) : nullptr;
     if (!dry) {
-      if (ad) attention_vt_clear_tail(s, vt_s, 768, T);
+      if (gs) attention_vt_clear_tail(s, vt_s, 768, T);
       for (int l = 0; l < need; ++l) {
         HubLayer& Y = H->layers[l];
         if (taps && l == 0) tap(taps->hidden_0, h, (size_t)768 * T);
         if (taps && l == 8) tap(taps->hidden_8, h, (size_t)768 * T);
         ConvEpilogue Er; Er.R = h; Er.ldR = T;
         if (gs) {
-          if (ad) {
-            static const bool qkv1 = (exp_int("RVC_QKV_FUSED", 1) != 0);
-            if (qkv1) {
-              // q | k | v in ONE launch: the q and k rows go to their image, the v rows through the transposing epilogue into the V^T image (v's bias after the attention)
-              ConvEpilogue Eqk; Eqk.ys_out = qk_s; Eqk.ys_tp = tp; Eqk.vt_out = vt_s; Eqk.vt_tp = attention_vt_tp(768); Eqk.vt_row0 = 1536;
-              conv_x3s_run(Y.qk, s, hs, tp, T, nullptr, T, Eqk);
-            } else {
-              ConvLayer qkL = Y.qk; qkL.Co = 1536;                               // the q and k rows of the 2304-row projection -> image only
-              ConvEpilogue Eqk; Eqk.ys_out = qk_s; Eqk.ys_tp = tp;
-              conv_x3s_run(qkL, s, hs, tp, T, nullptr, T, Eqk);
-              conv_x3s_run_swapped(Y.qk, 1536, 768, s, hs, tp, T, vt_s, attention_vt_tp(768));      // V^T image by the swapped product
-            }
-            attention_split(s, qk_s, tp, 1536, 0, 48, vt_s, 12, 64, T, 1.f, Y.bv.p, nullptr, T, attn_s, tp);
-          } else {
-            conv_x3s_run(Y.qk, s, hs, tp, T, qk, T, E0);
-            transpose(s, qk + (size_t)1536 * T, vr, 768, T, T, 768, 1, 0, 0);      // V row-major [T][768] for the fused attention
-            attention_fused(s, qk, qk + (size_t)768 * T, T, vr, 768, Y.bv.p, nullptr, T, 12, 64, T, attn_s, tp);
-          }
+          // q | k | v in ONE launch: the q and k rows go to their image, the v rows through the transposing epilogue into the V^T image (v's bias after the attention)
+          ConvEpilogue Eqk; Eqk.ys_out = qk_s; Eqk.ys_tp = tp; Eqk.vt_out = vt_s; Eqk.vt_tp = attention_vt_tp(768); Eqk.vt_row0 = 1536;
+          conv_x3s_run(Y.qk, s, hs, tp, T, nullptr, T, Eqk);
+          attention_split(s, qk_s, tp, 1536, 0, 48, vt_s, 12, 64, T, 1.f, Y.bv.p, nullptr, T, attn_s, tp);
           conv_x3s_run(Y.o, s, attn_s, tp, T, hb, T, Er);
           layernorm_c_split(s, hb, Y.g1.p, Y.b1.p, h, hs, tp, kSplitMargin, 768, T, T, 1e-5f);
           ConvEpilogue Eg; Eg.act = ACT_GELU; Eg.ys_out = ff_s; Eg.ys_tp = tp;

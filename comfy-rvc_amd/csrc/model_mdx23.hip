@@ -144,7 +144,7 @@ void mdx23_finalize(Mdx23* M) {
   conv1d_layer_init(M->fin2, ts.get("final_conv.2.weight", {c.num_targets * dim_c, ch, 1, 1}).data.data(), nullptr, c.num_targets * dim_c, ch, 1, 1, 0, 1, 1);
   {
     static const bool off = (knob_int("RVC_MDX_X3S", 1) == 0);
-    bool ok = !off && conv_x3_enabled();
+    bool ok = !off;
     auto blocks_ok = [&](const std::vector<TfcBlock>& bs) { for (const TfcBlock& B : bs) ok = ok && conv_x3s_eligible(B.tfc1) && conv_x3s_eligible(B.tfc2); };
     for (auto& S : M->enc) { blocks_ok(S.blocks); ok = ok && conv_x3s_eligible(S.rs); }
     for (auto& S : M->dec) { blocks_ok(S.blocks); ok = ok && conv_x3s_eligible(S.rs); }

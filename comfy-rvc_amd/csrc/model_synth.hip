@@ -62,7 +62,7 @@ struct Synth {
   std::vector<EncLayer> enc;
   ConvLayer proj;
   FlowLayer flow[4];
-  ConvLayer conv_pre, conv_post;
+  ConvLayer conv_pre;
   DevVec dec_cond_w, dec_cond_b, conv_post_w;   // conv_post_w: raw [Ci][7] weights of the 1-channel output conv (ops.hip::conv_to1)
   std::vector<GenStage> stages;
   float lin_w = 1.f, lin_b = 0.f;
@@ -77,7 +77,7 @@ static void synth_free(Synth& S) {
   S.enc.clear();
   fl(S.proj);
   for (auto& f : S.flow) { fl(f.pre); fl(f.post); for (auto& c : f.in) fl(c); for (auto& c : f.in_gate) fl(c); for (auto& c : f.res) fl(c); for (auto& c : f.skip) fl(c); for (auto& c : f.rs) fl(c); fl(f.post_neg); f.cond_w.free_(); f.cond_b.free_(); }
-  fl(S.conv_pre); fl(S.conv_post); S.dec_cond_w.free_(); S.dec_cond_b.free_(); S.conv_post_w.free_();
+  fl(S.conv_pre); S.dec_cond_w.free_(); S.dec_cond_b.free_(); S.conv_post_w.free_();
   for (auto& st : S.stages) { fl(st.up); fl(st.noise); st.noise_w.free_(); st.noise_b.free_(); for (auto& rb : st.rb) for (int m = 0; m < 3; ++m) { fl(rb.c1[m]); fl(rb.c2[m]); } }
   S.stages.clear();
   S.img_base = nullptr; S.img_gen = 0; S.img_bytes = 0; S.img_T = -1;
@@ -194,7 +194,6 @@ void synth_finalize(Synth* S) {
     F.cond_b.upload(ts.get(p + "enc.cond_layer.bias").data);
   }
   S->conv_pre = make_conv1d(ts, "dec.conv_pre", 1, 3, 1, false);
-  S->conv_post = make_conv1d(ts, "dec.conv_post", 1, 3, 1, false, false);
   S->conv_post_w.upload(ts.get("dec.conv_post.weight").data);
   S->dec_cond_w.upload(ts.get("dec.cond.weight").data);
   S->dec_cond_b.upload(ts.get("dec.cond.bias").data);
@@ -248,8 +247,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
   // ---- split-resident front (conv_x3s.hip): the activations that feed enc_p's / the flow's / conv_pre's projections live as bf16 hi / lo
   // images written by their producers; k = 3 / 5 / 7 layers read them with taps as row offsets, so the images' margins (the zero padding)
   // must stay zero: the block is the graph's first allocation (nothing else ever occupies it) and is zeroed once per layout.
-  static const bool x3s_on = (exp_int("RVC_X3S", 1) != 0);
-  bool gs = x3s_on && conv_x3_enabled() && (C & 15) == 0 && (IC & 31) == 0 && conv_x3s_eligible(S->proj) && conv_x3s_eligible(S->conv_pre);
+  bool gs = (C & 15) == 0 && (IC & 31) == 0 && conv_x3s_eligible(S->proj) && conv_x3s_eligible(S->conv_pre);
   for (int l = 0; l < S->n_layers && gs; ++l) {
     const EncLayer& e = S->enc[l];
     gs = conv_x3s_eligible(e.qk) && conv_x3s_eligible(e.o) && conv_x3s_eligible(e.ffn1) && conv_x3s_eligible(e.ffn2);
@@ -293,16 +291,14 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
   }
   {
     const size_t mark = A.off;
-    // attention on split-resident operands (attention_dma_kernel.h): q / k as one image, V^T by the swapped product; RVC_ATT_DMA=0: fp32 q / k / v
-    static const bool att_dma = (exp_int("RVC_ATT_DMA", 1) != 0);
-    static const bool rel_in = (exp_int("RVC_ENCP_REL_FUSED", 1) != 0);
-    const bool ad = gs && att_dma && rel_in && kc == 96 && (exp_int("RVC_ENCP_FUSED", 1) != 0);
+    // attention on split-resident operands (attention_dma_kernel.h): q / k as one image, V^T written by the q | k | v launch (or by the swapped product);
+    // otherwise fp32 q / k / v
+    const bool ad = gs && kc == 96;
     unsigned char* qk_s = ad ? A.alloc<unsigned char>(split_image_bytes(2 * C, T)) : nullptr;
     unsigned char* vt_s = ad ? A.alloc<unsigned char>(attention_vt_bytes(C, T)) : nullptr;
     float* qk = ad ? nullptr : A.alloc<float>((size_t)3 * C * T);
     float* vr = ad ? nullptr : A.alloc<float>((size_t)T * C);
-    static const bool fused_env = (exp_int("RVC_ENCP_FUSED", 1) != 0);
-    const bool fused_att = fused_env && kc == 96;
+    const bool fused_att = kc == 96;
     float* Sc = fused_att ? nullptr : A.alloc<float>((size_t)H * T * T);
     float* relk = ad ? nullptr : A.alloc<float>((size_t)H * 21 * T);
     float* pb = ad ? nullptr : A.alloc<float>((size_t)H * 21 * T);
@@ -313,8 +309,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
       for (int l = 0; l < S->n_layers; ++l) {
         EncLayer& e = S->enc[l];
         if (ad) {
-          static const bool qkv1 = (exp_int("RVC_QKV_FUSED", 1) != 0);
-          if (qkv1 && ((2 * C) & 127) == 0) {
+          if (((2 * C) & 127) == 0) {
             // q | k | v in ONE launch: q and k rows to their image, the v rows through the transposing epilogue into the V^T image
             ConvEpilogue Eqk; Eqk.ys_out = qk_s; Eqk.ys_tp = tp; Eqk.vt_out = vt_s; Eqk.vt_tp = attention_vt_tp(C); Eqk.vt_row0 = 2 * C;
             conv_x3s_run(e.qk, s, x_s, tp, T, nullptr, T, Eqk);
@@ -340,20 +335,15 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
         if (gs) conv_x3s_run(e.qk, s, x_s, tp, T, qk, T, E0); else
         conv1d_run(e.qk, s, x, T, T, qk, T, E0);
         transpose(s, qk + (size_t)2 * C * T, vr, C, T, T, C, 1, 0, 0);                                       // V row-major [T][C] (bias later)
-        if (fused_att && rel_in) {
+        if (fused_att) {
           // softmax(K^T Q + banded rel-k bias) V + bv + banded P . E_v in ONE kernel: both relative-position projections included
           attention_rel_fused(s, qk, qk + (size_t)C * T, T, vr, C, e.bv.p, nullptr, nullptr, 10, attn, T, H, kc, T, e.ek.p, e.ev.p);
         } else {
         for (int h = 0; h < H; ++h) conv1d_run(e.relk, s, qk + (size_t)h * kc * T, T, T, relk + (size_t)h * 21 * T, T, E0);
-        if (fused_att) {
-          // softmax(K^T Q + banded rel-k bias) V + bv in one kernel; the band of probabilities comes back in pb for the rel-v projection
-          attention_rel_fused(s, qk, qk + (size_t)C * T, T, vr, C, e.bv.p, relk, pb, 10, attn, T, H, kc, T);
-        } else {
-          gemm_tn_run(s, qk + (size_t)C * T, T, (long long)kc * T, qk, T, (long long)kc * T, Sc, T, (long long)T * T, T, T, kc, H, nullptr, 0, E0);
-          fill(s, pb, 0.f, (long long)H * 21 * T);
-          softmax_cols(s, Sc, T, T, T, (long long)T * T, H, relk, 21LL * T, 10, pb, 21LL * T);
-          gemm_tn_run(s, vr, C, kc, Sc, T, (long long)T * T, attn, T, (long long)kc * T, kc, T, T, H, e.bv.p, kc, E0);
-        }
+        gemm_tn_run(s, qk + (size_t)C * T, T, (long long)kc * T, qk, T, (long long)kc * T, Sc, T, (long long)T * T, T, T, kc, H, nullptr, 0, E0);
+        fill(s, pb, 0.f, (long long)H * 21 * T);
+        softmax_cols(s, Sc, T, T, T, (long long)T * T, H, relk, 21LL * T, 10, pb, 21LL * T);
+        gemm_tn_run(s, vr, C, kc, Sc, T, (long long)T * T, attn, T, (long long)kc * T, kc, T, T, H, e.bv.p, kc, E0);
         ConvEpilogue Ea; Ea.accumulate = 1;
         for (int h = 0; h < H; ++h) conv1d_run(e.relv, s, pb + (size_t)h * 21 * T, T, T, attn + (size_t)h * kc * T, T, Ea);
         }
@@ -413,8 +403,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
           conv_x3s_run(F.pre, s, x0_s, tp, T, h, T, Eh);
           fill(s, wo, 0.f, (long long)C * T);
           for (int i = 0; i < 3; ++i) {
-            static const bool gate1 = (exp_int("RVC_WN_GATE_FUSED", 1) != 0);
-            if (gate1 && F.in_gate[i].Wx_ && conv_x3s_eligible(F.in_gate[i])) {
+            if (F.in_gate[i].Wx_ && conv_x3s_eligible(F.in_gate[i])) {
               // k = 5 over the first H channels of the [h | wo] image, the gate in the epilogue: acts leaves as its image, the 2 H-row tensor is never stored
               ConvEpilogue Eg; Eg.ys_out = acts_s; Eg.ys_tp = tp; Eg.gate_h = C; Eg.gate_g = gcond[f] + (size_t)i * 2 * C;
               conv_x3s_run(F.in_gate[i], s, hw_s, tp, T, nullptr, T, Eg);
@@ -477,13 +466,12 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
     float* fr = (S->f0 && st.noise_k > 1) ? A.alloc<float>((size_t)st.noise_k * Tn) : nullptr;
     // split-resident intermediate of a ResBlock pair: c1's epilogue writes t = lrelu(c1(..) + b1) as the bf16 hi / lo image c2 stages in
     // LDS (DMA, no conversion, no staging registers; 4 b128 stores per accumulator instead of 16 dword stores on c1's side)
-    static const bool split_on = (exp_int("RVC_SPLIT", 1) != 0);
     // h2_pair: both halves on the persistent kernel in its fp16x2 arithmetic (two MFMAs per product; conv_x3q.hip) - the pair's image is then fp16 hi / lo
     bool split_pair[3][3], h2_pair[3][3];
     bool any_split = false;
     for (int j = 0; j < 3; ++j)
       for (int m = 0; m < 3; ++m) {
-        split_pair[j][m] = split_on && conv1d_split_eligible(st.rb[j].c1[m], Tn, SPLIT_PRODUCER) && conv1d_split_eligible(st.rb[j].c2[m], Tn, SPLIT_CONSUMER);
+        split_pair[j][m] = conv1d_split_eligible(st.rb[j].c1[m], Tn, SPLIT_PRODUCER) && conv1d_split_eligible(st.rb[j].c2[m], Tn, SPLIT_CONSUMER);
         h2_pair[j][m] = split_pair[j][m] && conv1d_pair_h2_eligible(st.rb[j].c1[m], st.rb[j].c2[m], Tn);
         any_split = any_split || split_pair[j][m];
       }
@@ -495,9 +483,8 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
       ConvEpilogue Eu; Eu.pre_act = ACT_LRELU; Eu.pre_slope = 0.1f;
       conv1d_run(st.up, s, cur, Tc, Tc, up, Tn, Eu);
       ConvEpilogue En; En.accumulate = 1;
-      static const bool noise_stream = (exp_int("RVC_NOISE_STREAM", 1) != 0);
       // last stage (one tap of the source per position) with all three ResBlocks on conv_rb3_kernel: the noise term is added where x is read
-      bool noise_in_rb3 = S->f0 && noise_stream && st.noise_k == 1 && st.noise_w.p != nullptr && N == (long long)Tn;
+      bool noise_in_rb3 = S->f0 && st.noise_k == 1 && st.noise_w.p != nullptr && N == (long long)Tn;
       for (int j = 0; j < 3 && noise_in_rb3; ++j) {
         const ConvLayer* r1[3] = {&st.rb[j].c1[0], &st.rb[j].c1[1], &st.rb[j].c1[2]};
         const ConvLayer* r2[3] = {&st.rb[j].c2[0], &st.rb[j].c2[1], &st.rb[j].c2[2]};
@@ -508,7 +495,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
         // nothing here
       } else if (!S->f0) {
         // plain Generator: nothing is added to the up-sampled signal
-      } else if (noise_stream && st.noise_w.p && noise_add(s, up, Tn, Cc, Tn, har, N, st.noise_k, st.noise_s, st.noise_k > 1 ? st.noise_s / 2 : 0, st.noise_w.p, st.noise_b.p)) {
+      } else if (st.noise_w.p && noise_add(s, up, Tn, Cc, Tn, har, N, st.noise_k, st.noise_s, st.noise_k > 1 ? st.noise_s / 2 : 0, st.noise_w.p, st.noise_b.p)) {
         // narrow stages (k <= 8 taps of the one source channel): a streaming add instead of im2col + GEMM
       } else if (st.noise_k > 1) {
         frames(s, har, fr, (int)N, st.noise_k, st.noise_s, st.noise_s / 2, Tn, 0);
@@ -552,15 +539,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
     }
     cur = xs; Tc = Tn;
   }
-  if (!dry) {
-    static const bool stream_post = (exp_int("RVC_CONVPOST_STREAM", 1) != 0);
-    if (stream_post) {
-      conv_to1(s, cur, Tc, S->conv_post_w.p, S->up_init >> nu, 7, 3, Tc, 0.01f, 1, out);
-    } else {
-      ConvEpilogue Ep; Ep.pre_act = ACT_LRELU; Ep.pre_slope = 0.01f; Ep.act = ACT_TANH;
-      conv1d_run(S->conv_post, s, cur, Tc, Tc, out, Tc, Ep);
-    }
-  }
+  if (!dry) conv_to1(s, cur, Tc, S->conv_post_w.p, S->up_init >> nu, 7, 3, Tc, 0.01f, 1, out);
 }
 
 void synth_infer(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, int sid,

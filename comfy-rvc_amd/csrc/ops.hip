@@ -831,113 +831,11 @@ void avgpool2(hipStream_t s, const float* x, float* y, int C, int H, int W, long
 #ifndef RVC_GRU_SLEEP
 #define RVC_GRU_SLEEP 1      // back-off of the polling loop, in units of 64 cycles (measured: see DESIGN.md)
 #endif
-#ifdef RVC_EXPERIMENTS      // the round-3 scan kernel (three barriers per step): kept for A/B in variant builds (RVC_GRU_V=1)
-__global__ __launch_bounds__(768) void gru_scan_kernel_v1(const float* __restrict__ gi, const float* __restrict__ b_ih,
-                                                          const float* __restrict__ w_hh, const float* __restrict__ b_hh,
-                                                          float* __restrict__ out, unsigned long long* xbuf, int* err, int T,
-                                                          unsigned spin_limit, int fault) {
-  constexpr int H = 256, HS = 32;
-  constexpr int HP = 36;                                   // padded pitch of one 32-value segment of h in LDS (float4 reads of the
-                                                           // eight segments then fall on disjoint banks)
-  // h and the gate pre-activations are double-buffered by step parity: the gate threads of step s read buffer s & 1 while the other threads
-  // already gather / multiply step s + 1 in the other one - no barrier at the end of a step; the data dependency orders the rest (nobody passes
-  // the gather of step s + 1 before every slice, this one included, has published h_s).  Same-box A/B, 6201 steps: 6.33 -> 6.11 ms.
-  __shared__ __attribute__((aligned(16))) float hs[2][8 * HP];
-  __shared__ float ghs[2][96];
-  const int xcd = blockIdx.x & 7;
-  if (xcd != 0 && xcd != 4) return;
-  const int dir = xcd >> 2, sl = blockIdx.x >> 3;
-  if (fault && dir == 1 && sl == 5) return;                 // fault injection (tests): one slice never publishes, its peers must time out
-  const int tid = threadIdx.x;
-  bool failed = false;                                       // sticky per thread: after one timeout the stale value is used without polling
-  const float* W = w_hh + (long long)dir * 3 * H * H;
-  const float* BH = b_hh + dir * 3 * H;
-  const float* BI = b_ih + dir * 3 * H;
-  unsigned long long* xb = xbuf + dir * 2 * H;
-
-  // weights of this thread: local row lr = tid >> 3 (gate g = lr / 32, unit jj = lr % 32), column segment seg = tid & 7 (32 columns).
-  // Eight lanes per row keep the per-step dot product at 8 LDS reads + 32 FMAs per thread (with 2 threads per row the serial
-  // read -> FMA chain was 1.0 us of a 1.5 us step).  Measured per step now (cycles): hand-off 1000, dot product 475, gates 200.
-  float w[32];
-  const int lr = tid >> 3, seg = tid & 7;
-  {
-    const int grow = (lr / HS) * H + sl * HS + (lr % HS);
-#pragma unroll
-    for (int c = 0; c < 32; ++c) w[c] = W[(long long)grow * H + seg * 32 + c];
-  }
-  float c_r = 0.f, c_z = 0.f, bi_n = 0.f, bh_n = 0.f;
-  const int unit = sl * HS + tid;   // valid for tid < 32
-  if (tid < HS) {
-    c_r = BI[unit] + BH[unit]; c_z = BI[H + unit] + BH[H + unit];          // (b_ih + b_hh) of the r and z gates
-    bi_n = BI[2 * H + unit]; bh_n = BH[2 * H + unit];
-  }
-  if (tid < H) hs[0][(tid >> 5) * HP + (tid & 31)] = 0.f;
-  __syncthreads();
-  for (int step = 0; step < T; ++step) {
-    float* hsb = hs[step & 1]; float* gb = ghs[step & 1];
-    const int t = dir ? (T - 1 - step) : step;
-    float gr = 0.f, gz = 0.f, gn = 0.f;
-    if (tid < HS) {
-      const float* g = gi + (long long)t * (6 * H) + dir * 3 * H + unit;
-      gr = g[0] + c_r; gz = g[H] + c_z; gn = g[2 * H] + bi_n;
-    }
-    if (step > 0) {
-      if (tid < H) {
-        // gather h_{step-1}: one granule per thread
-        const unsigned long long* gp = xb + ((step - 1) & 1) * H + tid;
-        unsigned long long v;
-        unsigned spins = 0;
-        for (;;) {
-          v = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((unsigned)(v >> 32) == (unsigned)step) break;
-          if (failed || ++spins > spin_limit) { if (!failed && err) atomicExch(err, 1); failed = true; break; }
-          __builtin_amdgcn_s_sleep(RVC_GRU_SLEEP);
-        }
-        hsb[(tid >> 5) * HP + (tid & 31)] = __uint_as_float((unsigned)v);
-      }
-      __syncthreads();
-    }
-    {
-      const float4* hv = reinterpret_cast<const float4*>(hsb + seg * HP);
-      float4 h4[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) h4[c] = hv[c];
-      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        a0 = fmaf(w[4 * c + 0], h4[c].x, a0); a1 = fmaf(w[4 * c + 1], h4[c].y, a1);
-        a2 = fmaf(w[4 * c + 2], h4[c].z, a2); a3 = fmaf(w[4 * c + 3], h4[c].w, a3);
-      }
-      float a = (a0 + a1) + (a2 + a3);
-      // sum over the 8 lanes of a row with DPP moves (VALU, no LDS crossbar round trips)
-      a += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-      a += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-      a += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), 0x141, 0xF, 0xF, true));   // row_half_mirror
-      if (seg == 0) gb[lr] = a;
-    }
-    __syncthreads();
-    if (tid < HS) {
-      // gates on the hardware exp2 / reciprocal (1 ulp each): sigmoid(x) = 1 / (1 + 2^(-x log2 e)), tanh(x) = 1 - 2 / (2^(2 x log2 e) + 1).
-      // The library expf / tanhf were 770 of the 2550 cycles of a step, on the critical path of all 16 workgroups.
-      constexpr float kL2E = 1.44269504088896340736f;
-      const float r = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-kL2E * (gr + gb[tid])));
-      const float zg = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-kL2E * (gz + gb[HS + tid])));
-      const float xn = gn + r * (gb[2 * HS + tid] + bh_n);
-      const float nn = 1.f - 2.f * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(2.f * kL2E * xn) + 1.f);
-      const float hprev = hsb[(unit >> 5) * HP + (unit & 31)];
-      const float hnew = (1.f - zg) * nn + zg * hprev;
-      const unsigned long long gran = ((unsigned long long)(unsigned)(step + 1) << 32) | (unsigned long long)__float_as_uint(hnew);
-      __hip_atomic_store(xb + (step & 1) * H + unit, gran, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      out[(long long)(dir * H + unit) * T + t] = hnew;
-    }
-  }
-}
-#endif
 // Round 4: the same scan with ONE barrier per step.  The three gate rows (r, z, n) of a hidden unit used to live in three different waves:
 // their dot products met in LDS (write, barrier, read) before 32 threads computed the gates.  Here a unit's eight lanes hold all three rows
 // (96 weights per thread, 256 threads = one wave per SIMD: the same 384 FMA issue cycles per SIMD as twelve waves of 32), the DPP tree leaves
 // the three sums in the unit's lane 0, which computes the gates at once - no second barrier, no LDS round trip.  Segments, FMA chains and the
-// reduction tree are those of gru_scan_kernel_v1: identical numerics.  (RVC_GRU_V=1 selects the old kernel.)
+// reduction tree are those of the round-3 kernel: identical numerics.
 // NP polls in flight per thread (round 5).  With one, a granule that lands just after a poll was issued is seen a whole L2 round trip + back-off
 // later, and a step waits for the LATEST of seven peers: close to a full poll period on top of the hand-off.  With NP staggered loads outstanding
 // (each re-issued the moment it returns un-tagged) the detection delay falls to a period / NP; the loads retire in order, so checking the oldest
@@ -1112,32 +1010,11 @@ void gru_scan(hipStream_t s, const float* gi, const float* b_ih, const float* w_
   (void)hipMemsetAsync(xbuf, 0, sizeof(unsigned long long) * 2 * 2 * 256, s);
   (void)hipMemsetAsync(err, 0, 2 * sizeof(int), s);
   unsigned sl = spin_limit ? spin_limit : (1u << 24);
-#ifdef RVC_EXPERIMENTS
-  // variant builds only (tools/build_variant.sh): cooperative launch (RVC_GRU_COOP=1: 1793 -> 1621 xRT with three clips in flight, round 3 - a cooperative dispatch
-  // waits until the grid is launchable as a whole, which idles the chip under the other lanes' kernels), the round-3 scan kernel (RVC_GRU_V=1), several polls in
-  // flight per thread (RVC_GRU_POLL) and longer poll back-off (RVC_GRU_SLEEPN) - all measured neutral or worse (profiles/r5_gru_poll.txt, r5_exp_gru_sleep.txt)
-  static const bool coop = (exp_int("RVC_GRU_COOP", 0) != 0);
-  static const int ver = exp_int("RVC_GRU_V", 2);
-  static const int np = exp_int("RVC_GRU_POLL", 1);
-  static const int slp = exp_int("RVC_GRU_SLEEPN", RVC_GRU_SLEEP);
-  if (coop) {
-    void* args[] = {(void*)&gi, (void*)&b_ih, (void*)&w_hh, (void*)&b_hh, (void*)&out, (void*)&xbuf, (void*)&err, (void*)&T, (void*)&sl, (void*)&fault};
-    if (ver == 1) RVC_HIP_CHECK(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(gru_scan_kernel_v1), dim3(64), dim3(768), args, 0, s));
-    else RVC_HIP_CHECK(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(gru_scan_kernel<1>), dim3(64), dim3(256), args, 0, s));
-  } else if (ver == 1) hipLaunchKernelGGL(gru_scan_kernel_v1, dim3(64), dim3(768), 0, s, gi, b_ih, w_hh, b_hh, out, xbuf, err, T, sl, fault);
-  else if (np == 2) hipLaunchKernelGGL(gru_scan_kernel<2>, dim3(64), dim3(256), 0, s, gi, b_ih, w_hh, b_hh, out, xbuf, err, T, sl, fault);
-  else if (np == 3) hipLaunchKernelGGL(gru_scan_kernel<3>, dim3(64), dim3(256), 0, s, gi, b_ih, w_hh, b_hh, out, xbuf, err, T, sl, fault);
-  else if (np >= 4) hipLaunchKernelGGL(gru_scan_kernel<4>, dim3(64), dim3(256), 0, s, gi, b_ih, w_hh, b_hh, out, xbuf, err, T, sl, fault);
-  else if (slp >= 16) hipLaunchKernelGGL((gru_scan_kernel<1, 16>), dim3(64), dim3(256), 0, s, gi, b_ih, w_hh, b_hh, out, xbuf, err, T, sl, fault);
-  else if (slp >= 8) hipLaunchKernelGGL((gru_scan_kernel<1, 8>), dim3(64), dim3(256), 0, s, gi, b_ih, w_hh, b_hh, out, xbuf, err, T, sl, fault);
-  else if (slp >= 4) hipLaunchKernelGGL((gru_scan_kernel<1, 4>), dim3(64), dim3(256), 0, s, gi, b_ih, w_hh, b_hh, out, xbuf, err, T, sl, fault);
-  else
-#endif
   // plain launch: the 16 working slices become resident as soon as ANY 16 CUs have free waves (every other kernel of the path terminates without waiting for
   // anything); the bounded spin detects the case that they do not, and the serial kernel behind it repairs it
+  // (a cooperative launch, several polls in flight and a longer back-off measured neutral or worse: profiles/r5_gru_poll.txt, r5_exp_gru_sleep.txt)
   hipLaunchKernelGGL((gru_scan_kernel<1>), dim3(64), dim3(256), 0, s, gi, b_ih, w_hh, b_hh, out, xbuf, err, T, sl, fault);
-  static const bool repair = (exp_int("RVC_GRU_REPAIR", 1) != 0);
-  if (repair && w_hh_t) hipLaunchKernelGGL(gru_serial_kernel, dim3(2), dim3(768), 0, s, gi, b_ih, w_hh_t, b_hh, out, err, T);
+  if (w_hh_t) hipLaunchKernelGGL(gru_serial_kernel, dim3(2), dim3(768), 0, s, gi, b_ih, w_hh_t, b_hh, out, err, T);
 }
 
 // ---------------------------------------------------------------------------------------------- RMVPE decode
@@ -1658,13 +1535,9 @@ static void iir_geometry(long long n, bool blocked, int& L, long long& Np) {
   RVC_REQUIRE(l <= (1LL << 30), "clip too long for the blocked filter");
   L = (int)l; Np = ((N + l - 1) / l) * l;                    // whole blocks (zero-filled behind N)
 }
-static bool iir_blocked(bool have_sos) {
-  static const bool blocked_env = (exp_int("RVC_IIR_BLOCKED", 1) != 0);
-  return blocked_env && have_sos;
-}
 size_t preprocess_scratch_doubles(long long n, bool have_sos) {
   int L; long long Np;
-  iir_geometry(n, iir_blocked(have_sos), L, Np);
+  iir_geometry(n, have_sos, L, Np);
   return (size_t)(2 * Np);
 }
 
@@ -1674,7 +1547,7 @@ void preprocess(hipStream_t s, const void* x, int is64, long long n, const doubl
   IirArgs p{};
   for (int i = 0; i <= kIirOrder; ++i) { p.b[i] = b[i] / a[0]; p.a[i] = a[i] / a[0]; }
   for (int i = 0; i < kIirOrder; ++i) p.zi[i] = zi[i];
-  const bool blocked = iir_blocked(sos != nullptr && sos_zi != nullptr);
+  const bool blocked = sos != nullptr && sos_zi != nullptr;
   p.x = x; p.is64 = is64; p.n = n; p.padlen = 3 * (kIirOrder + 1); p.N = n + 2 * p.padlen;
   p.W = 5120;
   iir_geometry(n, blocked, p.L, p.Np);

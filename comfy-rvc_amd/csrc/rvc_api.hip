@@ -818,14 +818,7 @@ int rvc_conv1d_plan_pair_split_run(rvc_conv1d_plan* c1, rvc_conv1d_plan* c2, voi
   ConvEpilogue E1; E1.pre_act = ACT_LRELU; E1.pre_slope = 0.1f; E1.ys_out = img; E1.ys_tp = split_image_tp(T); E1.ys_slope = 0.1f;
   // the arithmetic the generator would use for this pair at this length: fp16x2 on the persistent kernel where eligible (rvc_set_pair_arithmetic), else bf16x3
   E1.h2 = conv1d_pair_h2_eligible(c1->L, c2->L, T) ? 1 : 0;
-#ifdef RVC_EXPERIMENTS
-  if (exp_int("RVC_EXP_PAIR_ZERO", 0)) RVC_HIP_CHECK(hipMemsetAsync(img, 0, split_image_bytes(c1->L.Co, T), s));
-#endif
   conv1d_run(c1->L, s, x, T, T, nullptr, T, E1);
-#ifdef RVC_EXPERIMENTS
-  if (exp_int("RVC_EXP_PAIR_SYNC", 0)) RVC_HIP_CHECK(hipDeviceSynchronize());
-  if (exp_int("RVC_EXP_PAIR_C1ONLY", 0)) { check_launch(); return 0; }
-#endif
   ConvEpilogue E2; E2.R = x; E2.ldR = T; E2.out_scale = out_scale; E2.accumulate = accumulate; E2.xs_in = img; E2.xs_tp = E1.ys_tp; E2.h2 = E1.h2;
   conv1d_run(c2->L, s, nullptr, T, T, y, T, E2);
   check_launch();
@@ -927,7 +920,6 @@ int rvc_debug_read_scratch(void* stream, int slot, void* host_dst, size_t bytes)
   RVC_CATCH
 }
 int rvc_debug_conv_timing(uint64_t* out8, int reset) { RVC_TRY conv_timing_read((unsigned long long*)out8, reset != 0); RVC_CATCH }
-int rvc_debug_set_x3s_mode(int mode) { conv_x3s_set_mode(mode < 0 || mode > 2 ? 0 : mode); return 0; }
 int rvc_debug_x3p_check(void) { const int a = conv_x3p_check_read(), b = conv_x3q_check_read(); return a < 0 ? a : a + (b > 0 ? b : 0); }
 int rvc_debug_gemm_split_bench(void* stream, int Ci, int Co, int T, int ksplit, int am, int an, int split_out, int reps, float* us_out, int w2d, int nlayers) {
   RVC_TRY

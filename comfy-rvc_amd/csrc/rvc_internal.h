@@ -178,7 +178,6 @@ void conv2d_run(const ConvLayer& L, hipStream_t s, const float* X, long long ldX
 // bf16x3 GEMM of a k = 1 layer on a SPLIT-RESIDENT activation (conv_x3s.hip): both operand tiles by LDS-DMA, K split reduced inside the
 // launch.  Xs: image of the [Ci][T] input (split_image_tp(T) rows per plane); Y (fp32 [Co][ldY]) and / or e.ys_out (image of the output, the
 // activation e.act - identity, (leaky) ReLU, exact GELU - applied before the split).  e.R: residual, e.bias_override as in conv1d_run.
-bool conv_x3_enabled();                       // bf16x3 kernels not switched off at run time (RVC_X3=0)
 // Layers with taps run on the same kernel: a unit of the reduction is (16-channel chunk, tap) and a tap is a row offset into the image
 // (im2col by address).  1-D "same" convolutions need nothing else (rows in front of position 0 / behind position T - 1 are the zero padding:
 // producers keep the margins zero).  2-D convolutions run over PADDED images: row pitch W + 2 with a zero column on either side, position
@@ -209,7 +208,6 @@ void conv_x3s_run_swapped(const ConvLayer& L, int row0, int rows, hipStream_t s,
                           const float* Rrm = nullptr, long long ldRrm = 0);  // Rrm: residual added to the product, laid out like Yrm (MDX23C's x + tdf(x))
 void split_image_from_tm(hipStream_t s, const float* x, int C, int T, int M, unsigned char* img, long long tp);      // x [C][T][M] -> image of the (C M) x T tensor
 void conv_x3s_force(int ksplit, int am, int an);
-void conv_x3s_set_mode(int mode);      // 0: by shape, 1: LDS-ring kernel, 2: register-direct kernel
 // one ConvBlockRes of 16 or 32 channels (3 x 3, 3 x 3, + x) in one launch (conv_cbr2.hip): x, out fp32 [C][H W], distinct
 bool cbr2_small_eligible(const ConvLayer& c1, const ConvLayer& c2);
 void cbr2_small_run(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, const float* x, int H, int W, float* out);

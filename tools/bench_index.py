@@ -1,4 +1,4 @@
-"""Retrieval index: exact k = 1 search of T_h query frames over N rows (768-d), fp32-MFMA GEMM vs bf16x3 conv layers (RVC_INDEX_X3)."""
+"""Retrieval index: exact k = 1 search of T_h query frames over N rows (768-d), on the bf16x3 conv layers."""
 import sys, time
 sys.path.insert(0, '.')
 import numpy as np, torch

@@ -1,5 +1,5 @@
-"""Split-resident ResBlock pair (c1 -> image -> c2 + residual) per generator class: us per pair and TFLOP/s.  RVC_X3Q=0/1 selects the kernel family
-(read once per process).  python tools/bench_split.py [C ...]"""
+"""Split-resident ResBlock pair (c1 -> image -> c2 + residual) per generator class: us per pair and TFLOP/s.
+python tools/bench_split.py [C ...]"""
 import sys, os, ctypes as C
 sys.path.insert(0, '.')
 import numpy as np, torch
