@@ -153,28 +153,63 @@ int conv_prof_collect_ex(double* out /* [kProfCfgs][8] */, double ridge_fp32, do
 // second pass of a split-K launch (conv_mfma.hip): fixed-order sum of the partials + dense epilogue
 void splitk_reduce_launch(const ConvArgsX& a, int S, int batch, hipStream_t s);
 
-// bf16x3 path: returns false when the layer / geometry is not eligible (caller falls back to the fp32 kernel)
-bool conv_x3_try(ConvArgsX& a, int batch, hipStream_t s, double flops, bool dry = false);
-// software-pipelined kernel for stride-1 1-D convolutions on 2 x 2-wave tiles (conv_x3p.hip); `a` as conv_x3_try prepared it
-bool conv_x3p_try(ConvArgsX& a, int AM, int AN, hipStream_t s, dim3& grid_out, bool dry);
+// ---- dispatch of the split-MFMA family: a launch is PLANNED (pure: no stream, no launch, no allocation - callable as often as anyone likes, e.g. to size
+// buffers or to ask "what would run for this shape") and then the plan is launched.  Nothing is decided twice, so the answer and the launch cannot disagree.
+int device_cu_count();                        // CUs of the CURRENT device (cached per device; 256 when the runtime does not say)
+inline int x3_xcd_remap() { static const int v = exp_int("RVC_X3_XCD", 1); return v; }
+typedef void (*ConvLaunchFn)(const ConvArgsX&, dim3, size_t, hipStream_t);
+struct ConvPlan {
+  ConvArgsX a;                    // finished kernel arguments (a.ksplit > 1: a.partial is filled in by conv_plan_launch)
+  ConvLaunchFn launch = nullptr;  // the chosen kernel instantiation
+  dim3 grid; size_t lds = 0;
+  int prof_cfg = 0, prof_fused = 0;      // profiling: 14 + tile id, kernel family << 4 | pair flags
+  double alg_bytes = 0.0, flops = 0.0;   // algorithmic traffic / work (flops: the pair planner's formula; single convolutions: the caller's)
+};
+// the whole decision tree of the bf16x3 / fp16x2 path; false when the layer / geometry is not eligible (caller falls back to the fp32 kernel)
+bool conv_x3_plan(const ConvArgsX& a0, int batch, ConvPlan& p);
+// the only place that opens a profiling bracket, takes split-K scratch, launches and reduces
+void conv_plan_launch(const ConvPlan& p, hipStream_t s);
+// sub-planners: p.a = the arguments as conv_x3_plan / conv_x3_pair_plan prepared them (true taps); on success a, launch, grid and lds of p are filled,
+// on false p is untouched
+// software-pipelined kernel for stride-1 1-D convolutions on 2 x 2-wave tiles (conv_x3p.hip)
+bool conv_x3p_plan(ConvPlan& p, int AM, int AN);
 int conv_x3p_check_read();
 // persistent version of the above for the ResBlock convolutions: a workgroup per CU slot walks over its tiles, one continuous stream of
 // weight units / input chunks, residual added block by block inside the tile (conv_x3q.hip)
-bool conv_x3q_try(ConvArgsX& a, int AM, int AN, hipStream_t s, dim3& grid_out, bool dry);
+bool conv_x3q_plan(ConvPlan& p, int AM, int AN);
 int conv_x3q_check_read();
 // k = 1 (GEMM) on the pipelined kernel, fp32 [K][N] input (conv_x3p.hip)
-bool conv_x3g_try(ConvArgsX& a, hipStream_t s, dim3& grid_out, int& ksplit_out, bool dry);
+bool conv_x3g_plan(ConvPlan& p);
 // fused ResBlock pair of the 32-channel stage on the pipelined kernel (conv_x3p.hip)
-bool conv_x3pf_try(ConvArgsX& a, int T, hipStream_t s, dim3& grid_out, bool dry);
+bool conv_x3pf_plan(ConvPlan& p, int T);
 // the same pair in the fp16x2 arithmetic with both weight sets resident in LDS, persistent workgroups (conv_rbh.hip); Wx / Wx2 = the one-plane fp16 images
-bool conv_rbh_try(ConvArgsX& a, int T, hipStream_t s, dim3& grid_out, bool dry);
-// a whole ResBlock1 (three (dilated, plain) pairs) of the 32-channel stage in one launch, fp16x2 arithmetic, bit-identical to the chain of three conv_rbh
-// launches (conv_rb3.hip); y = x3 * out_scale [+ y]; false: not eligible (the caller runs the pairs one by one)
-bool conv_rb3_try(const ConvLayer* const* c1, const ConvLayer* const* c2, hipStream_t s, const float* X, long long ldX, int T, float* Y, long long ldY,
-                  float pre_slope, float out_scale, int accumulate, bool dry = false, const float* nsrc = nullptr, const float* nw = nullptr,
-                  const float* nb = nullptr);      // nsrc [T], nw [32], nb [32]: x[c][t] + fmaf(nw[c], nsrc[t], nb[c]) is what the ResBlock reads (the last stage's noise branch)
-// y = (x + c2(lrelu(c1(lrelu(x))))) * scale [+ y] for a ResBlock1 pair of narrow layers in ONE launch; false when not eligible
-bool conv_x3_pair_try(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, const float* X, long long ldX, int T, float* Y, long long ldY,
-                      const ConvEpilogue& e2, bool dry_only = false);
+bool conv_rbh_plan(ConvPlan& p, int T);
+// y = (x + c2(lrelu(c1(lrelu(x))))) * scale [+ y] for a ResBlock1 pair of narrow layers in ONE launch; false when not eligible.  h2: the pair arithmetic the
+// caller read once at the start of its call (see conv1d_pair_h2_eligible); p.a.h2 tells whether the plan is the fp16x2 kernel's
+bool conv_x3_pair_plan(const ConvLayer& c1, const ConvLayer& c2, const float* X, long long ldX, int T, float* Y, long long ldY, const ConvEpilogue& e2, int h2,
+                       ConvPlan& p);
+
+// a whole ResBlock1 (three (dilated, plain) pairs) of the narrow stages in one launch, fp16x2 arithmetic, bit-identical to the chain of three conv_rbh
+// launches (conv_rb3.hip); y = x3 * out_scale [+ y]
+struct Rb3Args {
+  const float* X; long long ldX; float* Y; long long ldY;
+  const unsigned char* W[6];      // c1_0, c2_0, c1_1, c2_1, c1_2, c2_2: one-plane fp16 images [chunk][tap][half][CoPx rows][8 ch]
+  const float* B[6];              // their biases (or null)
+  int CoPx;
+  int T, halo, NO;                // sequence length; columns lost per side of a tile; columns stored per tile (dilations 1 / 3 / 5, the margins and the rows of the image are compiled in)
+  float pre_slope, mid_slope, out_scale;
+  // NSF noise branch of the last generator stage folded into the read of x (reference models.py GeneratorNSF.forward: x = ups(x) + noise_convs[i](har), the
+  // last stage's Conv1d(1, C, 1)): x[c][t] + fmaf(nw[c], nsrc[t], nb[c]) - the same operations as noise_add_kernel<1> (ops.hip), whose pass over the
+  // tensor (one read, one write of 164 MB) disappears; null: x as it is
+  const float* nsrc; const float* nw; const float* nb;
+};
+struct Rb3Plan {
+  Rb3Args a; void (*launch)(const Rb3Args&, dim3, size_t, hipStream_t) = nullptr; dim3 grid; size_t lds = 0;
+  int C = 0, k = 0, accumulate = 0;
+};
+// pure like conv_x3_plan; false: not eligible (the caller runs the pairs one by one).  nsrc [T], nw [32], nb [32]: the last stage's noise branch
+bool conv_rb3_plan(const ConvLayer* const* c1, const ConvLayer* const* c2, const float* X, long long ldX, int T, float* Y, long long ldY, float pre_slope,
+                   float out_scale, int accumulate, int h2, const float* nsrc, const float* nw, const float* nb, Rb3Plan& p);
+void conv_rb3_launch(const Rb3Plan& p, hipStream_t s);
 
 }  // namespace rvc

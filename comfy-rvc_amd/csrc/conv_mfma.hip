@@ -574,9 +574,20 @@ static void pack_h2(ConvLayer& L, const float* w, int Co, int Ci, int k) {
 static std::atomic<int> g_pair_h2{-1};
 int conv_set_pair_arithmetic(int mode) {
   int cur = g_pair_h2.load(std::memory_order_relaxed);
-  if (cur < 0) { cur = knob_int("RVC_H2", 1) ? 1 : 0; g_pair_h2.store(cur, std::memory_order_relaxed); }
-  if (mode >= 0) g_pair_h2.store(mode ? 1 : 0, std::memory_order_relaxed);
+  // (lazy RVC_H2: only from "unset", so that a concurrent set is never overwritten; on failure cur is what the other thread stored)
+  if (cur < 0) { const int env = knob_int("RVC_H2", 1) ? 1 : 0; if (g_pair_h2.compare_exchange_strong(cur, env, std::memory_order_relaxed)) cur = env; }
+  if (mode >= 0) cur = g_pair_h2.exchange(mode ? 1 : 0, std::memory_order_relaxed);
   return cur;
+}
+// (per device: one process may drive several GPUs, and the persistent grids are sized by the CURRENT device's CU count)
+int device_cu_count() {
+  static std::atomic<int> ncu_of[64];
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64) dev = 0;
+  int ncu = ncu_of[dev].load(std::memory_order_relaxed);
+  if (ncu == 0) { int n = 256; (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); ncu = n > 0 ? n : 256; ncu_of[dev].store(ncu, std::memory_order_relaxed); }
+  return ncu;
 }
 
 void conv_layer_append_x3(ConvLayer& dst, const ConvLayer& extra) {
@@ -1040,7 +1051,9 @@ void conv1d_run(const ConvLayer& L, hipStream_t s, const float* X, long long ldX
     RVC_REQUIRE(L.Wh_ && (e.xs_in || e.ys_out), "fp16x2 arithmetic is for the two halves of a split-resident ResBlock pair (conv1d_pair_h2_eligible)");
     a.Wx = reinterpret_cast<const unsigned char*>(L.Wh_); a.h2 = 1;
   }
-  if (!(L.Wx_ && conv_x3_try(a, L.groups, s, flops))) {
+  ConvPlan p;
+  if (L.Wx_ && conv_x3_plan(a, L.groups, p)) { p.flops = flops; conv_plan_launch(p, s); }
+  else {
     RVC_REQUIRE(!e.xs_in && !e.ys_out, "split-resident tensors need the bf16x3 kernel (check conv1d_split_eligible first)");
     run_conv(a, 1, L.groups, s, flops);
   }
@@ -1050,8 +1063,8 @@ void conv1d_run(const ConvLayer& L, hipStream_t s, const float* X, long long ldX
   }
 }
 
-bool conv1d_pair_h2_eligible(const ConvLayer& c1, const ConvLayer& c2, int Tin) {
-  if (!conv_set_pair_arithmetic(-1) || !c1.Wh_ || !c2.Wh_) return false;
+bool conv1d_pair_h2_eligible(const ConvLayer& c1, const ConvLayer& c2, int Tin, int h2) {
+  if (!h2 || !c1.Wh_ || !c2.Wh_) return false;
   return conv1d_split_eligible(c1, Tin, SPLIT_PRODUCER, 1) && conv1d_split_eligible(c2, Tin, SPLIT_CONSUMER, 1);
 }
 
@@ -1063,10 +1076,11 @@ bool conv1d_split_eligible(const ConvLayer& L, int Tin, SplitRole role, int h2) 
   a.Tout = conv1d_out_len(L, Tin); a.ostride = 1; a.orows = L.Co; a.ldX = Tin; a.ldY = a.Tout; a.ldR = a.Tout;
   a.Wx = reinterpret_cast<const unsigned char*>(L.Wx_); a.CoPx = L.CoPx; a.kreal = L.k; a.h2 = h2;
   if (role == SPLIT_CONSUMER) a.R = reinterpret_cast<const float*>(L.Wx_);      // (c2 of a pair has a residual; the persistent kernel asks for it)
-  // any non-null value asks for the role's geometry (dry run: never dereferenced)
+  // any non-null value asks for the role's geometry (planning only: never dereferenced)
   if (role == SPLIT_PRODUCER) { a.Ys = reinterpret_cast<unsigned char*>(L.Wx_); a.ysTp = split_image_tp(Tin); a.pre_act = ACT_LRELU; a.pre_slope = 0.1f; }
   else { a.Xs = reinterpret_cast<const unsigned char*>(L.Wx_); a.xsTp = split_image_tp(Tin); }
-  return conv_x3_try(a, 1, nullptr, 0.0, true);
+  ConvPlan p;
+  return conv_x3_plan(a, 1, p);
 }
 
 void gemm_tn_run(hipStream_t s, const float* A, long long ldA, long long aBatch, const float* B, long long ldB, long long bBatch,
@@ -1104,29 +1118,18 @@ void conv2d_run(const ConvLayer& L, hipStream_t s, const float* X, long long ldX
     ConvArgsX d = a;
     float* tmp = (float*)stream_scratch(s, 4, (size_t)L.Co * H * Wd * sizeof(float));
     d.Y = tmp; d.ldY = (long long)H * Wd; d.up2 = 0; d.orows = L.Co; d.bias = L.bd4_;
-    if (conv_x3_try(d, 1, s, flops)) {
+    ConvPlan p;
+    if (conv_x3_plan(d, 1, p)) {
+      p.flops = flops; conv_plan_launch(p, s);
       const long long n = (long long)L.Co * H * Wd;
       int blocks = (int)((n + 255) / 256); if (blocks > 8192) blocks = 8192;
       hipLaunchKernelGGL(interleave2x2_kernel, dim3(blocks), dim3(256), 0, s, tmp, Y, L.co_real, H, Wd);
       return;
     }
   }
-  if (!(L.Wx_ && !L.up2 && conv_x3_try(a, 1, s, flops))) run_conv(a, 2, 1, s, flops);
-}
-
-bool conv2d_kx_try(const ConvLayer& L, hipStream_t s, const float* X, long long ldX, int H, int Wd, float* Y, long long ldY, const ConvEpilogue& e, bool dry) {
-  RVC_REQUIRE(L.mode == 2 && L.Wx_, "conv2d_kx_try on a layer without a bf16x3 image");
-  if ((Wd & (Wd - 1)) != 0 || Wd < 2 || !simple_act(e.act)) return false;
-  ConvArgsX a{};
-  a.X = X; a.W = nullptr; a.bias = L.bd_; a.Y = Y;
-  fill_epilogue(a, e);
-  a.Ci = L.Ci; a.Co = L.Co; a.CoP = L.CoP; a.Tin = H; a.Tout = H * Wd; a.Wd = Wd; a.ktaps = L.ktaps; a.dil = 1; a.stride = 1; a.pad = 0;
-  a.KH = L.kh; a.KW = L.kw; a.PH = L.ph; a.PWL = L.pwl;
-  a.CK = 16; a.nchunk = L.nchunk;
-  a.ldX = ldX; a.ldY = ldY; a.up2 = 0; a.ostride = 1; a.orows = L.Co;
-  a.xBatch = a.wBatch = a.yBatch = a.rBatch = 0; a.bBatch = L.Co;
-  a.Wx = reinterpret_cast<const unsigned char*>(L.Wx_); a.CoPx = L.CoPx; a.wxBatch = L.wxBatch; a.kreal = L.ktaps;
-  return conv_x3_try(a, 1, s, 2.0 * H * (double)Wd * L.ktaps * L.Ci * L.Co, dry);
+  ConvPlan p;
+  if (L.Wx_ && !L.up2 && conv_x3_plan(a, 1, p)) { p.flops = flops; conv_plan_launch(p, s); }
+  else run_conv(a, 2, 1, s, flops);
 }
 
 }  // namespace rvc

@@ -35,19 +35,6 @@
 
 namespace rvc {
 
-struct Rb3Args {
-  const float* X; long long ldX; float* Y; long long ldY;
-  const unsigned char* W[6];      // c1_0, c2_0, c1_1, c2_1, c1_2, c2_2: one-plane fp16 images [chunk][tap][half][CoPx rows][8 ch]
-  const float* B[6];              // their biases (or null)
-  int CoPx;
-  int T, halo, NO;                // sequence length; columns lost per side of a tile; columns stored per tile (dilations 1 / 3 / 5, the margins and the rows of the image are compiled in)
-  float pre_slope, mid_slope, out_scale;
-  // NSF noise branch of the last generator stage folded into the read of x (reference models.py GeneratorNSF.forward: x = ups(x) + noise_convs[i](har), the
-  // last stage's Conv1d(1, C, 1)): x[c][t] + fmaf(nw[c], nsrc[t], nb[c]) - the same operations as noise_add_kernel<1> (ops.hip), whose pass over the
-  // tensor (one read, one write of 164 MB) disappears; null: x as it is
-  const float* nsrc; const float* nw; const float* nb;
-};
-
 template <int T, int N, class F> __device__ __forceinline__ void rb3_for(F& f) {
   if constexpr (T < N) { f(std::integral_constant<int, T>{}); rb3_for<T + 1, N>(f); }
 }
@@ -371,15 +358,13 @@ static void launch_rb3c(const Rb3Args& a, dim3 grid, size_t lds, hipStream_t s) 
   conv_launch(kern, grid, dim3(512), lds, s, a);
 }
 template <int CH, int KT, int WM>
-static void launch_rb3(const Rb3Args& a, bool acc, dim3 grid, size_t lds, hipStream_t s) {
-  if (acc) launch_rb3c<CH, KT, true, WM>(a, grid, lds, s); else launch_rb3c<CH, KT, false, WM>(a, grid, lds, s);
-}
+static auto select_rb3(bool acc) { return acc ? &launch_rb3c<CH, KT, true, WM> : &launch_rb3c<CH, KT, false, WM>; }
 
 // c1[i] / c2[i]: the three (dilated, plain) pairs of one ResBlock1.  32 channels, equal odd kernel size 3 / 7 / 11, "same" padding, every layer with its
-// one-plane fp16 image, the fp16x2 pair arithmetic switched on, at least two rounds of tiles; false: not this kernel's (the caller runs the pairs one by one).
-bool conv_rb3_try(const ConvLayer* const* c1, const ConvLayer* const* c2, hipStream_t s, const float* X, long long ldX, int T, float* Y, long long ldY,
-                  float pre_slope, float out_scale, int accumulate, bool dry, const float* nsrc, const float* nw, const float* nb) {
-  if (!conv_set_pair_arithmetic(-1)) return false;
+// one-plane fp16 image, the fp16x2 pair arithmetic switched on (h2), at least two rounds of tiles; false: not this kernel's (the caller runs the pairs one by one).
+bool conv_rb3_plan(const ConvLayer* const* c1, const ConvLayer* const* c2, const float* X, long long ldX, int T, float* Y, long long ldY, float pre_slope,
+                   float out_scale, int accumulate, int h2, const float* nsrc, const float* nw, const float* nb, Rb3Plan& p) {
+  if (!h2) return false;
   const int k = c1[0]->k, C = c1[0]->Co;
   // (the 64-channel stage's 3- and 7-tap ResBlocks too: otherwise three conv_x3pf_kernel launches in bf16x3 / six conv_x3q_kernel launches with the images through HBM)
   if (!((C == 32 && (k == 3 || k == 7 || k == 11)) || (C == 64 && (k == 3 || k == 7)))) return false;
@@ -395,14 +380,12 @@ bool conv_rb3_try(const ConvLayer* const* c1, const ConvLayer* const* c2, hipStr
   const int P2 = (k - 1) / 2, M = P2 * 5, P = TILE + 2 * M, halo = P2 * (dsum + 3), NO = TILE - 2 * halo;
   if ((double)C * (double)ldX * 4.0 >= 2147483648.0 || (double)C * (double)ldY * 4.0 >= 2147483648.0) return false;
   if (nsrc && C != 32) return false;
-  int dev = 0, ncu = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (ncu <= 0) ncu = 256;
+  const int ncu = device_cu_count();
   const long long ntiles = ((long long)T + NO - 1) / NO;
   if (ntiles < 2LL * ncu) return false;                       // short sequences: the pair kernels' smaller tiles fill the chip better
-  if (dry) return true;
-  Rb3Args a{};
+  p = Rb3Plan{};
+  p.C = C; p.k = k; p.accumulate = accumulate;
+  Rb3Args& a = p.a;
   a.X = X; a.ldX = ldX; a.Y = Y; a.ldY = ldY; a.CoPx = c1[0]->CoPx;
   for (int i = 0; i < 3; ++i) {
     a.W[2 * i] = reinterpret_cast<const unsigned char*>(c1[i]->Wh_); a.W[2 * i + 1] = reinterpret_cast<const unsigned char*>(c2[i]->Wh_);
@@ -410,31 +393,37 @@ bool conv_rb3_try(const ConvLayer* const* c1, const ConvLayer* const* c2, hipStr
   }
   a.T = T; a.halo = halo; a.NO = NO;
   a.pre_slope = pre_slope; a.mid_slope = pre_slope; a.out_scale = out_scale;
-  RVC_REQUIRE((nsrc == nullptr) == (nw == nullptr) && (nsrc == nullptr) == (nb == nullptr), "conv_rb3_try: the noise branch is source, weights and biases together");
+  RVC_REQUIRE((nsrc == nullptr) == (nw == nullptr) && (nsrc == nullptr) == (nb == nullptr), "conv_rb3_plan: the noise branch is source, weights and biases together");
   a.nsrc = nsrc; a.nw = nw; a.nb = nb;
   const size_t wb = (size_t)(C / 16) * k * 2 * C * 16;
   const size_t tile_bytes = (size_t)P * (C / 16) * 64;
   // six weight sets beside the image: 36 / 84 KiB fit (32 channels, 3 / 7 taps); two buffers at 11 taps (2 x 22 KiB) and at 64 channels x 3 taps (2 x 24 KiB); one at
   // 64 channels x 7 taps (56 KiB beside the 82 KiB image)
   const int wm = (C == 32 && k <= 7) ? 0 : ((C == 64 && k == 7) ? 2 : 1);
-  const size_t lds = (wm == 0 ? 6 : (wm == 1 ? 2 : 1)) * wb + 2048 + tile_bytes;
-  RVC_REQUIRE(lds <= 160 * 1024, "conv_rb3_try: LDS budget");
-  dim3 grid((unsigned)(ntiles < ncu ? ntiles : ncu), 1, 1);
+  p.lds = (wm == 0 ? 6 : (wm == 1 ? 2 : 1)) * wb + 2048 + tile_bytes;
+  RVC_REQUIRE(p.lds <= 160 * 1024, "conv_rb3_plan: LDS budget");
+  p.grid = dim3((unsigned)(ntiles < ncu ? ntiles : ncu), 1, 1);
+  const bool acc = accumulate != 0;
+  if (C == 64 && k == 3) p.launch = select_rb3<64, 3, 1>(acc);
+  else if (C == 64) p.launch = select_rb3<64, 7, 2>(acc);
+  else if (k == 3) p.launch = select_rb3<32, 3, 0>(acc);
+  else if (k == 7) p.launch = select_rb3<32, 7, 0>(acc);
+  else p.launch = select_rb3<32, 11, 1>(acc);
+  return true;
+}
+
+void conv_rb3_launch(const Rb3Plan& p, hipStream_t s) {
+  const int C = p.C, k = p.k, T = p.a.T, accumulate = p.accumulate;
   ProfTicket tk = conv_prof_begin(s);
-  if (C == 64 && k == 3) launch_rb3<64, 3, 1>(a, accumulate != 0, grid, lds, s);
-  else if (C == 64) launch_rb3<64, 7, 2>(a, accumulate != 0, grid, lds, s);
-  else if (k == 3) launch_rb3<32, 3, 0>(a, accumulate != 0, grid, lds, s);
-  else if (k == 7) launch_rb3<32, 7, 0>(a, accumulate != 0, grid, lds, s);
-  else launch_rb3<32, 11, 1>(a, accumulate != 0, grid, lds, s);
+  p.launch(p.a, p.grid, p.lds, s);
   if (tk.on) {
     ConvArgsX pa{};
     pa.Ci = C; pa.Co = C; pa.ktaps = k; pa.kreal = k; pa.dil = 5; pa.stride = 1; pa.Tin = T; pa.Tout = T; pa.ksplit = 1; pa.h2 = 1;
-    pa.R = X; pa.X = X; pa.accumulate = accumulate;
+    pa.R = p.a.X; pa.X = p.a.X; pa.accumulate = accumulate;
     // algorithmic traffic of the ResBlock: x read once, y written once (+ the previous y when accumulating), six weight sets
     const double bytes = 4.0 * ((double)C * T * (2.0 + (accumulate ? 1.0 : 0.0)) + 6.0 * C * C * k);
-    conv_prof_end(tk, s, 3.0 * 2.0 * 2.0 * (double)C * C * k * (double)T, 14 + (C == 32 ? 1 : 5), bytes, &pa, (long long)grid.x, 3 | (7 << 4));
+    conv_prof_end(tk, s, 3.0 * 2.0 * 2.0 * (double)C * C * k * (double)T, 14 + (C == 32 ? 1 : 5), bytes, &pa, (long long)p.grid.x, 3 | (7 << 4));
   }
-  return true;
 }
 
 }  // namespace rvc

@@ -282,29 +282,23 @@ static void launch_rbh2(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s
   conv_launch(kern, grid, dim3(512), lds, s, a);
 }
 template <int KT>
-static void launch_rbh(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (a.accumulate) launch_rbh2<KT, true>(a, grid, lds, s); else launch_rbh2<KT, false>(a, grid, lds, s);
-}
+static ConvLaunchFn select_rbh(const ConvArgsX& a) { return a.accumulate ? &launch_rbh2<KT, true> : &launch_rbh2<KT, false>; }
 
-// a: the fused pair's arguments as conv_x3_pair_try prepared them, with Wx / Wx2 = the two layers' ONE-plane fp16 images (ConvLayer::Wh_).  32 channels,
+// p.a: the fused pair's arguments as conv_x3_pair_plan prepared them, with Wx / Wx2 = the two layers' ONE-plane fp16 images (ConvLayer::Wh_).  32 channels,
 // 3 / 7 / 11 taps, a sequence of at least two rounds of tiles; false: not this kernel's (conv_x3pf_kernel takes the pair in bf16x3).
-bool conv_rbh_try(ConvArgsX& a, int T, hipStream_t s, dim3& grid_out, bool dry) {
+bool conv_rbh_plan(ConvPlan& p, int T) {
+  ConvArgsX& a = p.a;
   if (a.Ci != 32 || a.Co != 32 || !(a.ktaps == 3 || a.ktaps == 7 || a.ktaps == 11) || a.CoPx < 32) return false;
   const int BN = 512, NO = BN - (a.ktaps - 1);
   const int P = BN + (a.ktaps - 1) * a.dil;
   if (P > 576 || a.dil < 1) return false;
-  int dev = 0, ncu = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (ncu <= 0) ncu = 256;
+  const int ncu = device_cu_count();
   const long long ntiles = ((long long)T + NO - 1) / NO;
   if (ntiles < 2LL * ncu) return false;                       // short sequences: conv_x3pf_kernel's smaller tiles fill the chip better
-  if (dry) return true;
   a.WROW = P; a.ni = (P + 63) / 64;
-  const size_t lds = (size_t)2 * (2 * a.ktaps) * 2 * 32 * 16 + 256 + (size_t)2 * 2 * P * 32;
-  dim3 grid((unsigned)(ntiles < ncu ? ntiles : ncu), 1, 1);
-  grid_out = grid;
-  if (a.ktaps == 3) launch_rbh<3>(a, grid, lds, s); else if (a.ktaps == 7) launch_rbh<7>(a, grid, lds, s); else launch_rbh<11>(a, grid, lds, s);
+  p.lds = (size_t)2 * (2 * a.ktaps) * 2 * 32 * 16 + 256 + (size_t)2 * 2 * P * 32;
+  p.grid = dim3((unsigned)(ntiles < ncu ? ntiles : ncu), 1, 1);
+  p.launch = a.ktaps == 3 ? select_rbh<3>(a) : (a.ktaps == 7 ? select_rbh<7>(a) : select_rbh<11>(a));
   return true;
 }
 

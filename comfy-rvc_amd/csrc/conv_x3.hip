@@ -48,7 +48,7 @@ void conv_x3_timing_read(unsigned long long* out8, bool reset) {
 // ReLU, zero outside the sequence = the second conv's zero padding) are split and written over the input tile in LDS in the
 // same row format; pass 2 runs the stage loop of the second conv (dilation 1) on those rows and the ordinary epilogue stores the
 // BN - (k - 1) columns that have their full halo.  The intermediate tensor never goes to HBM: x (tile + residual) and y instead of
-// x, t, t, x, y.  Used for the 32-channel generator stage (conv_x3_pair_try): k3 261 -> 196 us, k7 304 -> 233, k11 348 -> 308.
+// x, t, t, x, y.  Used for the 32-channel generator stage (conv_x3_pair_plan): k3 261 -> 196 us, k7 304 -> 233, k11 348 -> 308.
 // XSPLIT: the input arrives as a split-resident image (ConvEpilogue::xs_in) and is copied into LDS by DMA; no staging registers.
 // YSPLIT: the output is written as a split-resident image (ConvEpilogue::ys_out) - separate instantiations, so that the plain kernels keep
 // their register budgets (the 128 x 128 tile its three workgroups per CU).
@@ -486,7 +486,38 @@ static void launch_x3(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s) 
   conv_launch(kern, grid, dim3(WM * WN * 64), lds, s, a);
 }
 
-bool conv_x3_try(ConvArgsX& a0, int batch, hipStream_t s, double flops, bool dry) {
+template <int AM, int AN>
+static ConvLaunchFn select_x3_io(const ConvArgsX& a) {
+  if (a.Xs) return &launch_x3<2, 2, AM, AN, false, true>;
+  if (a.Ys) return &launch_x3<2, 2, AM, AN, false, false, true>;
+  return &launch_x3<2, 2, AM, AN>;
+}
+static ConvLaunchFn select_x3(const ConvArgsX& a, int id) {
+  switch (id) {
+    case 0: return &launch_x3<1, 4, 1, 4>;
+    case 1: return &launch_x3<1, 4, 1, 2>;
+    case 2: return &launch_x3<1, 4, 1, 1>;
+    case 3: return select_x3_io<2, 2>(a);
+    case 4: return select_x3_io<1, 4>(a);
+    case 5: return &launch_x3<2, 2, 1, 2>;
+    case 7: return select_x3_io<2, 4>(a);
+    default: return &launch_x3<2, 2, 1, 1>;
+  }
+}
+
+void conv_plan_launch(const ConvPlan& p, hipStream_t s) {
+  ConvArgsX a = p.a;
+  // (the caller's buffers, not eligibility)
+  if (a.Xs) RVC_REQUIRE(a.xsTp >= split_image_tp(a.Tin), "split-resident input image is shorter than split_image_tp(T)");
+  if (a.Ys) RVC_REQUIRE(a.ysTp >= split_image_tp(a.Tout), "split-resident output image is shorter than split_image_tp(T)");
+  if (a.ksplit > 1) a.partial = (float*)stream_scratch(s, 0, (size_t)a.ksplit * a.Co * a.ldP * sizeof(float));
+  ProfTicket tk = conv_prof_begin(s);
+  p.launch(a, p.grid, p.lds, s);
+  if (a.ksplit > 1) splitk_reduce_launch(a, a.ksplit, 1, s);
+  conv_prof_end(tk, s, p.flops, p.prof_cfg, p.alg_bytes, &a, (long long)p.grid.x * p.grid.y * p.grid.z, p.prof_fused);
+}
+
+bool conv_x3_plan(const ConvArgsX& a0, int batch, ConvPlan& p) {
   if (!a0.Wx) return false;
   const bool xs = a0.Xs != nullptr;
   if ((xs || a0.Ys) && (a0.Wd > 0 || a0.stride != 1 || a0.ostride != 1 || (a0.Co & 31) || batch != 1)) return false;
@@ -494,26 +525,20 @@ bool conv_x3_try(ConvArgsX& a0, int batch, hipStream_t s, double flops, bool dry
   // the image's rows are addressed as margin + t (global_load_lds is not bounds-checked): "same" convolutions whose left halo fits the
   // margin only, on an image with the documented number of rows per plane
   if ((xs || a0.Ys) && (a0.pad > kSplitMargin || a0.Tout != a0.Tin)) return false;
-  if (!dry && xs) RVC_REQUIRE(a0.xsTp >= split_image_tp(a0.Tin), "split-resident input image is shorter than split_image_tp(T)");
-  if (!dry && a0.Ys) RVC_REQUIRE(a0.ysTp >= split_image_tp(a0.Tout), "split-resident output image is shorter than split_image_tp(T)");
   const int KH2 = a0.KW > 0 ? a0.KH : 3, KW2 = a0.KW > 0 ? a0.KW : 3;
   if (a0.Wd > 0 && (a0.ktaps != KH2 * KW2 || a0.stride != 1)) return false;
   if ((a0.stride != 1 && a0.dil != 1) || a0.up2 || (a0.ostride != 1 && a0.R) || (a0.Ci & 15) || batch != 1) return false;
   if (!(a0.act == ACT_NONE || a0.act == ACT_LRELU || a0.act == ACT_RELU) || !(a0.pre_act == ACT_NONE || a0.pre_act == ACT_LRELU)) return false;
   if ((double)a0.orows * (double)a0.ldY * 4.0 >= 2147483648.0 || (double)a0.orows * (double)a0.ldR * 4.0 >= 2147483648.0 ||
       (double)a0.Ci * (double)a0.ldX * 4.0 >= 2147483648.0) return false;
-  ConvArgsX a = a0;
+  p = ConvPlan{};
+  ConvArgsX& a = p.a;
+  a = a0;
   if (a.Wd == 0) a.ktaps = a0.kreal;                      // true taps (the fp32 kernel folds the stride phases into virtual channels)
+  auto planned = [&](int cfg, int fused) { p.prof_cfg = cfg; p.prof_fused = fused; p.alg_bytes = conv_alg_bytes(a, batch); return true; };
   if (batch == 1 && a.up2 == 0 && !a.h2) {
     // k = 1, the 3 x 3 convolutions of small images and short 1-D sequences: the pipelined GEMM kernel (conv_x3p.hip)
-    dim3 g; int S = 1;
-    if (conv_x3g_try(a, s, g, S, true)) {
-      if (dry) return true;
-      ProfTicket tk = conv_prof_begin(s);
-      conv_x3g_try(a, s, g, S, false);
-      conv_prof_end(tk, s, flops, 14 + ((a.Co > 64 && a.Ci * a.ktaps > 1024) ? 3 : 5), conv_alg_bytes(a, batch), &a, (long long)g.x * g.y * g.z, 2 << 4);
-      return true;
-    }
+    if (conv_x3g_plan(p)) return planned(14 + ((a.Co > 64 && a.Ci * a.ktaps > 1024) ? 3 : 5), 2 << 4);
   }
   TileCfg t = choose_tile(a.Co, a.Tout, batch);
   {
@@ -545,27 +570,13 @@ bool conv_x3_try(ConvArgsX& a0, int batch, hipStream_t s, double flops, bool dry
   if (nblk < (a.Wd > 0 ? min_blk2d : min_blk)) return false;   // under-filled grids go to the fp32 kernel's split-K path
   if (t.WM == 2 && t.WN == 2 && batch == 1) {
     // the generator's stride-1 convolutions: software-pipelined kernel (conv_x3p.hip)
-    dim3 g;
     // (the stride-2 mode exists for 128 x 128 tiles only: a shorter layer that would take 64-row tiles uses it as long as >= 150 tiles remain)
     const bool s2_up = a.stride == 2 && a.ktaps == 3 && a.Co >= 128 && !(t.AM == 2 && t.AN == 2) &&
                        (long long)((a.Co + 127) / 128) * ((a.Tout + 127) / 128) >= 150;
     const int pam = s2_up ? 2 : t.AM, pan = s2_up ? 2 : t.AN;
-    if (!s2_up && conv_x3q_try(a, t.AM, t.AN, s, g, true)) {
-      // the ResBlock convolutions: persistent workgroups (conv_x3q.hip)
-      if (dry) return true;
-      ProfTicket tk = conv_prof_begin(s);
-      RVC_REQUIRE(conv_x3q_try(a, t.AM, t.AN, s, g, false), "conv_x3q_try accepted the layer in its dry run and declined the launch");
-      conv_prof_end(tk, s, flops, 14 + id, conv_alg_bytes(a, batch), &a, (long long)g.x * g.y, 6 << 4);
-      return true;
-    }
+    if (!s2_up && conv_x3q_plan(p, t.AM, t.AN)) return planned(14 + id, 6 << 4);   // the ResBlock convolutions: persistent workgroups (conv_x3q.hip)
     if (a.h2) return false;                                  // fp16x2 images are the persistent kernel's alone
-    if (conv_x3p_try(a, pam, pan, s, g, true)) {
-      if (dry) return true;
-      ProfTicket tk = conv_prof_begin(s);
-      RVC_REQUIRE(conv_x3p_try(a, pam, pan, s, g, false), "conv_x3p_try accepted the layer in its dry run and declined the launch");
-      conv_prof_end(tk, s, flops, 14 + (s2_up ? 3 : id), conv_alg_bytes(a, batch), &a, (long long)g.x * g.y, 1 << 4);
-      return true;
-    }
+    if (conv_x3p_plan(p, pam, pan)) return planned(14 + (s2_up ? 3 : id), 1 << 4);
   }
   if (a.h2) return false;
   static const int x3_split_blk = exp_int("RVC_X3_SPLITK_BLK", 600);
@@ -608,10 +619,8 @@ bool conv_x3_try(ConvArgsX& a0, int batch, hipStream_t s, double flops, bool dry
   if (ktmax > a.ktaps) ktmax = a.ktaps;
   const int ntb = (a.ktaps + ktmax - 1) / ktmax;
   a.KT = (a.ktaps + ntb - 1) / ntb;                        // balanced tap blocks
-  if (dry) return true;
   a.CK = 16; a.nchunk = nchunk; a.NC = NC; a.WROW = P; a.xbufs = xbufs; a.ksplit = 1; a.partial = nullptr;
-  static const int xcd_env = exp_int("RVC_X3_XCD", 1);
-  a.wbufs = NS; a.xcd_remap = xcd_env;
+  a.wbufs = NS; a.xcd_remap = x3_xcd_remap();
   // split-K (k = 1 GEMMs on small grids): every stage of such a workgroup is a dependent global -> LDS round trip, so slicing the
   // reduction over S workgroups shortens the chain and puts more of them on a CU; partials are reduced in a fixed order
   int S = 1;
@@ -627,44 +636,17 @@ bool conv_x3_try(ConvArgsX& a0, int batch, hipStream_t s, double flops, bool dry
     while (S > 1 && ((ngroups + S - 1) / S) * (S - 1) >= ngroups) --S;
   }
   a.ksplit = S; a.ldP = (a.Tout + 31) & ~31;
-  if (S > 1) a.partial = (float*)stream_scratch(s, 0, (size_t)S * a.Co * a.ldP * sizeof(float));
-  const size_t lds = (size_t)xbytes + (size_t)NS * NC * a.KT * 2 * BM * 32;
-  dim3 grid((unsigned)((a.Tout + BN - 1) / BN), (unsigned)((a.Co + BM - 1) / BM), (unsigned)S);
-  ProfTicket tk = conv_prof_begin(s);
-  if (xs) {
-    switch (id) {
-      case 3: launch_x3<2, 2, 2, 2, false, true>(a, grid, lds, s); break;
-      case 4: launch_x3<2, 2, 1, 4, false, true>(a, grid, lds, s); break;
-      default: launch_x3<2, 2, 2, 4, false, true>(a, grid, lds, s); break;
-    }
-  } else if (a.Ys) {
-    switch (id) {
-      case 3: launch_x3<2, 2, 2, 2, false, false, true>(a, grid, lds, s); break;
-      case 4: launch_x3<2, 2, 1, 4, false, false, true>(a, grid, lds, s); break;
-      default: launch_x3<2, 2, 2, 4, false, false, true>(a, grid, lds, s); break;
-    }
-  } else
-  switch (id) {
-    case 0: launch_x3<1, 4, 1, 4>(a, grid, lds, s); break;
-    case 1: launch_x3<1, 4, 1, 2>(a, grid, lds, s); break;
-    case 2: launch_x3<1, 4, 1, 1>(a, grid, lds, s); break;
-    case 3: launch_x3<2, 2, 2, 2>(a, grid, lds, s); break;
-    case 4: launch_x3<2, 2, 1, 4>(a, grid, lds, s); break;
-    case 5: launch_x3<2, 2, 1, 2>(a, grid, lds, s); break;
-    case 7: launch_x3<2, 2, 2, 4>(a, grid, lds, s); break;
-    default: launch_x3<2, 2, 1, 1>(a, grid, lds, s); break;
-  }
-  if (S > 1) splitk_reduce_launch(a, S, 1, s);
-  conv_prof_end(tk, s, flops, 14 + id, conv_alg_bytes(a, batch), &a, (long long)grid.x * grid.y * grid.z);
-  return true;
+  p.lds = (size_t)xbytes + (size_t)NS * NC * a.KT * 2 * BM * 32;
+  p.grid = dim3((unsigned)((a.Tout + BN - 1) / BN), (unsigned)((a.Co + BM - 1) / BM), (unsigned)S);
+  p.launch = select_x3(a, id);
+  return planned(14 + id, 0);
 }
 
 // ---------------------------------------------------------------------------- fused ResBlock pair (narrow generator stages)
 // The C = 32 stage of the generator is HBM-bound on the unfused kernels (each conv reads + writes [C][T] and the second one reads the
 // residual too: 5 tensor passes per pair); fused, a pair reads x (+ halo) twice (tile + residual, the second from L2) and writes y.
-// dry_only: answers whether the pair would run in the fp16x2 arithmetic on the LDS-resident-weights kernel (nothing is launched)
-bool conv_x3_pair_try(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, const float* X, long long ldX, int T, float* Y, long long ldY,
-                      const ConvEpilogue& e2, bool dry_only) {
+bool conv_x3_pair_plan(const ConvLayer& c1, const ConvLayer& c2, const float* X, long long ldX, int T, float* Y, long long ldY, const ConvEpilogue& e2, int h2,
+                       ConvPlan& p) {
   if (!c1.Wx_ || !c2.Wx_) return false;
   const int C = c1.Co, k = c1.k;
   if (c1.mode != 1 || c2.mode != 1 || c1.groups != 1 || c2.groups != 1 || c1.stride != 1 || c2.stride != 1 || c1.tconv_u || c2.tconv_u) return false;
@@ -677,7 +659,8 @@ bool conv_x3_pair_try(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, c
   const int P2 = (k - 1) / 2, P1 = c1.pad;
   const int NO = BN - 2 * P2;
   if ((long long)(T + NO - 1) / NO < 512) return false;          // short sequences: the unfused path fills the chip better
-  ConvArgsX a{};
+  p = ConvPlan{};
+  ConvArgsX& a = p.a;
   a.X = X; a.ldX = ldX; a.Y = Y; a.ldY = ldY; a.W = nullptr; a.bias = c2.bd_; a.bias1 = c1.bd_;
   a.R = e2.R; a.ldR = e2.ldR; a.pre_act = ACT_LRELU; a.pre_slope = 0.1f; a.fuse_slope = e2.pre_slope;
   a.act = ACT_NONE; a.act_slope = 0.f; a.act_before_res = 0; a.out_scale = e2.out_scale; a.accumulate = e2.accumulate;
@@ -687,35 +670,21 @@ bool conv_x3_pair_try(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, c
   a.Wx = reinterpret_cast<const unsigned char*>(c1.Wx_); a.Wx2 = reinterpret_cast<const unsigned char*>(c2.Wx_); a.CoPx = c1.CoPx;
   a.fuse_p2 = P2;
   if (c1.CoPx != c2.CoPx) return false;
-  if (C == 32 && c1.Wh_ && c2.Wh_ && conv_set_pair_arithmetic(-1)) {
+  // algorithmic traffic of the pair: x read ONCE (the residual is x itself: one tensor), y write (+ previous y when accumulating) + both weight sets
+  p.alg_bytes = 4.0 * ((double)C * T * (2.0 + (e2.accumulate ? 1.0 : 0.0)) + 2.0 * C * C * k);
+  p.flops = 2.0 * 2.0 * (double)C * C * k * T;
+  auto planned = [&](int cfg, int fused) { p.prof_cfg = cfg; p.prof_fused = fused; return true; };
+  if (C == 32 && c1.Wh_ && c2.Wh_ && h2) {
     // fp16x2 pair arithmetic: persistent workgroups with both weight sets resident in LDS (conv_rbh.hip)
-    ConvArgsX h = a;
-    h.Wx = reinterpret_cast<const unsigned char*>(c1.Wh_); h.Wx2 = reinterpret_cast<const unsigned char*>(c2.Wh_); h.h2 = 1;
-    dim3 gh;
-    if (conv_rbh_try(h, T, s, gh, true)) {
-      if (dry_only) return true;
-      ProfTicket tk = conv_prof_begin(s);
-      RVC_REQUIRE(conv_rbh_try(h, T, s, gh, false), "conv_rbh_try accepted the pair in its dry run and declined the launch");
-      const double bytes = 4.0 * ((double)C * T * (2.0 + (e2.accumulate ? 1.0 : 0.0)) + 2.0 * C * C * k);
-      conv_prof_end(tk, s, 2.0 * 2.0 * (double)C * C * k * T, 14 + 1, bytes, &h, (long long)gh.x, 1 | (5 << 4));
-      return true;
-    }
+    const ConvArgsX b = a;
+    a.Wx = reinterpret_cast<const unsigned char*>(c1.Wh_); a.Wx2 = reinterpret_cast<const unsigned char*>(c2.Wh_); a.h2 = 1;
+    if (conv_rbh_plan(p, T)) return planned(14 + 1, 1 | (5 << 4));
+    a = b;
   }
-  if (dry_only) return false;
-  {
-    // the software-pipelined fused pair (conv_x3p.hip): 32 and 64 channels
-    static const int xcd_env = exp_int("RVC_X3_XCD", 1);
-    a.xcd_remap = xcd_env;
-    dim3 gpf;
-    if (conv_x3pf_try(a, T, s, gpf, true)) {
-      ProfTicket tk = conv_prof_begin(s);
-      conv_x3pf_try(a, T, s, gpf, false);
-      const double bytes = 4.0 * ((double)C * T * (2.0 + (e2.accumulate ? 1.0 : 0.0)) + 2.0 * C * C * k);   // x ONCE (the residual is the same tensor), y [, previous y]
-      conv_prof_end(tk, s, 2.0 * 2.0 * (double)C * C * k * T, 14 + (C == 32 ? 1 : 5), bytes, &a, (long long)gpf.x, 1 | (3 << 4));
-      return true;
-    }
-    if (C == 64) return false;                                   // (the staged pair at 64 channels was measured and not kept)
-  }
+  // the software-pipelined fused pair (conv_x3p.hip): 32 and 64 channels
+  a.xcd_remap = x3_xcd_remap();
+  if (conv_x3pf_plan(p, T)) return planned(14 + (C == 32 ? 1 : 5), 1 | (3 << 4));
+  if (C == 64) return false;                                     // (the staged pair at 64 channels was measured and not kept)
   const int P = BN + 2 * P1;                                      // staged input columns
   a.ni = (P + 63) / 64;
   const int nchunk = C / 16, NC = nchunk;                         // every channel of the tile resident: one chunk group
@@ -731,16 +700,11 @@ bool conv_x3_pair_try(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, c
   const int ntb = (k + ktmax - 1) / ktmax;
   a.KT = (k + ntb - 1) / ntb;
   a.CK = 16; a.nchunk = nchunk; a.NC = NC; a.WROW = P; a.xbufs = 1; a.ksplit = 1; a.partial = nullptr; a.ldP = 0;
-  static const int xcd_env = exp_int("RVC_X3_XCD", 1);
-  a.wbufs = 2; a.xcd_remap = xcd_env;
-  const size_t lds = (size_t)xbytes + (size_t)2 * NC * a.KT * 2 * BM * 32;
-  dim3 grid((unsigned)((T + NO - 1) / NO), 1, 1);
-  ProfTicket tk = conv_prof_begin(s);
-  launch_x3<1, 4, 1, 2, true>(a, grid, lds, s);                 // 32 channels, 256 columns
-  // algorithmic traffic of the pair: x read (the residual is x itself: one tensor, counted once), y write (+ previous y when accumulating) + both weight sets
-  const double bytes = 4.0 * ((double)C * T * (2.0 + (e2.accumulate ? 1.0 : 0.0)) + 2.0 * C * C * k);   // x ONCE (the residual is the same tensor), y [, previous y]
-  conv_prof_end(tk, s, 2.0 * 2.0 * (double)C * C * k * T, 14 + 1, bytes, &a, (long long)grid.x, 1);
-  return true;
+  a.wbufs = 2;
+  p.lds = (size_t)xbytes + (size_t)2 * NC * a.KT * 2 * BM * 32;
+  p.grid = dim3((unsigned)((T + NO - 1) / NO), 1, 1);
+  p.launch = &launch_x3<1, 4, 1, 2, true>;                      // 32 channels, 256 columns
+  return planned(14 + 1, 1);
 }
 
 }  // namespace rvc

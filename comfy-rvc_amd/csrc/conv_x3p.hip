@@ -929,21 +929,22 @@ static void launch_x3p(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s)
   conv_launch(kern, grid, dim3(256), lds, s, a);
 }
 template <int AM, int AN, int KT>
-static void launch_x3p_io(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (a.Xs) launch_x3p<AM, AN, KT, true, false>(a, grid, lds, s);
-  else if (a.Ys) launch_x3p<AM, AN, KT, false, true>(a, grid, lds, s);
-  else launch_x3p<AM, AN, KT, false, false>(a, grid, lds, s);
+static ConvLaunchFn select_x3p_io(const ConvArgsX& a) {
+  if (a.Xs) return &launch_x3p<AM, AN, KT, true, false>;
+  if (a.Ys) return &launch_x3p<AM, AN, KT, false, true>;
+  return &launch_x3p<AM, AN, KT, false, false>;
 }
 template <int AM, int AN>
-static void launch_x3p_k(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (a.ktaps == 3) launch_x3p_io<AM, AN, 3>(a, grid, lds, s);
-  else if (a.ktaps == 7) launch_x3p_io<AM, AN, 7>(a, grid, lds, s);
-  else launch_x3p_io<AM, AN, 11>(a, grid, lds, s);
+static ConvLaunchFn select_x3p_k(const ConvArgsX& a) {
+  if (a.ktaps == 3) return select_x3p_io<AM, AN, 3>(a);
+  if (a.ktaps == 7) return select_x3p_io<AM, AN, 7>(a);
+  return select_x3p_io<AM, AN, 11>(a);
 }
 
-// a: arguments as conv_x3_try prepared them (true taps, tile chosen: WM = WN = 2).  Returns false when the geometry is not the
+// p.a: arguments as conv_x3_plan prepared them (true taps, tile chosen: WM = WN = 2).  Returns false when the geometry is not the
 // pipelined kernel's (the staged kernel takes it): kernel sizes 3 / 7 / 11 (the generator's), at least three 16-channel chunks.
-bool conv_x3p_try(ConvArgsX& a, int AM, int AN, hipStream_t s, dim3& grid_out, bool dry) {
+bool conv_x3p_plan(ConvPlan& p, int AM, int AN) {
+  ConvArgsX& a = p.a;
   const bool xs = a.Xs != nullptr, ys = a.Ys != nullptr;
   if (a.Wd > 0 || (a.Ci & 15) || a.Ci < 48 || (xs && ys)) return false;
   // stride 2: the k = 3 layers of HuBERT's feature encoder on 128 x 128 tiles
@@ -962,16 +963,14 @@ bool conv_x3p_try(ConvArgsX& a, int AM, int AN, hipStream_t s, dim3& grid_out, b
   const int R = (AM == 2 && AN == 4) ? RVC_X3P_R24 : 3;
   const size_t lds = (size_t)xbytes + (size_t)R * wslot;
   if (lds > (size_t)(AM * AN >= 8 || s2 ? 80 : 53) * 1024) return false;   // two / three workgroups per CU
-  if (dry) return true;
   a.WROW = P; a.ni = (P + 63) / 64; a.nchunk = a.Ci / 16; a.NC = 1; a.KT = 1; a.xbufs = 2; a.ksplit = 1; a.partial = nullptr; a.wbufs = R;
-  static const int xcd_env = exp_int("RVC_X3_XCD", 1);
-  a.xcd_remap = xcd_env;
-  dim3 grid((unsigned)((a.Tout + BN - 1) / BN), (unsigned)((a.Co + BM - 1) / BM), 1);
-  grid_out = grid;
-  if (s2) launch_x3p<2, 2, 3, false, false, true>(a, grid, lds, s);
-  else if (AM == 2 && AN == 4) launch_x3p_k<2, 4>(a, grid, lds, s);
-  else if (AM == 1 && AN == 4) launch_x3p_k<1, 4>(a, grid, lds, s);
-  else launch_x3p_k<2, 2>(a, grid, lds, s);
+  a.xcd_remap = x3_xcd_remap();
+  p.grid = dim3((unsigned)((a.Tout + BN - 1) / BN), (unsigned)((a.Co + BM - 1) / BM), 1);
+  p.lds = lds;
+  if (s2) p.launch = &launch_x3p<2, 2, 3, false, false, true>;
+  else if (AM == 2 && AN == 4) p.launch = select_x3p_k<2, 4>(a);
+  else if (AM == 1 && AN == 4) p.launch = select_x3p_k<1, 4>(a);
+  else p.launch = select_x3p_k<2, 2>(a);
   return true;
 }
 
@@ -983,8 +982,9 @@ static void launch_x3g(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s)
 }
 
 // k = 1 convolutions (GEMMs) on the pipelined kernel: fp32 [K][N] input, K a multiple of 64 and >= 128.  Small grids are split over K
-// (deterministic second pass: splitk_reduce_launch).  Returns false when the geometry is not this kernel's.
-bool conv_x3g_try(ConvArgsX& a, hipStream_t s, dim3& grid_out, int& ksplit_out, bool dry) {
+// (deterministic second pass: splitk_reduce_launch, run by conv_plan_launch).  Returns false when the geometry is not this kernel's.
+bool conv_x3g_plan(ConvPlan& p) {
+  ConvArgsX& a = p.a;
   // 2-D: 3 x 3, pad 1, plain (no 2 x 2 up-sampling interleave), on images small enough that the nine shifted reads come from L2
   static const int max2d = exp_int("RVC_X3G_2D_MAXPOS", 30000);
   const bool two_d = a.Wd > 0;
@@ -1011,17 +1011,13 @@ bool conv_x3g_try(ConvArgsX& a, hipStream_t s, dim3& grid_out, int& ksplit_out, 
     if (nblk * S >= target) break;
     if (U % (4 * c) == 0 && U / c >= 8) S = c;
   }
-  if (dry) return true;
   a.nchunk = U; a.NC = 1; a.KT = 1; a.ksplit = S; a.xcd_remap = 0; a.wbufs = 3; a.xbufs = 3;
   a.ldP = (a.Tout + 31) & ~31; a.partial = nullptr;
-  if (S > 1) a.partial = (float*)stream_scratch(s, 0, (size_t)S * a.Co * a.ldP * sizeof(float));
-  const size_t lds = (size_t)3 * (2 * BN * 32) + (size_t)3 * (2 * BM * 32);
-  dim3 grid((unsigned)((a.Tout + BN - 1) / BN), (unsigned)((a.Co + BM - 1) / BM), (unsigned)S);
-  grid_out = grid; ksplit_out = S;
-  if (two_d) { if (AM == 2) launch_x3g<2, 2, 1>(a, grid, lds, s); else launch_x3g<1, 2, 1>(a, grid, lds, s); }
-  else if (taps1d) { if (AM == 2) launch_x3g<2, 2, 2>(a, grid, lds, s); else launch_x3g<1, 2, 2>(a, grid, lds, s); }
-  else if (AM == 2) launch_x3g<2, 2>(a, grid, lds, s); else launch_x3g<1, 2>(a, grid, lds, s);
-  if (S > 1) splitk_reduce_launch(a, S, 1, s);
+  p.lds = (size_t)3 * (2 * BN * 32) + (size_t)3 * (2 * BM * 32);
+  p.grid = dim3((unsigned)((a.Tout + BN - 1) / BN), (unsigned)((a.Co + BM - 1) / BM), (unsigned)S);
+  if (two_d) p.launch = AM == 2 ? &launch_x3g<2, 2, 1> : &launch_x3g<1, 2, 1>;
+  else if (taps1d) p.launch = AM == 2 ? &launch_x3g<2, 2, 2> : &launch_x3g<1, 2, 2>;
+  else p.launch = AM == 2 ? &launch_x3g<2, 2> : &launch_x3g<1, 2>;
   return true;
 }
 
@@ -1031,9 +1027,10 @@ static void launch_x3pf(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s
   RVC_ALLOW_BIG_LDS(kern);
   conv_launch(kern, grid, dim3(256), lds, s, a);
 }
-// a: the fused pair's arguments as conv_x3_pair_try prepared them (C = 32: 256 intermediate columns per tile; C = 64: 128).  false: not
+// p.a: the fused pair's arguments as conv_x3_pair_plan prepared them (C = 32: 256 intermediate columns per tile; C = 64: 128).  false: not
 // this kernel's geometry.
-bool conv_x3pf_try(ConvArgsX& a, int T, hipStream_t s, dim3& grid_out, bool dry) {
+bool conv_x3pf_plan(ConvPlan& p, int T) {
+  ConvArgsX& a = p.a;
   if (!(a.Ci == 32 || a.Ci == 64) || a.Co != a.Ci || !(a.ktaps == 3 || a.ktaps == 7 || a.ktaps == 11)) return false;
   const int C = a.Ci, BN = C == 32 ? 256 : 128;
   // 64 channels: the narrow wave tile (32 rows: one operand read per MFMA) only wins where the pair is HBM-bound - k = 3: 220 -> 151 us;
@@ -1044,13 +1041,11 @@ bool conv_x3pf_try(ConvArgsX& a, int T, hipStream_t s, dim3& grid_out, bool dry)
   if (P > BN + 64) return false;
   const int NO = BN - (a.ktaps - 1);
   if ((long long)(T + NO - 1) / NO < 512) return false;          // short sequences: the unfused path fills the chip better
-  if (dry) return true;
   a.WROW = P; a.ni = (P + 63) / 64;
-  const size_t lds = (size_t)(((C / 16) * 2 * P * 32 + 1023) & ~1023) + 4 * (size_t)(2 * C * 32);
-  dim3 grid((unsigned)((T + NO - 1) / NO), 1, 1);
-  grid_out = grid;
-  if (C == 32) { if (a.ktaps == 3) launch_x3pf<3, 1>(a, grid, lds, s); else if (a.ktaps == 7) launch_x3pf<7, 1>(a, grid, lds, s); else launch_x3pf<11, 1>(a, grid, lds, s); }
-  else launch_x3pf<3, 2>(a, grid, lds, s);
+  p.lds = (size_t)(((C / 16) * 2 * P * 32 + 1023) & ~1023) + 4 * (size_t)(2 * C * 32);
+  p.grid = dim3((unsigned)((T + NO - 1) / NO), 1, 1);
+  if (C == 32) p.launch = a.ktaps == 3 ? &launch_x3pf<3, 1> : (a.ktaps == 7 ? &launch_x3pf<7, 1> : &launch_x3pf<11, 1>);
+  else p.launch = &launch_x3pf<3, 2>;
   return true;
 }
 

@@ -1,6 +1,6 @@
 // Persistent split-MFMA Conv1d for the generator's stride-1 ResBlock convolutions (gfx950 only), in two arithmetics: bf16x3 (three bf16 MFMAs
 // per product: hi_w lo_x + hi_w hi_x + lo_w hi_x) and fp16x2 (H2: two fp16 MFMAs, w lo_x + w hi_x with the weight as ONE fp16 term and the
-// activation as fp16 hi + lo - see the note above conv_x3q_try for what that costs in accuracy and why it is only offered to ResBlock pairs).
+// activation as fp16 hi + lo - see the note above conv_x3q_plan for what that costs in accuracy and why it is only offered to ResBlock pairs).
 //
 // conv_x3p_kernel (conv_x3p.hip) made the WAVE a pipeline; its tiles still were separate workgroups.  Per-phase cycle counters of that kernel
 // (profiles/r4a_x3p_phase_cycles.txt: C128 k11, 128 x 256 tiles) show what that costs: of 227 k cycles per tile 33 k are the prologue (all 512
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
           if (c0 && T < R - 2) { if (it > 0) X3Q_CHECK(NWT + EP, exact); q_wait<NWT + EP>(); }
           else { X3Q_CHECK(NWT, exact); q_wait<NWT>(); }
           // the split-resident chunk this unit's tail starts to read (requested one chunk ago, right behind that unit's weight request) is covered by the
-          // same wait as long as the weight request waited for is not older than it: R - 2 <= KT - 1 (conv_x3q_try clamps the ring for 3-tap layers)
+          // same wait as long as the weight request waited for is not older than it: R - 2 <= KT - 1 (conv_x3q_plan clamps the ring for 3-tap layers)
           static_assert(!XSPLIT || R - 2 <= KT - 1, "weight ring deeper than a chunk: the input chunk's DMA would not be covered by the weight wait");
           if constexpr (XSPLIT && last_tap) { if (it > 0 || c > 0) X3Q_CHECK(NWT, issued - mk_xs[xb ^ 1]); }
           [[maybe_unused]] const long long tb = XQTICK();
@@ -574,33 +574,27 @@ static void launch_x3q(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s)
   conv_launch(kern, grid, dim3(256), lds, s, a);
 }
 template <int AM, int AN, int KT, int R>
-static void launch_x3q_io(const ConvArgsX& a, int mode, dim3 grid, size_t lds, hipStream_t s) {
-  constexpr bool c2_ok = R - 2 <= KT - 1;      // image in: the ring may not be deeper than a chunk (see the static_assert in the kernel; conv_x3q_try clamps R)
-  if (a.h2) {
-    if (mode == 0) launch_x3q<AM, AN, KT, R, false, true, false, true>(a, grid, lds, s);
-    else if constexpr (c2_ok) launch_x3q<AM, AN, KT, R, true, false, true, true>(a, grid, lds, s);
-  } else {
-    if (mode == 0) launch_x3q<AM, AN, KT, R, false, true, false, false>(a, grid, lds, s);      // fp32 in, image out (c1 of a split pair)
-    else if constexpr (c2_ok) launch_x3q<AM, AN, KT, R, true, false, true, false>(a, grid, lds, s);   // image in, fp32 out + residual (c2 of a split pair)
-  }
-  if (mode != 0 && !c2_ok) throw Error("conv_x3q: weight ring deeper than a chunk on an image-in launch");
+static ConvLaunchFn select_x3q_io(const ConvArgsX& a, int mode) {
+  constexpr bool c2_ok = R - 2 <= KT - 1;      // image in: the ring may not be deeper than a chunk (see the static_assert in the kernel; conv_x3q_plan clamps R)
+  // mode 0: fp32 in, image out (c1 of a split pair); 1: image in, fp32 out + residual (c2 of a split pair)
+  if (mode == 0) return a.h2 ? &launch_x3q<AM, AN, KT, R, false, true, false, true> : &launch_x3q<AM, AN, KT, R, false, true, false, false>;
+  if constexpr (c2_ok) return a.h2 ? &launch_x3q<AM, AN, KT, R, true, false, true, true> : &launch_x3q<AM, AN, KT, R, true, false, true, false>;
+  throw Error("conv_x3q: weight ring deeper than a chunk on an image-in launch");
 }
 template <int AM, int AN, int R>
-static void launch_x3q_k(const ConvArgsX& a, int mode, dim3 grid, size_t lds, hipStream_t s) {
-  if (a.ktaps == 3) launch_x3q_io<AM, AN, 3, R>(a, mode, grid, lds, s);
-  else if (a.ktaps == 7) launch_x3q_io<AM, AN, 7, R>(a, mode, grid, lds, s);
-  else launch_x3q_io<AM, AN, 11, R>(a, mode, grid, lds, s);
+static ConvLaunchFn select_x3q_k(const ConvArgsX& a, int mode) {
+  if (a.ktaps == 3) return select_x3q_io<AM, AN, 3, R>(a, mode);
+  if (a.ktaps == 7) return select_x3q_io<AM, AN, 7, R>(a, mode);
+  return select_x3q_io<AM, AN, 11, R>(a, mode);
 }
 template <int AM, int AN>
-static void launch_x3q_r(const ConvArgsX& a, int R, int mode, dim3 grid, size_t lds, hipStream_t s) {
-  if constexpr (AM == 2 && AN == 4) {
-    if (R >= 5) launch_x3q_k<AM, AN, 5>(a, mode, grid, lds, s); else launch_x3q_k<AM, AN, 4>(a, mode, grid, lds, s);
-  } else {
-    if (R >= 5) launch_x3q_k<AM, AN, 5>(a, mode, grid, lds, s); else if (R == 4) launch_x3q_k<AM, AN, 4>(a, mode, grid, lds, s); else launch_x3q_k<AM, AN, 3>(a, mode, grid, lds, s);
-  }
+static ConvLaunchFn select_x3q_r(const ConvArgsX& a, int R, int mode) {
+  if (R >= 5) return select_x3q_k<AM, AN, 5>(a, mode);
+  if constexpr (AM == 2 && AN == 4) return select_x3q_k<AM, AN, 4>(a, mode);
+  else return R == 4 ? select_x3q_k<AM, AN, 4>(a, mode) : select_x3q_k<AM, AN, 3>(a, mode);
 }
 
-// a: arguments as conv_x3_try prepared them (true taps, tile chosen: WM = WN = 2).  Returns false when the layer is not this kernel's (the
+// p.a: arguments as conv_x3_plan prepared them (true taps, tile chosen: WM = WN = 2).  Returns false when the layer is not this kernel's (the
 // per-tile pipelined kernel of conv_x3p.hip takes it): the two halves of a split-resident ResBlock pair - stride-1 Conv1d with 3 / 7 / 11 taps,
 // whole row tiles, at least three 16-channel chunks, at least 8 tiles.
 //
@@ -610,7 +604,8 @@ static void launch_x3q_r(const ConvArgsX& a, int R, int mode, dim3 grid, size_t 
 // (tools/exp/fp16_weight_rounding.py): max 16 LSB / mean 2.2 on the 30 s golden (gate 33; bf16 weights: 142 / 16.9, which is what round 5
 // measured on the GPU for the bf16 2-term variant).  Only the pair convolutions of a residual branch are offered this arithmetic: their errors
 // enter the stage tensor additively beside the exact skip path.  fp16 range: hi saturates at 65504 (round toward zero), |x| < 131008 stays finite.
-bool conv_x3q_try(ConvArgsX& a, int AM, int AN, hipStream_t s, dim3& grid_out, bool dry) {
+bool conv_x3q_plan(ConvPlan& p, int AM, int AN) {
+  ConvArgsX& a = p.a;
   const bool xs = a.Xs != nullptr, ys = a.Ys != nullptr;
   if (a.Wd > 0 || (a.Ci & 15) || a.Ci < 48 || xs == ys || a.stride != 1 || a.ostride != 1 || a.orows != a.Co) return false;
   if (!(a.ktaps == 3 || a.ktaps == 7 || a.ktaps == 11)) return false;
@@ -640,13 +635,7 @@ bool conv_x3q_try(ConvArgsX& a, int AM, int AN, hipStream_t s, dim3& grid_out, b
   const size_t lds = fixed + (size_t)R * wslot;
   if (lds > budget) return false;
   const long long ntiles = (long long)((a.Tout + BN - 1) / BN) * (a.Co / BM);
-  // (per device: one process may drive several GPUs, and the persistent grid is sized by the CURRENT device's CU count)
-  static std::atomic<int> ncu_of[64];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64) dev = 0;
-  int ncu = ncu_of[dev].load(std::memory_order_relaxed);
-  if (ncu == 0) { int n = 256; (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); ncu = n > 0 ? n : 256; ncu_of[dev].store(ncu, std::memory_order_relaxed); }
+  const int ncu = device_cu_count();
   static const int wg_env = exp_int("RVC_X3Q_WGS", 0);     // workgroups per CU (0: what the tile's LDS / registers admit)
   // (RVC_X3Q_MINROUNDS: grids of fewer rounds of resident workgroups stay on the per-tile kernel.  Default 0: every eligible pair, also where a
   // workgroup owns a single tile - the 256-channel stage, short clips: measured neutral there against the per-tile kernel (C256 pairs 1018 -> 1008 us),
@@ -654,19 +643,16 @@ bool conv_x3q_try(ConvArgsX& a, int AM, int AN, hipStream_t s, dim3& grid_out, b
   static const int min_rounds = exp_int("RVC_X3Q_MINROUNDS", 0);
   const long long slots = (long long)(wg_env > 0 ? wg_env : per_cu) * ncu;
   if (ntiles < min_rounds * slots || ntiles < 8) return false;
-  // a multiple of 8 (a workgroup's later tiles stay on its XCD) unless every workgroup owns exactly one tile; decided before the dry-run answer and
-  // before `a` is touched, so that "yes" in the dry run is "launched" in the real call
+  // a multiple of 8 (a workgroup's later tiles stay on its XCD) unless every workgroup owns exactly one tile
   const long long G = ntiles <= slots ? ntiles : (slots & ~7LL);
   if (G < 8) return false;
-  if (dry) return true;
   a.WROW = P; a.ni = (P + 63) / 64; a.nchunk = a.Ci / 16; a.NC = 1; a.KT = 1; a.xbufs = 2; a.ksplit = 1; a.partial = nullptr; a.wbufs = R;
-  static const int xcd_env = exp_int("RVC_X3_XCD", 1);
-  a.xcd_remap = xcd_env;
-  dim3 grid((unsigned)G, 1, 1);
-  grid_out = grid;
-  if (AM == 2 && AN == 4) launch_x3q_r<2, 4>(a, R, mode, grid, lds, s);
-  else if (AM == 1 && AN == 4) launch_x3q_r<1, 4>(a, R, mode, grid, lds, s);
-  else launch_x3q_r<2, 2>(a, R, mode, grid, lds, s);
+  a.xcd_remap = x3_xcd_remap();
+  p.grid = dim3((unsigned)G, 1, 1);
+  p.lds = lds;
+  if (AM == 2 && AN == 4) p.launch = select_x3q_r<2, 4>(a, R, mode);
+  else if (AM == 1 && AN == 4) p.launch = select_x3q_r<1, 4>(a, R, mode);
+  else p.launch = select_x3q_r<2, 2>(a, R, mode);
   return true;
 }
 

@@ -786,8 +786,7 @@ void conv_x3s_run(const ConvLayer& L, hipStream_t s, const unsigned char* Xs, lo
   RVC_REQUIRE(L.CoPx % BM == 0, "weight image rows are padded to the tile");
   a.rows_pg = (L.Co + BM - 1) / BM;
   a.gx = (T + BN - 1) / BN; a.gy = a.rows_pg * G; a.ksplit = S;
-  static const int xcd_env = exp_int("RVC_X3_XCD", 1);
-  a.xcd_remap = xcd_env;
+  a.xcd_remap = x3_xcd_remap();
   const unsigned blocks = (unsigned)((long long)a.gx * a.gy * S);
   if (S > 1) {
     // slabs + one ticket word per tile (zeroed when the scratch is first handed out and by every launch's last arriver)
@@ -842,8 +841,7 @@ void conv_x3s_run_swapped(const ConvLayer& L, int row0, int rows, hipStream_t s,
   const int BM = 64 * AM, BN = 64 * AN;
   RVC_REQUIRE((long long)((T + BM - 1) / BM) * BM <= xsTp - kSplitMargin && (long long)row0 + (long long)((rows + BN - 1) / BN) * BN <= L.CoPx, "conv_x3s_run_swapped: a tile would read past an operand image");
   a.rows_pg = (T + BM - 1) / BM; a.gx = (rows + BN - 1) / BN; a.gy = a.rows_pg; a.ksplit = 1;
-  static const int xcd_env = exp_int("RVC_X3_XCD", 1);
-  a.xcd_remap = xcd_env;
+  a.xcd_remap = x3_xcd_remap();
   const unsigned blocks = (unsigned)((long long)a.gx * a.gy);
   ProfTicket tk = conv_prof_begin(s);
   x3s_dispatch(a, AM, AN, blocks, s);

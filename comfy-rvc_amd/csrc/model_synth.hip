@@ -240,6 +240,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
                         const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps) {
   const int C = S->hidden, H = S->n_heads, kc = C / H, IC = S->inter;
   const bool dry = A.dry;
+  const int h2 = conv_set_pair_arithmetic(-1);      // read once: the whole pass plans with the pair arithmetic it saw when it started
   auto tap = [&](float* dst, const float* src, size_t n) {
     if (!dry && dst) RVC_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
   };
@@ -472,7 +473,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
     for (int j = 0; j < 3; ++j)
       for (int m = 0; m < 3; ++m) {
         split_pair[j][m] = conv1d_split_eligible(st.rb[j].c1[m], Tn, SPLIT_PRODUCER) && conv1d_split_eligible(st.rb[j].c2[m], Tn, SPLIT_CONSUMER);
-        h2_pair[j][m] = split_pair[j][m] && conv1d_pair_h2_eligible(st.rb[j].c1[m], st.rb[j].c2[m], Tn);
+        h2_pair[j][m] = split_pair[j][m] && conv1d_pair_h2_eligible(st.rb[j].c1[m], st.rb[j].c2[m], Tn, h2);
         any_split = any_split || split_pair[j][m];
       }
     unsigned char* t1s = any_split ? A.alloc<unsigned char>(split_image_bytes(Cc, Tn)) : nullptr;
@@ -484,13 +485,23 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
       conv1d_run(st.up, s, cur, Tc, Tc, up, Tn, Eu);
       ConvEpilogue En; En.accumulate = 1;
       // last stage (one tap of the source per position) with all three ResBlocks on conv_rb3_kernel: the noise term is added where x is read
-      bool noise_in_rb3 = S->f0 && st.noise_k == 1 && st.noise_w.p != nullptr && N == (long long)Tn;
-      for (int j = 0; j < 3 && noise_in_rb3; ++j) {
-        const ConvLayer* r1[3] = {&st.rb[j].c1[0], &st.rb[j].c1[1], &st.rb[j].c1[2]};
-        const ConvLayer* r2[3] = {&st.rb[j].c2[0], &st.rb[j].c2[1], &st.rb[j].c2[2]};
-        noise_in_rb3 = conv_rb3_try(r1, r2, s, up, Tn, Tn, xs, Tn, 0.1f, 1.f / 3.f, j > 0, true);
-      }
-      if (taps && i == 0) noise_in_rb3 = false;                  // (the gen_ups0 tap wants the summed tensor)
+      // (the gen_ups0 tap wants the summed tensor)
+      bool noise_in_rb3 = S->f0 && st.noise_k == 1 && st.noise_w.p != nullptr && N == (long long)Tn && !(taps && i == 0);
+      // 32- / 64-channel stages in the fp16x2 arithmetic: a whole ResBlock (three pairs) in one launch, x read once, the sum written once (conv_rb3.hip).
+      // Each ResBlock is planned once; the noise decision and the launches below use these same plans.
+      Rb3Plan rb3[3]; bool rb3_ok[3];
+      auto plan_rb3 = [&](bool noise) {
+        bool all = true;
+        for (int j = 0; j < 3; ++j) {
+          const ConvLayer* r1[3] = {&st.rb[j].c1[0], &st.rb[j].c1[1], &st.rb[j].c1[2]};
+          const ConvLayer* r2[3] = {&st.rb[j].c2[0], &st.rb[j].c2[1], &st.rb[j].c2[2]};
+          rb3_ok[j] = conv_rb3_plan(r1, r2, up, Tn, Tn, xs, Tn, 0.1f, 1.f / 3.f, j > 0, h2, noise ? har : nullptr, noise ? st.noise_w.p : nullptr,
+                                    noise ? st.noise_b.p : nullptr, rb3[j]);
+          all = all && rb3_ok[j];
+        }
+        return all;
+      };
+      if (!plan_rb3(noise_in_rb3) && noise_in_rb3) { noise_in_rb3 = false; plan_rb3(false); }
       if (noise_in_rb3) {
         // nothing here
       } else if (!S->f0) {
@@ -506,20 +517,15 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
       if (taps && i == 0) tap(taps->gen_ups0, up, (size_t)Cc * Tn);
       for (int j = 0; j < 3; ++j) {
         const float* in = up;
-        {
-          // 32-channel stage in the fp16x2 arithmetic: the whole ResBlock (three pairs) in one launch, x read once, the sum written once (conv_rb3.hip)
-          const ConvLayer* r1[3] = {&st.rb[j].c1[0], &st.rb[j].c1[1], &st.rb[j].c1[2]};
-          const ConvLayer* r2[3] = {&st.rb[j].c2[0], &st.rb[j].c2[1], &st.rb[j].c2[2]};
-          if (conv_rb3_try(r1, r2, s, up, Tn, Tn, xs, Tn, 0.1f, 1.f / 3.f, j > 0, false, noise_in_rb3 ? har : nullptr, noise_in_rb3 ? st.noise_w.p : nullptr,
-                           noise_in_rb3 ? st.noise_b.p : nullptr)) continue;
-          RVC_REQUIRE(!noise_in_rb3, "conv_rb3_try accepted the ResBlock in its dry run and declined the launch");
-        }
+        if (rb3_ok[j]) { conv_rb3_launch(rb3[j], s); continue; }
         for (int m = 0; m < 3; ++m) {
           ConvEpilogue E2; E2.pre_act = ACT_LRELU; E2.pre_slope = 0.1f; E2.R = in; E2.ldR = Tn;
           float* dst = (m == 0) ? ya : (m == 1 ? yb : xs);
           if (m == 2) { E2.out_scale = 1.f / 3.f; E2.accumulate = (j > 0); }
           // narrow stages: both convs of the pair in one launch, the intermediate stays in LDS (conv_x3.hip, FUSE)
-          if (!conv_x3_pair_try(st.rb[j].c1[m], st.rb[j].c2[m], s, in, Tn, Tn, dst, Tn, E2)) {
+          ConvPlan pp;
+          if (conv_x3_pair_plan(st.rb[j].c1[m], st.rb[j].c2[m], in, Tn, Tn, dst, Tn, E2, h2, pp)) conv_plan_launch(pp, s);
+          else {
             ConvEpilogue E1; E1.pre_act = ACT_LRELU; E1.pre_slope = 0.1f;
             if (split_pair[j][m]) {
               E1.ys_out = t1s; E1.ys_tp = split_image_tp(Tn); E1.ys_slope = E2.pre_slope;       // c2's input activation, applied once by the producer

@@ -790,8 +790,10 @@ int rvc_conv1d_plan_pair_run(rvc_conv1d_plan* c1, rvc_conv1d_plan* c2, void* str
   RVC_TRY
   RVC_REQUIRE(c1 && c2 && x && y, "null argument");
   ConvEpilogue e; e.pre_act = ACT_LRELU; e.pre_slope = 0.1f; e.R = x; e.ldR = T; e.out_scale = out_scale; e.accumulate = accumulate;
-  RVC_REQUIRE(conv_x3_pair_try(c1->L, c2->L, (hipStream_t)stream, x, T, T, y, T, e),
+  ConvPlan p;
+  RVC_REQUIRE(conv_x3_pair_plan(c1->L, c2->L, x, T, T, y, T, e, conv_set_pair_arithmetic(-1), p),
               "this pair of layers is not eligible for the fused ResBlock kernel (needs bf16x3 images, C = 32, equal odd k, long T)");
+  conv_plan_launch(p, (hipStream_t)stream);
   check_launch();
   RVC_CATCH
 }
@@ -804,7 +806,9 @@ int rvc_conv1d_plan_resblock_run(rvc_conv1d_plan* const* plans6, void* stream, c
     RVC_REQUIRE(plans6[2 * i] && plans6[2 * i + 1], "null plan");
     c1[i] = &plans6[2 * i]->L; c2[i] = &plans6[2 * i + 1]->L;
   }
-  *ran_out = conv_rb3_try(c1, c2, (hipStream_t)stream, x, T, T, y, T, 0.1f, out_scale, accumulate, false, noise_src, noise_w, noise_b) ? 1 : 0;
+  Rb3Plan p;
+  *ran_out = conv_rb3_plan(c1, c2, x, T, T, y, T, 0.1f, out_scale, accumulate, conv_set_pair_arithmetic(-1), noise_src, noise_w, noise_b, p) ? 1 : 0;
+  if (*ran_out) conv_rb3_launch(p, (hipStream_t)stream);
   check_launch();
   RVC_CATCH
 }
@@ -817,7 +821,7 @@ int rvc_conv1d_plan_pair_split_run(rvc_conv1d_plan* c1, rvc_conv1d_plan* c2, voi
   unsigned char* img = (unsigned char*)stream_scratch(s, 5, split_image_bytes(c1->L.Co, T));
   ConvEpilogue E1; E1.pre_act = ACT_LRELU; E1.pre_slope = 0.1f; E1.ys_out = img; E1.ys_tp = split_image_tp(T); E1.ys_slope = 0.1f;
   // the arithmetic the generator would use for this pair at this length: fp16x2 on the persistent kernel where eligible (rvc_set_pair_arithmetic), else bf16x3
-  E1.h2 = conv1d_pair_h2_eligible(c1->L, c2->L, T) ? 1 : 0;
+  E1.h2 = conv1d_pair_h2_eligible(c1->L, c2->L, T, conv_set_pair_arithmetic(-1)) ? 1 : 0;
   conv1d_run(c1->L, s, x, T, T, nullptr, T, E1);
   ConvEpilogue E2; E2.R = x; E2.ldR = T; E2.out_scale = out_scale; E2.accumulate = accumulate; E2.xs_in = img; E2.xs_tp = E1.ys_tp; E2.h2 = E1.h2;
   conv1d_run(c2->L, s, nullptr, T, T, y, T, E2);
@@ -827,9 +831,12 @@ int rvc_conv1d_plan_pair_split_run(rvc_conv1d_plan* c1, rvc_conv1d_plan* c2, voi
 int rvc_conv1d_plan_pair_arithmetic(rvc_conv1d_plan* c1, rvc_conv1d_plan* c2, int T) {
   if (!c1 || !c2) return -1;
   try {
-    if (conv1d_pair_h2_eligible(c1->L, c2->L, T)) return 1;
-    ConvEpilogue e; e.pre_act = ACT_LRELU; e.pre_slope = 0.1f; const float* dummy = reinterpret_cast<const float*>(c1->L.Wd_); e.R = dummy; e.ldR = T;
-    return conv_x3_pair_try(c1->L, c2->L, nullptr, dummy, T, T, nullptr, T, e, true) ? 1 : 0;      // (the fused pair of the 32-channel stage: dry run)
+    const int h2 = conv_set_pair_arithmetic(-1);
+    if (conv1d_pair_h2_eligible(c1->L, c2->L, T, h2)) return 1;
+    // the fused pair of the narrow stages: which kernel family the plan chose (planning needs no tensors: x = residual = null)
+    ConvEpilogue e; e.pre_act = ACT_LRELU; e.pre_slope = 0.1f; e.ldR = T;
+    ConvPlan p;
+    return conv_x3_pair_plan(c1->L, c2->L, nullptr, T, T, nullptr, T, e, h2, p) && p.a.h2 ? 1 : 0;
   } catch (...) { return -1; }
 }
 int rvc_conv1d_plan_destroy(rvc_conv1d_plan* p) { if (p) { conv_layer_free(p->L); delete p; } return 0; }

@@ -129,12 +129,13 @@ inline long long split_image_tp(long long T) { return (T + kSplitMargin + 704 + 
 inline size_t split_image_bytes(int C, long long T) { return (size_t)(C / 16) * 2 * (size_t)split_image_tp(T) * 32; }
 // true when this layer at this length runs on the bf16x3 kernel with a tile that has the split-resident path of its ROLE: a producer
 // (writes the image: ConvEpilogue::ys_out) and a consumer (stages it: xs_in) take different branches of the tile choice, so each role
-// is dry-run with its own geometry.  pre_lrelu: the producer's input activation (part of the real launch's arguments).
+// is planned with its own geometry.  pre_lrelu: the producer's input activation (part of the real launch's arguments).
 enum SplitRole : int { SPLIT_CONSUMER = 0, SPLIT_PRODUCER = 1 };
 bool conv1d_split_eligible(const ConvLayer& L, int Tin, SplitRole role = SPLIT_CONSUMER, int h2 = 0);
-// both layers of a ResBlock pair carry an fp16 image and both launches land on the persistent kernel at this length; false when the pair arithmetic is
-// switched to bf16x3 (rvc_set_pair_arithmetic(0) / RVC_H2=0)
-bool conv1d_pair_h2_eligible(const ConvLayer& c1, const ConvLayer& c2, int Tin);
+// both layers of a ResBlock pair carry an fp16 image and both launches land on the persistent kernel at this length; false when the pair arithmetic is switched to bf16x3
+// (h2 = 0: rvc_set_pair_arithmetic(0) / RVC_H2=0).  h2: the process-wide pair arithmetic as the caller queried it ONCE at the start of its call - a
+// conversion uses the mode it saw when it started
+bool conv1d_pair_h2_eligible(const ConvLayer& c1, const ConvLayer& c2, int Tin, int h2);
 int conv_set_pair_arithmetic(int mode);   // process-wide: 1 = fp16x2 on eligible ResBlock pairs (default), 0 = bf16x3 everywhere; < 0 queries; returns the previous mode
 
 // host-side packing + upload (weights in PyTorch layouts)
@@ -144,8 +145,7 @@ void tconv1d_layer_init(ConvLayer& L, const float* w /*[Ci][Co][k]*/, const floa
 void conv2d3x3_layer_init(ConvLayer& L, const float* w /*[Co][Ci][3][3]*/, const float* bias, int Co, int Ci);
 void conv2d1x1_layer_init(ConvLayer& L, const float* w /*[Co][Ci]*/, const float* bias, int Co, int Ci);
 void tconv2d_layer_init(ConvLayer& L, const float* w /*[Ci][Co][3][3]*/, const float* bias, int Ci, int Co);
-// general KH x KW window with asymmetric zero padding, bf16x3 kernel only (no fp32 twin): conv2d_kx_try returns false when the
-// geometry does not fit the kernel's tile / LDS limits (callers keep another formulation for that case); dry = eligibility only
+// general KH x KW window with asymmetric zero padding, bf16x3 image only (no fp32 twin): the layers run on conv_x3s_run
 void conv2d_kx_layer_init(ConvLayer& L, const float* w /*[Co][Ci][KH][KW]*/, const float* bias, int Co, int Ci, int KH, int KW, int PH, int PWL);
 void conv_layer_free(ConvLayer& L);
 // Layers initialised while this is on also get a bf16x3 split weight image and run on conv_x3_kernel when eligible
@@ -184,7 +184,7 @@ void conv2d_run(const ConvLayer& L, hipStream_t s, const float* X, long long ldX
 // p = h (W + 2) + w + 1, T = H (W + 2); the kernel writes zeros into the pad columns of its outputs (SplitGeom from split_geom_2d).
 struct SplitGeom { int ktaps = 1; int toff[16] = {0}; int padw = 0; int margin = kSplitMargin;
                    long long seg2_off = 0;      // byte offset (from the first image, < 2 GiB, same rows per plane and margin) of the second image of a layer with seg2_chunks
-                   int s2_h = 0; };             // > 0: stride-2 "valid" convolution over a DE-INTERLEAVED image (split_geom_s2): even positions at rows margin + p, odd ones at margin + s2_h + p   // byte offset (from the first image, < 2 GiB, same rows per plane and margin) of the second image of a layer with seg2_chunks
+                   int s2_h = 0; };             // > 0: stride-2 "valid" convolution over a DE-INTERLEAVED image (split_geom_s2): even positions at rows margin + p, odd ones at margin + s2_h + p
 // dst (a conv_x3s-eligible layer) += the k = 1 layer `extra` over a second input: the weight image of `extra` is appended as further units of dst's reduction
 void conv_layer_append_x3(ConvLayer& dst, const ConvLayer& extra);
 SplitGeom split_geom_2d(int Wd, int KH = 3, int KW = 3, int PH = 1, int PWL = 1);
@@ -207,18 +207,15 @@ void conv_x3s_run_swapped(const ConvLayer& L, int row0, int rows, hipStream_t s,
                           float* Yrm = nullptr, long long ldYrm = 0,      // Yrm: also / instead fp32 out[t][j] with pitch ldYrm
                           const float* Rrm = nullptr, long long ldRrm = 0);  // Rrm: residual added to the product, laid out like Yrm (MDX23C's x + tdf(x))
 void split_image_from_tm(hipStream_t s, const float* x, int C, int T, int M, unsigned char* img, long long tp);      // x [C][T][M] -> image of the (C M) x T tensor
-void conv_x3s_force(int ksplit, int am, int an);
+void conv_x3s_force(int ksplit, int am, int an);      // tests / benchmarks: K split and tile of the calling thread's next launches (0 = automatic)
 // one ConvBlockRes of 16 or 32 channels (3 x 3, 3 x 3, + x) in one launch (conv_cbr2.hip): x, out fp32 [C][H W], distinct
 bool cbr2_small_eligible(const ConvLayer& c1, const ConvLayer& c2);
 void cbr2_small_run(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, const float* x, int H, int W, float* out);
 // one 3 x 3 convolution of 16 / 32 input and <= 64 output channels on the same structure: rows below relu_rows get the ReLU, rows >= split_row go to Y2, R added to Y's rows
 bool conv3_small_eligible(const ConvLayer& L);
-void conv3_small_run(const ConvLayer& L, hipStream_t s, const float* x, int H, int W, float* Y, float* Y2, int split_row, int relu_rows, const float* R);      // tests / benchmarks: K split and tile of the calling thread's next launches (0 = automatic)
+void conv3_small_run(const ConvLayer& L, hipStream_t s, const float* x, int H, int W, float* Y, float* Y2, int split_row, int relu_rows, const float* R);
 void split_image_from_f32(hipStream_t s, const float* X, long long ldX, int C, int T, unsigned char* img, long long tp);
 void split_image_to_f32(hipStream_t s, const unsigned char* img, long long tp, int C, int T, float* Y, long long ldY);
-
-bool conv2d_kx_try(const ConvLayer& L, hipStream_t s, const float* X, long long ldX, int H, int Wd, float* Y, long long ldY, const ConvEpilogue& e,
-                   bool dry = false);
 
 // fused multi-head attention (attention.hip): Q, K channel-major [heads*64][T], V row-major [T][heads*64], out channel-major
 // out (fp32, channel-major) and / or out_img (the split-resident image of conv_x3s.hip, img_tp rows per plane) receive the result

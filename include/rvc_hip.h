@@ -381,7 +381,8 @@ int rvc_resample(void* stream, const float* x_dev, int64_t n_in, const double* t
  *   2  bf16x3 for every eligible layer (stride 1, groups 1, Ci % 16 == 0), including rvc_op_conv1d / plans (parity tests) */
 int rvc_set_conv_precision(int mode);
 /* Arithmetic of the generator's ResBlock pairs (reference lib/infer_pack/modules.py:295-308: x + c2(lrelu(c1(lrelu(x))))) on the persistent kernel,
- * PROCESS-WIDE, read at every launch (switching needs no reload: layers carry both weight images):
+ * PROCESS-WIDE, read once at the start of every conversion / plan call - a conversion uses the mode it saw when it started (switching needs no
+ * reload: layers carry both weight images):
  *   1  default: fp16x2 - the weight is ONE fp16 term (2^-12 relative rounding), the activation fp16 hi + lo (22 bits), two
  *      v_mfma_f32_32x32x16_f16 per product, fp32 accumulation.  Full-size goldens stay within the 33-LSB (1e-3) gate; see DESIGN.md.
  *      Activations beyond +-131008 would saturate (fp16 range): not reachable by a tanh-terminated vocoder, and a layer whose weights

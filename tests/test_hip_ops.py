@@ -1172,6 +1172,60 @@ def test_fused_resblock_pair(L, pair_arith, arith, tmp_path, Cc, k, d, T, scale,
         L.lib.rvc_conv1d_plan_destroy(pl)
 
 
+# one short and one long length per width and kernel size from the three pair tests above (64 channels through rvc_conv1d_plan_pair_run: k = 3 only, the call
+# refuses the others; 256 channels: the two lengths test_split_resident_resblock_pair has)
+PAIR_PLAN_LAUNCH = [(32, 3, 1, 200001), (32, 3, 1, 700000), (32, 7, 3, 131072), (32, 7, 3, 777777), (32, 11, 5, 140003), (32, 11, 5, 600003),
+                    (64, 3, 3, 66000), (64, 3, 1, 80003),
+                    (128, 3, 1, 80000), (128, 3, 1, 262144 + 256 * 3 + 5), (128, 7, 3, 66001), (128, 7, 3, 270001), (128, 11, 5, 70003), (128, 11, 5, 274489),
+                    (256, 3, 5, 30001), (256, 11, 3, 32000)]
+
+
+@pytest.mark.parametrize("Cc,k,d,T", PAIR_PLAN_LAUNCH)
+@pytest.mark.parametrize("arith", [0, 1])
+def test_pair_plan_matches_launch(L, pair_arith, arith, tmp_path, Cc, k, d, T):
+    """What rvc_conv1d_plan_pair_arithmetic answers for a pair IS what the launches of that pair multiply with: the answer is asked before the run, the
+    run is profiled, and every launch row must say two matrix instructions per product (fp16x2) exactly when the answer was 1; asked again after the run
+    the answer is the same.  Narrow pairs (32 / 64 channels) run through rvc_conv1d_plan_pair_run (one fused launch), wide ones (128 / 256) through
+    rvc_conv1d_plan_pair_split_run (two launches around the split-resident image).  The question and the launch share one planner; this pins it."""
+    pair_arith(arith)
+    g = torch.Generator().manual_seed(7000 + 37 * k + d + Cc)
+    x = torch.randn(Cc, T, generator=g)
+    w1 = torch.randn(Cc, Cc, k, generator=g) / np.sqrt(Cc * k); b1 = torch.randn(Cc, generator=g) * 0.1
+    w2 = torch.randn(Cc, Cc, k, generator=g) / np.sqrt(Cc * k); b2 = torch.randn(Cc, generator=g) * 0.1
+    xg, y = dev(x), torch.zeros(Cc, T, device="cuda")
+    L.check(L.lib.rvc_set_conv_precision(2))
+    plans = []
+    try:
+        for w, b, dd in ((w1, b1, d), (w2, b2, 1)):
+            pl = C.c_void_p()
+            L.check(L.lib.rvc_conv1d_plan_create(L.ptr(w.contiguous().numpy()), L.ptr(b.numpy()), Cc, Cc, k, 1, (k - 1) // 2 * dd, dd, 1, C.byref(pl)))
+            plans.append(pl)
+    finally:
+        L.check(L.lib.rvc_set_conv_precision(1))
+    answer = L.lib.rvc_conv1d_plan_pair_arithmetic(plans[0], plans[1], T)
+    assert answer in (0, 1), answer
+    run = L.lib.rvc_conv1d_plan_pair_run if Cc <= 64 else L.lib.rvc_conv1d_plan_pair_split_run
+    csv_path = str(tmp_path / "launches.csv")
+    try:
+        L.check(L.lib.rvc_prof_enable(1))
+        L.check(run(plans[0], plans[1], None, L.ptr(xg), T, L.ptr(y), 1.0, 0))
+        torch.cuda.synchronize()
+        L.check(L.lib.rvc_prof_dump_csv(csv_path.encode()))
+    finally:
+        L.check(L.lib.rvc_prof_enable(0))
+    lines = open(csv_path).read().strip().split("\n")
+    col = lines[0].split(",").index("mfma_per_product")
+    rows = [ln.split(",") for ln in lines[1:]]
+    print("pair plan", (Cc, k, d, T), "arith", arith, "answer", answer, "rows", [(r[1], r[col]) for r in rows])
+    assert len(rows) == (1 if Cc <= 64 else 2), rows
+    for r in rows:
+        assert (int(r[col]) == 2) == (answer == 1), (answer, r)
+    assert L.lib.rvc_conv1d_plan_pair_arithmetic(plans[0], plans[1], T) == answer
+    assert bool(torch.isfinite(y).all())
+    for pl in plans:
+        L.lib.rvc_conv1d_plan_destroy(pl)
+
+
 # ------------------------------------------------------------------ split-resident GEMM (csrc/conv_x3s.hip)
 GEMM_SPLIT = [
     # Ci, Co, T, act, res, act_before_res, out_scale, ksplit, am, an
