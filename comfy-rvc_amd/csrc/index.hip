@@ -96,17 +96,21 @@ __global__ void index_topk_kernel(const float* __restrict__ Yc, int nlist, int T
   }
 }
 
-// score[t] = |f_t|^2 - 2 best[t]  (squared L2 distance, what faiss returns for an L2 index)
-__global__ void index_score_kernel(const float* __restrict__ f, const float* __restrict__ best, const long long* __restrict__ bidx,
-                                   float* __restrict__ score, int D, int T) {
+// score[t] = |f_t - b_idx[t]|^2  (squared L2 distance, what faiss returns for an L2 index), evaluated directly on the winner's row in fp64 and rounded
+// once.  (|f|^2 - 2 best[t] from the GEMM's score cancels ~|f|^2 against itself and carries the three-term product's dropped lo*lo sum, which is
+// one-sided for a query that IS a row of the index: such a member came out at ~5e-6 |f|^2 instead of 0.  The arg-max is unaffected.)
+__global__ void index_score_kernel(const float* __restrict__ f, const float* __restrict__ rows, const long long* __restrict__ bidx,
+                                   float* __restrict__ score, int D, int T, long long N) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
-  if (bidx[t] < 0) { score[t] = 3.4028234663852886e38f; return; }      // no vector in the probed lists: faiss reports FLT_MAX with label -1
-  float s = 0.f;
-  for (int c = 0; c < D; ++c) { const float v = f[(long long)c * T + t]; s = fmaf(v, v, s); }
-  // cancellation can leave an exact member of the index at 0 or slightly below; the generic VC.vc path weighs by 1 / score^2
-  // (reference vc_infer_pipeline.py:66-68), so the distance is kept strictly positive
-  score[t] = fmaxf(s - 2.f * best[t], 1e-10f);
+  long long r = bidx[t];
+  if (r < 0) { score[t] = 3.4028234663852886e38f; return; }      // no vector in the probed lists: faiss reports FLT_MAX with label -1
+  r = r >= N ? N - 1 : r;
+  double s = 0.0;
+  for (int c = 0; c < D; ++c) { const double v = (double)f[(long long)c * T + t] - (double)rows[r * D + c]; s += v * v; }
+  // an exact member of the index is at 0; the generic VC.vc path weighs by 1 / score^2 (reference vc_infer_pipeline.py:66-68), so the
+  // distance is kept strictly positive
+  score[t] = fmaxf((float)s, 1e-10f);
 }
 
 // out[c][t] = rate * rows[idx[t]][c] + (1 - rate) * f[c][t]      (reference :71-74; k = 1 makes the 1/score^2 weight exactly 1)
@@ -210,7 +214,7 @@ void index_search(FeatIndex* I, hipStream_t s, const float* feats_cm, int T, lon
     hipLaunchKernelGGL(index_argmax_kernel, dim3((T + 63) / 64), dim3(1024), 0, s, Y, M, T, (long long)T, m0, best, idx, m0 == 0 ? 1 : 0,
                        ivf ? I->list_of : nullptr, cells, ivf ? I->nprobe : 0);
   }
-  if (score) hipLaunchKernelGGL(index_score_kernel, dim3((T + 255) / 256), dim3(256), 0, s, feats_cm, best, idx, score, I->D, T);
+  if (score) hipLaunchKernelGGL(index_score_kernel, dim3((T + 63) / 64), dim3(64), 0, s, feats_cm, I->rows, idx, score, I->D, T, I->N);
 }
 
 void index_blend(FeatIndex* I, hipStream_t s, const float* feats_cm, const long long* idx, int T, float rate, float* out_cm) {

@@ -54,6 +54,14 @@ int index_dim(const FeatIndex* I);
 void index_search(FeatIndex* I, hipStream_t s, const float* feats_cm, int T, long long* idx, float* score);
 void index_blend(FeatIndex* I, hipStream_t s, const float* feats_cm, const long long* idx, int T, float rate, float* out_cm);
 
+// building the index (index_build.hip): k-means over rows [N][D] on the device - nearest centroid per row (ties: smallest index; dist: squared
+// distance or null), centroids = fp64 means of their rows with faiss's split rule for empty clusters (bit-identical between runs), and the whole
+// training: centroids from init_rows (host), niter x (assign, update), one last assign; inertia (host, niter + 1 sums of dist) may be null
+void kmeans_assign(Ctx* ctx, hipStream_t s, const float* rows, long long N, int D, const float* cent, int K, int* label, float* dist);
+void kmeans_update(hipStream_t s, const float* rows, const int* label, long long N, int D, int K, float* cent, int* count);
+void index_train(Ctx* ctx, hipStream_t s, const float* rows, long long N, int D, const long long* init_rows, int K, int niter, float* cent, int* label,
+                 double* inertia);
+
 void rmvpe_decode_rm(Rmvpe* R, hipStream_t s, const float* sal_rm, long long n, float thred, double* f0);
 int rmvpe_status(Rmvpe* R, hipStream_t s);                 // waits for the stream; bit 0: the last forward's GRU scan timed out
 void rmvpe_debug_fault(Rmvpe* R, int fault, unsigned spin_limit);   // tests: make the next scans fail / shorten their spin limit

@@ -336,6 +336,29 @@ int rvc_index_blend(rvc_index* h, void* stream, const float* feats_cm, const int
   check_launch();
   RVC_CATCH
 }
+// building the index: k-means on the device (index_build.hip)
+int rvc_kmeans_assign(rvc_ctx* ctx, void* stream, const float* rows, int64_t N, int D, const float* cent, int K, int32_t* label, float* dist) {
+  RVC_TRY
+  RVC_REQUIRE(ctx && rows && cent && label, "null argument");
+  kmeans_assign(&ctx->c, (hipStream_t)stream, rows, N, D, cent, K, (int*)label, dist);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_kmeans_update(void* stream, const float* rows, const int32_t* label, int64_t N, int D, int K, float* cent, int32_t* count) {
+  RVC_TRY
+  RVC_REQUIRE(rows && label && cent && count, "null argument");
+  kmeans_update((hipStream_t)stream, rows, (const int*)label, N, D, K, cent, (int*)count);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_index_train(rvc_ctx* ctx, void* stream, const float* rows, int64_t N, int D, const int64_t* init_rows, int K, int niter, float* cent,
+                    int32_t* label, double* inertia) {
+  RVC_TRY
+  RVC_REQUIRE(ctx && rows && init_rows && cent && label, "null argument");
+  index_train(&ctx->c, (hipStream_t)stream, rows, N, D, (const long long*)init_rows, K, niter, cent, (int*)label, inertia);
+  check_launch();
+  RVC_CATCH
+}
 
 int rvc_preprocess(void* stream, const void* audio, int is_f64, int64_t n, const double* b6, const double* a6, const double* zi5, int t_pad,
                    double* filt, float* padded, double* rms1, int n1, const double* sos18, const double* sos_zi6) {

@@ -63,6 +63,25 @@ def _memoised(kind, path, loader, extra=None):
     return _memo[key]
 
 
+def train_index(dataset_dir, sr, name):
+    """RVCTrainModelNode.train_index of the reference (custom_nodes/rvc_nodes.py:500-554) as a plain function - the training NODE stays out of
+    scope, a graph or the reference's node can call this: the HuBERT features under `dataset_dir/3_feature768` become
+    `BASE_MODELS_DIR/RVC/.index/{name}_v2_{sr}_{md5(dataset_dir, sr, name)}.index`, trained on the GPU (lib/feature_index.py::train_index).
+    An existing file is kept; returns the path, or None when the build failed (as the reference does)."""
+    from ..lib.feature_index import train_index as build
+    key = hashlib.md5("".join(str(v) for v in (dataset_dir, sr, name)).encode()).hexdigest()      # reference lib/utils.py::get_hash
+    index_file = os.path.join(BASE_MODELS_DIR, "RVC", ".index", f"{name}_v2_{sr}_{key}.index")
+    try:
+        if not os.path.isfile(index_file):
+            os.makedirs(os.path.dirname(index_file), exist_ok=True)
+            build(os.path.join(dataset_dir, "3_feature768"), index_file)
+            print(f"saved index file to {index_file}")
+        return index_file
+    except Exception as e:   # noqa: BLE001 - the reference reports and returns None
+        print(f"Failed to train index: {e}")
+    return None
+
+
 class LoadPitchExtractionParams:
     @classmethod
     def INPUT_TYPES(cls):

@@ -222,6 +222,23 @@ int rvc_index_destroy(rvc_index* h);
 int64_t rvc_index_ntotal(const rvc_index* h);
 int rvc_index_search(rvc_index* h, void* stream, const float* feats_cm_dev, int64_t T, int64_t* idx_dev, float* score_dev /* may be NULL */);
 int rvc_index_blend(rvc_index* h, void* stream, const float* feats_cm_dev, const int64_t* idx_dev, int64_t T, float index_rate, float* out_cm_dev);
+/* Building that index (RVCTrainModelNode.train_index, custom_nodes/rvc_nodes.py:500-554, without faiss): k-means over rows_dev [N][D] (D a multiple
+ * of 8) on the device.
+ * rvc_kmeans_assign: label[i] = the centroid nearest to row i in squared L2 (ties: smallest index), in the arithmetic of rvc_index_search; the
+ *   [K][N] scores are never stored.  dist_dev (may be NULL) receives the squared distance to that centroid.
+ * rvc_kmeans_update: cent[k] = mean of the rows with label k (fp64 sum in row order, one rounding; bit-identical between runs), count[k] = their
+ *   number.  Empty clusters, in increasing order, take the centroid of the then most populated cluster (smallest index on ties): the copy is
+ *   multiplied by 1 + 1/1024 in even and 1 - 1/1024 in odd dimensions, the donor by the opposite factors, and the donor's count is shared
+ *   (count[empty] = count[donor] / 2) - faiss Clustering.cpp::split_clusters with a fixed donor.
+ * rvc_index_train: centroids = rows init_rows_host[0 .. K), then niter x (assign, update) and one last assign against the final centroids
+ *   (faiss's add): label_dev is that assignment, inertia_host[i] (niter + 1 values, may be NULL) the fp64 sum of dist at assign step i.  Returns
+ *   after the stream has finished. */
+int rvc_kmeans_assign(rvc_ctx* ctx, void* stream, const float* rows_dev, int64_t N, int D, const float* cent_dev /* [K][D] */, int K, int32_t* label_dev,
+                      float* dist_dev /* may be NULL */);
+int rvc_kmeans_update(void* stream, const float* rows_dev, const int32_t* label_dev, int64_t N, int D, int K, float* cent_dev /* in: old, out: new */,
+                      int32_t* count_dev);
+int rvc_index_train(rvc_ctx* ctx, void* stream, const float* rows_dev, int64_t N, int D, const int64_t* init_rows_host /* [K] */, int K, int niter,
+                    float* cent_dev /* [K][D] */, int32_t* label_dev, double* inertia_host /* may be NULL */);
 /* Input pre-processing of VC.pipeline on the device: the zero-phase 5th-order high-pass (vc_infer_pipeline.py:19,121:
  * scipy.signal.filtfilt(bh, ah, audio) - odd extension by 18 samples, lfilter_zi initial conditions, float64), the reflect
  * padding by t_pad with the float32 cast the networks consume (:141) and the RMS frames of the filtered input that change_rms
