@@ -121,6 +121,11 @@ SIGNATURES = {
     "rvc_preprocess": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                              c_void_p, c_int, c_void_p, c_void_p]),
     "rvc_postprocess": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_float, c_void_p]),
+    "rvc_lfilter_hp": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "rvc_frame_rms": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64]),
+    "rvc_slice_tags": (c_int, [c_void_p, c_int64, c_int64, C.c_double, c_int64, c_int64, c_int64, c_void_p, c_int64, P(c_int64)]),
+    "rvc_cut_windows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int64,
+                                c_void_p, c_int64]),
     "rvc_op_gemm_split": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_float, c_int, c_float] + [c_int] * 5),
     "rvc_op_conv2d_split": (c_int, [c_void_p] * 7 + [c_int] * 9),
     "rvc_op_wn_in_gate_split": (c_int, [c_void_p] * 6 + [c_int] * 4),

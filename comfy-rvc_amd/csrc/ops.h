@@ -52,6 +52,19 @@ void preprocess(hipStream_t s, const void* x, int is64, long long n, const doubl
                 double* filt, float* padded, double* rms1, int n1, int frame, int hop, double* scratch, const double* sos = nullptr,
                 const double* sos_zi = nullptr);      // sos [3][6] + sosfilt_zi [3][2]: block-propagated cascade evaluation (ops.hip)
 void postprocess(hipStream_t s, float* x, long long N, const double* rms1, int n1, int sr2, float rate, short* out, float* rms2, unsigned* maxbits);
+// librosa-style centred framed RMS of a float64 signal (zero padding of frame / 2 on both sides): rms [n_frames], one block per frame
+void rms_frames_f64(hipStream_t s, const double* x, long long n, int frame, int hop, double* rms, long long n_frames);
+
+// training-set preparation (dataset_prep.hip)
+// y = scipy.signal.lfilter(b, a, x) from a zero state for the filter given as three normalised second-order sections (host [3][6]); 5 launches
+void lfilter_sos(hipStream_t s, const void* x, int is64, long long n, const double* sos18, double* y);
+// the slicer's silence scan over a HOST RMS list: writes (begin, end) frame pairs to tags [cap][2], returns their number
+long long slice_tags(const double* rms, long long nf, long long n_samples, double threshold, long long min_length, long long min_interval,
+                     long long max_sil_kept, long long* tags, long long cap);
+// windows (start, length) [nw][2] (device) of filt -> gt: float32 casts, packed; y16: resampled by up / down (taps: design of rvc_resample) and
+// peak-limited to max_volume per window, packed; 4 launches
+void cut_windows(hipStream_t s, const double* filt, long long n, const long long* win, int nw, int sr, int target, const double* taps, int half,
+                 int up, int down, float max_volume, float* gt, long long total_gt, float* y16, long long total_16);
 
 // padded 2-D split-resident images (split2d.hip): level changes of RMVPE's U-Net in the layout conv_x3s.hip convolves
 void pool2_pad_split(hipStream_t s, const float* x, long long ldx, bool x_padded, int C, int H, int W, float* y, long long ldy, unsigned char* img,

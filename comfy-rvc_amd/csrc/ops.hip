@@ -2,6 +2,7 @@
 // changes, SineGen source, GRU recurrence, RMVPE decode.  All tensors are channel-major [C][T] unless noted.
 #include "rvc_internal.h"
 #include "ops.h"
+#include "signal_dev.h"
 
 namespace rvc {
 
@@ -629,14 +630,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
                                                        int U, int D, float* __restrict__ y, long long n_out) {
   const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= n_out) return;
-  const long long c = n * D;                       // position of output n on the up-sampled grid
-  long long lo = c - half, hi = c + half;
-  long long m0 = lo <= 0 ? 0 : (lo + U - 1) / U;   // ceil(lo / U), clamped to the signal
-  long long m1 = hi / U;                           // floor (hi >= 0)
-  if (m1 > n_in - 1) m1 = n_in - 1;
-  double acc = 0.0;
-  for (long long m = m0; m <= m1; ++m) acc += (double)x[m] * h[m * U - c + half];
-  y[n] = (float)acc;
+  y[n] = (float)polyphase_sum([&](long long m) { return x[m]; }, n_in, h, half, U, D, n);      // signal_dev.h
 }
 void resample(hipStream_t s, const float* x, long long n_in, const double* h, int half, int U, int D, float* y, long long n_out) {
   if (n_out <= 0) return;
@@ -1353,17 +1347,8 @@ __global__ void iir_chunk_kernel(const IirArgs p) {
 // rounding noise (~4e-8 of full scale, one float32 ulp of what the networks consume; tests/test_hip_ops.py gates 3e-7).
 // 2 L steps per L outputs, and the samples travel through LDS tiles: 64 blocks x 32 samples are loaded as 256-byte rows (coalesced) and read
 // back one row per lane (row pitch 33 doubles: conflict-free).
-constexpr int kIirTile = 32, kSosN = 6;
-__device__ __forceinline__ double sos_step(const IirArgs& p, double (&z)[kSosN], double x) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double y = fma(p.sos[k][0], x, z[2 * k]);
-    z[2 * k] = fma(-p.sos[k][4], y, fma(p.sos[k][1], x, z[2 * k + 1]));
-    z[2 * k + 1] = fma(-p.sos[k][5], y, p.sos[k][2] * x);
-    x = y;
-  }
-  return x;
-}
+constexpr int kIirTile = 32;
+__device__ __forceinline__ double sos_step(const IirArgs& p, double (&z)[kSosN], double x) { return sos_cascade_step(p.sos, z, x); }   // signal_dev.h
 template <int DIR, bool OUT>
 __global__ __launch_bounds__(64) void iir_block_kernel(const IirArgs p) {
   __shared__ double tile[2][64][kIirTile + 1];
@@ -1519,6 +1504,10 @@ __global__ __launch_bounds__(256) void rms_frames_f64_kernel(const double* __res
   if (threadIdx.x == 0) rms[blockIdx.x] = sqrt(red[0] / frame);
 }
 
+void rms_frames_f64(hipStream_t s, const double* x, long long n, int frame, int hop, double* rms, long long n_frames) {
+  if (n_frames > 0) hipLaunchKernelGGL(rms_frames_f64_kernel, dim3((unsigned)n_frames), dim3(256), 0, s, x, n, frame, hop, rms);
+}
+
 // Block length L and padded length Np of the filter pass for an input of n samples: ONE definition for the caller's scratch (2 Np doubles,
 // preprocess_scratch_doubles) and for the kernels (advisor, round 3: the scratch used to assume L <= 65536, which clips beyond ~2e8 samples
 // exceed, and an RVC_IIR_L that is not a power of two >= 32 silently dropped samples).
@@ -1562,23 +1551,8 @@ void preprocess(hipStream_t s, const void* x, int is64, long long n, const doubl
     for (int i = 0; i < 6; ++i) p.zis[i] = sos_zi[i];
     // M / Mg: column j = the cascade's state after L (g L) zero-input samples from the unit state e_j (the recurrence itself, float64: O(1) entries)
     const int gsz = (p.nb + 63) / 64;
-    auto transition = [&](long long steps, double* out) {
-      for (int j = 0; j < 6; ++j) {
-        double z[6] = {0, 0, 0, 0, 0, 0}; z[j] = 1.0;
-        for (long long t = 0; t < steps; ++t) {
-          double xx = 0.0;
-          for (int k = 0; k < 3; ++k) {
-            const double y = std::fma(p.sos[k][0], xx, z[2 * k]);
-            z[2 * k] = std::fma(-p.sos[k][4], y, std::fma(p.sos[k][1], xx, z[2 * k + 1]));
-            z[2 * k + 1] = std::fma(-p.sos[k][5], y, p.sos[k][2] * xx);
-            xx = y;
-          }
-        }
-        for (int i = 0; i < 6; ++i) out[i * 6 + j] = z[i];
-      }
-    };
-    transition(p.L, p.M);
-    transition((long long)p.L * gsz, p.Mg);
+    sos_transition(p.sos, p.L, p.M);
+    sos_transition(p.sos, (long long)p.L * gsz, p.Mg);
     double* st = (double*)stream_scratch(s, 8, (size_t)2 * p.nb * 6 * sizeof(double));
     p.Z0 = st; p.Zin = st + (size_t)p.nb * 6;
     const dim3 g((unsigned)((p.nb + 63) / 64));

@@ -384,6 +384,42 @@ int rvc_postprocess(void* stream, float* wav, int64_t N, const double* rms1, int
   RVC_CATCH
 }
 
+// ------------------------------------------------------------------------------------------------ training-set preparation (dataset_prep.hip)
+int rvc_lfilter_hp(void* stream, const void* x, int is_f64, int64_t n, const double* sos18, double* y) {
+  RVC_TRY
+  RVC_REQUIRE(x && sos18 && y && n > 0, "bad argument");
+  lfilter_sos((hipStream_t)stream, x, is_f64, n, sos18, y);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_frame_rms(void* stream, const double* x, int64_t n, int win, int hop, double* rms, int64_t n_frames) {
+  RVC_TRY
+  RVC_REQUIRE(x && rms && n > 0 && win > 0 && hop > 0, "bad argument");
+  RVC_REQUIRE(n_frames == (n + 2 * (int64_t)(win / 2) - win) / hop + 1 && n_frames < (1LL << 31), "rms must hold (n + 2 (win / 2) - win) / hop + 1 frames");
+  rms_frames_f64((hipStream_t)stream, x, n, win, hop, rms, n_frames);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_slice_tags(const double* rms, int64_t n_frames, int64_t n_samples, double threshold, int64_t min_length, int64_t min_interval,
+                   int64_t max_sil_kept, int64_t* tags, int64_t cap, int64_t* n_tags) {
+  RVC_TRY
+  RVC_REQUIRE((rms || n_frames == 0) && tags && n_tags && n_frames >= 0 && cap >= 0, "bad argument");
+  RVC_REQUIRE(min_interval >= 1 && max_sil_kept >= 1 && min_length >= min_interval, "min_length >= min_interval >= 1 and max_sil_kept >= 1 frames");
+  *n_tags = slice_tags(rms, n_frames, n_samples, threshold, min_length, min_interval, max_sil_kept, (long long*)tags, cap);
+  RVC_CATCH
+}
+int rvc_cut_windows(void* stream, const double* filt, int64_t n, const int64_t* windows, int n_windows, int sr, int target_sr, const double* taps,
+                    int half, int up, int down, float max_volume, float* gt, int64_t total_gt, float* y16, int64_t total_16) {
+  RVC_TRY
+  RVC_REQUIRE(filt && windows && taps && n > 0 && n_windows >= 0 && half >= 0 && up > 0 && down > 0, "bad argument");
+  RVC_REQUIRE(sr > 0 && target_sr > 0 && (int64_t)sr * up == (int64_t)target_sr * down, "up / down must be target_sr / sr");
+  RVC_REQUIRE(max_volume > 0.f && total_gt >= 0 && total_16 >= 0 && (gt || total_gt == 0) && (y16 || total_16 == 0), "bad argument");
+  cut_windows((hipStream_t)stream, filt, n, (const long long*)windows, n_windows, sr, target_sr, taps, half, up, down, max_volume, gt, total_gt,
+              y16, total_16);
+  check_launch();
+  RVC_CATCH
+}
+
 // ------------------------------------------------------------------------------------------------ single ops
 int rvc_op_conv1d(void* stream, const float* x, const float* w, const float* bias, const float* res, float* y, int Ci, int Co, int Tin, int k,
                   int stride, int pad, int dil, int groups, int pre_act, float pre_slope, int act, float act_slope, int act_before_res,

@@ -1,0 +1,48 @@
+// Arithmetic shared by the input high-pass of the conversion path (ops.hip: filtfilt) and the dataset preparation (dataset_prep.hip: lfilter,
+// windowed resampling): ONE definition each of the second-order-section step, of the state transition of a block and of the polyphase tap
+// sum, so the two users cannot drift apart (the dataset path is tested bit for bit against rvc_resample).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cmath>
+
+namespace rvc {
+
+constexpr int kSosN = 6;      // states of the cascade: 2 per section, 3 sections (a 5th-order filter: the last section is first order, b2 = a2 = 0)
+
+// one sample through the cascade sos[k] = {b0, b1, b2, 1, a1, a2} (direct form II transposed per section, float64)
+__host__ __device__ __forceinline__ double sos_cascade_step(const double (&sos)[3][6], double (&z)[kSosN], double x) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double y = fma(sos[k][0], x, z[2 * k]);
+    z[2 * k] = fma(-sos[k][4], y, fma(sos[k][1], x, z[2 * k + 1]));
+    z[2 * k + 1] = fma(-sos[k][5], y, sos[k][2] * x);
+    x = y;
+  }
+  return x;
+}
+
+// M [6][6]: column j = the cascade's state after `steps` zero-input samples from the unit state e_j (the recurrence itself: O(1) entries)
+inline void sos_transition(const double (&sos)[3][6], long long steps, double* M) {
+  for (int j = 0; j < kSosN; ++j) {
+    double z[kSosN] = {0, 0, 0, 0, 0, 0};
+    z[j] = 1.0;
+    for (long long t = 0; t < steps; ++t) sos_cascade_step(sos, z, 0.0);
+    for (int i = 0; i < kSosN; ++i) M[i * kSosN + j] = z[i];
+  }
+}
+
+// output n of the rational resampler (ops.hip: resample_kernel): sum_m x(m) h[m U - n D + half] over the taps that meet [0, n_in), ascending m,
+// float64 accumulation; x(m) returns sample m as float32
+template <class X>
+__device__ __forceinline__ double polyphase_sum(X x, long long n_in, const double* __restrict__ h, int half, int U, int D, long long n) {
+  const long long c = n * D;                       // position of output n on the up-sampled grid
+  long long lo = c - half, hi = c + half;
+  long long m0 = lo <= 0 ? 0 : (lo + U - 1) / U;   // ceil(lo / U), clamped to the signal
+  long long m1 = hi / U;                           // floor (hi >= 0)
+  if (m1 > n_in - 1) m1 = n_in - 1;
+  double acc = 0.0;
+  for (long long m = m0; m <= m1; ++m) acc += (double)x(m) * h[m * U - c + half];
+  return acc;
+}
+
+}  // namespace rvc

@@ -13,13 +13,16 @@ Note the reference's quirk that training prep quantises the pitch with f0_max = 
 1600 Hz (vc_infer_pipeline.py:118).
 """
 import os
+import sys
 import traceback
 
 import numpy as np
 import torch
 
 from .config import Config
+from .lib import dataset_prep
 from .lib.audio import hz_to_mel
+from .lib.utils import gc_collect
 from .pitch_extraction import FeatureExtractor
 
 
@@ -40,6 +43,104 @@ def load_wav(path, sr, device="cuda:0"):
         x = resample_audio(x.T if x.ndim > 1 else x, rate, sr, device=device)       # along the last axis, like librosa.resample
         x = np.ascontiguousarray(x.T) if x.ndim > 1 else x
     return x, sr
+
+
+class Preprocess:
+    """Slices the recordings of a folder into training clips (mirror of the reference's `Preprocess`, preprocessing_utils.py:13-100):
+    `exp_dir/0_gt_wavs/{idx0}_{idx1}.wav` at the model rate `sr` and `exp_dir/1_16k_wavs/{idx0}_{idx1}.wav` at 16 kHz, peak-limited to
+    `max_volume`, both IEEE-float WAV; `exp_dir/preprocess.log` gets the same lines.  Slicer parameters, window arithmetic and file numbering are
+    the reference's (lib/dataset_prep.py::plan_windows, including the numbers a remainder shares with the next chunk's first window).
+
+    Differences: filter, RMS, cut and resampling run on the device, one launch sequence per recording (lib/dataset_prep.py); the high-pass is
+    evaluated in its sections form, so samples differ from scipy's lfilter by that routine's own rounding noise; files are read with
+    `load_wav` (WAV only), and a stereo file is AVERAGED TO MONO before slicing (the reference slices what its loader returns, which is mono);
+    `preprocessor`, when given, is any callable (audio, sr) -> (audio, sr) applied on the host; `n_p` only partitions the file list - there is one
+    process and one device, so `noparallel` is accepted and ignored."""
+
+    def __init__(self, sr, exp_dir, preprocessor=None, noparallel=True, period=3.0, overlap=.3, max_volume=.95, device="cuda:0"):
+        self.slicer = dataset_prep.slicer_params(sr)
+        self.sr = sr
+        self.per = period
+        self.overlap = overlap
+        self.tail = self.per + self.overlap
+        self.max_volume = max_volume
+        self.exp_dir = exp_dir
+        self.gt_wavs_dir = os.path.join(exp_dir, "0_gt_wavs")
+        self.wavs16k_dir = os.path.join(exp_dir, "1_16k_wavs")
+        self.noparallel = noparallel
+        self.preprocessor = preprocessor
+        self.device = device
+        os.makedirs(self.exp_dir, exist_ok=True)
+        os.makedirs(self.gt_wavs_dir, exist_ok=True)
+        os.makedirs(self.wavs16k_dir, exist_ok=True)
+
+    def println(self, strr):
+        print(strr)
+        with open("%s/preprocess.log" % self.exp_dir, "a+") as f:
+            f.write("%s\n" % strr)
+            f.flush()
+
+    def norm_write(self, tmp_audio, idx0, idx1, audio16k=None):
+        """Writes one clip pair if it is longer than 2 * overlap s.  `audio16k` is the clip's peak-limited 16 kHz version when the caller already
+        has it (pipeline: rvc_cut_windows); without it the clip takes the per-clip route (remix_audio), as in the reference."""
+        from scipy.io import wavfile   # noqa: PLC0415
+        if len(tmp_audio) > self.overlap * self.sr * 2:
+            if audio16k is None:
+                from .lib.audio import remix_audio   # noqa: PLC0415
+                audio16k = remix_audio((tmp_audio, self.sr), target_sr=16000, max_volume=self.max_volume, device=self.device)[0]
+            wavfile.write(os.path.join(self.gt_wavs_dir, f"{idx0}_{idx1}.wav"), self.sr, np.asarray(tmp_audio).astype(np.float32))
+            wavfile.write(os.path.join(self.wavs16k_dir, f"{idx0}_{idx1}.wav"), 16000, np.asarray(audio16k).astype(np.float32))
+        else:
+            print(f"skipped short audio clip: {idx0}_{idx1}.wav ({len(tmp_audio)=})")
+
+    def slice_on_device(self, audio):
+        """float32 / float64 mono recording -> (filtered float64 CUDA tensor, window plan of lib/dataset_prep.py::plan_windows)."""
+        sp = self.slicer
+        x = torch.from_numpy(np.ascontiguousarray(audio)).to(self.device)
+        filt = dataset_prep.lfilter_hp(x, self.sr)
+        n = int(x.numel())
+        tags, nf = [], 0
+        if n > sp["min_length"]:              # (a sample count against a frame count: the reference's early return, kept)
+            rms = dataset_prep.frame_rms(filt, sp["win_size"], sp["hop_size"]).cpu().numpy()
+            nf = rms.shape[0]
+            tags = dataset_prep.slice_tags(rms, n, sp)
+        chunks = dataset_prep.chunk_bounds(tags, nf, sp["hop_size"], n)
+        return filt, dataset_prep.plan_windows(chunks, self.sr, self.per, self.overlap)
+
+    def pipeline(self, path, idx0):
+        try:
+            audio, _ = load_wav(path, self.sr, self.device)
+            if audio.ndim > 1:
+                audio = audio.mean(-1)                                     # [N, C] -> mono
+            if self.preprocessor is not None:
+                audio, _ = self.preprocessor(audio, self.sr)
+                audio = np.asarray(audio)
+            if audio.dtype not in (np.float32, np.float64):
+                audio = audio.astype(np.float32)
+            filt, plan = self.slice_on_device(audio)
+            todo = [(start, length, idx1) for start, length, idx1, written in plan if written]
+            gt, y16 = dataset_prep.cut_windows(filt, [(s_, l_) for s_, l_, _ in todo], self.sr, self.max_volume)
+            for (start, length, idx1), a, b in zip(todo, gt, y16):
+                self.norm_write(a, idx0, idx1, b)
+            for start, length, idx1, written in plan:
+                if not written:
+                    print(f"skipped short audio clip: {idx0}_{idx1}.wav (len(tmp_audio)={length})")
+            self.println("%s->Suc." % path)
+        except Exception:   # noqa: BLE001 - reference behaviour: log and continue
+            self.println("%s->%s" % (path, traceback.format_exc()))
+
+    def pipeline_mp(self, infos):
+        for path, idx0 in infos:
+            self.pipeline(path, idx0)
+
+    def pipeline_mp_inp_dir(self, inp_root, n_p):
+        try:
+            infos = [("%s/%s" % (inp_root, name), idx) for idx, name in enumerate(sorted(list(os.listdir(inp_root))))]
+            n_p = max(int(n_p), 1)
+            for i in range(n_p):
+                self.pipeline_mp(infos[i::n_p])
+        except Exception:   # noqa: BLE001 - reference behaviour
+            self.println("Fail. %s" % traceback.format_exc())
 
 
 class FeatureInput(FeatureExtractor):
@@ -109,3 +210,53 @@ class FeatureInput(FeatureExtractor):
             except Exception:   # noqa: BLE001 - reference behaviour: log and continue
                 self.printt("f0fail-%s-%s-%s" % (idx, inp_path, traceback.format_exc()))
         return done
+
+
+def preprocess_trainset(inp_root, sr, n_p, exp_dir, preprocessor=None, period=3.0, overlap=.3, max_volume=1., device="cuda:0"):
+    """Folder of recordings -> sliced training clips under exp_dir (reference preprocessing_utils.py:195-208); True / False like the reference."""
+    try:
+        pp = Preprocess(sr, exp_dir, preprocessor=preprocessor, period=period, overlap=overlap, max_volume=max_volume, device=device)
+        pp.println("start preprocess")
+        pp.println(sys.argv)
+        pp.pipeline_mp_inp_dir(inp_root, n_p)
+        pp.println("end preprocess")
+        del pp
+        gc_collect()
+        print("Successfully preprocessed data")
+        return True
+    except Exception as e:   # noqa: BLE001 - reference behaviour
+        print(f"Failed to preprocess data: {e}")
+        return False
+
+
+def extract_features_trainset(hubert_model, exp_dir, n_p, f0method, device, version, if_f0, crepe_hop_length):
+    """HuBERT features and pitch of every clip in exp_dir/1_16k_wavs (reference preprocessing_utils.py:210-253): outputs named
+    "{f0method},{clip}" under 2a_f0, 2b-f0nsf and 3_feature768 (3_feature256 for v1); inputs with "spec" in their path are skipped.  `n_p`
+    partitions the list, every part runs on the one device in turn."""
+    try:
+        dev = str(device) if device is not None and str(device).startswith("cuda") else "cuda:0"
+        if dev == "cuda":
+            dev = "cuda:0"
+        feature_input = FeatureInput(f0_method=f0method, exp_dir=exp_dir, device=dev, version=version, if_f0=if_f0, model=hubert_model,
+                                     hop_size=crepe_hop_length)
+        inp_root = os.path.join(exp_dir, "1_16k_wavs")
+        opt_root1 = os.path.join(exp_dir, "2a_f0")
+        opt_root2 = os.path.join(exp_dir, "2b-f0nsf")
+        opt_root3 = os.path.join(exp_dir, "3_feature256" if version == "v1" else "3_feature768")
+        for d in (opt_root1, opt_root2, opt_root3):
+            os.makedirs(d, exist_ok=True)
+        paths = []
+        for name in sorted(list(os.listdir(inp_root))):
+            inp_path = os.path.join(inp_root, name)
+            if "spec" in inp_path:
+                continue
+            out_name = ",".join([str(f0method), name])
+            paths.append([inp_path, os.path.join(opt_root1, out_name), os.path.join(opt_root2, out_name), os.path.join(opt_root3, out_name)])
+        n_p = max(int(n_p), 1)
+        for i in range(n_p):
+            feature_input.go(paths[i::n_p])
+        print(f"Successfully extracted features using {f0method}")
+        return True
+    except Exception as e:   # noqa: BLE001 - reference behaviour
+        print(f"Failed to extract features: {e}")
+        return False

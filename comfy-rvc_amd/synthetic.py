@@ -447,6 +447,31 @@ def synth_audio(seconds, seed=0, sr=16000):
     return x.astype(np.float32)
 
 
+# the recording the dataset-preparation tests slice (tests/golden/slicer_cases.npz holds what the reference's Slicer / Preprocess make of it):
+# ("s" | "v", seconds) segments; silences of 0.3 - 1.3 s between voiced stretches reach the leading-silence cut, the "<= 2 x max_sil_kept" and
+# the long-silence cut positions and the trailing tag of the slicer
+SLICER_SEGMENTS = (("s", 0.9), ("v", 2.2), ("s", 0.3), ("v", 1.1), ("s", 0.7), ("v", 4.6), ("s", 1.3), ("v", 0.8), ("s", 0.45), ("v", 1.9),
+                   ("s", 0.6))
+# a 0.48 s silence after 2 s of signal: the "<= max_sil_kept" cut position, which the recording above does not reach
+SLICER_SEGMENTS_SHORT_SIL = (("s", 0.2), ("v", 2.0), ("s", 0.48), ("v", 2.5), ("s", 0.2))
+
+
+def slicer_test_signal(sr, seed=0, segments=SLICER_SEGMENTS):
+    """float32 recording at `sr` of voiced ("v": AM'd tone of 110 - 330 Hz at 0.3 plus noise at 0.02) and near-silent ("s": noise at 2e-4, slowly
+    modulated) segments; one generator, drawn in segment order (a voiced segment draws its frequency first, then its noise)."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for kind, seconds in segments:
+        n = int(round(seconds * sr))
+        t = np.arange(n, dtype=np.float64) / sr
+        if kind == "v":
+            f = rng.uniform(110.0, 330.0)
+            parts.append(0.3 * np.sin(2 * np.pi * f * t) * (0.6 + 0.4 * np.sin(2 * np.pi * 3 * t)) + 0.02 * rng.standard_normal(n))
+        else:
+            parts.append(2e-4 * rng.standard_normal(n) * (1 + 0.5 * np.sin(2 * np.pi * 1.7 * t)))
+    return np.concatenate(parts).astype(np.float32)
+
+
 def designed_f0(n_frames, seed=0):
     """A voiced/unvoiced contour at 100 fps (Hz, 0 = unvoiced) for driving the synthesizer directly."""
     t = np.arange(n_frames, dtype=np.float64) / 100.0

@@ -258,6 +258,29 @@ int rvc_preprocess(void* stream, const void* audio_dev, int is_f64, int64_t n, c
  * place; rms1_dev = RMS frames of the 16 kHz input (float64 [n1], hop 0.5 s); sr2 = output rate. */
 int rvc_postprocess(void* stream, float* wav_dev, int64_t N, const double* rms1_dev, int n1, int sr2, float rms_mix_rate, int16_t* out_i16_dev);
 
+/* ------------------------------------------------------------------ training-set preparation (reference preprocessing_utils.py:13-100) */
+/* The slicer's forward high-pass: y_dev [n] float64 = scipy.signal.lfilter(bh, ah, x) from a zero state, bh, ah = butter(5, 48, "high", fs=sr),
+ * with the filter given as its three normalised second-order sections sos18_host [3][6] (scipy.signal.butter(..., output="sos")) and evaluated
+ * block-propagated in that cascade form (5 launches for any n).  x_dev [n] float32 (is_f64 = 0) or float64 (1).  Accurate to ~1e-13; scipy's
+ * transfer-function loop carries 1e-6 .. 1e-5 of full scale of rounding noise at 32 - 48 kHz, so the two differ by THAT. */
+int rvc_lfilter_hp(void* stream, const void* x_dev, int is_f64, int64_t n, const double* sos18_host, double* y_dev);
+/* librosa-style centred framed RMS (lib/slicer2.py::get_rms): zero padding of win / 2 on both sides, frame j = sqrt(mean(x[j hop - win / 2 ...]^2))
+ * in float64, n_frames = (n + 2 (win / 2) - win) / hop + 1.  One launch. */
+int rvc_frame_rms(void* stream, const double* x_dev, int64_t n, int win, int hop, double* rms_dev, int64_t n_frames);
+/* The silence scan of Slicer.slice over a HOST RMS list (no device work): the (begin, end) frame pairs of the silences to drop -> tags_host
+ * [cap][2], their number -> *n_tags.  min_length / min_interval / max_sil_kept in frames, as Slicer.__init__ derives them; n_samples <=
+ * min_length returns no tags (the whole recording is one clip).  cap = n_frames + 1 always suffices. */
+int rvc_slice_tags(const double* rms_host, int64_t n_frames, int64_t n_samples, double threshold, int64_t min_length, int64_t min_interval,
+                   int64_t max_sil_kept, int64_t* tags_host, int64_t cap, int64_t* n_tags);
+/* Cuts filt_dev [n] float64 into the windows (start, length) of windows_dev [n_windows][2] (int64): gt_dev = every window cast to float32, packed
+ * (total_gt = sum of lengths); y16_dev = every window resampled to target_sr exactly as rvc_resample would resample that float32 window on its
+ * own (same taps, zero extension at the window's edges, ceil(length * target_sr / sr) outputs), then divided by m = max|y| / max_volume where
+ * m > 1 (float32, lib/audio.py::remix_audio), packed (total_16 = sum of the output lengths).  Four launches however many windows.  Samples
+ * outside [0, n) read as zero; nothing is written beyond total_gt / total_16. */
+int rvc_cut_windows(void* stream, const double* filt_dev, int64_t n, const int64_t* windows_dev, int n_windows, int sr, int target_sr,
+                    const double* taps_dev, int half, int up, int down, float max_volume, float* gt_dev, int64_t total_gt, float* y16_dev,
+                    int64_t total_16);
+
 /* ------------------------------------------------------------------ single ops (parity tests / kernel benchmarks) */
 /* Conv1d: x_dev [Ci][Tin], w_host [Co][Ci/groups][k], y_dev [Co][Tout]; act codes: 0 none 1 lrelu 2 relu 3 gelu 4 tanh 5 sigmoid */
 int rvc_op_conv1d(void* stream, const float* x_dev, const float* w_host, const float* bias_host, const float* res_dev, float* y_dev,
