@@ -22,8 +22,8 @@ WEB_DIRECTORY = None
 
 def __getattr__(name):
     if name in ("NODE_CLASS_MAPPINGS", "NODE_DISPLAY_NAME_MAPPINGS"):
-        from .custom_nodes import rvc_nodes as _n, uvr as _u
-        globals()["NODE_CLASS_MAPPINGS"] = {**_u.NODE_CLASS_MAPPINGS, **_n.NODE_CLASS_MAPPINGS}
+        from .custom_nodes import audio_nodes as _a, rvc_nodes as _n, uvr as _u
+        globals()["NODE_CLASS_MAPPINGS"] = {**_u.NODE_CLASS_MAPPINGS, **_n.NODE_CLASS_MAPPINGS, **_a.NODE_CLASS_MAPPINGS}
         globals()["NODE_DISPLAY_NAME_MAPPINGS"] = {**_u.NODE_DISPLAY_NAME_MAPPINGS, **_n.NODE_DISPLAY_NAME_MAPPINGS}
         return globals()[name]
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

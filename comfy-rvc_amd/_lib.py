@@ -126,6 +126,14 @@ SIGNATURES = {
     "rvc_slice_tags": (c_int, [c_void_p, c_int64, c_int64, C.c_double, c_int64, c_int64, c_int64, c_void_p, c_int64, P(c_int64)]),
     "rvc_cut_windows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int64,
                                 c_void_p, c_int64]),
+    "rvc_gate_levels": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64]),
+    "rvc_gate_ranges": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, C.c_double, c_void_p, c_int64, P(c_int64)]),
+    "rvc_gate_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64]),
+    "rvc_declick": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "rvc_peak_normalize": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
+    "rvc_peak_limit": (c_int, [c_void_p, c_void_p, c_int64, c_float]),
+    "rvc_merge_tracks": (c_int, [c_void_p, P(c_void_p), P(c_int64), c_int, c_int, c_void_p, c_int64]),
+    "rvc_segment_energy": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "rvc_op_gemm_split": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_float, c_int, c_float] + [c_int] * 5),
     "rvc_op_conv2d_split": (c_int, [c_void_p] * 7 + [c_int] * 9),
     "rvc_op_wn_in_gate_split": (c_int, [c_void_p] * 6 + [c_int] * 4),

@@ -66,6 +66,27 @@ long long slice_tags(const double* rms, long long nf, long long n_samples, doubl
 void cut_windows(hipStream_t s, const double* filt, long long n, const long long* win, int nw, int sr, int target, const double* taps, int half,
                  int up, int down, float max_volume, float* gt, long long total_gt, float* y16, long long total_16);
 
+// audio nodes (audio_fx.hip)
+constexpr int kMaxClickKernel = 31;      // largest median window of declick
+// ss [n_windows][2]: float64 sums of squares of the (at most two) centred frames of every window of `win` samples; 1 launch
+void gate_levels(hipStream_t s, const float* x, long long n, int win, double* ss, long long n_windows);
+// the silence gate's scan over HOST window levels (dB): (begin, end, kind) ranges -> ranges [cap][3], kind 0 fade-out, 1 zero, 2 fade-in; returns their number
+long long gate_ranges(const double* level, long long nw, long long n, long long win, long long min_size, long long fade, double threshold,
+                      long long* ranges, long long cap);
+// y = x with the ranges (device [nr][3], sorted, disjoint) applied: float64 linspace ramps of `fade` samples, zeros; 1 launch
+void gate_apply(hipStream_t s, const float* x, float* y, long long n, const long long* ranges, int nr, long long fade);
+// click mask (|x| > multiplier * local RMS over `size` samples, reflect boundary) -> mask [n]; clicks replaced by the median of ksize neighbours
+// (method 0, 4 launches) or by linear interpolation between the nearest non-click samples (method 1, 11 launches) -> y [n]; detect 0: mask is an input
+void declick(hipStream_t s, const float* x, long long n, int size, float multiplier, int method, int ksize, int detect, float* y, unsigned char* mask);
+// y = (x - mean(x)) / max|x - mean| * gain in float32 steps, mean and peak by float64 / exact device reductions; 3 launches
+void peak_normalize(hipStream_t s, const float* x, long long n, float gain, float* y);
+// x /= max|x| / max_volume where that exceeds 1 (remix_audio's limiter); 2 launches
+void peak_limit(hipStream_t s, float* x, long long n, float max_volume);
+// out [n_out] = NaN-ignoring mean (mode 0) / median (1) / min (2) / max (3) over k <= 4 zero-extended tracks; 1 launch
+void merge_tracks(hipStream_t s, const float* const* tracks, const long long* lens, int k, int mode, float* out, long long n_out);
+// out [k] = exact int64 sum of squares of every np.array_split segment of the int16 samples; 1 launch
+void segment_energy(hipStream_t s, const short* x, long long n, int k, long long* out);
+
 // padded 2-D split-resident images (split2d.hip): level changes of RMVPE's U-Net in the layout conv_x3s.hip convolves
 void pool2_pad_split(hipStream_t s, const float* x, long long ldx, bool x_padded, int C, int H, int W, float* y, long long ldy, unsigned char* img,
                      long long tp, int margin);

@@ -420,6 +420,76 @@ int rvc_cut_windows(void* stream, const double* filt, int64_t n, const int64_t* 
   RVC_CATCH
 }
 
+// ------------------------------------------------------------------------------------------------ audio nodes (audio_fx.hip)
+int rvc_gate_levels(void* stream, const float* x, int64_t n, int win, double* ss, int64_t n_windows) {
+  RVC_TRY
+  RVC_REQUIRE(x && ss && n > 0 && win > 0, "bad argument");
+  RVC_REQUIRE(n_windows == (n + win - 1) / win && n_windows < (1LL << 31), "ss must hold ceil(n / win) windows");
+  gate_levels((hipStream_t)stream, x, n, win, ss, n_windows);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_gate_ranges(const double* level, int64_t n_windows, int64_t n, int64_t win, int64_t min_size, int64_t fade, double threshold_db,
+                    int64_t* ranges, int64_t cap, int64_t* n_ranges) {
+  RVC_TRY
+  RVC_REQUIRE(level && ranges && n_ranges && n > 0 && win > 0 && cap >= 0, "bad argument");
+  RVC_REQUIRE(n_windows == (n + win - 1) / win, "level must hold ceil(n / win) windows");
+  RVC_REQUIRE(fade >= 2 && min_size >= 2 * fade, "fade >= 2 samples and min_size >= 2 fade");
+  *n_ranges = gate_ranges(level, n_windows, n, win, min_size, fade, threshold_db, (long long*)ranges, cap);
+  RVC_CATCH
+}
+int rvc_gate_apply(void* stream, const float* x, float* y, int64_t n, const int64_t* ranges, int n_ranges, int64_t fade) {
+  RVC_TRY
+  RVC_REQUIRE(x && y && n > 0 && n_ranges >= 0 && (ranges || n_ranges == 0) && fade >= 2, "bad argument");
+  gate_apply((hipStream_t)stream, x, y, n, (const long long*)ranges, n_ranges, fade);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_declick(void* stream, const float* x, int64_t n, int size, float multiplier, int method, int kernel_size, int detect, float* y, uint8_t* mask) {
+  RVC_TRY
+  if (!detect) size = 1;
+  RVC_REQUIRE(x && y && mask && n > 0 && size > 0 && (method == 0 || method == 1) && multiplier >= 0.f, "bad argument");
+  RVC_REQUIRE(kernel_size >= 1 && (kernel_size & 1) && kernel_size <= kMaxClickKernel, "kernel_size must be odd and at most 31");
+  RVC_REQUIRE(n >= size && n >= kernel_size, "the signal must be at least as long as the RMS window and the median window");
+  RVC_REQUIRE(x != y, "declick reads the unmodified input: y must not be x");
+  declick((hipStream_t)stream, x, n, size, multiplier, method, kernel_size, detect != 0, y, mask);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_peak_normalize(void* stream, const float* x, int64_t n, float gain, float* y) {
+  RVC_TRY
+  RVC_REQUIRE(x && y && n > 0 && gain > 0.f, "bad argument");
+  peak_normalize((hipStream_t)stream, x, n, gain, y);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_peak_limit(void* stream, float* x, int64_t n, float max_volume) {
+  RVC_TRY
+  RVC_REQUIRE(x && n > 0 && max_volume > 0.f, "bad argument");
+  peak_limit((hipStream_t)stream, x, n, max_volume);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_merge_tracks(void* stream, const float* const* tracks, const int64_t* lens, int k, int mode, float* out, int64_t n_out) {
+  RVC_TRY
+  RVC_REQUIRE(tracks && lens && out && k >= 2 && k <= 4 && mode >= 0 && mode <= 3 && n_out > 0, "bad argument");
+  long long l[4];
+  for (int j = 0; j < k; ++j) {
+    RVC_REQUIRE(lens[j] >= 0 && lens[j] <= n_out && (tracks[j] || lens[j] == 0), "every track must fit the output");
+    l[j] = lens[j];
+  }
+  merge_tracks((hipStream_t)stream, tracks, l, k, mode, out, n_out);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_segment_energy(void* stream, const int16_t* x, int64_t n, int k, int64_t* out) {
+  RVC_TRY
+  RVC_REQUIRE(x && out && k >= 1 && n >= k, "bad argument");
+  segment_energy((hipStream_t)stream, x, n, k, (long long*)out);
+  check_launch();
+  RVC_CATCH
+}
+
 // ------------------------------------------------------------------------------------------------ single ops
 int rvc_op_conv1d(void* stream, const float* x, const float* w, const float* bias, const float* res, float* y, int Ci, int Co, int Tin, int k,
                   int stride, int pad, int dil, int groups, int pre_act, float pre_slope, int act, float act_slope, int act_before_res,

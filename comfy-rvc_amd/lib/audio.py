@@ -1,4 +1,5 @@
-"""Host-side audio helpers on the inference path (mirror of reference lib/audio.py:14,:115-124,:144-163,:274-304)."""
+"""Audio helpers (mirror of reference lib/audio.py:14,:33-124,:144-163,:257-304): host plumbing of the inference path, and AudioProcessor / merge_audio
+whose sample work runs on the device (lib/audio_fx.py)."""
 import functools
 import math
 from collections.abc import Mapping
@@ -21,6 +22,75 @@ AUTOTUNE_NOTES = np.array([
 def get_merge_func(merge_type):
     """reference lib/utils.py:104-108"""
     return {"min": np.nanmin, "max": np.nanmax, "median": np.nanmedian}.get(merge_type, np.nanmean)
+
+
+def get_hash(*args, **kwargs):
+    """reference lib/utils.py:19-20 (the same function as custom_nodes/rvc_nodes.py::get_hash, which cannot be imported from here)"""
+    import hashlib
+    return hashlib.md5("".join([str(data) for data in args] + list(kwargs.values())).encode()).hexdigest()
+
+
+class AudioProcessor:
+    """Silence gate -> click removal -> peak normalisation (reference lib/audio.py:33-113), every step on the device and the samples kept there
+    between the steps.  Constructor arguments, defaults and __str__ (the hash RVCProcessDatasetNode puts into its cache key) are the reference's.
+    Deviations: a signal with several channels is averaged to mono first (Silent takes one channel, lib/karafan/audio_utils.py); __call__ also
+    takes the (samples, sr) two-argument form Preprocess uses."""
+
+    def __init__(self, normalize=True, threshold_silence=True, dynamic_threshold=True, sample_size=16000, multiplier=2.0, fill_method="median",
+                 kernel_size=5, silence_threshold_db=-50, normalize_threshold_db=-1):
+        self.normalize = normalize
+        self.threshold_silence = threshold_silence
+        self.dynamic_threshold = dynamic_threshold
+        self.sample_size = sample_size
+        self.multiplier = multiplier
+        self.fill_method = fill_method
+        self.kernel_size = kernel_size
+        self.silence_threshold_db = silence_threshold_db
+        self.normalize_threshold_db = normalize_threshold_db
+
+    def __str__(self):
+        values = [self.normalize, self.threshold_silence, self.dynamic_threshold]
+        if self.normalize:
+            values.append(self.normalize_threshold_db)
+        if self.threshold_silence:
+            values.append(self.silence_threshold_db)
+        if self.dynamic_threshold:
+            values.extend([self.sample_size, self.multiplier, self.fill_method, self.kernel_size])
+        return get_hash(*values)
+
+    def __call__(self, audio, sr=None, device="cuda:0"):
+        """AUDIO dict, VHS_AUDIO thunk or (samples, sr) - or samples and sr as two arguments -> (float32 samples [n], sr)."""
+        from . import audio_fx
+        from .karafan.audio_utils import Normalize, Silent
+        samples, sr = get_audio(audio) if sr is None else (audio, sr)
+        samples = np.asarray(samples, dtype=np.float32)
+        if samples.ndim > 1:                                         # [n, C] of get_audio, or [C, n]: the short axis holds the channels
+            samples = samples.mean(axis=int(np.argmin(samples.shape)), dtype=np.float32)
+        x = audio_fx.to_device(samples, device)
+        if self.threshold_silence:
+            x = Silent(x, sample_rate=sr, threshold_dB=self.silence_threshold_db)
+        if self.dynamic_threshold:
+            x = self.dynamic_thresholding(x, multiplier=self.multiplier, sample_size=self.sample_size, method=self.fill_method,
+                                          kernel_size=self.kernel_size)
+        if self.normalize:
+            x = Normalize(x, threshold_dB=self.normalize_threshold_db)
+        return x.cpu().numpy(), sr
+
+    @staticmethod
+    def dynamic_thresholding(samples, multiplier=2., sample_size=16000, method="median", kernel_size=5):
+        """Samples above multiplier x the local RMS (over sample_size samples) are clicks and are replaced (numpy in -> numpy out, CUDA tensor in ->
+        CUDA tensor out).  The signal must be at least sample_size and kernel_size long (ValueError): a window longer than the signal would need
+        repeated reflection, which this build does not implement."""
+        from . import audio_fx
+        y = audio_fx.declick(samples, multiplier=multiplier, sample_size=int(sample_size), method=method, kernel_size=kernel_size)
+        return y if hasattr(samples, "is_cuda") else y.cpu().numpy()
+
+    @staticmethod
+    def replace_clicks(samples, clicks, method="median", kernel_size=5):
+        """The reference's fill step for a given click mask (lib/audio.py:89-113): the same device fill as dynamic_thresholding, detection skipped."""
+        from . import audio_fx
+        y = audio_fx.declick(samples, method=method, kernel_size=kernel_size, clicks=clicks)
+        return y if hasattr(samples, "is_cuda") else y.cpu().numpy()
 
 
 def hz_to_mel(hz):
@@ -200,3 +270,16 @@ def pad_audio(*audios, axis=0):
     arrs = [a for a in audios if a is not None]
     maxlen = max((len(a) for a in arrs), default=0)
     return np.stack([np.pad(a, (0, maxlen - len(a))) for a in arrs], axis=axis)
+
+
+def merge_audio(audio1, audio2, sr=40000, **kwargs):
+    """Two (samples, sr) tracks at `sr` (None: the lower of their rates), zero-extended to the longer, averaged and peak-limited (reference
+    lib/audio.py:264-272).  The per-sample mean and the limiter run on the device (rvc_merge_tracks, rvc_peak_limit)."""
+    from . import audio_fx
+    if sr is None:
+        sr = min(audio1[-1], audio2[-1])
+    m1, _ = remix_audio(audio1, target_sr=sr, axis=0, **kwargs)
+    m2, _ = remix_audio(audio2, target_sr=sr, axis=0, **kwargs)
+    mixed = audio_fx.merge_tracks([m1, m2], kwargs.get("merge_type"), **{k: v for k, v in kwargs.items() if k == "device"})
+    audio_fx.peak_limit_(mixed, kwargs.get("max_volume", .95))
+    return mixed.cpu().numpy(), sr

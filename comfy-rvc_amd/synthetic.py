@@ -472,6 +472,16 @@ def slicer_test_signal(sr, seed=0, segments=SLICER_SEGMENTS):
     return np.concatenate(parts).astype(np.float32)
 
 
+def add_clicks(x, seed=0):
+    """The click recipe of the audio-effect tests (tests/golden/audio_fx_cases.npz): +-0.5 impulses written over len(x) // 2000 distinct positions
+    drawn from default_rng(seed) -> (float32 copy, sorted positions)."""
+    rng = np.random.default_rng(seed)
+    y = np.array(x, dtype=np.float32)
+    pos = np.sort(rng.choice(y.shape[0], size=y.shape[0] // 2000, replace=False))
+    y[pos] = np.where(rng.random(pos.shape[0]) < 0.5, np.float32(-0.5), np.float32(0.5))
+    return y, pos
+
+
 def designed_f0(n_frames, seed=0):
     """A voiced/unvoiced contour at 100 fps (Hz, 0 = unvoiced) for driving the synthesizer directly."""
     t = np.arange(n_frames, dtype=np.float64) / 100.0

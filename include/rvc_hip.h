@@ -281,6 +281,44 @@ int rvc_cut_windows(void* stream, const double* filt_dev, int64_t n, const int64
                     const double* taps_dev, int half, int up, int down, float max_volume, float* gt_dev, int64_t total_gt, float* y16_dev,
                     int64_t total_16);
 
+/* ------------------------------------------------------------------ audio nodes (reference lib/audio.py, lib/karafan/audio_utils.py, custom_nodes/audio_nodes.py) */
+/* Silence gate, step 1 (lib/karafan/audio_utils.py:129-132): for every window of `win` samples of x_dev [n] float32 (n_windows = ceil(n / win), the
+ * last one may be short) the float64 sums of squares of the frames librosa.feature.rms(frame_length=win, hop_length=win) takes of that window
+ * alone, centred and zero-padded: frame f covers samples [f win - win / 2, f win - win / 2 + win) of the window.  ss_dev [n_windows][2]; a
+ * window of `len` samples has 1 + (len + 2 (win / 2) - win) / win frames (1 or 2), the caller ignores the other entry.  One launch. */
+int rvc_gate_levels(void* stream, const float* x_dev, int64_t n, int win, double* ss_dev, int64_t n_windows);
+/* Silence gate, step 2 (lib/karafan/audio_utils.py:125-165; host, no device work): the reference's loop over the window levels level_db_host
+ * [n_windows] (max over the frames of 20 log10(max(1e-5, rms))) with its start / end bookkeeping and its last-window branch -> ranges_host
+ * [cap][3] of (begin, end, kind), kind 0 = fade-out, 1 = zero, 2 = fade-in, ascending and disjoint; their number -> *n_ranges.
+ * cap = 3 n_windows always suffices. */
+int rvc_gate_ranges(const double* level_db_host, int64_t n_windows, int64_t n, int64_t win, int64_t min_size, int64_t fade, double threshold_db,
+                    int64_t* ranges_host, int64_t cap, int64_t* n_ranges);
+/* Silence gate, step 3 (lib/karafan/audio_utils.py:140-163): y_dev = x_dev with every range of ranges_dev [n_ranges][3] applied - the fades are
+ * np.linspace(1, 0, fade) / np.linspace(0, 1, fade) in float64 multiplied into the float32 samples.  y_dev may be x_dev.  One launch. */
+int rvc_gate_apply(void* stream, const float* x_dev, float* y_dev, int64_t n, const int64_t* ranges_dev, int n_ranges, int64_t fade);
+/* Click removal (lib/audio.py:74-113, AudioProcessor.dynamic_thresholding / replace_clicks): mask_dev [n] (uint8) = |x| > multiplier *
+ * sqrt(uniform_filter1d(x^2, size)) with scipy's "reflect" boundary and window [i - size / 2, i - size / 2 + size); the window sum in float64 over
+ * the float32 squares, then float32 mean, sqrtf and multiply as the reference's float32 arrays take them.  y_dev [n] = x with the clicks replaced:
+ * method 0 "median" - the median of kernel_size (odd, <= 31) neighbours of the unmodified input, reflect boundary (4 launches); method 1
+ * "interpolation" - interp1d(kind="linear", fill_value="extrapolate") over the non-click samples (11 launches; with fewer than two non-click
+ * samples the clicks stay).  Needs n >= size and n >= kernel_size (one reflection).  detect = 0 (replace_clicks, lib/audio.py:89-113): mask_dev
+ * is the CALLER'S mask and only the fill runs; size and multiplier are not read. */
+int rvc_declick(void* stream, const float* x_dev, int64_t n, int size, float multiplier, int method, int kernel_size, int detect, float* y_dev,
+                uint8_t* mask_dev);
+/* Peak normalisation (lib/karafan/audio_utils.py:89-107, Normalize): y = (x - mean) / max|x - mean| * gain, gain = 10^(threshold_dB / 20) as
+ * float32; the mean is a float64 device reduction rounded to float32, the other steps are the reference's float32 steps; a peak of 0 leaves
+ * x - mean.  y_dev may be x_dev.  3 launches. */
+int rvc_peak_normalize(void* stream, const float* x_dev, int64_t n, float gain, float* y_dev);
+/* The limiter at the end of lib/audio.py::remix_audio (:157-158), in place: m = max|x| / max_volume; m > 1: x / m.  2 launches. */
+int rvc_peak_limit(void* stream, float* x_dev, int64_t n, float max_volume);
+/* Track merge (custom_nodes/audio_nodes.py:152-170 -> lib/audio.py::pad_audio, lib/utils.py::get_merge_func): k = 2..4 float32 tracks
+ * (tracks_host: k device pointers, lens_host: their lengths) zero-extended to n_out >= every length and reduced per sample by np.nanmean
+ * (mode 0), np.nanmedian (1), np.nanmin (2) or np.nanmax (3) in numpy's float32 operation order; all-NaN gives NaN.  One launch. */
+int rvc_merge_tracks(void* stream, const float* const* tracks_host, const int64_t* lens_host, int k, int mode, float* out_dev, int64_t n_out);
+/* Segment energy (custom_nodes/audio_nodes.py:307-317, AudioBatchValueNode.get_rms over np.array_split): out_dev [k] = exact int64 sum of squares
+ * of every array_split segment of x_dev [n] int16 (the first n % k segments one sample longer), k <= n.  One launch. */
+int rvc_segment_energy(void* stream, const int16_t* x_dev, int64_t n, int k, int64_t* out_dev);
+
 /* ------------------------------------------------------------------ single ops (parity tests / kernel benchmarks) */
 /* Conv1d: x_dev [Ci][Tin], w_host [Co][Ci/groups][k], y_dev [Co][Tout]; act codes: 0 none 1 lrelu 2 relu 3 gelu 4 tanh 5 sigmoid */
 int rvc_op_conv1d(void* stream, const float* x_dev, const float* w_host, const float* bias_host, const float* res_dev, float* y_dev,
