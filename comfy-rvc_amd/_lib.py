@@ -104,6 +104,16 @@ SIGNATURES = {
     "rvc_synth_has_f0": (c_int, [c_void_p]),
     "rvc_synth_infer": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                 c_void_p, P(SynthTaps)]),
+    "rvc_synth_infer_window": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                       c_void_p, P(SynthTaps), c_int64, c_int64]),
+    "rvc_synth_dec_halo": (c_int, [c_void_p]),
+    "rvc_synth_window_frames": (c_int, [c_void_p, c_int64, c_int64, c_int64, P(c_int64), P(c_int64)]),
+    "rvc_synth_infer_window_halo": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                            c_void_p, P(SynthTaps), c_int64, c_int64, c_int]),
+    "rvc_vc_segment_window": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_float, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_int64, c_int64]),
+    "rvc_vc_segment_feats_window": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p,
+                                            c_void_p, c_void_p, c_int64, c_int64]),
     "rvc_vc_segment": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_float, c_int,
                                c_void_p, c_void_p, c_void_p]),
     "rvc_vc_segment_feats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p,

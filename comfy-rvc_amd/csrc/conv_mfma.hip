@@ -776,7 +776,15 @@ static void launch_cfg(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s)
   conv_launch(kern, grid, dim3(256), lds, s, a);
 }
 
+static thread_local long long t_plan_win = 0, t_plan_full = 0;
+long long conv_plan_len(long long n) { return t_plan_win > 0 ? (n * t_plan_full + t_plan_win - 1) / t_plan_win : n; }
+ConvPlanLenScope::ConvPlanLenScope(long long win, long long full) : prev_win(t_plan_win), prev_full(t_plan_full) {
+  if (win > 0 && full > win) { t_plan_win = win; t_plan_full = full; } else { t_plan_win = 0; t_plan_full = 0; }
+}
+ConvPlanLenScope::~ConvPlanLenScope() { t_plan_win = prev_win; t_plan_full = prev_full; }
+
 TileCfg choose_tile(int M, long long N, int batch) {
+  N = conv_plan_len(N);                                       // (a tile is a kernel choice: planned for the whole sequence)
   // candidates ordered by preference for large problems; pick the first that yields enough workgroups
   const int Mp = (M + 31) / 32 * 32;
   TileCfg best{2, 2, 1, 1};
@@ -954,7 +962,7 @@ static void run_conv(ConvArgsX a, int mode, int batch, hipStream_t s, double flo
               (double)a.Ci * (double)a.ldX * 4.0 < 2147483648.0, "tensor extent exceeds the 32-bit buffer addressing of the conv kernel");
   // split-K: small grids (deep U-Net levels, 1599-frame GEMMs) leave most CUs idle and expose every stage's load latency;
   // slicing the reduction over S workgroups restores occupancy.  Partials are reduced in a fixed order (deterministic).
-  const long long nblk = (long long)((a.Tout + BN - 1) / BN) * ((a.Co + BM - 1) / BM) * batch;
+  const long long nblk = ((conv_plan_len(a.Tout) + BN - 1) / BN) * ((a.Co + BM - 1) / BM) * batch;      // (the K split is part of the sum order: planning length)
   int S = 1;
   static const int max_split = exp_int("RVC_SPLITK", 8);
   static const int split_blk = exp_int("RVC_SPLITK_BLK", 400);
@@ -1068,7 +1076,7 @@ bool conv1d_pair_h2_eligible(const ConvLayer& c1, const ConvLayer& c2, int Tin, 
   return conv1d_split_eligible(c1, Tin, SPLIT_PRODUCER, 1) && conv1d_split_eligible(c2, Tin, SPLIT_CONSUMER, 1);
 }
 
-bool conv1d_split_eligible(const ConvLayer& L, int Tin, SplitRole role, int h2) {
+static bool plan_split_role(const ConvLayer& L, int Tin, SplitRole role, int h2, ConvPlan& p) {
   if (L.mode != 1 || !L.Wx_ || (h2 && !L.Wh_) || L.tconv_u || L.stride != 1 || L.groups != 1 || (L.Co & 31) || (L.Ci & 15)) return false;
   if (conv1d_out_len(L, Tin) != Tin || L.pad > kSplitMargin) return false;      // the image is addressed as a "same" convolution's: row = margin + t
   ConvArgsX a{};
@@ -1079,8 +1087,17 @@ bool conv1d_split_eligible(const ConvLayer& L, int Tin, SplitRole role, int h2) 
   // any non-null value asks for the role's geometry (planning only: never dereferenced)
   if (role == SPLIT_PRODUCER) { a.Ys = reinterpret_cast<unsigned char*>(L.Wx_); a.ysTp = split_image_tp(Tin); a.pre_act = ACT_LRELU; a.pre_slope = 0.1f; }
   else { a.Xs = reinterpret_cast<const unsigned char*>(L.Wx_); a.xsTp = split_image_tp(Tin); }
-  ConvPlan p;
   return conv_x3_plan(a, 1, p);
+}
+bool conv1d_split_eligible(const ConvLayer& L, int Tin, SplitRole role, int h2) { ConvPlan p; return plan_split_role(L, Tin, role, h2, p); }
+
+int conv1d_residual_period(const ConvLayer& L, int Tin, int h2) {
+  ConvPlan p;
+  if (!plan_split_role(L, Tin, SPLIT_CONSUMER, h2, p) || (p.prof_fused >> 4) != 6) return 1;
+  // conv_x3q_kernel: the residual and the bias of accumulator block b = (row block) AN + (32-column block) join the sum after chunk b (conv_x3q.hip, step E):
+  // the order of a column's fp32 additions repeats with the tile's width
+  const int id = p.prof_cfg - 14;
+  return id == 3 ? 128 : 256;                                  // 2 x 2 x 2 x 2: 128 columns; 2 x 2 x 1 x 4 and 2 x 2 x 2 x 4: 256
 }
 
 void gemm_tn_run(hipStream_t s, const float* A, long long ldA, long long aBatch, const float* B, long long ldB, long long bBatch,

@@ -382,7 +382,7 @@ bool conv_rb3_plan(const ConvLayer* const* c1, const ConvLayer* const* c2, const
   if (nsrc && C != 32) return false;
   const int ncu = device_cu_count();
   const long long ntiles = ((long long)T + NO - 1) / NO;
-  if (ntiles < 2LL * ncu) return false;                       // short sequences: the pair kernels' smaller tiles fill the chip better
+  if ((conv_plan_len(T) + NO - 1) / NO < 2LL * ncu) return false;      // short sequences: the pair kernels' smaller tiles fill the chip better
   p = Rb3Plan{};
   p.C = C; p.k = k; p.accumulate = accumulate;
   Rb3Args& a = p.a;

@@ -294,7 +294,7 @@ bool conv_rbh_plan(ConvPlan& p, int T) {
   if (P > 576 || a.dil < 1) return false;
   const int ncu = device_cu_count();
   const long long ntiles = ((long long)T + NO - 1) / NO;
-  if (ntiles < 2LL * ncu) return false;                       // short sequences: conv_x3pf_kernel's smaller tiles fill the chip better
+  if ((conv_plan_len(T) + NO - 1) / NO < 2LL * ncu) return false;      // short sequences: conv_x3pf_kernel's smaller tiles fill the chip better
   a.WROW = P; a.ni = (P + 63) / 64;
   p.lds = (size_t)2 * (2 * a.ktaps) * 2 * 32 * 16 + 256 + (size_t)2 * 2 * P * 32;
   p.grid = dim3((unsigned)(ntiles < ncu ? ntiles : ncu), 1, 1);

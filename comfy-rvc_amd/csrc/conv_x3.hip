@@ -546,7 +546,7 @@ bool conv_x3_plan(const ConvArgsX& a0, int batch, ConvPlan& p) {
     // per output halves with twice the positions per workgroup; taken when the grid still fills the chip several times over
     // (measured: C128 k11 610 -> 470 us; deeper weight buffering instead of wider tiles was slower)
     static const int wide_blk = exp_int("RVC_X3_WIDE", 600);
-    auto blocks = [&](int bm, int bn) { return (long long)((a.Co + bm - 1) / bm) * ((a.Tout + bn - 1) / bn); };
+    auto blocks = [&](int bm, int bn) { return (long long)((a.Co + bm - 1) / bm) * ((conv_plan_len(a.Tout) + bn - 1) / bn); };
     if (wide_blk > 0 && a.stride == 1 && a.Wd == 0) {
       // (k <= 3 at 128+ channels is HBM-bound: three 128 x 128 workgroups per CU beat two wide ones, C128 k3 238 -> 219 us)
       // (round 2, after the staging / epilogue changes and with split-resident inputs: the 64 x 256 tile at three workgroups per CU now
@@ -564,7 +564,7 @@ bool conv_x3_plan(const ConvArgsX& a0, int batch, ConvPlan& p) {
   if ((xs || a0.Ys) && !(id == 3 || id == 4 || id == 7)) return false;             // tiles instantiated with the split-resident paths
   if (xs && a0.Ys) return false;                                                    // (one side at a time)
   const int BM = t.WM * t.AM * 32, BN = t.WN * t.AN * 32;
-  const long long nblk = (long long)((a.Tout + BN - 1) / BN) * ((a.Co + BM - 1) / BM);
+  const long long nblk = ((conv_plan_len(a.Tout) + BN - 1) / BN) * ((a.Co + BM - 1) / BM);      // decisions (fp32 fall-back, K split): planning length; the grid below: a.Tout
   static const int min_blk = exp_int("RVC_X3_MINBLK", 250);
   static const int min_blk2d = exp_int("RVC_X3_MINBLK2D", 20);   // deep U-Net levels: bf16x3 + split-K beats fp32 + split-K
   if (nblk < (a.Wd > 0 ? min_blk2d : min_blk)) return false;   // under-filled grids go to the fp32 kernel's split-K path
@@ -658,7 +658,7 @@ bool conv_x3_pair_plan(const ConvLayer& c1, const ConvLayer& c2, const float* X,
   const int BN = C == 64 ? 128 : 256;
   const int P2 = (k - 1) / 2, P1 = c1.pad;
   const int NO = BN - 2 * P2;
-  if ((long long)(T + NO - 1) / NO < 512) return false;          // short sequences: the unfused path fills the chip better
+  if ((conv_plan_len(T) + NO - 1) / NO < 512) return false;      // short sequences: the unfused path fills the chip better
   p = ConvPlan{};
   ConvArgsX& a = p.a;
   a.X = X; a.ldX = ldX; a.Y = Y; a.ldY = ldY; a.W = nullptr; a.bias = c2.bd_; a.bias1 = c1.bd_;

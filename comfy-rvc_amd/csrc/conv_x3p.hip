@@ -994,14 +994,14 @@ bool conv_x3g_plan(ConvPlan& p) {
   if (two_d && a.Ci >= 512 && a.Co <= 512 && a.Tout < 1000) return false;
   // 1-D with taps: only where the tiled kernels would not run (grids below their minimum: the 100-frames-per-second layers)
   const bool taps1d = !two_d && a.ktaps > 1;
-  if (taps1d && !(a.ktaps <= 16 && (long long)((a.Co + 127) / 128) * ((a.Tout + 127) / 128) < 250)) return false;
+  if (taps1d && !(a.ktaps <= 16 && (long long)((a.Co + 127) / 128) * ((conv_plan_len(a.Tout) + 127) / 128) < 250)) return false;
   if (a.stride != 1 || a.ostride != 1 || a.Xs || a.Ys || (a.Ci & 15)) return false;
   if (!two_d && !taps1d && a.Tin != a.Tout) return false;
   // 64-row tiles for short reductions (K <= 1024: q/k/v 49 -> 40 us, flow 192 -> 192 16 -> 11), 128-row tiles for long ones (FFN2, K = 3072: 61 vs 75 us)
   const int AM = (a.Co > 64 && a.Ci * a.ktaps > 1024) ? 2 : 1, BM = 64 * AM, BN = 128;
   const int U = a.Ci / 16 * a.ktaps;
   if ((U & 3) || U < 8) return false;                              // unit loop unrolled by four
-  const long long nblk = (long long)((a.Co + BM - 1) / BM) * ((a.Tout + BN - 1) / BN);
+  const long long nblk = (long long)((a.Co + BM - 1) / BM) * ((conv_plan_len(a.Tout) + BN - 1) / BN);      // (eligibility and K split: planning length)
   static const int min_blk = exp_int("RVC_X3G_MINBLK", 24);
   if (nblk < (two_d ? 8 : min_blk)) return false;
   // K split: enough workgroups for the chip (a 128 x 128 tile of a K = 768 GEMM is 9 us of MFMAs), at least 8 units per split, groups of 4
@@ -1040,7 +1040,7 @@ bool conv_x3pf_plan(ConvPlan& p, int T) {
   const int P = BN + (a.ktaps - 1) * a.dil;
   if (P > BN + 64) return false;
   const int NO = BN - (a.ktaps - 1);
-  if ((long long)(T + NO - 1) / NO < 512) return false;          // short sequences: the unfused path fills the chip better
+  if ((conv_plan_len(T) + NO - 1) / NO < 512) return false;      // short sequences: the unfused path fills the chip better
   a.WROW = P; a.ni = (P + 63) / 64;
   p.lds = (size_t)(((C / 16) * 2 * P * 32 + 1023) & ~1023) + 4 * (size_t)(2 * C * 32);
   p.grid = dim3((unsigned)((T + NO - 1) / NO), 1, 1);

@@ -671,7 +671,8 @@ static thread_local int t_force_s = 0, t_force_am = 0, t_force_an = 0;
 void conv_x3s_force(int ksplit, int am, int an) { t_force_s = ksplit; t_force_am = am; t_force_an = an; }
 static void x3s_plan(int M, int N, int units, int& AM, int& AN, int& S, int groups = 1) {
   static const int target = exp_int("RVC_X3S_BLK", 440);
-  auto tiles = [&](int am, int an) { return (long long)groups * ((M + 64 * am - 1) / (64 * am)) * ((N + 64 * an - 1) / (64 * an)); };
+  const long long Np = conv_plan_len(N);                     // tile and K split (the sum order) are planned for the whole sequence, the grid covers the columns there are
+  auto tiles = [&](int am, int an) { return (long long)groups * ((M + 64 * am - 1) / (64 * am)) * ((Np + 64 * an - 1) / (64 * an)); };
   // measured on MI355X at N = 1599 (tools/bench_gemm.py, profiles/r3b_bench_gemm.txt): 768 -> 3072 128 x 64 35 us (64 x 128 the same, 128 x 128 38),
   // 768 -> 2304 128 x 64 28 us, 768 -> 768 64 x 64 16.3 us un-split (17.6 split in two), 3072 -> 768 64 x 64 split in two 37.8 us (128 x 64 in three 39.0)
   AM = 2; AN = 2;

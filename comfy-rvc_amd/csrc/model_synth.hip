@@ -66,7 +66,7 @@ struct Synth {
   DevVec dec_cond_w, dec_cond_b, conv_post_w;   // conv_post_w: raw [Ci][7] weights of the 1-channel output conv (ops.hip::conv_to1)
   std::vector<GenStage> stages;
   float lin_w = 1.f, lin_b = 0.f;
-  const void* img_base = nullptr; unsigned img_gen = 0; size_t img_bytes = 0; int img_T = -1;   // split-resident image block whose margins are known to be zero (synth_graph)
+  const void* img_base = nullptr; unsigned img_gen = 0; size_t img_bytes = 0; int img_T = -1, img_W = -1;   // split-resident image block whose margins are known to be zero (synth_graph); img_W: columns of the z image (the generator's window)
   bool f0 = true;        // false: the *_nono family (no pitch embedding, plain Generator: reference models.py:244-311,:812-1022)
 };
 
@@ -80,7 +80,7 @@ static void synth_free(Synth& S) {
   fl(S.conv_pre); S.dec_cond_w.free_(); S.dec_cond_b.free_(); S.conv_post_w.free_();
   for (auto& st : S.stages) { fl(st.up); fl(st.noise); st.noise_w.free_(); st.noise_b.free_(); for (auto& rb : st.rb) for (int m = 0; m < 3; ++m) { fl(rb.c1[m]); fl(rb.c2[m]); } }
   S.stages.clear();
-  S.img_base = nullptr; S.img_gen = 0; S.img_bytes = 0; S.img_T = -1;
+  S.img_base = nullptr; S.img_gen = 0; S.img_bytes = 0; S.img_T = -1; S.img_W = -1;
 }
 
 Synth* synth_create(Ctx* ctx, const SynthConfig& c) {
@@ -101,6 +101,30 @@ void synth_set_tensor(Synth* S, const char* name, const float* d, const long lon
 int synth_upp(const Synth* S) { return S->upp; }
 int synth_feat_dim(const Synth* S) { return S->feat_dim; }
 bool synth_has_f0(const Synth* S) { return S->f0; }
+
+// Frames of z on either side of a kept output window that the generator's result inside the window depends on (GeneratorNSF / Generator, reference
+// lib/infer_pack/models.py:460-566,:244-311): the layer table walked backwards from the waveform.  h = reach in samples at the current rate.
+//   conv_post (k = 7)                                  h += (k - 1) / 2
+//   per stage, the widest ResBlock1                    h += sum_m [(k - 1) / 2 * d_m + (k - 1) / 2]      (convs1 dilated, convs2 plain)
+//   ConvTranspose1d(k_u, stride u, padding p)          output t reads inputs q with t = q u - p + j, 0 <= j < k_u: for outputs from A u - h to B u - 1 + h (A, B whole
+//                                                      input positions) that is floor((h + k_u - 1 - p) / u) inputs in front of A and ceil((h + p) / u) behind B - 1
+//   conv_pre (k = 7)                                   h += (k - 1) / 2, now in frames
+// The noise branch reads the harmonic source, which exists at full length: no dependence on z.  40k_v2: 3 -> 63 -> 32 -> 92 -> 47 -> 107 -> 11 -> 71 -> 8 -> 11.
+int synth_dec_halo_frames(const Synth* S) {
+  long long h = 3;
+  for (int i = (int)S->up_rates.size() - 1; i >= 0; --i) {
+    long long rb = 0;
+    for (size_t j = 0; j < S->rb_k.size(); ++j) {
+      long long r = 0;
+      for (int d : S->rb_d[j]) r += (long long)(S->rb_k[j] - 1) / 2 * d + (S->rb_k[j] - 1) / 2;
+      rb = std::max(rb, r);
+    }
+    h += rb;
+    const long long u = S->up_rates[i], ku = S->up_k[i], p = (ku - u) / 2;
+    h = std::max((h + ku - 1 - p) / u, (h + p + u - 1) / u);
+  }
+  return (int)(h + 3);
+}
 
 void synth_finalize(Synth* S) {
   const TensorStore& ts = S->ts;
@@ -237,7 +261,9 @@ void synth_finalize(Synth* S) {
 
 // ------------------------------------------------------------------------------------------------ forward
 static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm, const long long* pitch, const float* pitchf, int sid,
-                        const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps) {
+                        const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps, int g0, int g1) {
+  // [g0, g1): the frames the generator runs on (synth_infer: the keep window plus its halo; [0, T): the whole sequence).  Everything up to the flow is full length.
+  const int W = g1 - g0;
   const int C = S->hidden, H = S->n_heads, kc = C / H, IC = S->inter;
   const bool dry = A.dry;
   const int h2 = conv_set_pair_arithmetic(-1);      // read once: the whole pass plans with the pair arithmetic it saw when it started
@@ -265,12 +291,13 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
     x_s = A.alloc<unsigned char>(split_image_bytes(C, T)); attn_s = A.alloc<unsigned char>(split_image_bytes(C, T));
     ff_s = A.alloc<unsigned char>(split_image_bytes(S->filt, T));
     x0_s = A.alloc<unsigned char>(split_image_bytes(IC / 2, T)); hw_s = A.alloc<unsigned char>(split_image_bytes(2 * C, T));
-    acts_s = A.alloc<unsigned char>(split_image_bytes(C, T)); z_s = A.alloc<unsigned char>(split_image_bytes(IC, T));
+    acts_s = A.alloc<unsigned char>(split_image_bytes(C, T)); z_s = A.alloc<unsigned char>(split_image_bytes(IC, W));
     const size_t img_bytes = A.off - img0;
-    // (a shorter sequence in the same allocation leaves the longer one's rows behind its end: the length is part of the layout)
-    if (!dry && (S->img_base != A.base + img0 || S->img_gen != A.gen || S->img_bytes != img_bytes || S->img_T != T)) {
+    // (a shorter sequence in the same allocation leaves the longer one's rows behind its end: the length is part of the layout - both lengths: the z image
+    // holds the generator's W columns)
+    if (!dry && (S->img_base != A.base + img0 || S->img_gen != A.gen || S->img_bytes != img_bytes || S->img_T != T || S->img_W != W)) {
       RVC_HIP_CHECK(hipMemsetAsync(A.base + img0, 0, img_bytes, s));
-      S->img_base = A.base + img0; S->img_gen = A.gen; S->img_bytes = img_bytes; S->img_T = T;
+      S->img_base = A.base + img0; S->img_gen = A.gen; S->img_bytes = img_bytes; S->img_T = T; S->img_W = W;
     }
   }
   // ---- speaker conditioning vectors
@@ -447,13 +474,25 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
       if (taps) tap(taps->har_source, har, (size_t)N);
     }
   }
-  float* cur = A.alloc<float>((size_t)S->up_init * T);
+  // From here on every tensor holds the W columns of the window; the three full-length operands are addressed at its start: z + g0 (pitch T), har + g0 upp,
+  // out + g0 upp.  Inside the planning-length scope every launch is planned for the whole sequence and sized for the window (ConvPlanLenScope): a window's
+  // columns are computed by the kernels, tiles and K splits of the full pass.  Columns within the halo of a cut edge see zero padding there and are wrong;
+  // the caller keeps none of them.
+  ConvPlanLenScope plan_len(W, T);
+  const long long Nw = (long long)W * S->upp;
+  const float* har_w = har ? har + (size_t)g0 * S->upp : nullptr;
+  float* zw = (!gs && W != T) ? A.alloc<float>((size_t)IC * W) : nullptr;      // (the fp32 path stages rows from an aligned base: the window densely)
+  float* cur = A.alloc<float>((size_t)S->up_init * W);
   if (!dry) {
     ConvEpilogue Eb; Eb.bias_override = pre_bias;
-    if (gs) { split_image_from_f32(s, z, T, IC, T, z_s, tp); conv_x3s_run(S->conv_pre, s, z_s, tp, T, cur, T, Eb); }     // k = 7
-    else conv1d_run(S->conv_pre, s, z, T, T, cur, T, Eb);
+    const long long tpw = split_image_tp(W);
+    if (gs) { split_image_from_f32(s, z + g0, T, IC, W, z_s, tpw); conv_x3s_run(S->conv_pre, s, z_s, tpw, W, cur, W, Eb); }     // k = 7
+    else if (zw) {
+      RVC_HIP_CHECK(hipMemcpy2DAsync(zw, (size_t)W * sizeof(float), z + g0, (size_t)T * sizeof(float), (size_t)W * sizeof(float), IC, hipMemcpyDeviceToDevice, s));
+      conv1d_run(S->conv_pre, s, zw, W, W, cur, W, Eb);
+    } else conv1d_run(S->conv_pre, s, z, T, T, cur, T, Eb);
   }
-  int Tc = T;
+  int Tc = W;
   const int nu = (int)S->stages.size();
   for (int i = 0; i < nu; ++i) {
     GenStage& st = S->stages[i];
@@ -486,7 +525,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
       ConvEpilogue En; En.accumulate = 1;
       // last stage (one tap of the source per position) with all three ResBlocks on conv_rb3_kernel: the noise term is added where x is read
       // (the gen_ups0 tap wants the summed tensor)
-      bool noise_in_rb3 = S->f0 && st.noise_k == 1 && st.noise_w.p != nullptr && N == (long long)Tn && !(taps && i == 0);
+      bool noise_in_rb3 = S->f0 && st.noise_k == 1 && st.noise_w.p != nullptr && Nw == (long long)Tn && !(taps && i == 0);
       // 32- / 64-channel stages in the fp16x2 arithmetic: a whole ResBlock (three pairs) in one launch, x read once, the sum written once (conv_rb3.hip).
       // Each ResBlock is planned once; the noise decision and the launches below use these same plans.
       Rb3Plan rb3[3]; bool rb3_ok[3];
@@ -495,7 +534,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
         for (int j = 0; j < 3; ++j) {
           const ConvLayer* r1[3] = {&st.rb[j].c1[0], &st.rb[j].c1[1], &st.rb[j].c1[2]};
           const ConvLayer* r2[3] = {&st.rb[j].c2[0], &st.rb[j].c2[1], &st.rb[j].c2[2]};
-          rb3_ok[j] = conv_rb3_plan(r1, r2, up, Tn, Tn, xs, Tn, 0.1f, 1.f / 3.f, j > 0, h2, noise ? har : nullptr, noise ? st.noise_w.p : nullptr,
+          rb3_ok[j] = conv_rb3_plan(r1, r2, up, Tn, Tn, xs, Tn, 0.1f, 1.f / 3.f, j > 0, h2, noise ? har_w : nullptr, noise ? st.noise_w.p : nullptr,
                                     noise ? st.noise_b.p : nullptr, rb3[j]);
           all = all && rb3_ok[j];
         }
@@ -506,13 +545,13 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
         // nothing here
       } else if (!S->f0) {
         // plain Generator: nothing is added to the up-sampled signal
-      } else if (st.noise_w.p && noise_add(s, up, Tn, Cc, Tn, har, N, st.noise_k, st.noise_s, st.noise_k > 1 ? st.noise_s / 2 : 0, st.noise_w.p, st.noise_b.p)) {
+      } else if (st.noise_w.p && noise_add(s, up, Tn, Cc, Tn, har_w, Nw, st.noise_k, st.noise_s, st.noise_k > 1 ? st.noise_s / 2 : 0, st.noise_w.p, st.noise_b.p)) {
         // narrow stages (k <= 8 taps of the one source channel): a streaming add instead of im2col + GEMM
       } else if (st.noise_k > 1) {
-        frames(s, har, fr, (int)N, st.noise_k, st.noise_s, st.noise_s / 2, Tn, 0);
+        frames(s, har_w, fr, (int)Nw, st.noise_k, st.noise_s, st.noise_s / 2, Tn, 0);
         conv1d_run(st.noise, s, fr, Tn, Tn, up, Tn, En);
       } else {
-        conv1d_run(st.noise, s, har, Tn, Tn, up, Tn, En);
+        conv1d_run(st.noise, s, har_w, Tn, Tn, up, Tn, En);
       }
       if (taps && i == 0) tap(taps->gen_ups0, up, (size_t)Cc * Tn);
       for (int j = 0; j < 3; ++j) {
@@ -545,14 +584,50 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
     }
     cur = xs; Tc = Tn;
   }
-  if (!dry) conv_to1(s, cur, Tc, S->conv_post_w.p, S->up_init >> nu, 7, 3, Tc, 0.01f, 1, out);
+  if (!dry) conv_to1(s, cur, Tc, S->conv_post_w.p, S->up_init >> nu, 7, 3, Tc, 0.01f, 1, out + (size_t)g0 * S->upp);
 }
 
-void synth_infer(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, int sid,
-                 const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps) {
+// [keep0, keep1): the frames whose samples the caller keeps.  out[keep0 upp, keep1 upp) is defined, nothing else is promised: the generator (conv_pre on) runs on the
+// window widened by its halo, clamped to the sequence; enc_p, the flow and the harmonic source run at full length (global attention, a running phase sum, and the
+// caller's noise tensors keep their shapes).  halo < 0: synth_dec_halo_frames (anything else is for the test that shows the derived value is tight).
+// The frames [g0, g1) the generator runs on for a keep window: the window widened by the halo, clamped, and its start moved down to a frame at which every
+// stage's first column is a multiple of conv1d_residual_period of the pair launches planned for the whole sequence - the persistent pair kernel adds the
+// residual of a tile block by block, so the order of a column's additions depends on its place in the tile (40k_v2 at 30 s: 64 frames, [89, ..) -> [64, ..)).
+void synth_window_frames(const Synth* S, int T, long long keep0, long long keep1, int halo, int* og0, int* og1) {
+  RVC_REQUIRE(keep0 >= 0 && keep0 < keep1 && keep1 <= T, "keep window must be a non-empty range of frames inside [0, T)");
+  const int Hd = halo < 0 ? synth_dec_halo_frames(S) : halo;
+  int g0 = (int)std::max<long long>(0, keep0 - Hd), g1 = (int)std::min<long long>(T, keep1 + Hd);
+  // a window of a few frames would leave some launches fewer tiles than the kernel the whole sequence is planned on accepts: widened (costs microseconds)
+  const int kMinWindow = 128;
+  if (g1 - g0 < kMinWindow && halo < 0) { g0 = std::max(0, std::min(g0, T - kMinWindow)); g1 = std::min(T, std::max(g1, g0 + kMinWindow)); }
+  const int h2 = conv_set_pair_arithmetic(-1);
+  auto gcd = [](long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; };
+  long long align = 1, pu = 1;
+  for (const GenStage& st : S->stages) {
+    pu *= st.u;
+    const long long Tn = (long long)T * pu;
+    if (Tn >= (1LL << 31)) break;
+    for (int j = 0; j < 3; ++j)
+      for (int m = 0; m < 3; ++m) {
+        const ConvLayer& c1 = st.rb[j].c1[m]; const ConvLayer& c2 = st.rb[j].c2[m];
+        if (!(conv1d_split_eligible(c1, (int)Tn, SPLIT_PRODUCER) && conv1d_split_eligible(c2, (int)Tn, SPLIT_CONSUMER))) continue;
+        const long long per = conv1d_residual_period(c2, (int)Tn, conv1d_pair_h2_eligible(c1, c2, (int)Tn, h2) ? 1 : 0);
+        const long long need = per / gcd(per, pu);               // frames whose columns at this stage are a multiple of the period
+        align = align / gcd(align, need) * need;
+      }
+  }
+  g0 -= (int)(g0 % align);
+  *og0 = g0; *og1 = g1;
+}
+
+void synth_infer_window(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, int sid,
+                        const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps, long long keep0, long long keep1, int halo) {
   RVC_REQUIRE(S->ready, "synth_finalize has not been called");
   RVC_REQUIRE(T >= 11, "need at least 11 frames (relative-position window)");
   RVC_REQUIRE(sid >= 0 && sid < S->n_spk, "speaker id out of range");
+  int g0, g1;
+  synth_window_frames(S, T, keep0, keep1, halo, &g0, &g1);
+  if (taps) { g0 = 0; g1 = T; }                                  // (the generator's taps are whole tensors)
   Arena& A = S->arena;
   for (int pass = 0; pass < 2; ++pass) {
     A.dry = (pass == 0); A.reset(); if (pass == 0) A.peak = 0;
@@ -562,10 +637,14 @@ void synth_infer(Synth* S, hipStream_t s, const float* feat, int feat_channel_ma
       if (!A.dry) transpose(s, feat, t, T, S->feat_dim, S->feat_dim, T, 1, 0, 0);
       fcm = t;
     }
-    synth_graph(S, s, A, fcm, pitch, pitchf, sid, noise_z, noise_src, T, out, taps);
+    synth_graph(S, s, A, fcm, pitch, pitchf, sid, noise_z, noise_src, T, out, taps, g0, g1);
     if (pass == 0) A.ensure(A.peak);
   }
   A.dry = false;
+}
+void synth_infer(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, int sid,
+                 const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps) {
+  synth_infer_window(S, s, feat, feat_channel_major, pitch, pitchf, sid, noise_z, noise_src, T, out, taps, 0, T, -1);
 }
 
 size_t synth_workspace(const Synth* M) { return M->arena.cap; }

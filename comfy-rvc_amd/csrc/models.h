@@ -21,6 +21,12 @@ int synth_feat_dim(const Synth* S);
 bool synth_has_f0(const Synth* S);      // false: *_nono family (decided by the checkpoint: no enc_p.emb_pitch)
 void synth_infer(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, int sid,
                  const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps);
+// the same with a keep window in frames: only out[keep0 upp, keep1 upp) is defined (the generator runs on the window plus synth_dec_halo_frames per side);
+// halo < 0: the derived halo
+void synth_infer_window(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, int sid,
+                        const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps, long long keep0, long long keep1, int halo);
+void synth_window_frames(const Synth* S, int T, long long keep0, long long keep1, int halo, int* g0, int* g1);   // the frames the generator runs on for a keep window
+int synth_dec_halo_frames(const Synth* S);   // pure host: frames of z the generator's output depends on to either side
 
 struct Hubert;
 Hubert* hubert_create(Ctx* ctx);

@@ -244,18 +244,38 @@ static void check_pitch_args(rvc_synth* s, const void* pitch, const void* pitchf
     RVC_REQUIRE(!pitch && !pitchf && !noise_src && !do_protect, "no-f0 model: pitch, pitchf, source noise must be NULL and protect off");
   }
 }
-int rvc_synth_infer(rvc_synth* s, void* stream, const float* phone, int phone_cm, const int64_t* pitch, const float* pitchf, int sid,
-                    const float* noise_z, const float* noise_src, int64_t T, float* out, const rvc_synth_taps* taps) {
+int rvc_synth_dec_halo(rvc_synth* s) { return s ? synth_dec_halo_frames(s->m) : 0; }
+int rvc_synth_window_frames(rvc_synth* s, int64_t T, int64_t keep0, int64_t keep1, int64_t* g0, int64_t* g1) {
+  RVC_TRY
+  RVC_REQUIRE(s && g0 && g1 && T > 0 && T < (1LL << 30), "bad argument");
+  RVC_HIP_CHECK(hipSetDevice(s->ctx->c.device));                  // (the plans that decide the alignment ask for the device's CU count)
+  int a, b;
+  synth_window_frames(s->m, (int)T, keep0, keep1, -1, &a, &b);
+  *g0 = a; *g1 = b;
+  RVC_CATCH
+}
+int rvc_synth_infer_window_halo(rvc_synth* s, void* stream, const float* phone, int phone_cm, const int64_t* pitch, const float* pitchf, int sid,
+                                const float* noise_z, const float* noise_src, int64_t T, float* out, const rvc_synth_taps* taps, int64_t keep0, int64_t keep1,
+                                int halo) {
   RVC_TRY
   RVC_REQUIRE(s && phone && noise_z && out, "null argument");
   check_pitch_args(s, pitch, pitchf, noise_src, 0);
-  synth_infer(s->m, (hipStream_t)stream, phone, phone_cm, (const long long*)pitch, pitchf, sid, noise_z, noise_src, (int)T, out, taps);
+  synth_infer_window(s->m, (hipStream_t)stream, phone, phone_cm, (const long long*)pitch, pitchf, sid, noise_z, noise_src, (int)T, out, taps, keep0, keep1, halo);
   check_launch();
   RVC_CATCH
 }
+int rvc_synth_infer_window(rvc_synth* s, void* stream, const float* phone, int phone_cm, const int64_t* pitch, const float* pitchf, int sid,
+                           const float* noise_z, const float* noise_src, int64_t T, float* out, const rvc_synth_taps* taps, int64_t keep0, int64_t keep1) {
+  return rvc_synth_infer_window_halo(s, stream, phone, phone_cm, pitch, pitchf, sid, noise_z, noise_src, T, out, taps, keep0, keep1, -1);
+}
+int rvc_synth_infer(rvc_synth* s, void* stream, const float* phone, int phone_cm, const int64_t* pitch, const float* pitchf, int sid,
+                    const float* noise_z, const float* noise_src, int64_t T, float* out, const rvc_synth_taps* taps) {
+  return rvc_synth_infer_window(s, stream, phone, phone_cm, pitch, pitchf, sid, noise_z, noise_src, T, out, taps, 0, T);
+}
 
-int rvc_vc_segment(rvc_hubert* h, rvc_synth* s, void* stream, const float* audio, int64_t L, int version, const int64_t* pitch,
-                   const float* pitchf, int sid, float protect, int do_protect, const float* noise_z, const float* noise_src, float* out) {
+int rvc_vc_segment_window(rvc_hubert* h, rvc_synth* s, void* stream, const float* audio, int64_t L, int version, const int64_t* pitch,
+                          const float* pitchf, int sid, float protect, int do_protect, const float* noise_z, const float* noise_src, float* out,
+                          int64_t keep0, int64_t keep1) {
   RVC_TRY
   RVC_REQUIRE(h && s && audio && noise_z && out, "null argument");
   check_pitch_args(s, pitch, pitchf, noise_src, do_protect);
@@ -266,18 +286,24 @@ int rvc_vc_segment(rvc_hubert* h, rvc_synth* s, void* stream, const float* audio
   RVC_REQUIRE(D == synth_feat_dim(s->m), "feature width of `version` does not match the synthesizer (v1 models take 256-d, v2 models 768-d features)");
   RVC_REQUIRE(Th > 0 && 2 * Th < (1LL << 30), "segment length out of range");
   const int T = (int)(2 * Th);
+  if (keep1 < 0) keep1 = T;                                      // (the un-windowed entry point: the sequence length is only known here)
   // scratch for the channel-major features lives in two small allocations owned by this call's stream order
   float* fcm = (float*)stream_scratch(st, 1, (size_t)D * Th * sizeof(float));
   float* fup = (float*)stream_scratch(st, 2, (size_t)D * T * sizeof(float));
   hubert_forward(h->m, st, audio, L, version, 0, nullptr, fcm, nullptr);
   feats_prepare(st, fcm, nullptr, pitchf, fup, D, (int)Th, T, protect, do_protect);
-  synth_infer(s->m, st, fup, 1, (const long long*)pitch, pitchf, sid, noise_z, noise_src, T, out, nullptr);
+  synth_infer_window(s->m, st, fup, 1, (const long long*)pitch, pitchf, sid, noise_z, noise_src, T, out, nullptr, keep0, keep1, -1);
   check_launch();
   RVC_CATCH
 }
+int rvc_vc_segment(rvc_hubert* h, rvc_synth* s, void* stream, const float* audio, int64_t L, int version, const int64_t* pitch,
+                   const float* pitchf, int sid, float protect, int do_protect, const float* noise_z, const float* noise_src, float* out) {
+  return rvc_vc_segment_window(h, s, stream, audio, L, version, pitch, pitchf, sid, protect, do_protect, noise_z, noise_src, out, 0, -1);
+}
 
-int rvc_vc_segment_feats(rvc_synth* s, void* stream, const float* feats_cm, const float* feats0_cm, int64_t Th, int feat_dim, const int64_t* pitch,
-                         const float* pitchf, int sid, float protect, int do_protect, const float* noise_z, const float* noise_src, float* out) {
+int rvc_vc_segment_feats_window(rvc_synth* s, void* stream, const float* feats_cm, const float* feats0_cm, int64_t Th, int feat_dim, const int64_t* pitch,
+                                const float* pitchf, int sid, float protect, int do_protect, const float* noise_z, const float* noise_src, float* out,
+                                int64_t keep0, int64_t keep1) {
   RVC_TRY
   RVC_REQUIRE(s && feats_cm && noise_z && out, "null argument");
   check_pitch_args(s, pitch, pitchf, noise_src, do_protect);
@@ -287,9 +313,13 @@ int rvc_vc_segment_feats(rvc_synth* s, void* stream, const float* feats_cm, cons
   const int T = (int)(2 * Th);
   float* fup = (float*)stream_scratch(st, 2, (size_t)feat_dim * T * sizeof(float));
   feats_prepare(st, feats_cm, feats0_cm, pitchf, fup, feat_dim, (int)Th, T, protect, do_protect);
-  synth_infer(s->m, st, fup, 1, (const long long*)pitch, pitchf, sid, noise_z, noise_src, T, out, nullptr);
+  synth_infer_window(s->m, st, fup, 1, (const long long*)pitch, pitchf, sid, noise_z, noise_src, T, out, nullptr, keep0, keep1, -1);
   check_launch();
   RVC_CATCH
+}
+int rvc_vc_segment_feats(rvc_synth* s, void* stream, const float* feats_cm, const float* feats0_cm, int64_t Th, int feat_dim, const int64_t* pitch,
+                         const float* pitchf, int sid, float protect, int do_protect, const float* noise_z, const float* noise_src, float* out) {
+  return rvc_vc_segment_feats_window(s, stream, feats_cm, feats0_cm, Th, feat_dim, pitch, pitchf, sid, protect, do_protect, noise_z, noise_src, out, 0, 2 * Th);
 }
 
 int rvc_resample(void* stream, const float* x, int64_t n_in, const double* taps, int half, int up, int down, float* y, int64_t n_out) {

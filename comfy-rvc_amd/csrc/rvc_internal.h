@@ -136,7 +136,23 @@ bool conv1d_split_eligible(const ConvLayer& L, int Tin, SplitRole role = SPLIT_C
 // (h2 = 0: rvc_set_pair_arithmetic(0) / RVC_H2=0).  h2: the process-wide pair arithmetic as the caller queried it ONCE at the start of its call - a
 // conversion uses the mode it saw when it started
 bool conv1d_pair_h2_eligible(const ConvLayer& c1, const ConvLayer& c2, int Tin, int h2);
+// Columns after which the order of the fp32 additions of this layer as the CONSUMER of a split-resident pair (c2: image in, residual added) repeats: 1 when
+// every column is summed alike, the tile width where the persistent kernel adds the residual block by block.  A launch over a column window computes what the
+// launch over the whole sequence computes only if the window starts at a multiple of it (synth_infer_window aligns its window).
+int conv1d_residual_period(const ConvLayer& L, int Tin, int h2);
 int conv_set_pair_arithmetic(int mode);   // process-wide: 1 = fp16x2 on eligible ResBlock pairs (default), 0 = bf16x3 everywhere; < 0 queries; returns the previous mode
+
+// Planning length.  A launch over a column WINDOW of a longer sequence (the generator behind synth_infer's keep window) must compute, column for column, what the
+// launch over the whole sequence computes: every question that picks a kernel, a tile, an arithmetic or a K split is therefore asked with the length of the WHOLE
+// sequence, and only grids and buffers are sized by the window.  Inside a scope conv_plan_len(n) = n * full / win (the stage lengths of a window are multiples of
+// `win`, so the scaling is exact); outside one it is n.  Thread-local, like the build scopes below.
+long long conv_plan_len(long long n);
+struct ConvPlanLenScope {
+  long long prev_win, prev_full;
+  ConvPlanLenScope(long long win, long long full);
+  ~ConvPlanLenScope();
+  ConvPlanLenScope(const ConvPlanLenScope&) = delete; ConvPlanLenScope& operator=(const ConvPlanLenScope&) = delete;
+};
 
 // host-side packing + upload (weights in PyTorch layouts)
 void conv1d_layer_init(ConvLayer& L, const float* w /*[Co][Ci/groups][k]*/, const float* bias, int Co, int Ci, int k,

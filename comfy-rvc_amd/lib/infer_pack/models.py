@@ -81,7 +81,8 @@ class _SynthesizerNSFsid:
     def to(self, device):
         return self
 
-    def infer(self, phone, phone_lengths, pitch, nsff0, sid, rate=None, noise=None, taps=None, phone_channel_major=False):
+    def infer(self, phone, phone_lengths, pitch, nsff0, sid, rate=None, noise=None, taps=None, phone_channel_major=False, keep=None):
+        """keep=(k0, k1): frames whose samples the caller keeps - only out[..., k0 * upp : k1 * upp] is defined then (rvc_synth_infer_window)."""
         assert self._loaded, "load_state_dict first"
         assert rate is None, "`rate` is unused by every caller of the reference (SURVEY 8a9)"
         dev = self.device
@@ -118,9 +119,10 @@ class _SynthesizerNSFsid:
             tp = _lib.SynthTaps(*[_lib.ptr(tbuf.get(n)) for n, _ in _lib.SynthTaps._fields_])
         sid_i = int(torch.as_tensor(sid).reshape(-1)[0])
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib.rvc_synth_infer(self._h, _lib.current_stream(), _lib.ptr(ph), 1 if phone_channel_major else 0,
-                                                _lib.ptr(pc), _lib.ptr(pf), sid_i, _lib.ptr(nz), _lib.ptr(ns), T, _lib.ptr(out),
-                                                C.byref(tp) if tp is not None else None))
+            k0, k1 = (0, T) if keep is None else (int(keep[0]), int(keep[1]))
+            _lib.check(_lib.lib.rvc_synth_infer_window(self._h, _lib.current_stream(), _lib.ptr(ph), 1 if phone_channel_major else 0,
+                                                       _lib.ptr(pc), _lib.ptr(pf), sid_i, _lib.ptr(nz), _lib.ptr(ns), T, _lib.ptr(out),
+                                                       C.byref(tp) if tp is not None else None, k0, k1))
         if taps is not None:
             taps.update(tbuf)
         x_mask = torch.ones(1, 1, T, dtype=torch.float32, device=dev)
@@ -137,7 +139,7 @@ class _SynthesizerNSFsid_nono(_SynthesizerNSFsid):
             config, sr = config[:17], config[17]
         super().__init__(*config, sr if sr is not None else 40000, **kwargs)
 
-    def infer(self, phone, phone_lengths, sid, rate=None, noise=None, taps=None, phone_channel_major=False):
+    def infer(self, phone, phone_lengths, sid, rate=None, noise=None, taps=None, phone_channel_major=False, keep=None):
         assert self._loaded, "load_state_dict first"
         assert rate is None, "`rate` is unused by every caller of the reference (SURVEY 8a9)"
         dev = self.device
@@ -155,8 +157,9 @@ class _SynthesizerNSFsid_nono(_SynthesizerNSFsid):
             tp = _lib.SynthTaps(*[_lib.ptr(tbuf.get(n)) for n, _ in _lib.SynthTaps._fields_])
         sid_i = int(torch.as_tensor(sid).reshape(-1)[0])
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib.rvc_synth_infer(self._h, _lib.current_stream(), _lib.ptr(ph), 1 if phone_channel_major else 0, None, None, sid_i,
-                                                _lib.ptr(nz), None, T, _lib.ptr(out), C.byref(tp) if tp is not None else None))
+            k0, k1 = (0, T) if keep is None else (int(keep[0]), int(keep[1]))
+            _lib.check(_lib.lib.rvc_synth_infer_window(self._h, _lib.current_stream(), _lib.ptr(ph), 1 if phone_channel_major else 0, None, None, sid_i,
+                                                       _lib.ptr(nz), None, T, _lib.ptr(out), C.byref(tp) if tp is not None else None, k0, k1))
         if taps is not None:
             taps.update(tbuf)
         x_mask = torch.ones(1, 1, T, dtype=torch.float32, device=dev)

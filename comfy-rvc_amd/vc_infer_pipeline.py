@@ -54,7 +54,17 @@ class VC(FeatureExtractor):
         ns = self._draw((1, T * upp, 1))
         return nz, ns
 
-    def vc(self, model, net_g, sid, audio0, pitch, pitchf, times, index, big_npy, index_rate, version, protect):
+    decoder_window = True    # the generator synthesizes only the frames whose samples the pipeline keeps (False: the whole padded segment, same result)
+
+    def _keep_frames(self, T, upp, trim):
+        """Frames [k0, k1) whose samples cover out[trim : T * upp - trim], widened outwards to whole frames; the whole sequence when nothing is trimmed."""
+        if not self.decoder_window or trim <= 0 or 2 * trim >= T * upp:
+            return 0, T
+        return trim // upp, T - trim // upp
+
+    def vc(self, model, net_g, sid, audio0, pitch, pitchf, times, index, big_npy, index_rate, version, protect, trim=0):
+        """`trim`: samples the caller drops at either end of the result (VC.pipeline: t_pad_tgt).  The fused path then generates and copies only what
+        lies between; the array keeps its full length (zeros outside) so that the caller's slice is unchanged."""
         feats = torch.from_numpy(audio0).float()
         if feats.dim() == 2:
             feats = feats.mean(-1)
@@ -78,11 +88,16 @@ class VC(FeatureExtractor):
             ns = ns.to(dev, torch.float32).contiguous()
             out = torch.empty(T * net_g.upp, dtype=torch.float32, device=dev)
             sid_i = int(torch.as_tensor(sid).reshape(-1)[0])
+            k0, k1 = self._keep_frames(T, net_g.upp, trim)
             with torch.cuda.device(dev):
-                _lib.check(_lib.lib.rvc_vc_segment(model._h, net_g._h, _lib.current_stream(), _lib.ptr(a), L, 1 if version == "v1" else 2,
-                                                   _lib.ptr(pc), _lib.ptr(pf), sid_i, float(protect), 1 if protect < 0.5 else 0,
-                                                   _lib.ptr(nz), _lib.ptr(ns), _lib.ptr(out)))
-            return out.cpu().numpy()
+                _lib.check(_lib.lib.rvc_vc_segment_window(model._h, net_g._h, _lib.current_stream(), _lib.ptr(a), L, 1 if version == "v1" else 2,
+                                                          _lib.ptr(pc), _lib.ptr(pf), sid_i, float(protect), 1 if protect < 0.5 else 0,
+                                                          _lib.ptr(nz), _lib.ptr(ns), _lib.ptr(out), k0, k1))
+            if (k0, k1) == (0, T):
+                return out.cpu().numpy()
+            res = np.zeros(T * net_g.upp, dtype=np.float32)
+            res[trim: res.shape[0] - trim] = out[trim: res.shape[0] - trim].cpu().numpy()
+            return res
         # ---- generic callee-protocol path (any extract_features / infer implementation)
         dev = self.device
         feats = model.extract_features(version=version, source=feats.to(dev), padding_mask=None, output_layer=9 if version == "v1" else 12)
@@ -169,18 +184,20 @@ class VC(FeatureExtractor):
             p_len = min(pitch.shape[0], pitchf.shape[0])
             pitch = torch.from_numpy(pitch[:p_len].astype(np.int64)).unsqueeze(0)
             pitchf = torch.from_numpy(pitchf[:p_len].astype(np.float32)).unsqueeze(0)
+        # (a subclass's own vc keeps the reference's signature and returns the whole segment)
+        trim_kw = {"trim": self.t_pad_tgt} if ("vc" not in self.__dict__ and type(self).vc is VC.vc) else {}
         for t in opt_ts:
             t = t // self.window * self.window
             start, end = s, t + self.t_pad2 + self.window
             ps = pitch[:, start // self.window: end // self.window] if if_f0 else None
             pfs = pitchf[:, start // self.window: end // self.window] if if_f0 else None
             audio_opt.append(self.vc(model, net_g, sid, audio_pad[start:end], ps, pfs, times, index, big_npy, index_rate, version,
-                                     protect)[self.t_pad_tgt: -self.t_pad_tgt])
+                                     protect, **trim_kw)[self.t_pad_tgt: -self.t_pad_tgt])
             s = t
         ps = pitch[:, t // self.window:] if if_f0 and t is not None else pitch
         pfs = pitchf[:, t // self.window:] if if_f0 and t is not None else pitchf
         audio_opt.append(self.vc(model, net_g, sid, audio_pad[t:], ps, pfs, times, index, big_npy, index_rate, version,
-                                 protect)[self.t_pad_tgt: -self.t_pad_tgt])
+                                 protect, **trim_kw)[self.t_pad_tgt: -self.t_pad_tgt])
         audio_opt = np.concatenate(audio_opt)
         if rms_mix_rate < 1:
             audio_opt = change_rms(audio, 16000, audio_opt, tgt_sr, rms_mix_rate)
@@ -319,8 +336,11 @@ def _pipeline_device(self, model, net_g, sid, audio, f0_up_key, f0_method, merge
             pf = pitchf_d[b0 // self.window: b0 // self.window + T].contiguous()
             assert pc.numel() == T, "pitch track shorter than the feature sequence"
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib.rvc_vc_segment_feats(net_g._h, _lib.current_stream(), _lib.ptr(f), _lib.ptr(f0c), Th, D, _lib.ptr(pc), _lib.ptr(pf), sid_i,
-                                                     float(protect), 1 if (protect < 0.5 and if_f0) else 0, _lib.ptr(nz), _lib.ptr(ns), _lib.ptr(out)))
+            # only the frames whose samples survive the slice below are generated (the rest of `out` stays undefined)
+            k0, k1 = self._keep_frames(T, net_g.upp, self.t_pad_tgt)
+            _lib.check(_lib.lib.rvc_vc_segment_feats_window(net_g._h, _lib.current_stream(), _lib.ptr(f), _lib.ptr(f0c), Th, D, _lib.ptr(pc), _lib.ptr(pf), sid_i,
+                                                            float(protect), 1 if (protect < 0.5 and if_f0) else 0, _lib.ptr(nz), _lib.ptr(ns), _lib.ptr(out),
+                                                            k0, k1))
         outs.append(out[self.t_pad_tgt: out.numel() - self.t_pad_tgt])
     _mark("synth enqueued")
     wav = torch.cat(outs) if len(outs) > 1 else outs[0].contiguous()

@@ -186,6 +186,23 @@ int rvc_synth_has_f0(rvc_synth* s);
 int rvc_synth_infer(rvc_synth* s, void* stream, const float* phone_dev, int phone_channel_major, const int64_t* pitch_dev,
                     const float* pitchf_dev, int sid, const float* noise_z_dev, const float* noise_src_dev, int64_t T,
                     float* out_dev, const rvc_synth_taps* taps);
+/* Keep window [keep0, keep1) in frames, 0 <= keep0 < keep1 <= T: for a caller that discards the rest (VC.pipeline drops t_pad_tgt samples at either end of
+ * every segment).  Only out_dev[keep0 * upp, keep1 * upp) is defined afterwards - bit for bit what rvc_synth_infer writes there; nothing is promised about
+ * the other samples of out_dev [T*upp].  The text encoder, the flow and the harmonic source run at full length, the noise tensors keep their shapes; the
+ * generator (conv_pre on) runs on the window widened by rvc_synth_dec_halo frames per side.  rvc_synth_infer is this call with [0, T).  With taps the
+ * whole sequence is generated. */
+int rvc_synth_infer_window(rvc_synth* s, void* stream, const float* phone_dev, int phone_channel_major, const int64_t* pitch_dev,
+                           const float* pitchf_dev, int sid, const float* noise_z_dev, const float* noise_src_dev, int64_t T,
+                           float* out_dev, const rvc_synth_taps* taps, int64_t keep0, int64_t keep1);
+/* Frames of z to either side of a window that the generator's samples inside it depend on, derived from the layer table (40k_v2: 11). */
+int rvc_synth_dec_halo(rvc_synth* s);
+/* The frames [g0, g1) rvc_synth_infer_window generates for a keep window of a T-frame sequence in the current pair arithmetic: [keep0 - halo, keep1 + halo)
+ * clamped to the sequence, g0 moved down to the next frame at which the kernels planned for the whole sequence sum every column as the full run does. */
+int rvc_synth_window_frames(rvc_synth* s, int64_t T, int64_t keep0, int64_t keep1, int64_t* g0, int64_t* g1);
+/* Tests only: the same call with the halo given (halo < 0: the derived one) - a halo one frame short must change samples inside the window. */
+int rvc_synth_infer_window_halo(rvc_synth* s, void* stream, const float* phone_dev, int phone_channel_major, const int64_t* pitch_dev,
+                                const float* pitchf_dev, int sid, const float* noise_z_dev, const float* noise_src_dev, int64_t T,
+                                float* out_dev, const rvc_synth_taps* taps, int64_t keep0, int64_t keep1, int halo);
 
 /* ------------------------------------------------------------------ fused segment: VC.vc without index retrieval */
 /* audio_dev [L] 16 kHz segment; pitch/pitchf as above with at least p_len = 2*T_h entries; out_dev [2*T_h*upp].
@@ -201,6 +218,13 @@ int rvc_vc_segment_feats(rvc_synth* s, void* stream, const float* feats_cm_dev, 
                          const float* noise_z_dev, const float* noise_src_dev, float* out_dev);
 /* feats0_cm_dev: the features before index retrieval (the reference's feats0 of the protect blend, :58-59,:89-95) or NULL when
  * no index is used. */
+/* Both with a keep window in frames of the synthesizer (T = 2*T_h), as rvc_synth_infer_window: only out_dev[keep0 * upp, keep1 * upp) is defined. */
+int rvc_vc_segment_window(rvc_hubert* h, rvc_synth* s, void* stream, const float* audio_dev, int64_t L, int version,
+                          const int64_t* pitch_dev, const float* pitchf_dev, int sid, float protect, int do_protect,
+                          const float* noise_z_dev, const float* noise_src_dev, float* out_dev, int64_t keep0, int64_t keep1);
+int rvc_vc_segment_feats_window(rvc_synth* s, void* stream, const float* feats_cm_dev, const float* feats0_cm_dev, int64_t T_h, int feat_dim,
+                                const int64_t* pitch_dev, const float* pitchf_dev, int sid, float protect, int do_protect,
+                                const float* noise_z_dev, const float* noise_src_dev, float* out_dev, int64_t keep0, int64_t keep1);
 
 /* ------------------------------------------------------------------ feature retrieval (vc_infer_pipeline.py:60-75) */
 /* The reference looks every HuBERT frame up in a faiss IVF-Flat index over the training features big_npy [N][D]
