@@ -125,7 +125,7 @@ __device__ __forceinline__ void dense_epilogue(const ConvArgsX& p, f32x16 (&acc)
 
 // ---- host side
 struct TileCfg { int WM, WN, AM, AN; };
-TileCfg choose_tile(int M, long long N, int batch);
+TileCfg choose_tile(int M, long long N, int batch);   // N: the planning length (a tile is a kernel choice)
 int tile_cfg_id(const TileCfg& t);            // 0..6, -1 if not an instantiated tiling
 
 // per-launch HIP-event profiling (cfg: 0..6 fp32 1-D, 7..13 fp32 2-D, 14..20 bf16x3 1-D)
@@ -155,22 +155,27 @@ void splitk_reduce_launch(const ConvArgsX& a, int S, int batch, hipStream_t s);
 
 // ---- dispatch of the split-MFMA family: a launch is PLANNED (pure: no stream, no launch, no allocation - callable as often as anyone likes, e.g. to size
 // buffers or to ask "what would run for this shape") and then the plan is launched.  Nothing is decided twice, so the answer and the launch cannot disagree.
+// A planner's answer depends on its arguments alone.  One of them is the planning length (rvc_internal.h): the output columns of the whole sequence of which the
+// launch is a column window, equal to the real length everywhere but behind synth_infer's keep window.  The rule, in every planner: DECISIONS (kernel, tile,
+// arithmetic, K split, fall-back thresholds) READ THE PLANNING LENGTH, SIZES (grid, ldP, buffers, image rows) READ THE REAL ONE (a.Tout / T).
 int device_cu_count();                        // CUs of the CURRENT device (cached per device; 256 when the runtime does not say)
 inline int x3_xcd_remap() { static const int v = exp_int("RVC_X3_XCD", 1); return v; }
 typedef void (*ConvLaunchFn)(const ConvArgsX&, dim3, size_t, hipStream_t);
 struct ConvPlan {
   ConvArgsX a;                    // finished kernel arguments (a.ksplit > 1: a.partial is filled in by conv_plan_launch)
+  long long plan_T = 0;           // the planning length this plan was made for (host side only: the kernel arguments hold the real length, a.Tout)
   ConvLaunchFn launch = nullptr;  // the chosen kernel instantiation
   dim3 grid; size_t lds = 0;
   int prof_cfg = 0, prof_fused = 0;      // profiling: 14 + tile id, kernel family << 4 | pair flags
   double alg_bytes = 0.0, flops = 0.0;   // algorithmic traffic / work (flops: the pair planner's formula; single convolutions: the caller's)
 };
 // the whole decision tree of the bf16x3 / fp16x2 path; false when the layer / geometry is not eligible (caller falls back to the fp32 kernel)
-bool conv_x3_plan(const ConvArgsX& a0, int batch, ConvPlan& p);
+// Tplan: the planning length (a0.Tout when the launch is the whole sequence; for a 2-D launch the positions H * Wd)
+bool conv_x3_plan(const ConvArgsX& a0, int batch, long long Tplan, ConvPlan& p);
 // the only place that opens a profiling bracket, takes split-K scratch, launches and reduces
 void conv_plan_launch(const ConvPlan& p, hipStream_t s);
-// sub-planners: p.a = the arguments as conv_x3_plan / conv_x3_pair_plan prepared them (true taps); on success a, launch, grid and lds of p are filled,
-// on false p is untouched
+// sub-planners: p.a = the arguments as conv_x3_plan / conv_x3_pair_plan prepared them (true taps), p.plan_T = the planning length beside the real p.a.Tout;
+// on success a, launch, grid and lds of p are filled, on false p is untouched
 // software-pipelined kernel for stride-1 1-D convolutions on 2 x 2-wave tiles (conv_x3p.hip)
 bool conv_x3p_plan(ConvPlan& p, int AM, int AN);
 int conv_x3p_check_read();
@@ -181,13 +186,14 @@ int conv_x3q_check_read();
 // k = 1 (GEMM) on the pipelined kernel, fp32 [K][N] input (conv_x3p.hip)
 bool conv_x3g_plan(ConvPlan& p);
 // fused ResBlock pair of the 32-channel stage on the pipelined kernel (conv_x3p.hip)
-bool conv_x3pf_plan(ConvPlan& p, int T);
+bool conv_x3pf_plan(ConvPlan& p);
 // the same pair in the fp16x2 arithmetic with both weight sets resident in LDS, persistent workgroups (conv_rbh.hip); Wx / Wx2 = the one-plane fp16 images
-bool conv_rbh_plan(ConvPlan& p, int T);
+bool conv_rbh_plan(ConvPlan& p);
 // y = (x + c2(lrelu(c1(lrelu(x))))) * scale [+ y] for a ResBlock1 pair of narrow layers in ONE launch; false when not eligible.  h2: the pair arithmetic the
-// caller read once at the start of its call (see conv1d_pair_h2_eligible); p.a.h2 tells whether the plan is the fp16x2 kernel's
-bool conv_x3_pair_plan(const ConvLayer& c1, const ConvLayer& c2, const float* X, long long ldX, int T, float* Y, long long ldY, const ConvEpilogue& e2, int h2,
-                       ConvPlan& p);
+// caller read once at the start of its call (see conv1d_pair_h2_eligible); p.a.h2 tells whether the plan is the fp16x2 kernel's.  T: the columns of X / Y,
+// Tplan: the planning length (= T unless X / Y are a column window)
+bool conv_x3_pair_plan(const ConvLayer& c1, const ConvLayer& c2, const float* X, long long ldX, int T, long long Tplan, float* Y, long long ldY,
+                       const ConvEpilogue& e2, int h2, ConvPlan& p);
 
 // a whole ResBlock1 (three (dilated, plain) pairs) of the narrow stages in one launch, fp16x2 arithmetic, bit-identical to the chain of three conv_rbh
 // launches (conv_rb3.hip); y = x3 * out_scale [+ y]
@@ -207,9 +213,10 @@ struct Rb3Plan {
   Rb3Args a; void (*launch)(const Rb3Args&, dim3, size_t, hipStream_t) = nullptr; dim3 grid; size_t lds = 0;
   int C = 0, k = 0, accumulate = 0;
 };
-// pure like conv_x3_plan; false: not eligible (the caller runs the pairs one by one).  nsrc [T], nw [32], nb [32]: the last stage's noise branch
-bool conv_rb3_plan(const ConvLayer* const* c1, const ConvLayer* const* c2, const float* X, long long ldX, int T, float* Y, long long ldY, float pre_slope,
-                   float out_scale, int accumulate, int h2, const float* nsrc, const float* nw, const float* nb, Rb3Plan& p);
+// pure like conv_x3_plan, T / Tplan as in conv_x3_pair_plan; false: not eligible (the caller runs the pairs one by one).  nsrc [T], nw [32], nb [32]: the last
+// stage's noise branch
+bool conv_rb3_plan(const ConvLayer* const* c1, const ConvLayer* const* c2, const float* X, long long ldX, int T, long long Tplan, float* Y, long long ldY,
+                   float pre_slope, float out_scale, int accumulate, int h2, const float* nsrc, const float* nw, const float* nb, Rb3Plan& p);
 void conv_rb3_launch(const Rb3Plan& p, hipStream_t s);
 
 }  // namespace rvc

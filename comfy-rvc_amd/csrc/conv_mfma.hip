@@ -776,15 +776,7 @@ static void launch_cfg(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s)
   conv_launch(kern, grid, dim3(256), lds, s, a);
 }
 
-static thread_local long long t_plan_win = 0, t_plan_full = 0;
-long long conv_plan_len(long long n) { return t_plan_win > 0 ? (n * t_plan_full + t_plan_win - 1) / t_plan_win : n; }
-ConvPlanLenScope::ConvPlanLenScope(long long win, long long full) : prev_win(t_plan_win), prev_full(t_plan_full) {
-  if (win > 0 && full > win) { t_plan_win = win; t_plan_full = full; } else { t_plan_win = 0; t_plan_full = 0; }
-}
-ConvPlanLenScope::~ConvPlanLenScope() { t_plan_win = prev_win; t_plan_full = prev_full; }
-
 TileCfg choose_tile(int M, long long N, int batch) {
-  N = conv_plan_len(N);                                       // (a tile is a kernel choice: planned for the whole sequence)
   // candidates ordered by preference for large problems; pick the first that yields enough workgroups
   const int Mp = (M + 31) / 32 * 32;
   TileCfg best{2, 2, 1, 1};
@@ -944,10 +936,11 @@ static bool setup_tile(ConvArgsX& a, int mode, const TileCfg& t, size_t& lds) {
   return lds <= 160 * 1024;
 }
 
-static void run_conv(ConvArgsX a, int mode, int batch, hipStream_t s, double flops) {
+// Tplan: the planning length (rvc_internal.h) - a.Tout unless the launch is a column window of a longer sequence
+static void run_conv(ConvArgsX a, int mode, int batch, long long Tplan, hipStream_t s, double flops) {
   RVC_REQUIRE(a.act == ACT_NONE || a.act == ACT_LRELU || a.act == ACT_RELU, "in-kernel activations are identity / ReLU / leaky ReLU");
   RVC_REQUIRE(a.pre_act == ACT_NONE || a.pre_act == ACT_LRELU, "input activation must be identity or leaky ReLU");
-  TileCfg t = choose_tile(a.Co, a.Tout, batch);
+  TileCfg t = choose_tile(a.Co, Tplan, batch);
   size_t lds = 0;
   if (!setup_tile(a, mode, t, lds)) {
     // fall back to narrower tiles (fewer staged columns per row)
@@ -962,7 +955,7 @@ static void run_conv(ConvArgsX a, int mode, int batch, hipStream_t s, double flo
               (double)a.Ci * (double)a.ldX * 4.0 < 2147483648.0, "tensor extent exceeds the 32-bit buffer addressing of the conv kernel");
   // split-K: small grids (deep U-Net levels, 1599-frame GEMMs) leave most CUs idle and expose every stage's load latency;
   // slicing the reduction over S workgroups restores occupancy.  Partials are reduced in a fixed order (deterministic).
-  const long long nblk = ((conv_plan_len(a.Tout) + BN - 1) / BN) * ((a.Co + BM - 1) / BM) * batch;      // (the K split is part of the sum order: planning length)
+  const long long nblk = ((Tplan + BN - 1) / BN) * ((a.Co + BM - 1) / BM) * batch;      // (the K split is part of the sum order: planning length)
   int S = 1;
   static const int max_split = exp_int("RVC_SPLITK", 8);
   static const int split_blk = exp_int("RVC_SPLITK_BLK", 400);
@@ -1041,14 +1034,18 @@ void conv1d_run(const ConvLayer& L, hipStream_t s, const float* X, long long ldX
   if (e.bias_override) a.bias = e.bias_override;
   int Tout = conv1d_out_len(L, Tin);
   if (e.tout_limit > 0 && e.tout_limit < Tout) { RVC_REQUIRE(L.tconv_u == 0, "tout_limit on a transposed conv"); Tout = e.tout_limit; }
+  auto gemm_cols = [&](int tout) { return L.tconv_u > 0 ? (tout + L.tconv_u - 1) / L.tconv_u : tout; };      // ConvTranspose1d: GEMM positions q
+  a.Tout = gemm_cols(Tout);
+  // the same arithmetic for the whole sequence: what every decision below reads
+  RVC_REQUIRE(e.plan_tin == 0 || (e.plan_tin >= Tin && !e.tout_limit), "plan_tin is the input length of the whole sequence this launch is a column window of");
+  const long long Tplan = e.plan_tin > 0 ? gemm_cols(conv1d_out_len(L, e.plan_tin)) : a.Tout;
   if (L.tconv_u > 0) {
     a.pad = L.conv_pad;                             // left pad of the equivalent stride-1 conv
-    a.Tout = (Tout + L.tconv_u - 1) / L.tconv_u;    // GEMM positions q
     a.ostride = L.tconv_u; a.orows = L.co_real;
     RVC_REQUIRE(ldY == Tout, "interleaved ConvTranspose1d store needs a dense output (ldY == Tout)");
     RVC_REQUIRE(e.R == nullptr, "residual not supported on the interleaved store");
   } else {
-    a.pad = L.pad; a.Tout = Tout; a.ostride = 1; a.orows = L.Co;
+    a.pad = L.pad; a.ostride = 1; a.orows = L.Co;
   }
   a.xBatch = (long long)L.Ci * ldX; a.wBatch = L.wBatch; a.yBatch = (long long)L.Co * ldY; a.rBatch = (long long)L.Co * e.ldR;
   a.bBatch = L.Co;
@@ -1060,10 +1057,10 @@ void conv1d_run(const ConvLayer& L, hipStream_t s, const float* X, long long ldX
     a.Wx = reinterpret_cast<const unsigned char*>(L.Wh_); a.h2 = 1;
   }
   ConvPlan p;
-  if (L.Wx_ && conv_x3_plan(a, L.groups, p)) { p.flops = flops; conv_plan_launch(p, s); }
+  if (L.Wx_ && conv_x3_plan(a, L.groups, Tplan, p)) { p.flops = flops; conv_plan_launch(p, s); }
   else {
     RVC_REQUIRE(!e.xs_in && !e.ys_out, "split-resident tensors need the bf16x3 kernel (check conv1d_split_eligible first)");
-    run_conv(a, 1, L.groups, s, flops);
+    run_conv(a, 1, L.groups, Tplan, s, flops);
   }
   if (post) {
     RVC_REQUIRE(L.tconv_u == 0, "post-activation on a transposed conv");
@@ -1087,7 +1084,7 @@ static bool plan_split_role(const ConvLayer& L, int Tin, SplitRole role, int h2,
   // any non-null value asks for the role's geometry (planning only: never dereferenced)
   if (role == SPLIT_PRODUCER) { a.Ys = reinterpret_cast<unsigned char*>(L.Wx_); a.ysTp = split_image_tp(Tin); a.pre_act = ACT_LRELU; a.pre_slope = 0.1f; }
   else { a.Xs = reinterpret_cast<const unsigned char*>(L.Wx_); a.xsTp = split_image_tp(Tin); }
-  return conv_x3_plan(a, 1, p);
+  return conv_x3_plan(a, 1, a.Tout, p);
 }
 bool conv1d_split_eligible(const ConvLayer& L, int Tin, SplitRole role, int h2) { ConvPlan p; return plan_split_role(L, Tin, role, h2, p); }
 
@@ -1112,7 +1109,7 @@ void gemm_tn_run(hipStream_t s, const float* A, long long ldA, long long aBatch,
   a.ldX = ldB; a.ldY = ldY; a.up2 = 0; a.ostride = 1; a.orows = M;
   a.ldW = ldA; a.Wcols = M; a.Wrows = K;
   a.xBatch = bBatch; a.wBatch = aBatch; a.yBatch = yBatch; a.rBatch = 0; a.bBatch = biasBatch;
-  run_conv(a, 1, batch, s, 2.0 * M * (double)N * K * batch);
+  run_conv(a, 1, batch, N, s, 2.0 * M * (double)N * K * batch);
 }
 
 void conv2d_run(const ConvLayer& L, hipStream_t s, const float* X, long long ldX, int H, int Wd, float* Y, long long ldY,
@@ -1136,7 +1133,7 @@ void conv2d_run(const ConvLayer& L, hipStream_t s, const float* X, long long ldX
     float* tmp = (float*)stream_scratch(s, 4, (size_t)L.Co * H * Wd * sizeof(float));
     d.Y = tmp; d.ldY = (long long)H * Wd; d.up2 = 0; d.orows = L.Co; d.bias = L.bd4_;
     ConvPlan p;
-    if (conv_x3_plan(d, 1, p)) {
+    if (conv_x3_plan(d, 1, d.Tout, p)) {
       p.flops = flops; conv_plan_launch(p, s);
       const long long n = (long long)L.Co * H * Wd;
       int blocks = (int)((n + 255) / 256); if (blocks > 8192) blocks = 8192;
@@ -1145,8 +1142,8 @@ void conv2d_run(const ConvLayer& L, hipStream_t s, const float* X, long long ldX
     }
   }
   ConvPlan p;
-  if (L.Wx_ && !L.up2 && conv_x3_plan(a, 1, p)) { p.flops = flops; conv_plan_launch(p, s); }
-  else run_conv(a, 2, 1, s, flops);
+  if (L.Wx_ && !L.up2 && conv_x3_plan(a, 1, a.Tout, p)) { p.flops = flops; conv_plan_launch(p, s); }
+  else run_conv(a, 2, 1, a.Tout, s, flops);
 }
 
 }  // namespace rvc

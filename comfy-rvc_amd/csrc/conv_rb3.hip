@@ -362,8 +362,8 @@ static auto select_rb3(bool acc) { return acc ? &launch_rb3c<CH, KT, true, WM> :
 
 // c1[i] / c2[i]: the three (dilated, plain) pairs of one ResBlock1.  32 channels, equal odd kernel size 3 / 7 / 11, "same" padding, every layer with its
 // one-plane fp16 image, the fp16x2 pair arithmetic switched on (h2), at least two rounds of tiles; false: not this kernel's (the caller runs the pairs one by one).
-bool conv_rb3_plan(const ConvLayer* const* c1, const ConvLayer* const* c2, const float* X, long long ldX, int T, float* Y, long long ldY, float pre_slope,
-                   float out_scale, int accumulate, int h2, const float* nsrc, const float* nw, const float* nb, Rb3Plan& p) {
+bool conv_rb3_plan(const ConvLayer* const* c1, const ConvLayer* const* c2, const float* X, long long ldX, int T, long long Tplan, float* Y, long long ldY,
+                   float pre_slope, float out_scale, int accumulate, int h2, const float* nsrc, const float* nw, const float* nb, Rb3Plan& p) {
   if (!h2) return false;
   const int k = c1[0]->k, C = c1[0]->Co;
   // (the 64-channel stage's 3- and 7-tap ResBlocks too: otherwise three conv_x3pf_kernel launches in bf16x3 / six conv_x3q_kernel launches with the images through HBM)
@@ -382,7 +382,7 @@ bool conv_rb3_plan(const ConvLayer* const* c1, const ConvLayer* const* c2, const
   if (nsrc && C != 32) return false;
   const int ncu = device_cu_count();
   const long long ntiles = ((long long)T + NO - 1) / NO;
-  if ((conv_plan_len(T) + NO - 1) / NO < 2LL * ncu) return false;      // short sequences: the pair kernels' smaller tiles fill the chip better
+  if ((Tplan + NO - 1) / NO < 2LL * ncu) return false;      // short sequences: the pair kernels' smaller tiles fill the chip better
   p = Rb3Plan{};
   p.C = C; p.k = k; p.accumulate = accumulate;
   Rb3Args& a = p.a;

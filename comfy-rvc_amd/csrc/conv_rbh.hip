@@ -286,15 +286,16 @@ static ConvLaunchFn select_rbh(const ConvArgsX& a) { return a.accumulate ? &laun
 
 // p.a: the fused pair's arguments as conv_x3_pair_plan prepared them, with Wx / Wx2 = the two layers' ONE-plane fp16 images (ConvLayer::Wh_).  32 channels,
 // 3 / 7 / 11 taps, a sequence of at least two rounds of tiles; false: not this kernel's (conv_x3pf_kernel takes the pair in bf16x3).
-bool conv_rbh_plan(ConvPlan& p, int T) {
+bool conv_rbh_plan(ConvPlan& p) {
   ConvArgsX& a = p.a;
+  const int T = a.Tout;
   if (a.Ci != 32 || a.Co != 32 || !(a.ktaps == 3 || a.ktaps == 7 || a.ktaps == 11) || a.CoPx < 32) return false;
   const int BN = 512, NO = BN - (a.ktaps - 1);
   const int P = BN + (a.ktaps - 1) * a.dil;
   if (P > 576 || a.dil < 1) return false;
   const int ncu = device_cu_count();
   const long long ntiles = ((long long)T + NO - 1) / NO;
-  if ((conv_plan_len(T) + NO - 1) / NO < 2LL * ncu) return false;      // short sequences: conv_x3pf_kernel's smaller tiles fill the chip better
+  if ((p.plan_T + NO - 1) / NO < 2LL * ncu) return false;      // short sequences: conv_x3pf_kernel's smaller tiles fill the chip better
   a.WROW = P; a.ni = (P + 63) / 64;
   p.lds = (size_t)2 * (2 * a.ktaps) * 2 * 32 * 16 + 256 + (size_t)2 * 2 * P * 32;
   p.grid = dim3((unsigned)(ntiles < ncu ? ntiles : ncu), 1, 1);

@@ -517,7 +517,7 @@ void conv_plan_launch(const ConvPlan& p, hipStream_t s) {
   conv_prof_end(tk, s, p.flops, p.prof_cfg, p.alg_bytes, &a, (long long)p.grid.x * p.grid.y * p.grid.z, p.prof_fused);
 }
 
-bool conv_x3_plan(const ConvArgsX& a0, int batch, ConvPlan& p) {
+bool conv_x3_plan(const ConvArgsX& a0, int batch, long long Tplan, ConvPlan& p) {
   if (!a0.Wx) return false;
   const bool xs = a0.Xs != nullptr;
   if ((xs || a0.Ys) && (a0.Wd > 0 || a0.stride != 1 || a0.ostride != 1 || (a0.Co & 31) || batch != 1)) return false;
@@ -532,6 +532,7 @@ bool conv_x3_plan(const ConvArgsX& a0, int batch, ConvPlan& p) {
   if ((double)a0.orows * (double)a0.ldY * 4.0 >= 2147483648.0 || (double)a0.orows * (double)a0.ldR * 4.0 >= 2147483648.0 ||
       (double)a0.Ci * (double)a0.ldX * 4.0 >= 2147483648.0) return false;
   p = ConvPlan{};
+  p.plan_T = Tplan;                                       // every decision below reads Tplan, every size a.Tout
   ConvArgsX& a = p.a;
   a = a0;
   if (a.Wd == 0) a.ktaps = a0.kreal;                      // true taps (the fp32 kernel folds the stride phases into virtual channels)
@@ -540,13 +541,13 @@ bool conv_x3_plan(const ConvArgsX& a0, int batch, ConvPlan& p) {
     // k = 1, the 3 x 3 convolutions of small images and short 1-D sequences: the pipelined GEMM kernel (conv_x3p.hip)
     if (conv_x3g_plan(p)) return planned(14 + ((a.Co > 64 && a.Ci * a.ktaps > 1024) ? 3 : 5), 2 << 4);
   }
-  TileCfg t = choose_tile(a.Co, a.Tout, batch);
+  TileCfg t = choose_tile(a.Co, Tplan, batch);
   {
     // wide tiles (8 accumulators per wave): every workgroup re-fetches the whole weight image from L2, so the L2 -> LDS stream
     // per output halves with twice the positions per workgroup; taken when the grid still fills the chip several times over
     // (measured: C128 k11 610 -> 470 us; deeper weight buffering instead of wider tiles was slower)
     static const int wide_blk = exp_int("RVC_X3_WIDE", 600);
-    auto blocks = [&](int bm, int bn) { return (long long)((a.Co + bm - 1) / bm) * ((conv_plan_len(a.Tout) + bn - 1) / bn); };
+    auto blocks = [&](int bm, int bn) { return (long long)((a.Co + bm - 1) / bm) * ((Tplan + bn - 1) / bn); };
     if (wide_blk > 0 && a.stride == 1 && a.Wd == 0) {
       // (k <= 3 at 128+ channels is HBM-bound: three 128 x 128 workgroups per CU beat two wide ones, C128 k3 238 -> 219 us)
       // (round 2, after the staging / epilogue changes and with split-resident inputs: the 64 x 256 tile at three workgroups per CU now
@@ -564,15 +565,16 @@ bool conv_x3_plan(const ConvArgsX& a0, int batch, ConvPlan& p) {
   if ((xs || a0.Ys) && !(id == 3 || id == 4 || id == 7)) return false;             // tiles instantiated with the split-resident paths
   if (xs && a0.Ys) return false;                                                    // (one side at a time)
   const int BM = t.WM * t.AM * 32, BN = t.WN * t.AN * 32;
-  const long long nblk = ((conv_plan_len(a.Tout) + BN - 1) / BN) * ((a.Co + BM - 1) / BM);      // decisions (fp32 fall-back, K split): planning length; the grid below: a.Tout
+  const long long nblk = ((Tplan + BN - 1) / BN) * ((a.Co + BM - 1) / BM);      // decisions (fp32 fall-back, K split): planning length; the grid below: a.Tout
   static const int min_blk = exp_int("RVC_X3_MINBLK", 250);
   static const int min_blk2d = exp_int("RVC_X3_MINBLK2D", 20);   // deep U-Net levels: bf16x3 + split-K beats fp32 + split-K
   if (nblk < (a.Wd > 0 ? min_blk2d : min_blk)) return false;   // under-filled grids go to the fp32 kernel's split-K path
   if (t.WM == 2 && t.WN == 2 && batch == 1) {
     // the generator's stride-1 convolutions: software-pipelined kernel (conv_x3p.hip)
     // (the stride-2 mode exists for 128 x 128 tiles only: a shorter layer that would take 64-row tiles uses it as long as >= 150 tiles remain)
+    // (a kernel choice, so the planning length; no stride-2 launch is ever a column window - HuBERT's alone have stride 2 - so it equals a.Tout on every path there is)
     const bool s2_up = a.stride == 2 && a.ktaps == 3 && a.Co >= 128 && !(t.AM == 2 && t.AN == 2) &&
-                       (long long)((a.Co + 127) / 128) * ((a.Tout + 127) / 128) >= 150;
+                       (long long)((a.Co + 127) / 128) * ((Tplan + 127) / 128) >= 150;
     const int pam = s2_up ? 2 : t.AM, pan = s2_up ? 2 : t.AN;
     if (!s2_up && conv_x3q_plan(p, t.AM, t.AN)) return planned(14 + id, 6 << 4);   // the ResBlock convolutions: persistent workgroups (conv_x3q.hip)
     if (a.h2) return false;                                  // fp16x2 images are the persistent kernel's alone
@@ -645,8 +647,8 @@ bool conv_x3_plan(const ConvArgsX& a0, int batch, ConvPlan& p) {
 // ---------------------------------------------------------------------------- fused ResBlock pair (narrow generator stages)
 // The C = 32 stage of the generator is HBM-bound on the unfused kernels (each conv reads + writes [C][T] and the second one reads the
 // residual too: 5 tensor passes per pair); fused, a pair reads x (+ halo) twice (tile + residual, the second from L2) and writes y.
-bool conv_x3_pair_plan(const ConvLayer& c1, const ConvLayer& c2, const float* X, long long ldX, int T, float* Y, long long ldY, const ConvEpilogue& e2, int h2,
-                       ConvPlan& p) {
+bool conv_x3_pair_plan(const ConvLayer& c1, const ConvLayer& c2, const float* X, long long ldX, int T, long long Tplan, float* Y, long long ldY,
+                       const ConvEpilogue& e2, int h2, ConvPlan& p) {
   if (!c1.Wx_ || !c2.Wx_) return false;
   const int C = c1.Co, k = c1.k;
   if (c1.mode != 1 || c2.mode != 1 || c1.groups != 1 || c2.groups != 1 || c1.stride != 1 || c2.stride != 1 || c1.tconv_u || c2.tconv_u) return false;
@@ -658,8 +660,9 @@ bool conv_x3_pair_plan(const ConvLayer& c1, const ConvLayer& c2, const float* X,
   const int BN = C == 64 ? 128 : 256;
   const int P2 = (k - 1) / 2, P1 = c1.pad;
   const int NO = BN - 2 * P2;
-  if ((conv_plan_len(T) + NO - 1) / NO < 512) return false;      // short sequences: the unfused path fills the chip better
+  if ((Tplan + NO - 1) / NO < 512) return false;                 // short sequences: the unfused path fills the chip better
   p = ConvPlan{};
+  p.plan_T = Tplan;
   ConvArgsX& a = p.a;
   a.X = X; a.ldX = ldX; a.Y = Y; a.ldY = ldY; a.W = nullptr; a.bias = c2.bd_; a.bias1 = c1.bd_;
   a.R = e2.R; a.ldR = e2.ldR; a.pre_act = ACT_LRELU; a.pre_slope = 0.1f; a.fuse_slope = e2.pre_slope;
@@ -678,12 +681,12 @@ bool conv_x3_pair_plan(const ConvLayer& c1, const ConvLayer& c2, const float* X,
     // fp16x2 pair arithmetic: persistent workgroups with both weight sets resident in LDS (conv_rbh.hip)
     const ConvArgsX b = a;
     a.Wx = reinterpret_cast<const unsigned char*>(c1.Wh_); a.Wx2 = reinterpret_cast<const unsigned char*>(c2.Wh_); a.h2 = 1;
-    if (conv_rbh_plan(p, T)) return planned(14 + 1, 1 | (5 << 4));
+    if (conv_rbh_plan(p)) return planned(14 + 1, 1 | (5 << 4));
     a = b;
   }
   // the software-pipelined fused pair (conv_x3p.hip): 32 and 64 channels
   a.xcd_remap = x3_xcd_remap();
-  if (conv_x3pf_plan(p, T)) return planned(14 + (C == 32 ? 1 : 5), 1 | (3 << 4));
+  if (conv_x3pf_plan(p)) return planned(14 + (C == 32 ? 1 : 5), 1 | (3 << 4));
   if (C == 64) return false;                                     // (the staged pair at 64 channels was measured and not kept)
   const int P = BN + 2 * P1;                                      // staged input columns
   a.ni = (P + 63) / 64;

@@ -988,20 +988,20 @@ bool conv_x3g_plan(ConvPlan& p) {
   // 2-D: 3 x 3, pad 1, plain (no 2 x 2 up-sampling interleave), on images small enough that the nine shifted reads come from L2
   static const int max2d = exp_int("RVC_X3G_2D_MAXPOS", 30000);
   const bool two_d = a.Wd > 0;
-  if (two_d && !(a.ktaps == 9 && a.KW == 0 && !a.up2 && (a.Wd & (a.Wd - 1)) == 0 && a.Tout <= max2d)) return false;
+  if (two_d && !(a.ktaps == 9 && a.KW == 0 && !a.up2 && (a.Wd & (a.Wd - 1)) == 0 && p.plan_T <= max2d)) return false;
   // (measured against the staged kernel + split-K, launch incl. the reduction: 128 / 256 channels 36 -> 31 us, the level changes 50 -> 38;
   // 512 x 512 on 404 positions 34.5 -> 37: that one stays)
-  if (two_d && a.Ci >= 512 && a.Co <= 512 && a.Tout < 1000) return false;
+  if (two_d && a.Ci >= 512 && a.Co <= 512 && p.plan_T < 1000) return false;
   // 1-D with taps: only where the tiled kernels would not run (grids below their minimum: the 100-frames-per-second layers)
   const bool taps1d = !two_d && a.ktaps > 1;
-  if (taps1d && !(a.ktaps <= 16 && (long long)((a.Co + 127) / 128) * ((conv_plan_len(a.Tout) + 127) / 128) < 250)) return false;
+  if (taps1d && !(a.ktaps <= 16 && (long long)((a.Co + 127) / 128) * ((p.plan_T + 127) / 128) < 250)) return false;
   if (a.stride != 1 || a.ostride != 1 || a.Xs || a.Ys || (a.Ci & 15)) return false;
   if (!two_d && !taps1d && a.Tin != a.Tout) return false;
   // 64-row tiles for short reductions (K <= 1024: q/k/v 49 -> 40 us, flow 192 -> 192 16 -> 11), 128-row tiles for long ones (FFN2, K = 3072: 61 vs 75 us)
   const int AM = (a.Co > 64 && a.Ci * a.ktaps > 1024) ? 2 : 1, BM = 64 * AM, BN = 128;
   const int U = a.Ci / 16 * a.ktaps;
   if ((U & 3) || U < 8) return false;                              // unit loop unrolled by four
-  const long long nblk = (long long)((a.Co + BM - 1) / BM) * ((conv_plan_len(a.Tout) + BN - 1) / BN);      // (eligibility and K split: planning length)
+  const long long nblk = (long long)((a.Co + BM - 1) / BM) * ((p.plan_T + BN - 1) / BN);      // (eligibility and K split: planning length)
   static const int min_blk = exp_int("RVC_X3G_MINBLK", 24);
   if (nblk < (two_d ? 8 : min_blk)) return false;
   // K split: enough workgroups for the chip (a 128 x 128 tile of a K = 768 GEMM is 9 us of MFMAs), at least 8 units per split, groups of 4
@@ -1029,8 +1029,9 @@ static void launch_x3pf(const ConvArgsX& a, dim3 grid, size_t lds, hipStream_t s
 }
 // p.a: the fused pair's arguments as conv_x3_pair_plan prepared them (C = 32: 256 intermediate columns per tile; C = 64: 128).  false: not
 // this kernel's geometry.
-bool conv_x3pf_plan(ConvPlan& p, int T) {
+bool conv_x3pf_plan(ConvPlan& p) {
   ConvArgsX& a = p.a;
+  const int T = a.Tout;
   if (!(a.Ci == 32 || a.Ci == 64) || a.Co != a.Ci || !(a.ktaps == 3 || a.ktaps == 7 || a.ktaps == 11)) return false;
   const int C = a.Ci, BN = C == 32 ? 256 : 128;
   // 64 channels: the narrow wave tile (32 rows: one operand read per MFMA) only wins where the pair is HBM-bound - k = 3: 220 -> 151 us;
@@ -1040,7 +1041,7 @@ bool conv_x3pf_plan(ConvPlan& p, int T) {
   const int P = BN + (a.ktaps - 1) * a.dil;
   if (P > BN + 64) return false;
   const int NO = BN - (a.ktaps - 1);
-  if ((conv_plan_len(T) + NO - 1) / NO < 512) return false;      // short sequences: the unfused path fills the chip better
+  if ((p.plan_T + NO - 1) / NO < 512) return false;      // short sequences: the unfused path fills the chip better
   a.WROW = P; a.ni = (P + 63) / 64;
   p.lds = (size_t)(((C / 16) * 2 * P * 32 + 1023) & ~1023) + 4 * (size_t)(2 * C * 32);
   p.grid = dim3((unsigned)((T + NO - 1) / NO), 1, 1);

@@ -642,7 +642,7 @@ bool conv_x3q_plan(ConvPlan& p, int AM, int AN) {
   // one kernel for every ResBlock pair of the three wide stages)
   static const int min_rounds = exp_int("RVC_X3Q_MINROUNDS", 0);
   const long long slots = (long long)(wg_env > 0 ? wg_env : per_cu) * ncu;
-  const long long ptiles = ((conv_plan_len(a.Tout) + BN - 1) / BN) * (a.Co / BM);      // the decision: planning length; the grid: the tiles there are
+  const long long ptiles = ((p.plan_T + BN - 1) / BN) * (a.Co / BM);      // the decision: planning length; the grid: the tiles there are
   if (ptiles < min_rounds * slots || ptiles < 8) return false;
   RVC_REQUIRE(ntiles >= 8, "column window too narrow for the kernel its whole sequence runs on");
   // a multiple of 8 (a workgroup's later tiles stay on its XCD) unless every workgroup owns exactly one tile

@@ -669,10 +669,10 @@ static void x3s_dispatch(const GemmSArgs& a, int AM, int AN, unsigned blocks, hi
 // barriers and operand reads), tiles as large as that allows (L2 -> LDS bytes per MFMA fall with the tile), the deep reductions cut along K.
 static thread_local int t_force_s = 0, t_force_am = 0, t_force_an = 0;
 void conv_x3s_force(int ksplit, int am, int an) { t_force_s = ksplit; t_force_am = am; t_force_an = an; }
-static void x3s_plan(int M, int N, int units, int& AM, int& AN, int& S, int groups = 1) {
+// Nplan: the planning length - tile and K split (the sum order) are planned for the whole sequence, the caller's grid covers the columns there are.
+static void x3s_plan(int M, long long Nplan, int units, int& AM, int& AN, int& S, int groups = 1) {
   static const int target = exp_int("RVC_X3S_BLK", 440);
-  const long long Np = conv_plan_len(N);                     // tile and K split (the sum order) are planned for the whole sequence, the grid covers the columns there are
-  auto tiles = [&](int am, int an) { return (long long)groups * ((M + 64 * am - 1) / (64 * am)) * ((Np + 64 * an - 1) / (64 * an)); };
+  auto tiles = [&](int am, int an) { return (long long)groups * ((M + 64 * am - 1) / (64 * am)) * ((Nplan + 64 * an - 1) / (64 * an)); };
   // measured on MI355X at N = 1599 (tools/bench_gemm.py, profiles/r3b_bench_gemm.txt): 768 -> 3072 128 x 64 35 us (64 x 128 the same, 128 x 128 38),
   // 768 -> 2304 128 x 64 28 us, 768 -> 768 64 x 64 16.3 us un-split (17.6 split in two), 3072 -> 768 64 x 64 split in two 37.8 us (128 x 64 in three 39.0)
   AM = 2; AN = 2;
@@ -747,6 +747,7 @@ void conv_x3s_run(const ConvLayer& L, hipStream_t s, const unsigned char* Xs, lo
   }
   RVC_REQUIRE(Y != nullptr || e.ys_out != nullptr, "conv_x3s_run: no output");
   RVC_REQUIRE(e.pre_act == ACT_NONE && !e.accumulate && !e.tout_limit && !e.xs_in, "conv_x3s_run: unsupported epilogue option");
+  RVC_REQUIRE(e.plan_tin == 0 || (!s2 && L.mode == 1 && e.plan_tin >= T), "conv_x3s_run: a column window is a window of a longer 1-D 'same' convolution");
   RVC_REQUIRE(e.act == ACT_NONE || e.act == ACT_LRELU || e.act == ACT_RELU || e.act == ACT_GELU, "conv_x3s_run: activation must be identity / (leaky) ReLU / GELU");
   RVC_REQUIRE(!e.ys_out || ((e.ys_deint_h > 0 ? (e.ys_tp >= geom->margin + 2LL * e.ys_deint_h + 704 && (T + 1) / 2 + 1 <= e.ys_deint_h) : e.ys_tp >= geom->margin + T + 704) && (L.Co & 15) == 0),
               "conv_x3s_run: split output image too short or Co not a multiple of 16");
@@ -782,7 +783,7 @@ void conv_x3s_run(const ConvLayer& L, hipStream_t s, const unsigned char* Xs, lo
   a.bias = e.bias_override ? e.bias_override : L.bd_; a.R = e.R; a.ldR = e.ldR; a.Y = Y; a.ldY = ldY; a.Ys = e.ys_out; a.ysTp = e.ys_tp;
   a.act = e.act; a.act_slope = e.act_slope; a.act_before_res = e.act_before_res; a.out_scale = e.out_scale;
   int AM, AN, S;
-  x3s_plan(L.Co, T, a.nunits, AM, AN, S, G);
+  x3s_plan(L.Co, e.plan_tin > 0 ? e.plan_tin : T, a.nunits, AM, AN, S, G);      // ("same" convolution: output columns = input columns)
   const int BM = 64 * AM, BN = 64 * AN;
   RVC_REQUIRE(L.CoPx % BM == 0, "weight image rows are padded to the tile");
   a.rows_pg = (L.Co + BM - 1) / BM;

@@ -260,6 +260,27 @@ void synth_finalize(Synth* S) {
 }
 
 // ------------------------------------------------------------------------------------------------ forward
+// What a generator stage asks about its nine ResBlock pairs, asked in ONE place with the length of the WHOLE sequence at that stage (Tfull) - synth_graph launches
+// by the answers, synth_window_frames aligns the window by them.  split_pair: c1 writes the pair's intermediate as the split-resident image c2 stages in LDS;
+// h2_pair: both halves on the persistent kernel in its fp16x2 arithmetic (the image is then fp16 hi / lo; conv_x3q.hip); period: columns after which the order of
+// a column's fp32 additions repeats in every split pair (the least common multiple of conv1d_residual_period; 1 without split pairs).
+struct GenPairs { bool split_pair[3][3], h2_pair[3][3]; bool any_split = false; long long period = 1; };
+static long long gcd_ll(long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; }
+static GenPairs gen_stage_pairs(const GenStage& st, int Tfull, int h2) {
+  GenPairs g;
+  for (int j = 0; j < 3; ++j)
+    for (int m = 0; m < 3; ++m) {
+      const ConvLayer& c1 = st.rb[j].c1[m]; const ConvLayer& c2 = st.rb[j].c2[m];
+      g.split_pair[j][m] = conv1d_split_eligible(c1, Tfull, SPLIT_PRODUCER) && conv1d_split_eligible(c2, Tfull, SPLIT_CONSUMER);
+      g.h2_pair[j][m] = g.split_pair[j][m] && conv1d_pair_h2_eligible(c1, c2, Tfull, h2);
+      if (!g.split_pair[j][m]) continue;
+      g.any_split = true;
+      const long long per = conv1d_residual_period(c2, Tfull, g.h2_pair[j][m] ? 1 : 0);
+      g.period = g.period / gcd_ll(g.period, per) * per;
+    }
+  return g;
+}
+
 static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm, const long long* pitch, const float* pitchf, int sid,
                         const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps, int g0, int g1) {
   // [g0, g1): the frames the generator runs on (synth_infer: the keep window plus its halo; [0, T): the whole sequence).  Everything up to the flow is full length.
@@ -475,10 +496,11 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
     }
   }
   // From here on every tensor holds the W columns of the window; the three full-length operands are addressed at its start: z + g0 (pitch T), har + g0 upp,
-  // out + g0 upp.  Inside the planning-length scope every launch is planned for the whole sequence and sized for the window (ConvPlanLenScope): a window's
-  // columns are computed by the kernels, tiles and K splits of the full pass.  Columns within the halo of a cut edge see zero padding there and are wrong;
+  // out + g0 upp.  Every launch is planned for the whole sequence and sized for the window: beside a stage's window length (Tc, Tn) runs the whole sequence's
+  // (Tfull_c, Tfull_n), handed to every planner and, as ConvEpilogue::plan_tin, to every *_run - a window's columns are computed by the kernels, tiles and K
+  // splits of the full pass.  With [0, T) the two are equal and plan_tin stays 0.  Columns within the halo of a cut edge see zero padding there and are wrong;
   // the caller keeps none of them.
-  ConvPlanLenScope plan_len(W, T);
+  auto plan_tin = [&](int tin_full) { return W != T ? tin_full : 0; };
   const long long Nw = (long long)W * S->upp;
   const float* har_w = har ? har + (size_t)g0 * S->upp : nullptr;
   float* zw = (!gs && W != T) ? A.alloc<float>((size_t)IC * W) : nullptr;      // (the fp32 path stages rows from an aligned base: the window densely)
@@ -486,18 +508,19 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
   if (!dry) {
     ConvEpilogue Eb; Eb.bias_override = pre_bias;
     const long long tpw = split_image_tp(W);
+    Eb.plan_tin = plan_tin(T);
     if (gs) { split_image_from_f32(s, z + g0, T, IC, W, z_s, tpw); conv_x3s_run(S->conv_pre, s, z_s, tpw, W, cur, W, Eb); }     // k = 7
     else if (zw) {
       RVC_HIP_CHECK(hipMemcpy2DAsync(zw, (size_t)W * sizeof(float), z + g0, (size_t)T * sizeof(float), (size_t)W * sizeof(float), IC, hipMemcpyDeviceToDevice, s));
       conv1d_run(S->conv_pre, s, zw, W, W, cur, W, Eb);
     } else conv1d_run(S->conv_pre, s, z, T, T, cur, T, Eb);
   }
-  int Tc = W;
+  int Tc = W, Tfull_c = T;
   const int nu = (int)S->stages.size();
   for (int i = 0; i < nu; ++i) {
     GenStage& st = S->stages[i];
     const int Cc = S->up_init >> (i + 1);
-    const int Tn = Tc * st.u;
+    const int Tn = Tc * st.u, Tfull_n = Tfull_c * st.u;
     float* up = A.alloc<float>((size_t)Cc * Tn);
     float* t1 = A.alloc<float>((size_t)Cc * Tn);
     float* ya = A.alloc<float>((size_t)Cc * Tn);
@@ -507,22 +530,15 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
     // split-resident intermediate of a ResBlock pair: c1's epilogue writes t = lrelu(c1(..) + b1) as the bf16 hi / lo image c2 stages in
     // LDS (DMA, no conversion, no staging registers; 4 b128 stores per accumulator instead of 16 dword stores on c1's side)
     // h2_pair: both halves on the persistent kernel in its fp16x2 arithmetic (two MFMAs per product; conv_x3q.hip) - the pair's image is then fp16 hi / lo
-    bool split_pair[3][3], h2_pair[3][3];
-    bool any_split = false;
-    for (int j = 0; j < 3; ++j)
-      for (int m = 0; m < 3; ++m) {
-        split_pair[j][m] = conv1d_split_eligible(st.rb[j].c1[m], Tn, SPLIT_PRODUCER) && conv1d_split_eligible(st.rb[j].c2[m], Tn, SPLIT_CONSUMER);
-        h2_pair[j][m] = split_pair[j][m] && conv1d_pair_h2_eligible(st.rb[j].c1[m], st.rb[j].c2[m], Tn, h2);
-        any_split = any_split || split_pair[j][m];
-      }
-    unsigned char* t1s = any_split ? A.alloc<unsigned char>(split_image_bytes(Cc, Tn)) : nullptr;
+    const GenPairs gp = gen_stage_pairs(st, Tfull_n, h2);
+    unsigned char* t1s = gp.any_split ? A.alloc<unsigned char>(split_image_bytes(Cc, Tn)) : nullptr;
     if (!dry) {
       RVC_REQUIRE(conv1d_out_len(st.up, Tc) == Tn, "ConvTranspose1d geometry must give T_out = u * T_in");
       // up-sampled signal first (interleaved store of the transposed conv's phases, no read-modify-write), then the noise branch is
       // added by its own convolution's dense epilogue: the same two-operand fp32 sum as noise first / up-conv accumulating
-      ConvEpilogue Eu; Eu.pre_act = ACT_LRELU; Eu.pre_slope = 0.1f;
+      ConvEpilogue Eu; Eu.plan_tin = plan_tin(Tfull_c); Eu.pre_act = ACT_LRELU; Eu.pre_slope = 0.1f;
       conv1d_run(st.up, s, cur, Tc, Tc, up, Tn, Eu);
-      ConvEpilogue En; En.accumulate = 1;
+      ConvEpilogue En; En.plan_tin = plan_tin(Tfull_n); En.accumulate = 1;
       // last stage (one tap of the source per position) with all three ResBlocks on conv_rb3_kernel: the noise term is added where x is read
       // (the gen_ups0 tap wants the summed tensor)
       bool noise_in_rb3 = S->f0 && st.noise_k == 1 && st.noise_w.p != nullptr && Nw == (long long)Tn && !(taps && i == 0);
@@ -534,7 +550,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
         for (int j = 0; j < 3; ++j) {
           const ConvLayer* r1[3] = {&st.rb[j].c1[0], &st.rb[j].c1[1], &st.rb[j].c1[2]};
           const ConvLayer* r2[3] = {&st.rb[j].c2[0], &st.rb[j].c2[1], &st.rb[j].c2[2]};
-          rb3_ok[j] = conv_rb3_plan(r1, r2, up, Tn, Tn, xs, Tn, 0.1f, 1.f / 3.f, j > 0, h2, noise ? har_w : nullptr, noise ? st.noise_w.p : nullptr,
+          rb3_ok[j] = conv_rb3_plan(r1, r2, up, Tn, Tn, Tfull_n, xs, Tn, 0.1f, 1.f / 3.f, j > 0, h2, noise ? har_w : nullptr, noise ? st.noise_w.p : nullptr,
                                     noise ? st.noise_b.p : nullptr, rb3[j]);
           all = all && rb3_ok[j];
         }
@@ -558,17 +574,17 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
         const float* in = up;
         if (rb3_ok[j]) { conv_rb3_launch(rb3[j], s); continue; }
         for (int m = 0; m < 3; ++m) {
-          ConvEpilogue E2; E2.pre_act = ACT_LRELU; E2.pre_slope = 0.1f; E2.R = in; E2.ldR = Tn;
+          ConvEpilogue E2; E2.plan_tin = plan_tin(Tfull_n); E2.pre_act = ACT_LRELU; E2.pre_slope = 0.1f; E2.R = in; E2.ldR = Tn;
           float* dst = (m == 0) ? ya : (m == 1 ? yb : xs);
           if (m == 2) { E2.out_scale = 1.f / 3.f; E2.accumulate = (j > 0); }
           // narrow stages: both convs of the pair in one launch, the intermediate stays in LDS (conv_x3.hip, FUSE)
           ConvPlan pp;
-          if (conv_x3_pair_plan(st.rb[j].c1[m], st.rb[j].c2[m], in, Tn, Tn, dst, Tn, E2, h2, pp)) conv_plan_launch(pp, s);
+          if (conv_x3_pair_plan(st.rb[j].c1[m], st.rb[j].c2[m], in, Tn, Tn, Tfull_n, dst, Tn, E2, h2, pp)) conv_plan_launch(pp, s);
           else {
-            ConvEpilogue E1; E1.pre_act = ACT_LRELU; E1.pre_slope = 0.1f;
-            if (split_pair[j][m]) {
+            ConvEpilogue E1; E1.plan_tin = plan_tin(Tfull_n); E1.pre_act = ACT_LRELU; E1.pre_slope = 0.1f;
+            if (gp.split_pair[j][m]) {
               E1.ys_out = t1s; E1.ys_tp = split_image_tp(Tn); E1.ys_slope = E2.pre_slope;       // c2's input activation, applied once by the producer
-              E1.h2 = h2_pair[j][m] ? 1 : 0;
+              E1.h2 = gp.h2_pair[j][m] ? 1 : 0;
               conv1d_run(st.rb[j].c1[m], s, in, Tn, Tn, nullptr, Tn, E1);
               ConvEpilogue E2s = E2; E2s.pre_act = ACT_NONE; E2s.xs_in = t1s; E2s.xs_tp = E1.ys_tp; E2s.h2 = E1.h2;
               conv1d_run(st.rb[j].c2[m], s, nullptr, Tn, Tn, dst, Tn, E2s);
@@ -582,7 +598,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
       }
       if (taps && i == nu - 1) tap(taps->gen_last, xs, (size_t)Cc * Tn);
     }
-    cur = xs; Tc = Tn;
+    cur = xs; Tc = Tn; Tfull_c = Tfull_n;
   }
   if (!dry) conv_to1(s, cur, Tc, S->conv_post_w.p, S->up_init >> nu, 7, 3, Tc, 0.01f, 1, out + (size_t)g0 * S->upp);
 }
@@ -601,20 +617,14 @@ void synth_window_frames(const Synth* S, int T, long long keep0, long long keep1
   const int kMinWindow = 128;
   if (g1 - g0 < kMinWindow && halo < 0) { g0 = std::max(0, std::min(g0, T - kMinWindow)); g1 = std::min(T, std::max(g1, g0 + kMinWindow)); }
   const int h2 = conv_set_pair_arithmetic(-1);
-  auto gcd = [](long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; };
   long long align = 1, pu = 1;
   for (const GenStage& st : S->stages) {
     pu *= st.u;
     const long long Tn = (long long)T * pu;
     if (Tn >= (1LL << 31)) break;
-    for (int j = 0; j < 3; ++j)
-      for (int m = 0; m < 3; ++m) {
-        const ConvLayer& c1 = st.rb[j].c1[m]; const ConvLayer& c2 = st.rb[j].c2[m];
-        if (!(conv1d_split_eligible(c1, (int)Tn, SPLIT_PRODUCER) && conv1d_split_eligible(c2, (int)Tn, SPLIT_CONSUMER))) continue;
-        const long long per = conv1d_residual_period(c2, (int)Tn, conv1d_pair_h2_eligible(c1, c2, (int)Tn, h2) ? 1 : 0);
-        const long long need = per / gcd(per, pu);               // frames whose columns at this stage are a multiple of the period
-        align = align / gcd(align, need) * need;
-      }
+    const long long per = gen_stage_pairs(st, (int)Tn, h2).period;
+    const long long need = per / gcd_ll(per, pu);                // frames whose columns at this stage are a multiple of the period
+    align = align / gcd_ll(align, need) * need;
   }
   g0 -= (int)(g0 % align);
   *og0 = g0; *og1 = g1;

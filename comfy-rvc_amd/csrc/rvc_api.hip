@@ -950,7 +950,7 @@ int rvc_conv1d_plan_pair_run(rvc_conv1d_plan* c1, rvc_conv1d_plan* c2, void* str
   RVC_REQUIRE(c1 && c2 && x && y, "null argument");
   ConvEpilogue e; e.pre_act = ACT_LRELU; e.pre_slope = 0.1f; e.R = x; e.ldR = T; e.out_scale = out_scale; e.accumulate = accumulate;
   ConvPlan p;
-  RVC_REQUIRE(conv_x3_pair_plan(c1->L, c2->L, x, T, T, y, T, e, conv_set_pair_arithmetic(-1), p),
+  RVC_REQUIRE(conv_x3_pair_plan(c1->L, c2->L, x, T, T, T, y, T, e, conv_set_pair_arithmetic(-1), p),
               "this pair of layers is not eligible for the fused ResBlock kernel (needs bf16x3 images, C = 32, equal odd k, long T)");
   conv_plan_launch(p, (hipStream_t)stream);
   check_launch();
@@ -966,7 +966,7 @@ int rvc_conv1d_plan_resblock_run(rvc_conv1d_plan* const* plans6, void* stream, c
     c1[i] = &plans6[2 * i]->L; c2[i] = &plans6[2 * i + 1]->L;
   }
   Rb3Plan p;
-  *ran_out = conv_rb3_plan(c1, c2, x, T, T, y, T, 0.1f, out_scale, accumulate, conv_set_pair_arithmetic(-1), noise_src, noise_w, noise_b, p) ? 1 : 0;
+  *ran_out = conv_rb3_plan(c1, c2, x, T, T, T, y, T, 0.1f, out_scale, accumulate, conv_set_pair_arithmetic(-1), noise_src, noise_w, noise_b, p) ? 1 : 0;
   if (*ran_out) conv_rb3_launch(p, (hipStream_t)stream);
   check_launch();
   RVC_CATCH
@@ -995,7 +995,7 @@ int rvc_conv1d_plan_pair_arithmetic(rvc_conv1d_plan* c1, rvc_conv1d_plan* c2, in
     // the fused pair of the narrow stages: which kernel family the plan chose (planning needs no tensors: x = residual = null)
     ConvEpilogue e; e.pre_act = ACT_LRELU; e.pre_slope = 0.1f; e.ldR = T;
     ConvPlan p;
-    return conv_x3_pair_plan(c1->L, c2->L, nullptr, T, T, nullptr, T, e, h2, p) && p.a.h2 ? 1 : 0;
+    return conv_x3_pair_plan(c1->L, c2->L, nullptr, T, T, T, nullptr, T, e, h2, p) && p.a.h2 ? 1 : 0;
   } catch (...) { return -1; }
 }
 int rvc_conv1d_plan_destroy(rvc_conv1d_plan* p) { if (p) { conv_layer_free(p->L); delete p; } return 0; }

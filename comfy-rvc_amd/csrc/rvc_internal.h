@@ -108,6 +108,7 @@ struct ConvEpilogue {
   float out_scale = 1.f; int accumulate = 0;
   const float* bias_override = nullptr;   // per-call bias vector replacing the layer's own (speaker conditioning)
   int tout_limit = 0;                     // >0: compute only the first tout_limit output positions
+  int plan_tin = 0;                       // >0: this launch is a column window of a sequence of plan_tin INPUT columns ("Planning length" below); 0: it is the whole sequence
   // split-resident activations (bf16x3 kernel only, conv_x3.hip): the tensor lives as the bf16 hi / lo image the kernel stages in LDS,
   // [16-channel chunk][hi | lo][8-channel half][kSplitMargin + t][8 ch], written by the producer's epilogue (activation `ys_slope` already applied)
   // and copied straight into LDS by the consumer (no conversion, no registers).  xs_in replaces X, ys_out replaces Y.
@@ -130,6 +131,8 @@ inline size_t split_image_bytes(int C, long long T) { return (size_t)(C / 16) * 
 // true when this layer at this length runs on the bf16x3 kernel with a tile that has the split-resident path of its ROLE: a producer
 // (writes the image: ConvEpilogue::ys_out) and a consumer (stages it: xs_in) take different branches of the tile choice, so each role
 // is planned with its own geometry.  pre_lrelu: the producer's input activation (part of the real launch's arguments).
+// These three questions are pure functions of their arguments.  Tin is the length the decision is made for: where the launch is a column window of a longer
+// sequence, the caller passes the WHOLE sequence's length ("Planning length" below).
 enum SplitRole : int { SPLIT_CONSUMER = 0, SPLIT_PRODUCER = 1 };
 bool conv1d_split_eligible(const ConvLayer& L, int Tin, SplitRole role = SPLIT_CONSUMER, int h2 = 0);
 // both layers of a ResBlock pair carry an fp16 image and both launches land on the persistent kernel at this length; false when the pair arithmetic is switched to bf16x3
@@ -142,17 +145,11 @@ bool conv1d_pair_h2_eligible(const ConvLayer& c1, const ConvLayer& c2, int Tin, 
 int conv1d_residual_period(const ConvLayer& L, int Tin, int h2);
 int conv_set_pair_arithmetic(int mode);   // process-wide: 1 = fp16x2 on eligible ResBlock pairs (default), 0 = bf16x3 everywhere; < 0 queries; returns the previous mode
 
-// Planning length.  A launch over a column WINDOW of a longer sequence (the generator behind synth_infer's keep window) must compute, column for column, what the
-// launch over the whole sequence computes: every question that picks a kernel, a tile, an arithmetic or a K split is therefore asked with the length of the WHOLE
-// sequence, and only grids and buffers are sized by the window.  Inside a scope conv_plan_len(n) = n * full / win (the stage lengths of a window are multiples of
-// `win`, so the scaling is exact); outside one it is n.  Thread-local, like the build scopes below.
-long long conv_plan_len(long long n);
-struct ConvPlanLenScope {
-  long long prev_win, prev_full;
-  ConvPlanLenScope(long long win, long long full);
-  ~ConvPlanLenScope();
-  ConvPlanLenScope(const ConvPlanLenScope&) = delete; ConvPlanLenScope& operator=(const ConvPlanLenScope&) = delete;
-};
+// Planning length: the output columns of the WHOLE sequence that a launch is a column window of (the generator behind synth_infer's keep window).  Such a launch
+// must compute, column for column, what the launch over the whole sequence computes, so DECISIONS READ THE PLANNING LENGTH (kernel, tile, arithmetic, K split,
+// fall-back thresholds) and SIZES READ THE REAL ONE (grids, ldP, buffers, image rows).  It is an argument like the pair arithmetic h2: ConvEpilogue::plan_tin
+// for the *_run functions (0 = the launch is the whole sequence), a parameter of the planners (conv_kernels.h), the length itself for the three questions
+// above.  It lives in host-side types only: no kernel-argument struct holds it, so no kernel can see it.
 
 // host-side packing + upload (weights in PyTorch layouts)
 void conv1d_layer_init(ConvLayer& L, const float* w /*[Co][Ci/groups][k]*/, const float* bias, int Co, int Ci, int k,

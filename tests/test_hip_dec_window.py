@@ -136,6 +136,51 @@ def test_window_equals_full_run(net, full, T, arith, tmp_path):
             assert "conv_rb3_kernel" in kernels, kernels
 
 
+def _launch_table(n, d, keep, path):
+    """(output, rows of the launch table as dicts) of one run with per-launch profiling on."""
+    L = _lib()
+    try:
+        L.check(L.lib.rvc_prof_enable(1))
+        out = _run(n, d, keep)
+        L.check(L.lib.rvc_prof_dump_csv(str(path).encode()))
+    finally:
+        L.check(L.lib.rvc_prof_enable(0))
+    lines = open(path).read().strip().split("\n")
+    cols = lines[0].split(",")
+    return out, [dict(zip(cols, ln.split(","))) for ln in lines[1:]]
+
+
+@pytest.mark.parametrize("arith", [0, 1], indirect=True)
+def test_short_window_of_a_long_sequence_runs_the_full_runs_kernels(net, full, arith, tmp_path):
+    """A window far too short to earn the full run's kernels on its own length: every launch is planned for the whole sequence, only its grid follows the window.
+
+    The other cases would also pass with a planner that looked at the window's length (T = 300 runs nothing persistent, [64, 811) of 900 is long enough for
+    every kernel of the full run).  Here the last stage has about 53 000 columns where conv_rb3_kernel asks for two rounds of 512-column tiles on 256 CUs and
+    the fused pairs for 512 tiles."""
+    L = _lib()
+    T, (k0, k1) = 900, (400, 500)
+    d, ref = full[(T, arith)]
+    g0, g1 = C.c_int64(), C.c_int64()
+    L.check(L.lib.rvc_synth_window_frames(net._h, T, k0, k1, C.byref(g0), C.byref(g1)))
+    g0, g1 = g0.value, g1.value
+    assert 0 <= g0 <= k0 and k1 <= g1 <= T and (g1 - g0) * UPP < 2 * 256 * 512, (g0, g1)
+    _, rows_full = _launch_table(net, d, None, tmp_path / "full.csv")
+    out, rows_win = _launch_table(net, d, (k0, k1), tmp_path / "window.csv")
+    _same_in_window(out, ref, k0, k1)
+    # the generator's rows: in the windowed table everything behind the last full-length launch (text encoder and flow run on all T frames)
+    assert len(rows_full) == len(rows_win), (len(rows_full), len(rows_win))
+    first = max(i for i, r in enumerate(rows_win) if int(r["Tout"]) == T) + 1
+    assert first < len(rows_win)
+    same = ("kernel", "tile", "Ci", "Co", "k", "dil", "stride", "fused_pair", "ksplit", "mfma_per_product")      # only Tout and workgroups may differ
+    for i in range(first, len(rows_win)):
+        assert [rows_win[i][c] for c in same] == [rows_full[i][c] for c in same], (i, rows_win[i], rows_full[i])
+        assert int(rows_win[i]["Tout"]) < int(rows_full[i]["Tout"]), (i, rows_win[i], rows_full[i])
+    kernels = set(r["kernel"] for r in rows_win[first:])
+    assert "conv_x3q_kernel" in kernels, kernels
+    if arith == 1:
+        assert "conv_rb3_kernel" in kernels, kernels
+
+
 @pytest.mark.parametrize("arith", [0, 1], indirect=True)
 def test_halo_is_sufficient_and_tight(net, full, arith):
     """The derived halo reproduces the window; one frame less must not (otherwise the derivation is loose by a frame)."""
