@@ -43,6 +43,7 @@ struct Ctx {
   size_t workspace_bytes = 0;   // sum of the model arenas (informational)
   int precision = -1;           // conv arithmetic of the models built on this context: 0 fp32 MFMA only, 1 / 2 bf16x3 split where eligible,
                                 // -1 (default): the mode of the thread that finalizes the model (rvc_set_conv_precision, default 1)
+  struct SpecState* spec = nullptr;   // FFT tables per n_fft and mel filterbanks per (n_fft, n_mels), made on first use (spectrogram.hip); spec_state_free
 };
 
 // device vector owned by a model

@@ -68,6 +68,16 @@ void kmeans_update(hipStream_t s, const float* rows, const int* label, long long
 void index_train(Ctx* ctx, hipStream_t s, const float* rows, long long N, int D, const long long* init_rows, int K, int niter, float* cent, int* label,
                  double* inertia);
 
+// training inputs (spectrogram.hip): magnitude spectrograms of a ragged batch of clips by an LDS FFT, out [n_fft / 2 + 1][pitch]; clips (HOST)
+// [n_clips][3] = (sample offset, samples, first output column); one launch.  Mel: the banded filterbank of (n_fft, n_mels) is set once, then
+// mel [n_mels][mel_pitch] = log(max(W spec, 1e-5)) over clips (HOST) [n_clips][2] = (first column, frames); one launch.
+void spectrogram_batch(Ctx* ctx, hipStream_t s, const float* audio, long long n_audio, const long long* clips, int n_clips, int n_fft, int hop, float eps,
+                       int clamp, float* out, long long pitch);
+void mel_filterbank_set(Ctx* ctx, int n_fft, int n_mels, const int* first, const int* count, const float* weights);
+void spec_to_mel_batch(Ctx* ctx, hipStream_t s, const float* spec, long long spec_pitch, const long long* clips, int n_clips, int n_fft, int n_mels,
+                       float* mel, long long mel_pitch);
+void spec_state_free(Ctx* ctx);
+
 void rmvpe_decode_rm(Rmvpe* R, hipStream_t s, const float* sal_rm, long long n, float thred, double* f0);
 int rmvpe_status(Rmvpe* R, hipStream_t s);                 // waits for the stream; bit 0: the last forward's GRU scan timed out
 void rmvpe_debug_fault(Rmvpe* R, int fault, unsigned spin_limit);   // tests: make the next scans fail / shorten their spin limit

@@ -58,6 +58,7 @@ int rvc_ctx_destroy(rvc_ctx* ctx) {
   bool last;
   { std::lock_guard<std::mutex> lk(g_ctx_mu); last = --g_ctx_count[ctx->c.device] <= 0; }
   if (last) { (void)hipSetDevice(ctx->c.device); stream_scratch_release(ctx->c.device); }   // per-stream scratch goes with the last context of a device
+  spec_state_free(&ctx->c);
   delete ctx;
   return 0;
 }
@@ -516,6 +517,31 @@ int rvc_segment_energy(void* stream, const int16_t* x, int64_t n, int k, int64_t
   RVC_TRY
   RVC_REQUIRE(x && out && k >= 1 && n >= k, "bad argument");
   segment_energy((hipStream_t)stream, x, n, k, (long long*)out);
+  check_launch();
+  RVC_CATCH
+}
+
+// ------------------------------------------------------------------------------------------------ training inputs (spectrogram.hip)
+int rvc_spectrogram_batch(rvc_ctx* ctx, void* stream, const float* audio, int64_t n_audio, const int64_t* clips, int n_clips, int n_fft, int hop, float eps,
+                          int clamp, float* out, int64_t pitch) {
+  RVC_TRY
+  RVC_REQUIRE(ctx && audio && out && (clips || n_clips == 0), "null argument");
+  spectrogram_batch(&ctx->c, (hipStream_t)stream, audio, n_audio, (const long long*)clips, n_clips, n_fft, hop, eps, clamp, out, pitch);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_mel_filterbank_set(rvc_ctx* ctx, int n_fft, int n_mels, const int32_t* first, const int32_t* count, const float* weights) {
+  RVC_TRY
+  RVC_REQUIRE(ctx, "null argument");
+  RVC_HIP_CHECK(hipSetDevice(ctx->c.device));
+  mel_filterbank_set(&ctx->c, n_fft, n_mels, (const int*)first, (const int*)count, weights);
+  RVC_CATCH
+}
+int rvc_spec_to_mel_batch(rvc_ctx* ctx, void* stream, const float* spec, int64_t spec_pitch, const int64_t* clips, int n_clips, int n_fft, int n_mels,
+                          float* mel, int64_t mel_pitch) {
+  RVC_TRY
+  RVC_REQUIRE(ctx && spec && mel && (clips || n_clips == 0), "null argument");
+  spec_to_mel_batch(&ctx->c, (hipStream_t)stream, spec, spec_pitch, (const long long*)clips, n_clips, n_fft, n_mels, mel, mel_pitch);
   check_launch();
   RVC_CATCH
 }

@@ -229,6 +229,50 @@ def preprocess_trainset(inp_root, sr, n_p, exp_dir, preprocessor=None, period=3.
         return False
 
 
+# (n_fft, hop, window) of the reference's configs/*.json by model rate: 32k.json / 32k_v2.json, 40k.json, 48k.json / 48k_v2.json
+SPEC_GEOMETRY = {32000: (1024, 320, 1024), 40000: (2048, 400, 2048), 48000: (2048, 480, 2048)}
+
+
+def cache_spectrograms_trainset(exp_dir, sr_or_hparams, device="cuda:0", rank=0, world=1, max_batch_bytes=256 << 20):
+    """Writes `{clip}.spec.pt` next to every exp_dir/0_gt_wavs/*.wav that has none: the linear spectrogram TextAudioLoaderMultiNSFsid.get_audio would
+    compute and cache on first touch (reference lib/train/data_utils.py:93-131), a CPU float32 [n_fft / 2 + 1, samples // hop] tensor saved with
+    _use_new_zipfile_serialization=False as the reference saves it.  sr_or_hparams: a model rate (32000 / 40000 / 48000: the geometry of the reference's
+    configs) or an object with sampling_rate, filter_length, hop_length and win_length (lib/train/utils.py::HParams, or its `data` section).  The sorted
+    file list is sharded rank::world like FeatureInput.go; the clips are packed into ragged batches of at most max_batch_bytes of output and every batch
+    is ONE rvc_spectrogram_batch launch.  Existing caches are left alone (the loaders would load them).  Returns the number of files written."""
+    from scipy.io import wavfile   # noqa: PLC0415
+    from .lib.train import mel_processing as MP   # noqa: PLC0415
+    if isinstance(sr_or_hparams, (int, np.integer)):
+        sr = int(sr_or_hparams)
+        if sr not in SPEC_GEOMETRY:
+            raise ValueError(f"no training configuration for {sr} Hz: pass hparams")
+        n_fft, hop, win = SPEC_GEOMETRY[sr]
+    else:
+        hp = getattr(sr_or_hparams, "data", sr_or_hparams)
+        sr, n_fft, hop, win = int(hp.sampling_rate), int(hp.filter_length), int(hp.hop_length), int(hp.win_length)
+    gt_dir = os.path.join(exp_dir, "0_gt_wavs")
+    names = sorted(n for n in os.listdir(gt_dir) if n.endswith(".wav"))[int(rank)::max(int(world), 1)]
+    todo = [os.path.join(gt_dir, n) for n in names if not os.path.exists(os.path.join(gt_dir, n.replace(".wav", ".spec.pt")))]
+    bins, written, i = n_fft // 2 + 1, 0, 0
+    while i < len(todo):
+        paths, clips, nbytes = [], [], 0
+        while i < len(todo) and (not clips or nbytes < max_batch_bytes):
+            rate, data = wavfile.read(todo[i])
+            if rate != sr:
+                raise ValueError("{} SR doesn't match target {} SR".format(rate, sr))
+            x = np.asarray(data).astype(np.float32)
+            paths.append(todo[i])
+            clips.append(x if x.ndim == 1 else x.mean(-1))
+            nbytes += bins * (-(-(x.shape[0] // hop) // MP.FRAME_ALIGN) * MP.FRAME_ALIGN) * 4
+            i += 1
+        packed, cols = MP.spectrogram_batch(clips, n_fft, hop, win, device=device)
+        host = packed.cpu()
+        for path, (col, nf) in zip(paths, cols.tolist()):
+            torch.save(host[:, col:col + nf].clone(), path.replace(".wav", ".spec.pt"), _use_new_zipfile_serialization=False)
+            written += 1
+    return written
+
+
 def extract_features_trainset(hubert_model, exp_dir, n_p, f0method, device, version, if_f0, crepe_hop_length):
     """HuBERT features and pitch of every clip in exp_dir/1_16k_wavs (reference preprocessing_utils.py:210-253): outputs named
     "{f0method},{clip}" under 2a_f0, 2b-f0nsf and 3_feature768 (3_feature256 for v1); inputs with "spec" in their path are skipped.  `n_p`

@@ -472,6 +472,115 @@ def slicer_test_signal(sr, seed=0, segments=SLICER_SEGMENTS):
     return np.concatenate(parts).astype(np.float32)
 
 
+SPEC_ZERO_RUN = 2048 + 480 + 72      # the longest n_fft + hop of the training configurations, and a little more
+
+
+def spec_test_signal(sr, n, seed=0):
+    """float32 [n] for the spectrogram tests: a tone gliding from 110 to 880 Hz at 0.5 with a 5 Hz amplitude modulation plus 1 % white noise; samples
+    [n // 3, n // 3 + SPEC_ZERO_RUN) are exact zeros where n >= 3 SPEC_ZERO_RUN (whole silent frames: the epsilon under the root and the mel floor),
+    and max(1, n // 500) samples at positions drawn after the noise are set to +-1.2, so that the clamp to +-1.05 matters."""
+    rng = np.random.default_rng(seed)
+    t = np.arange(n, dtype=np.float64) / sr
+    dur = max(n / sr, 1e-9)
+    phase = 2 * np.pi * (110.0 * t + (880.0 - 110.0) * t * t / (2 * dur))
+    x = 0.5 * np.sin(phase) * (0.7 + 0.3 * np.sin(2 * np.pi * 5.0 * t)) + 0.01 * rng.standard_normal(n)
+    pos = rng.choice(n, size=max(1, n // 500), replace=False)
+    x[pos] = np.where(rng.random(pos.shape[0]) < 0.5, -1.2, 1.2)
+    if n >= 3 * SPEC_ZERO_RUN:
+        x[n // 3:n // 3 + SPEC_ZERO_RUN] = 0.0            # (last: the run stays whole)
+    return x.astype(np.float32)
+
+
+# spectrogram frames of the 12 clips of write_train_filelist (one beyond the 900-frame label cut) and the 50 fps label rows relative to frames // 2
+TRAIN_FILELIST_FRAMES = (12, 30, 33, 47, 58, 75, 76, 90, 101, 140, 150, 910)
+TRAIN_FILELIST_PHONE_DELTA = (0, 1, -1, 0, 3, 0, -2, 0, 1, 0, 0, 5)
+TRAIN_FILELIST_BOUNDARIES = (32, 100, 150, 180, 300, 2000)      # over getsize // (3 hop): one clip below, (150, 180] empty
+
+
+def write_train_filelist(root, sr=40000, hop=400, seed=0, feat_dim=16, spec_bins=None):
+    """A 12-row training file list under `root` for the loader tests: 0_gt_wavs/{i}_0.wav (IEEE-float WAV of spec_test_signal, frames * hop + 7 i
+    samples), 3_feature768/{i}_0.npy (float32 [frames // 2 + delta, feat_dim]), 2a_f0 / 2b-f0nsf (int64 / float32 [frames + 3]) and filelist.txt with
+    speaker ids i % 3.  spec_bins: also write {i}_0.spec.pt, zeros [spec_bins, samples // hop], so that a loader needs no device.  Returns the path
+    of filelist.txt."""
+    import os                              # noqa: PLC0415
+    from scipy.io import wavfile           # noqa: PLC0415
+    rng = np.random.default_rng(seed)
+    dirs = {k: os.path.join(root, k) for k in ("0_gt_wavs", "2a_f0", "2b-f0nsf", "3_feature768")}
+    for d in dirs.values():
+        os.makedirs(d, exist_ok=True)
+    rows = []
+    for i, (frames, delta) in enumerate(zip(TRAIN_FILELIST_FRAMES, TRAIN_FILELIST_PHONE_DELTA)):
+        n = frames * hop + 7 * i
+        wav = os.path.join(dirs["0_gt_wavs"], f"{i}_0.wav")
+        wavfile.write(wav, sr, spec_test_signal(sr, n, seed + i))
+        phone = rng.standard_normal((frames // 2 + delta, feat_dim)).astype(np.float32)
+        pitch = rng.integers(1, 256, size=frames + 3).astype(np.int64)
+        pitchf = rng.uniform(60.0, 800.0, size=frames + 3).astype(np.float32)
+        paths = [os.path.join(dirs[k], f"{i}_0.npy") for k in ("3_feature768", "2a_f0", "2b-f0nsf")]
+        for p, a in zip(paths, (phone, pitch, pitchf)):
+            np.save(p, a)
+        if spec_bins is not None:
+            import torch                   # noqa: PLC0415
+            torch.save(torch.zeros(spec_bins, n // hop), wav.replace(".wav", ".spec.pt"), _use_new_zipfile_serialization=False)
+        rows.append("|".join([wav] + paths + [str(i % 3)]))
+    filelist = os.path.join(root, "filelist.txt")
+    with open(filelist, "w", encoding="utf-8") as f:
+        f.write("\n".join(rows) + "\n")
+    return filelist
+
+
+def train_loader_summary(du, filelist, hparams, batch_size=2):
+    """What a data_utils module (this package's, or the reference's) makes of write_train_filelist's list, as a dict of arrays: the loader's bucketing
+    lengths, the sizes of every item, one collated batch of the first six items, and for both samplers the buckets, the boundaries they leave, the
+    filled-up bucket sizes and the unshuffled batches for (replicas, rank) in (1, 0), (2, 0), (2, 1).  tests/golden/train_loader_cases.npz is this
+    dict for the reference (tools/gen_golden_spec.py)."""
+    out = {}
+    ds = du.TextAudioLoaderMultiNSFsid(filelist, hparams)
+    out["lengths"] = np.array(ds.lengths, dtype=np.int64)
+    items = [ds[i] for i in range(len(ds))]
+    out["item_sizes"] = np.array([[it[0].shape[0], it[0].shape[1], it[1].shape[1], it[2].shape[0], it[2].shape[1], it[3].shape[0], it[4].shape[0],
+                                   int(it[5])] for it in items], dtype=np.int64)
+    batch = du.TextAudioCollateMultiNSFsid()(items[:6])
+    for name, t in zip(("phone", "phone_lengths", "pitch", "pitchf", "spec", "spec_lengths", "wave", "wave_lengths", "sid"), batch):
+        out[f"collate_{name}_shape"] = np.array(t.shape, dtype=np.int64)
+    for name, k in (("phone_lengths", 1), ("pitch", 2), ("spec_lengths", 5), ("wave_lengths", 7), ("sid", 8)):
+        out[f"collate_{name}"] = batch[k].numpy().astype(np.int64)
+    out["collate_pitchf"] = batch[3].numpy().astype(np.float32)
+    ds3 = du.TextAudioLoader(filelist + ".nof0", hparams)
+    b3 = du.TextAudioCollate()([ds3[i] for i in (7, 2, 5)])
+    out["nof0_lengths"] = np.array(ds3.lengths, dtype=np.int64)
+    out["nof0_collate_shapes"] = np.array([list(t.shape) + [0] * (3 - t.dim()) for t in b3], dtype=np.int64)
+    out["nof0_collate_spec_lengths"] = b3[3].numpy().astype(np.int64)
+    out["nof0_collate_sid"] = b3[6].numpy().astype(np.int64)
+
+    def flat(lists):
+        return (np.array([v for li in lists for v in li], dtype=np.int64), np.array([len(li) for li in lists], dtype=np.int64))
+
+    for tag, make in (("dist", lambda r, k, b: du.DistributedBucketSampler(ds, batch_size, b, num_replicas=r, rank=k, shuffle=False)),
+                      ("single", lambda r, k, b: du.BucketSampler(ds, batch_size, b, shuffle=False))):
+        for replicas, rank in ((1, 0), (2, 0), (2, 1)):
+            if tag == "single" and replicas != 1:
+                continue
+            bounds = list(TRAIN_FILELIST_BOUNDARIES)
+            sm = make(replicas, rank, bounds)
+            key = f"{tag}_{replicas}_{rank}"
+            out[f"{key}_buckets"], out[f"{key}_bucket_sizes"] = flat(sm.buckets)
+            out[f"{key}_boundaries"] = np.array(bounds, dtype=np.int64)
+            out[f"{key}_num_samples_per_bucket"] = np.array(sm.num_samples_per_bucket, dtype=np.int64)
+            out[f"{key}_batches"] = np.array(list(iter(sm)), dtype=np.int64).reshape(-1, batch_size)
+            out[f"{key}_len"] = np.array([len(sm)], dtype=np.int64)
+    return out
+
+
+def write_nof0_filelist(filelist):
+    """The three-column twin (`wav|phone|speaker`) of a write_train_filelist list, for TextAudioLoader: `{filelist}.nof0`."""
+    with open(filelist, encoding="utf-8") as f:
+        rows = [line.strip().split("|") for line in f]
+    with open(filelist + ".nof0", "w", encoding="utf-8") as f:
+        f.write("\n".join("|".join([r[0], r[1], r[4]]) for r in rows) + "\n")
+    return filelist + ".nof0"
+
+
 def add_clicks(x, seed=0):
     """The click recipe of the audio-effect tests (tests/golden/audio_fx_cases.npz): +-0.5 impulses written over len(x) // 2000 distinct positions
     drawn from default_rng(seed) -> (float32 copy, sorted positions)."""

@@ -343,6 +343,29 @@ int rvc_merge_tracks(void* stream, const float* const* tracks_host, const int64_
  * of every array_split segment of x_dev [n] int16 (the first n % k segments one sample longer), k <= n.  One launch. */
 int rvc_segment_energy(void* stream, const int16_t* x_dev, int64_t n, int k, int64_t* out_dev);
 
+/* ------------------------------------------------------------------ training inputs (reference lib/train/mel_processing.py, lib/train/data_utils.py) */
+/* Linear magnitude spectrograms of a ragged batch of clips (lib/train/mel_processing.py:47-87 spectrogram_torch, the spectrogram
+ * TextAudioLoaderMultiNSFsid.get_audio caches, lib/train/data_utils.py:93-131; with eps = 0 and clamp = 0 the torch.abs(torch.stft(...)) of
+ * mel_spectrogram_torch, :117-143): per clip F.pad(x, ((n_fft - hop) / 2,) * 2, "reflect"), frames of n_fft samples every hop, periodic Hann window
+ * of n_fft, sqrt(re^2 + im^2 + eps); clamp != 0 first limits the samples to +-1.05.  One launch of an fp32 LDS FFT (radix-4 Stockham over n_fft / 2
+ * packed complex values plus the real-input split; twiddles and window from float64 host tables uploaded once per (ctx, n_fft)), whatever the number
+ * and the lengths of the clips.  audio_dev [n_audio] float32; clips_host [n_clips][3] int64 (HOST: the call checks every clip before it launches
+ * anything and copies the table to the device itself) = (sample offset, samples N, first output column); clip c fills columns [column, column + N / hop)
+ * of out_dev [n_fft / 2 + 1][pitch] float32, the reference's (Freq, Frame) layout; other columns are not touched.  n_fft 1024 or 2048 (window =
+ * n_fft), 0 < hop <= n_fft with n_fft - hop even, every N > (n_fft - hop) / 2 (one reflection, as torch requires): anything else is an error and
+ * launches nothing. */
+int rvc_spectrogram_batch(rvc_ctx* ctx, void* stream, const float* audio_dev, int64_t n_audio, const int64_t* clips_host, int n_clips, int n_fft, int hop,
+                          float eps, int clamp, float* out_dev, int64_t pitch);
+/* The mel filterbank of (n_fft, n_mels) on this context (lib/train/mel_processing.py:36-39 get_mel_filters -> librosa.filters.mel) in banded form,
+ * HOST arrays: row m weighs bins [first[m], first[m] + count[m]) with the next count[m] values of weights (librosa's triangles are contiguous).
+ * Replaces an earlier bank of the same (n_fft, n_mels). */
+int rvc_mel_filterbank_set(rvc_ctx* ctx, int n_fft, int n_mels, const int32_t* first_host, const int32_t* count_host, const float* weights_host);
+/* Log-mel projection of a ragged batch (lib/train/mel_processing.py:89-96 spec_to_mel_torch, and :145-150 of mel_spectrogram_torch):
+ * mel[m][t] = log(max(sum_b W[m][b] spec[b][t], 1e-5)), fp32 accumulation, for the columns of clips_host [n_clips][2] int64 (HOST) = (first column,
+ * frames); spec_dev [n_fft / 2 + 1][spec_pitch], mel_dev [n_mels][mel_pitch], same columns in both.  One launch. */
+int rvc_spec_to_mel_batch(rvc_ctx* ctx, void* stream, const float* spec_dev, int64_t spec_pitch, const int64_t* clips_host, int n_clips, int n_fft,
+                          int n_mels, float* mel_dev, int64_t mel_pitch);
+
 /* ------------------------------------------------------------------ single ops (parity tests / kernel benchmarks) */
 /* Conv1d: x_dev [Ci][Tin], w_host [Co][Ci/groups][k], y_dev [Co][Tout]; act codes: 0 none 1 lrelu 2 relu 3 gelu 4 tanh 5 sigmoid */
 int rvc_op_conv1d(void* stream, const float* x_dev, const float* w_host, const float* bias_host, const float* res_dev, float* y_dev,
