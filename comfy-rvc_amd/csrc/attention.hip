@@ -6,24 +6,13 @@
 // in the bf16x3 arithmetic below; keys beyond T are masked, query tails are not stored.  (The first version ran fp32 MFMAs: 195 us at 12 heads,
 // T = 1599, against 312 us for the three-kernel path it replaced.)
 #include "rvc_internal.h"
+#include "phase_timing.h"
 
 namespace rvc {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#ifdef RVC_CONV_TIMING
-__device__ unsigned long long g_att_timing[8];   // [0] blocks, [1] K/V store + barriers, [2] S MFMAs, [3] softmax + P, [4] PV MFMAs, [6] total
-#define ATICK() wall_clock64()
-#define ATACC(i, v) do { if (threadIdx.x == 0) atomicAdd(&g_att_timing[i], (unsigned long long)(v)); } while (0)
-void attention_timing_read(unsigned long long* out8, bool reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_att_timing), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_att_timing), z, sizeof(z)); }
-}
-#else
-#define ATICK() 0ull
-#define ATACC(i, v) do {} while (0)
-#endif
+RVC_PHASE_TABLE_REGISTER;
 
 // LDS-only workgroup barrier: __syncthreads() also fences global memory (s_waitcnt vmcnt(0)), which would drain the K / V prefetch
 // of the next tile at every one of the four barriers of an iteration
@@ -126,17 +115,17 @@ __global__ __launch_bounds__(256) void attention_x3_kernel(const float* __restri
   const int boff_s = (wn * 32 + li) * kXP + lh * 8;              // B of S: query row
   const int aoff_o = (wm * 32 + li) * kXP + lh * 8;              // A of O: d row
   const int boff_o = (wn * 32 + li) * kXP + lh * 8;              // B of O: query row
-  const unsigned long long t_begin = ATICK();
+  // [0] blocks, [1] K/V store + barriers, [2] S MFMAs, [3] softmax + P, [4] PV MFMAs, [6] total
+  PhaseTimer<PhaseClock::wall> tm;
   load_kv(0);
   for (int it = 0; it < ntiles; ++it) {
     const int k0 = it * 64;
-    const unsigned long long t0 = ATICK();
+    tm.mark();
     lds_barrier();                          // previous tile's Ks / Vs / Ps reads are done
     store_kv();
     lds_barrier();
     if (it + 1 < ntiles) load_kv(k0 + 64);
-    const unsigned long long t1 = ATICK();
-    ATACC(1, t1 - t0);
+    tm.lap(1);
     // ---- S = K^T Q for this wave's 32 keys x 32 queries
     f32x16 sacc, sacc1;
 #pragma unroll
@@ -144,8 +133,7 @@ __global__ __launch_bounds__(256) void attention_x3_kernel(const float* __restri
     x3_block(&Ks[0][aoff_s], &Ks[1][aoff_s], &Qs[0][boff_s], &Qs[1][boff_s], sacc, sacc1);
 #pragma unroll
     for (int r = 0; r < 16; ++r) sacc[r] += sacc1[r];
-    const unsigned long long t2 = ATICK();
-    ATACC(2, t2 - t1);
+    tm.lap(2);
     // rows of sacc: key = k0 + wm*32 + (r&3) + 8(r>>2) + 4 lh; column: query wn*32 + li
     if (k0 + 64 > T) {                        // only the last key tile has a masked tail
 #pragma unroll
@@ -178,13 +166,12 @@ __global__ __launch_bounds__(256) void attention_x3_kernel(const float* __restri
     lds_barrier();
     l_run = l_run * alpha + red[1][0][wn * 32 + li] + red[1][1][wn * 32 + li];
     m_run = m_new;
-    const unsigned long long t3 = ATICK();
-    ATACC(3, t3 - t2);
+    tm.lap(3);
     // ---- O += V^T P : rows d = wm*32 + .., columns queries wn*32 + li
     x3_block(&Vs[0][aoff_o], &Vs[1][aoff_o], &Ps[0][boff_o], &Ps[1][boff_o], o, o1);
-    ATACC(4, ATICK() - t3);
+    tm.lap(4);
   }
-  ATACC(6, ATICK() - t_begin); ATACC(0, 1);
+  tm.add(0, 1); tm.flush();
   const int q = q0 + wn * 32 + li;
   const float inv = 1.f / l_run;
   float val[16];

@@ -23,23 +23,6 @@ struct AttnDmaArgs {
   int win; const unsigned char* ek_img; const unsigned char* evt_img; float* sband; unsigned sband_bytes;
 };
 
-#ifdef RVC_CONV_TIMING
-static __device__ unsigned long long g_attd_timing[8];   // [0] workgroups, [1] prologue, [2] tile loop, [3] slab store + ticket, [4] merge, [5] epilogue, [6] total (all: first wave of each workgroup)
-static inline void attd_timing_read_tu(unsigned long long* out8, bool reset) {      // this translation unit's copy
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_attd_timing), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attd_timing), z, sizeof(z)); }
-}
-#define DTICK() wall_clock64()
-#define DTACC(i, v) do { if (threadIdx.x == 0) atomicAdd(&g_attd_timing[i], (unsigned long long)(v)); } while (0)
-#else
-#define DTICK() 0ull
-#define DTACC(i, v) do {} while (0)
-#endif
-
-__device__ __forceinline__ void att_dma(__amdgpu_buffer_rsrc_t rs, unsigned char* lds_dst, int voffset, int soffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
 template <int D, int NWQ, int KS, bool REL>
 __global__ __launch_bounds__(64 * NWQ * KS) void attention_dma_kernel(const AttnDmaArgs p) {
   constexpr int NC = D / 16, DB = D / 32;
@@ -48,7 +31,8 @@ __global__ __launch_bounds__(64 * NWQ * KS) void attention_dma_kernel(const Attn
   static_assert(NPK % NWQ == 0 && NPV % NWQ == 0, "every wave's i-th piece is of one kind");
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem_att[];
 
-  const unsigned long long dt0 = DTICK();
+  // [0] workgroups, [1] prologue, [2] tile loop, [3] slab store + ticket, [4] merge (from the end of the tile loop), [5] epilogue, [6] total
+  PhaseTimer<PhaseClock::wall> tm;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave_wg = __builtin_amdgcn_readfirstlane(tid >> 6);
   // KS wave groups share the workgroup's queries and take the key tiles round-robin, each with its own (m, l, O) and its own pair of
@@ -84,8 +68,8 @@ __global__ __launch_bounds__(64 * NWQ * KS) void attention_dma_kernel(const Attn
 #pragma unroll
     for (int i = 0; i < NPW; ++i) {
       const int pi = wave + NWQ * i;
-      if (i * NWQ < NPK) att_dma(krs, base + pi * 1024, voff[i], tile * 1024);
-      else att_dma(vrs, base + KT_BYTES + (pi - NPK) * 1024, voff[i], tile * vstep);
+      if (i * NWQ < NPK) buf_dma(krs, base + pi * 1024, voff[i], tile * 1024);
+      else buf_dma(vrs, base + KT_BYTES + (pi - NPK) * 1024, voff[i], tile * vstep);
     }
   };
   // this workgroup's slice of the key tiles
@@ -128,8 +112,7 @@ __global__ __launch_bounds__(64 * NWQ * KS) void attention_dma_kernel(const Attn
   const float c2 = p.scale * 1.4426950408889634f;              // exp(s scale - m scale) = exp2((s - m) c2)
   float m_run = -3.0e38f, l_run = 0.f;
 
-  const unsigned long long dt1 = DTICK();
-  DTACC(1, dt1 - dt0);
+  tm.lap(1);
   for (int st = 0; st < nsteps; ++st) {
     const int itl = st * KS + grp, it = tile0 + itl;           // tile inside the slice, absolute tile
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's pieces of the tile (and, the first time, its queries)
@@ -249,8 +232,7 @@ __global__ __launch_bounds__(64 * NWQ * KS) void attention_dma_kernel(const Attn
     }
   }
 
-  const unsigned long long dt2 = DTICK();
-  DTACC(2, dt2 - dt1);
+  const long long dt2 = tm.lap(2);
   if (KS > 1) {
     // ---- merge the groups' states into group 0 (through the dead tile buffers): m = max m_g, l = sum l_g 2^((m_g - m) c2), O likewise
     constexpr int NV = 2 + 16 * DB;
@@ -309,9 +291,8 @@ __global__ __launch_bounds__(64 * NWQ * KS) void attention_dma_kernel(const Attn
       *flag = t;
     }
     __syncthreads();
-    const unsigned long long dt3 = DTICK();
-    DTACC(3, dt3 - dt2);
-    if (*flag != (unsigned)kz - 1u) { DTACC(0, 1); DTACC(6, dt3 - dt0); return; }
+    tm.lap(3);
+    if (*flag != (unsigned)kz - 1u) { tm.add(0, 1); tm.flush(); return; }
     // up to KZB slices per batch, EVERY load of a batch in flight before the first is used (a slab lives in another XCD's write-through
     // path: one round trip of ~2 us per dependent batch); slices past kz read through a zero-extent offset and weigh 0
     constexpr int KZB = 5;
@@ -354,8 +335,7 @@ __global__ __launch_bounds__(64 * NWQ * KS) void attention_dma_kernel(const Attn
     for (int db = 0; db < DB; ++db) o[db] = om[db];
     m_run = m; l_run = l;
   }
-  const unsigned long long dt4 = DTICK();
-  DTACC(4, dt4 - dt2);
+  tm.since(4, dt2); tm.mark();
   // ---- normalise, + bv; fp32 rows and / or the image the out-projection stages
   const int q = q0 + li;
   const float inv = 1.f / l_run;
@@ -430,8 +410,7 @@ __global__ __launch_bounds__(64 * NWQ * KS) void attention_dma_kernel(const Attn
       }
     }
   }
-  const unsigned long long dt5 = DTICK();
-  DTACC(5, dt5 - dt4); DTACC(6, dt5 - dt0); DTACC(0, 1);
+  tm.lap(5); tm.add(0, 1); tm.flush();
 }
 
 template <int D, int NWQ, int KS, bool REL>

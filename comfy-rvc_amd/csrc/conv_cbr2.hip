@@ -18,19 +18,7 @@
 
 namespace rvc {
 
-#ifdef RVC_CONV_TIMING
-__device__ unsigned long long g_cbr_timing[8];   // [0] workgroups, [1] staging (loads + convert), [2] conv1, [3] y1 -> LDS, [4] conv2, [5] epilogue, [6] total
-#define CTICK() wall_clock64()
-#define CTACC(i, v) do { if (threadIdx.x == 0) atomicAdd(&g_cbr_timing[i], (unsigned long long)(v)); } while (0)
-void cbr2_timing_read(unsigned long long* out8, bool reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_cbr_timing), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_cbr_timing), z, sizeof(z)); }
-}
-#else
-#define CTICK() 0ull
-#define CTACC(i, v) do {} while (0)
-#endif
+RVC_PHASE_TABLE_REGISTER;
 
 // LDS bytes of cbr2_small_kernel<C, TH> (the kernel's NPOS, restated for the launch)
 constexpr size_t cbr2_lds_bytes(int C, int TH) {
@@ -65,7 +53,8 @@ __global__ __launch_bounds__(256, 2) void cbr2_small_kernel(const Cbr2Args p) {
 
   // ---- weights of a convolution -> registers: unit u = chunk * 9 + tap, lane (row li, half lh).  Requested first: their latency hides
   // behind the staging of x.
-  const unsigned long long t_begin = CTICK();
+  // [0] workgroups, [1] staging (loads + convert), [2] conv1, [3] y1 -> LDS, [4] conv2, [5] epilogue, [6] total
+  PhaseTimer<PhaseClock::wall> tm;
   u32x4 wh[NU], wl[NU];
   auto load_w = [&](const unsigned char* Wimg, int CoPx) {
 #pragma unroll
@@ -121,8 +110,7 @@ __global__ __launch_bounds__(256, 2) void cbr2_small_kernel(const Cbr2Args p) {
   }
 
   __syncthreads();
-  const unsigned long long t_staged = CTICK();
-  CTACC(1, t_staged - t_begin);
+  tm.lap(1);
 
   // this wave's blocks of 32 positions (block wave + 4 i starts at LDS position qbase + 32 (wave + 4 i)): acc[i][co][position] over the 9 taps x
   // NCH chunks.  The (chunk, tap) unit is the OUTER loop: the blocks are independent accumulation chains (a lone chain would wait out the
@@ -174,8 +162,7 @@ __global__ __launch_bounds__(256, 2) void cbr2_small_kernel(const Cbr2Args p) {
       for (int r = 0; r < 8 * RB; ++r) y1[i][r] = ok ? fmaxf(y1[i][r] + bias1[r], 0.f) : 0.f;
     }
   }
-  const unsigned long long t_c1 = CTICK();
-  CTACC(2, t_c1 - t_staged);
+  tm.lap(2);
   if constexpr (C == 16) load_w(p.W2, p.CoPx2);              // (conv1's MFMAs have read their weight registers: in order)
   __syncthreads();                                             // every wave has finished reading x
 #pragma unroll
@@ -208,14 +195,12 @@ __global__ __launch_bounds__(256, 2) void cbr2_small_kernel(const Cbr2Args p) {
   if constexpr (C != 16) load_w(p.W2, p.CoPx2);              // (32 channels: after the intermediate has left the registers)
   __syncthreads();
 
-  const unsigned long long t_y1 = CTICK();
-  CTACC(3, t_y1 - t_c1);
+  tm.lap(3);
   // ---- conv2 over rows 0 .. TH - 1: bias, ReLU, + x, fp32 rows
   f32x16 y2[NBW2];
   conv_blocks(y2, std::integral_constant<int, NBW2>{}, NB2, 2 * P);
   asm volatile("s_nop 0" ::: "memory");
-  const unsigned long long t_c2 = CTICK();
-  CTACC(4, t_c2 - t_y1);
+  tm.lap(4);
   // epilogue through LDS: relu(acc + b2) as an fp32 tile [co][row][col] over the dead image, then 16-byte residual loads / stores
   // (the MFMA layout holds one position per lane: 4-byte accesses, 5x the instructions)
   typedef float f32x4_t __attribute__((ext_vector_type(4)));
@@ -252,8 +237,7 @@ __global__ __launch_bounds__(256, 2) void cbr2_small_kernel(const Cbr2Args p) {
       *reinterpret_cast<f32x4_t*>(p.Y + (long long)co * p.plane + (long long)ir * W + ic) = o;
     }
   }
-  const unsigned long long t_end = CTICK();
-  CTACC(5, t_end - t_c2); CTACC(6, t_end - t_begin); CTACC(0, 1);
+  tm.lap(5); tm.add(0, 1); tm.flush();
 }
 
 template <int C, int TH>

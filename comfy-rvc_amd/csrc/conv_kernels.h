@@ -37,6 +37,10 @@ constexpr unsigned kOOB = 0x80000000u;
 __device__ __forceinline__ float buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff = 0) {
   return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
 }
+// 1 KiB (16 B per lane) from a buffer straight into LDS: address = descriptor base + per-lane voffset + wave-uniform soffset
+__device__ __forceinline__ void buf_dma(__amdgpu_buffer_rsrc_t rs, unsigned char* lds_dst, int voffset, int soffset) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_dst, 16, voffset, soffset, 0, 0);
+}
 
 // Dense-row epilogue shared by the MFMA kernels (32x32 accumulator layout: col = lane & 31,
 // row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)):  v = acc + bias; act in {identity, ReLU, leaky ReLU} as max(v, slope v),
@@ -178,11 +182,10 @@ void conv_plan_launch(const ConvPlan& p, hipStream_t s);
 // on success a, launch, grid and lds of p are filled, on false p is untouched
 // software-pipelined kernel for stride-1 1-D convolutions on 2 x 2-wave tiles (conv_x3p.hip)
 bool conv_x3p_plan(ConvPlan& p, int AM, int AN);
-int conv_x3p_check_read();
+int conv_x3p_check_read();   // -1, or in -DRVC_X3P_CHECK builds the wait-count violations of every checked kernel since the last call (conv_x3_dev.h)
 // persistent version of the above for the ResBlock convolutions: a workgroup per CU slot walks over its tiles, one continuous stream of
 // weight units / input chunks, residual added block by block inside the tile (conv_x3q.hip)
 bool conv_x3q_plan(ConvPlan& p, int AM, int AN);
-int conv_x3q_check_read();
 // k = 1 (GEMM) on the pipelined kernel, fp32 [K][N] input (conv_x3p.hip)
 bool conv_x3g_plan(ConvPlan& p);
 // fused ResBlock pair of the 32-channel stage on the pipelined kernel (conv_x3p.hip)

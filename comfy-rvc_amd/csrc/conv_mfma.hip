@@ -14,6 +14,7 @@
 // both are single conflict-free ds_read_b32 per operand; fp32 accumulate, bitwise an fmaf chain.
 // Workgroup = 4 waves (WM x WN), each wave owns AM x AN accumulators of 32x32.
 #include "conv_kernels.h"
+#include "phase_timing.h"
 #include <atomic>
 #include <tuple>
 
@@ -23,14 +24,7 @@
 
 namespace rvc {
 
-#ifdef RVC_CONV_TIMING
-__device__ unsigned long long g_conv_timing[8];   // [0] blocks, [1] prologue, [2] stage sync+LDS fill, [3] prefetch issue, [4] MFMA loops, [5] epilogue, [6] total
-#define TICK() clock64()
-#define TACC(i, v) do { if (threadIdx.x == 0) atomicAdd(&g_conv_timing[i], (unsigned long long)(v)); } while (0)
-#else
-#define TICK() 0ll
-#define TACC(i, v) do {} while (0)
-#endif
+RVC_PHASE_TABLE_REGISTER;
 
 constexpr int kWSlots = 32;   // register slots (floats per thread) for the prefetched weight slab (<= 32 KB / 256 threads)
 // register slots for the prefetched input tile, per tile width and mode (checked against the launch geometry on the host)
@@ -201,24 +195,22 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgsX p) {
 
   // Iteration `it` moves stage it-1 from registers to LDS, prefetches stage `it` into registers and runs the MFMAs of stage
   // it-1 (one copy of every code section; the prefetch latency hides under the matrix work).
-  const long long t_begin = TICK();
+  // [0] blocks, [1] prologue, [2] stage sync+LDS fill, [3] prefetch issue, [4] MFMA loops, [5] epilogue, [6] total
+  PhaseTimer<PhaseClock::clock64> tm;
   int chunk = chunk0, tb = 0, pchunk = chunk0, ptb = 0;
   for (int it = 0; it <= nstages; ++it) {
-    const long long ta = TICK();
     if (it > 0) {
       __syncthreads();                       // every wave is done reading the previous stage from LDS
       if (ptb == 0) store_x();
       store_w(ptb);
       __syncthreads();
     }
-    const long long tb_ = TICK();
-    TACC(it <= 1 ? 1 : 2, tb_ - ta);
+    if (it <= 1) tm.lap(1); else tm.lap(2);
     if (it < nstages) {
       if (tb == 0) load_x(chunk);
       load_w(chunk, tb);
     }
-    const long long tc = TICK();
-    TACC(3, tc - tb_);
+    tm.lap(3);
     if (it > 0) {
       const int ut = min(p.KT, p.ktaps - ptb * p.KT);
       for (int uu = 0; uu < ut; ++uu) {
@@ -242,12 +234,12 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgsX p) {
         }
       }
     }
-    TACC(4, TICK() - tc);
+    tm.lap(4);
     pchunk = chunk; ptb = tb;
     if (++tb == ntb) { tb = 0; ++chunk; }
   }
   (void)pchunk;
-  const long long t_epi = TICK();
+  tm.mark();
 
   // -------------------------------------------------------------------------- epilogue
   // v = acc + bias; act in {identity, ReLU, leaky ReLU} as max(v, slope * v), before or after the residual; * out_scale;
@@ -305,7 +297,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgsX p) {
       }
     }
   }
-  TACC(5, TICK() - t_epi); TACC(6, TICK() - t_begin); TACC(0, 1);
+  tm.lap(5); tm.add(0, 1); tm.flush();
 }
 
 // Elementwise pass for the activations kept out of the MFMA kernel: y = act(y) [+ r]  or  y = act(y + r)
@@ -372,42 +364,15 @@ void splitk_reduce_launch(const ConvArgsX& a, int S, int batch, hipStream_t s) {
 }
 
 // ============================================================================ host side
-#ifdef RVC_CONV_TIMING
-void conv_x3_timing_read(unsigned long long* out8, bool reset);
-void attention_timing_read(unsigned long long* out8, bool reset);
-void conv_x3p_timing_read(unsigned long long* out8, bool reset);
-void conv_x3q_timing_read(unsigned long long* out8, bool reset);
-void conv_rbh_timing_read(unsigned long long* out8, bool reset);
-void conv_rb3_timing_read(unsigned long long* out8, bool reset);
-void conv_x3s_timing_read(unsigned long long* out8, bool reset);
-void cbr2_timing_read(unsigned long long* out8, bool reset);
-void attention_dma_timing_read(unsigned long long* out8, bool reset);
+// the sum over every translation unit's table (phase_timing.h); zeros when nothing registered (builds without -DRVC_CONV_TIMING)
+std::vector<PhaseTableReader>& phase_table_readers() { static std::vector<PhaseTableReader> v; return v; }
 void conv_timing_read(unsigned long long* out8, bool reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_conv_timing), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_conv_timing), z, sizeof(z)); }
-  unsigned long long x3[8]; conv_x3_timing_read(x3, reset);
-  for (int i = 0; i < 8; ++i) out8[i] += x3[i];
-  attention_timing_read(x3, reset);
-  for (int i = 0; i < 8; ++i) out8[i] += x3[i];
-  attention_dma_timing_read(x3, reset); // (attention on images: [0] workgroups, [1] prologue, [2] tile loop, [3] slab store + ticket, [4] merge, [5] epilogue, [6] total)
-  for (int i = 0; i < 8; ++i) out8[i] += x3[i];
-  cbr2_timing_read(x3, reset);          // (fused ConvBlockRes: [0] workgroups, [1] staging, [2] conv1, [3] y1 -> LDS, [4] conv2, [5] epilogue, [6] total)
-  for (int i = 0; i < 8; ++i) out8[i] += x3[i];
-  conv_x3p_timing_read(x3, reset);      // (pipelined kernel: [0] tiles, [1] prologue, [2] compute, [3] weight wait, [4] barrier, [5] epilogue, [6] total)
-  for (int i = 0; i < 8; ++i) out8[i] += x3[i];
-  conv_x3q_timing_read(x3, reset);      // (persistent kernel: the same slots; [1] once per workgroup, [6] per workgroup)
-  for (int i = 0; i < 8; ++i) out8[i] += x3[i];
-  conv_rbh_timing_read(x3, reset);      // (persistent fused pair, LDS-resident weights: [0] tiles, [1] stage, [2] conv1, [3] h + requests, [4] conv2, [5] epilogue, [6] total per workgroup)
-  for (int i = 0; i < 8; ++i) out8[i] += x3[i];
-  conv_rb3_timing_read(x3, reset);      // (whole ResBlock per launch: [0] tiles, [1] x image + requests, [2] first convolutions, [3] images, [4] second convolutions, [5] epilogue, [6] total per workgroup, [7] barrier waits)
-  for (int i = 0; i < 8; ++i) out8[i] += x3[i];
-  conv_x3s_timing_read(x3, reset);      // (split-resident GEMM: [0] workgroups, [1] prologue, [2] reads + MFMA issue, [3] DMA wait, [4] barrier, [5] split-K + epilogue, [6] total)
-  for (int i = 0; i < 8; ++i) out8[i] += x3[i];
+  for (int i = 0; i < 8; ++i) out8[i] = 0;
+  for (PhaseTableReader read : phase_table_readers()) {
+    unsigned long long t[8]; read(t, reset);
+    for (int i = 0; i < 8; ++i) out8[i] += t[i];
+  }
 }
-#else
-void conv_timing_read(unsigned long long* out8, bool) { for (int i = 0; i < 8; ++i) out8[i] = 0; }
-#endif
 float* dev_upload(const float* host, size_t n) {
   float* d = nullptr;
   RVC_HIP_CHECK(hipMalloc(&d, (n ? n : 1) * sizeof(float)));

@@ -35,25 +35,9 @@
 
 namespace rvc {
 
-template <int T, int N, class F> __device__ __forceinline__ void rb3_for(F& f) {
-  if constexpr (T < N) { f(std::integral_constant<int, T>{}); rb3_for<T + 1, N>(f); }
-}
 typedef float f32x4q __attribute__((ext_vector_type(4)));
 
-#ifdef RVC_CONV_TIMING
-__device__ unsigned long long g_rb3_timing[8];   // [0] tiles, [1] x image + requests, [2] first convolutions, [3] intermediate images, [4] second convolutions, [5] epilogue, [6] total, [7] barrier waits
-void conv_rb3_timing_read(unsigned long long* out8, bool reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_rb3_timing), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_rb3_timing), z, sizeof(z)); }
-}
-#define R3TICK() ((long long)__builtin_readcyclecounter())
-#define R3ACC(i, v) do { r3t[i] += (v); } while (0)
-#else
-void conv_rb3_timing_read(unsigned long long* out8, bool) { for (int i = 0; i < 8; ++i) out8[i] = 0; }
-#define R3TICK() 0ll
-#define R3ACC(i, v) do {} while (0)
-#endif
+RVC_PHASE_TABLE_REGISTER;
 
 template <int CH, int KT, bool ACC, int WM>
 __global__ __launch_bounds__(512, 2) void conv_rb3_kernel(const Rb3Args p) {
@@ -229,7 +213,7 @@ __global__ __launch_bounds__(512, 2) void conv_rb3_kernel(const Rb3Args p) {
         for (int j = 0; j < AN; ++j) { bh[j] = bhn[j]; bl[j] = bln[j]; }
       }
     };
-    rb3_for<0, NU>(unit);
+    static_for<0, NU>(unit);
   };
   // convolution c of the tile (0 .. 5): resident weights are where they are; streamed ones alternate between the two buffers and the next
   // convolution's travel through registers under this one
@@ -246,9 +230,6 @@ __global__ __launch_bounds__(512, 2) void conv_rb3_kernel(const Rb3Args p) {
     }
   };
 
-#ifdef RVC_CONV_TIMING
-  long long r3t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
   // xn: the next tile's x, in flight across the whole tile.  rs: the fp32 residual stream x_i - the second convolution of every pair accumulates INTO it
   // (x_{i+1} = x_i + b2 + c2(h): no copies).  ac: the first convolution's accumulators; dead once h is written, so the previous output (ACC) is loaded into them
   f32x16 xn[AM][AN], rs[AM][AN], ac[AM][AN];
@@ -264,10 +245,10 @@ __global__ __launch_bounds__(512, 2) void conv_rb3_kernel(const Rb3Args p) {
   load_tile(xrs, p.ldX, (int)blockIdx.x, xn, 0, TILE);
   load_src((int)blockIdx.x);
   __syncthreads();                                            // weights, biases and the zero margins are in LDS
-  [[maybe_unused]] long long tq = R3TICK();
-  [[maybe_unused]] const long long tq0 = tq;
-#define R3PHASE(i) do { [[maybe_unused]] const long long t_ = R3TICK(); R3ACC(i, t_ - tq); tq = t_; } while (0)
-#define R3BARRIER() do { [[maybe_unused]] const long long t0_ = R3TICK(); lds_barrier(); [[maybe_unused]] const long long t1_ = R3TICK(); R3ACC(7, t1_ - t0_); } while (0)
+  // [0] tiles, [1] x image + requests, [2] first convolutions, [3] intermediate images, [4] second convolutions, [5] epilogue, [6] total (per workgroup),
+  // [7] barrier waits (also inside the phases they end)
+  PhaseTimer<PhaseClock::cycle> tm;
+  auto barrier = [&]() __attribute__((always_inline)) { tm.span(7, [] { lds_barrier(); }); };
   for (int tile = (int)blockIdx.x; tile < ntiles; tile += (int)gridDim.x) {
     const int n0 = tile * NO - HALO;                          // position of tile column 0
     // ---- x (requested a tile ago) becomes the residual stream and, leaky-ReLU'd, the first image; the next tile's x is requested
@@ -291,13 +272,13 @@ __global__ __launch_bounds__(512, 2) void conv_rb3_kernel(const Rb3Args p) {
     put_image(rs, nullptr, pre_slope, n0);
     load_tile(xrs, p.ldX, tile + (int)gridDim.x, xn, 0, TILE);
     load_src(tile + (int)gridDim.x);
-    R3BARRIER();
-    R3PHASE(1);
+    barrier();
+    tm.lap(1);
     auto pair = [&](auto ic) __attribute__((always_inline)) {
       constexpr int i = decltype(ic)::value;
       run_conv(std::true_type{}, std::integral_constant<int, 2 * i + 1>{}, ac, 2 * i);      // dilation 1, 3, 5
-      R3PHASE(2);
-      R3BARRIER();                                            // every wave is done with the pair's input image
+      tm.lap(2);
+      barrier();                                            // every wave is done with the pair's input image
       if constexpr (WM == 2) wstore(Ws);
       put_image(ac, Bs + (2 * i) * C, hs, n0);                 // h = lrelu(c1 + b1) over it
 #pragma unroll
@@ -312,20 +293,20 @@ __global__ __launch_bounds__(512, 2) void conv_rb3_kernel(const Rb3Args p) {
         }
       // the previous output, under the last convolution (at 7 and 11 taps and at 64 channels there are no registers for it beside the convolution's operands: requested behind it)
       if constexpr (ACC && KT < 7 && C == 32 && i == 2) load_tile(yrs, p.ldY, tile, ac, HALO, HALO + NO);
-      R3BARRIER();                                            // the intermediate is complete
-      R3PHASE(3);
+      barrier();                                            // the intermediate is complete
+      tm.lap(3);
       run_conv(std::false_type{}, std::integral_constant<int, 1>{}, rs, 2 * i + 1);          // rs = x_{i+1}
       if constexpr (ACC && !(KT < 7 && C == 32) && i == 2) load_tile(yrs, p.ldY, tile, ac, HALO, HALO + NO);
-      R3PHASE(4);
+      tm.lap(4);
       if constexpr (i < 2) {
-        R3BARRIER();                                          // every wave is done with the intermediate
+        barrier();                                          // every wave is done with the intermediate
         if constexpr (WM == 2) wstore(Ws);
         put_image(rs, nullptr, pre_slope, n0);
-        R3BARRIER();
-        R3PHASE(3);
+        barrier();
+        tm.lap(3);
       }
     };
-    rb3_for<0, 3>(pair);
+    static_for<0, 3>(pair);
     // ---- epilogue: the inner NO columns
 #pragma unroll
     for (int j = 0; j < AN; ++j) {
@@ -339,16 +320,11 @@ __global__ __launch_bounds__(512, 2) void conv_rb3_kernel(const Rb3Args p) {
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yrs, (int)voff, (int)((unsigned)(32 * am + (r & 3) + 8 * (r >> 2)) * (unsigned)p.ldY * 4u), 0);
         }
     }
-    R3BARRIER();                                              // every wave is done with the last intermediate: the next tile's image may be written over it
-    R3PHASE(5);
-    R3ACC(0, 1);
+    barrier();                                              // every wave is done with the last intermediate: the next tile's image may be written over it
+    tm.lap(5);
+    tm.add(0, 1);
   }
-#undef R3PHASE
-#undef R3BARRIER
-#ifdef RVC_CONV_TIMING
-  r3t[6] = R3TICK() - tq0;
-  if (threadIdx.x == 0) for (int i = 0; i < 8; ++i) atomicAdd(&g_rb3_timing[i], (unsigned long long)r3t[i]);
-#endif
+  tm.flush();
 }
 
 template <int CH, int KT, bool ACC, int WM>

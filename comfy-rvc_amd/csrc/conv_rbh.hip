@@ -27,25 +27,9 @@
 
 namespace rvc {
 
-template <int T, int N, class F> __device__ __forceinline__ void rbh_for(F& f) {
-  if constexpr (T < N) { f(std::integral_constant<int, T>{}); rbh_for<T + 1, N>(f); }
-}
 typedef float f32x4r __attribute__((ext_vector_type(4)));
 
-#ifdef RVC_CONV_TIMING
-__device__ unsigned long long g_rbh_timing[8];   // [0] tiles, [1] stage + barrier, [2] conv1, [3] barrier + h + requests + barrier, [4] conv2, [5] epilogue + barrier, [6] total
-void conv_rbh_timing_read(unsigned long long* out8, bool reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_rbh_timing), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_rbh_timing), z, sizeof(z)); }
-}
-#define RBTICK() ((long long)__builtin_readcyclecounter())
-#define RBACC(i, v) do { rbt[i] += (v); } while (0)
-#else
-void conv_rbh_timing_read(unsigned long long* out8, bool) { for (int i = 0; i < 8; ++i) out8[i] = 0; }
-#define RBTICK() 0ll
-#define RBACC(i, v) do {} while (0)
-#endif
+RVC_PHASE_TABLE_REGISTER;
 
 template <int KT, bool ACC>
 __global__ __launch_bounds__(512, 2) void conv_rbh_kernel(const ConvArgsX p) {
@@ -159,16 +143,13 @@ __global__ __launch_bounds__(512, 2) void conv_rbh_kernel(const ConvArgsX p) {
         for (int j = 0; j < AN; ++j) { bh[j] = bhn[j]; bl[j] = bln[j]; }
       }
     };
-    rbh_for<0, NU>(unit);
+    static_for<0, NU>(unit);
   };
 
-#ifdef RVC_CONV_TIMING
-  long long rbt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
   load_x((int)blockIdx.x);
   __syncthreads();                                            // weights and biases are in LDS
-  [[maybe_unused]] long long tq = RBTICK();
-  [[maybe_unused]] const long long tq0 = tq;
+  // [0] tiles, [1] stage + barrier, [2] conv1, [3] barrier + h + requests + barrier, [4] conv2, [5] epilogue + barrier, [6] total (per workgroup)
+  PhaseTimer<PhaseClock::cycle> tm;
   float rr[AN][16];
   [[maybe_unused]] float yo[AN][16];
   for (int tile = (int)blockIdx.x; tile < ntiles; tile += (int)gridDim.x) {
@@ -185,14 +166,14 @@ __global__ __launch_bounds__(512, 2) void conv_rbh_kernel(const ConvArgsX p) {
         rr[j][r] = buf_load(xrs, ok ? ((unsigned)((r & 3) + 8 * (r >> 2) + 4 * lh) * (unsigned)p.ldX + (unsigned)n) * 4u : kOOB);
     }
     __syncthreads();
-    { [[maybe_unused]] const long long t = RBTICK(); RBACC(1, t - tq); tq = t; }
+    tm.lap(1);
     // ---- phase 2: the dilated convolution over the 512 intermediate columns
 #pragma unroll
     for (int j = 0; j < AN; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
     conv(W1s, dil16);
-    { [[maybe_unused]] const long long t = RBTICK(); RBACC(2, t - tq); tq = t; }
+    tm.lap(2);
     __syncthreads();                                          // every wave is done with the input tile
     // ---- phase 3: h = lrelu(acc + b1) (0 outside the sequence: the second convolution's zero padding) as fp16 hi / lo rows over the input tile
 #pragma unroll
@@ -250,9 +231,9 @@ __global__ __launch_bounds__(512, 2) void conv_rbh_kernel(const ConvArgsX p) {
         for (int e = 0; e < 4; ++e) acc[j][4 * g + e] = rr[j][4 * g + e] + b2[e];
     }
     __syncthreads();                                          // the intermediate is complete
-    { [[maybe_unused]] const long long t = RBTICK(); RBACC(3, t - tq); tq = t; }
+    tm.lap(3);
     conv(W2s, 16);
-    { [[maybe_unused]] const long long t = RBTICK(); RBACC(4, t - tq); tq = t; }
+    tm.lap(4);
 #pragma unroll
     for (int j = 0; j < AN; ++j) {
       const int no = (wave * AN + j) * 32 + li;
@@ -267,12 +248,9 @@ __global__ __launch_bounds__(512, 2) void conv_rbh_kernel(const ConvArgsX p) {
       }
     }
     __syncthreads();                                          // every wave is done with the intermediate: the next tile may be staged over it
-    { [[maybe_unused]] const long long t = RBTICK(); RBACC(5, t - tq); tq = t; RBACC(0, 1); }
+    tm.lap(5); tm.add(0, 1);
   }
-#ifdef RVC_CONV_TIMING
-  rbt[6] = RBTICK() - tq0;
-  if (threadIdx.x == 0) for (int i = 0; i < 8; ++i) atomicAdd(&g_rbh_timing[i], (unsigned long long)rbt[i]);
-#endif
+  tm.flush();
 }
 
 template <int KT, bool ACC>

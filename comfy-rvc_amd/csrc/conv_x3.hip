@@ -24,24 +24,7 @@
 
 namespace rvc {
 
-#ifdef RVC_CONV_TIMING
-__device__ unsigned long long g_x3_timing[8];   // [0] blocks, [1] prologue, [2] X store + DMA wait + barrier, [3] prefetch issue, [4] MFMA loops, [5] epilogue, [6] total
-// (accumulated in registers and published once per workgroup: an atomic per stage is a VMEM operation on the path the counted vmcnt waits watch)
-#define X3TICK() ((long long)__builtin_readcyclecounter())
-#define X3TACC(i, v) do { x3t[i] += (v); } while (0)
-#define X3TDECL() long long x3t[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define X3TFLUSH() do { if (threadIdx.x == 0) { for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_x3_timing[i_], (unsigned long long)x3t[i_]); } } while (0)
-void conv_x3_timing_read(unsigned long long* out8, bool reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_x3_timing), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_x3_timing), z, sizeof(z)); }
-}
-#else
-#define X3TICK() 0ll
-#define X3TACC(i, v) do {} while (0)
-#define X3TDECL() do {} while (0)
-#define X3TFLUSH() do {} while (0)
-#endif
+RVC_PHASE_TABLE_REGISTER;
 
 // FUSE: ResBlock pair  y = (x + W2 * lrelu(W1 *_d lrelu(x) + b1) + b2) * scale [+ y]  in one launch (Ci = Co, all channels of the
 // tile resident in LDS): pass 1 is the ordinary stage loop of the dilated conv over BN columns; its accumulators (+ b1, leaky
@@ -85,7 +68,6 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : ((WM == 2 && WN ==
   const float* __restrict__ X = p.X + (long long)z * p.xBatch;
   const unsigned char* __restrict__ Wg = p.Wx + (long long)z * p.wxBatch * 2;
 
-  X3TDECL();
   f32x16 acc[AM][AN];
 #pragma unroll
   for (int am = 0; am < AM; ++am)
@@ -319,7 +301,9 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : ((WM == 2 && WN ==
   // weights of stages it .. it + 3.  The input rows of chunk c + 1 are requested as soon as chunk c's registers are free (first stage
   // of chunk c), a whole chunk ahead of their use; nothing in the loop waits for vmcnt(0).
   int chunk = g0, tb = 0;
-  const long long t_begin = X3TICK();
+  // [0] blocks, [1] prologue + barriers, [2] X store, [3] prefetch issue, [4] MFMA loops, [5] epilogue, [6] total, [7] DMA wait
+  // (sums in registers, published once per workgroup: an atomic per stage is a VMEM operation on the path the counted vmcnt waits watch)
+  PhaseTimer<PhaseClock::cycle> tm;
   int issued = 0, we0 = 0, we1 = 0, we2 = 0, we3 = 0, xe = 0;   // xe: `issued` right after the input pieces of the current chunk
   int nchunk_i = g0, ntb_i = 0, issued_stages = 0;         // next (chunk, tap block) whose weights are to be requested
   auto issue_next = [&]() {
@@ -336,9 +320,8 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : ((WM == 2 && WN ==
     if constexpr (XSPLIT) { issued += issue_x(g0, p.xbufs == 2 ? (g0 & 1) : 0); xe = issued; }
     else { load_x(g0); issued += XS * 8; }
   }
-  X3TACC(1, X3TICK() - t_begin);
+  tm.lap(1);
   for (int it = 0; it < nstages; ++it) {
-    const long long ta = X3TICK();
     const int buf = it % NS;
     const int xb = p.xbufs == 2 ? (chunk & 1) : 0;
     if (!XSPLIT && tb == 0) {
@@ -346,13 +329,12 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : ((WM == 2 && WN ==
       store_x(xb);
       if (chunk + 1 < g1) { load_x(chunk + 1); issued += XS * 8; }
     }
-    const long long tw0 = X3TICK();
+    tm.lap(2);
     // this stage's weight pieces (of this wave) have landed - and, at the start of a chunk, its split-resident input pieces
     wait_vmcnt_le((XSPLIT && tb == 0) ? min(issued - we0, issued - xe) : issued - we0);
-    const long long tw1 = X3TICK();
+    tm.lap(7);
     lds_barrier();                                          // ... and everybody else's; the slab of stage it - 1 is free again
-    const long long tb_ = X3TICK();
-    X3TACC(2, tw0 - ta); X3TACC(7, tw1 - tw0); X3TACC(1, tb_ - tw1);      // [2] input store, [7] DMA wait, [1] += barrier
+    tm.lap(1);
     if (XSPLIT && tb == 0) {
       if (x_edge) { zero_edges(xb); lds_barrier(); }        // (first / last tiles only) zero padding rows, published before the MFMAs
       // the other input buffer was read during the previous chunk; every wave is past it now (barrier above): request the next chunk
@@ -365,11 +347,10 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : ((WM == 2 && WN ==
       const int m2 = -(int)(NS == 2), m3 = -(int)(NS == 3), m4 = -(int)(NS >= 4);
       we0 = (e & m2) | (we0 & ~m2); we1 = (e & m3) | (we1 & ~m3); we2 = (e & m4) | (we2 & ~m4);
     }
-    const long long tc = X3TICK();
-    X3TACC(3, tc - tb_);
+    tm.lap(3);
     mfma_stage(buf, xb, tb, p.dil);
     if (++tb == ntb) { tb = 0; ++chunk; }
-    X3TACC(4, X3TICK() - tc);
+    tm.lap(4);
   }
   if constexpr (FUSE) {
     // ---- pass 1 -> LDS: h = lrelu(acc + b1) (0 outside the sequence), split, written over the input tile (row = tile column)
@@ -417,7 +398,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : ((WM == 2 && WN ==
       mfma_stage(it & 1, 0, it, 1);
     }
   }
-  const long long t_epi = X3TICK();
+  tm.mark();
 #ifdef RVC_X3_NOEPI
   if (acc[0][0][0] == 12345.678f)
 #endif
@@ -474,8 +455,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : ((WM == 2 && WN ==
       }
     }
   }
-  X3TACC(5, X3TICK() - t_epi); X3TACC(6, X3TICK() - t_begin); X3TACC(0, 1);
-  X3TFLUSH();
+  tm.lap(5); tm.add(0, 1); tm.flush();
 }
 
 // ============================================================================ host side

@@ -1,9 +1,25 @@
-// Device helpers shared by the bf16x3 kernels (conv_x3.hip: staged kernel for every geometry; conv_x3p.hip: software-pipelined kernel
-// for the stride-1 1-D convolutions of the generator).  Private to csrc/.
+// Device helpers shared by the split-MFMA kernels: the bf16x3 convolutions (conv_x3.hip staged, conv_x3p.hip pipelined, conv_x3q.hip
+// persistent, conv_x3s.hip split-resident GEMM), the fp16x2 ResBlock kernels (conv_rbh.hip, conv_rb3.hip), the fused ConvBlockRes
+// (conv_cbr2.hip), attention on images (attention_dma_kernel.h) and the image producers of the models.  Operand splits, compile-time
+// unrolling, vmcnt waits, the non-draining barrier, the XCD renumbering, the split-image epilogue and the wait-count check of debug
+// builds live here once; the per-phase counters come with phase_timing.h.  Private to csrc/.
 #pragma once
 #include "conv_kernels.h"
+#include "phase_timing.h"
 
 namespace rvc {
+
+// f(integral_constant<int, T>) for T = T .. N - 1, unrolled at compile time: the body sees its index as a constant (immediate waits)
+template <int T, int N, class F> __device__ __forceinline__ void static_for(F& f) {
+  if constexpr (T < N) { f(std::integral_constant<int, T>{}); static_for<T + 1, N>(f); }
+}
+constexpr int tap_mod(int t, int KT) { return ((t % KT) + KT) % KT; }
+// conversion schedule of the pipelined kernels' fp32 input: staging slot s (of XS) of the next chunk is converted during tap (s * KT) / XS
+constexpr int x3_cv(int t, int KT, int XS) {
+  t = tap_mod(t, KT);
+  for (int s = 0; s < XS; ++s) if ((s * KT) / XS == t) return 1;
+  return 0;
+}
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -38,6 +54,30 @@ __device__ __forceinline__ void split2h(float a, float b, unsigned& hi, unsigned
   // round-to-nearest-even (v_cvt_pk_f16_f32): below |x| = 0.125 lo is an fp16 subnormal and a truncation there would be a bias that does not average out
   lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2_t));
 }
+
+// s_waitcnt vmcnt(N), N an immediate derived from the kernel's schedule: waits until at most N of this wave's VMEM operations (LDS-DMA
+// pieces and register loads alike, retired in issue order) are outstanding.  The counter has 6 bits; where a schedule's count can exceed
+// them the call site passes vm6(N): a smaller count than necessary only waits longer.
+template <int N> __device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+constexpr int vm6(int n) { return n > 63 ? 63 : n; }
+// Debug builds (-DRVC_X3P_CHECK) of the kernels whose waits are immediates keep exact run-time bookkeeping beside them and count every
+// wait whose compile-time count exceeded the exact one (must stay 0).  One counter per translation unit, registered with
+// RVC_X3P_CHECK_REGISTER; at file scope; conv_x3p_check_read() (conv_x3p.hip) sums and resets them.
+std::vector<int (*)()>& x3p_check_readers();                 // conv_x3p.hip
+#ifdef RVC_X3P_CHECK
+static __device__ int g_x3p_bad;
+static int x3p_bad_read() { int v = 0, z = 0; (void)hipDeviceSynchronize(); (void)hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_x3p_bad), sizeof(int)); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_x3p_bad), &z, sizeof(int)); return v; }
+#define RVC_X3P_CHECK_REGISTER static const bool x3p_check_registered = (rvc::x3p_check_readers().push_back(&rvc::x3p_bad_read), true)
+#define X3P_CHECK(N, exact) do { if ((N) > (exact) && (threadIdx.x & 63) == 0) atomicAdd(&g_x3p_bad, 1); } while (0)
+#define X3P_ISSUED(n) (issued += (n))
+#else
+#define RVC_X3P_CHECK_REGISTER static_assert(true, "")
+#define X3P_CHECK(N, exact) do {} while (0)
+#define X3P_ISSUED(n) do {} while (0)
+#endif
 
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n: waits until at most n of this wave's VMEM operations (LDS-DMA pieces and register
 // loads alike, retired in issue order) are outstanding.  A smaller count than necessary only waits longer, so n is clamped to the table.

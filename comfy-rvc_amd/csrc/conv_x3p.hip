@@ -24,49 +24,22 @@
 
 namespace rvc {
 
-// conversion schedule: slot s (of XS) of the next chunk is converted during tap (s * KT) / XS
-constexpr int x3p_cv(int t, int KT, int XS) {
-  t = ((t % KT) + KT) % KT;
-  for (int s = 0; s < XS; ++s) if ((s * KT) / XS == t) return 1;
-  return 0;
-}
-constexpr int x3p_cvsum(int t0, int t1, int KT, int XS) { int n = 0; for (int t = t0; t <= t1; ++t) n += x3p_cv(t, KT, XS); return n; }
+constexpr int x3p_cvsum(int t0, int t1, int KT, int XS) { int n = 0; for (int t = t0; t <= t1; ++t) n += x3_cv(t, KT, XS); return n; }
 
 #ifdef RVC_X3P_SETPRIO
 #define X3P_PRIO(n) __builtin_amdgcn_s_setprio(n)
 #else
 #define X3P_PRIO(n) do {} while (0)
 #endif
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+RVC_PHASE_TABLE_REGISTER;
+RVC_X3P_CHECK_REGISTER;
+// the sum over every translation unit's wait-count check (conv_x3_dev.h), counters reset; -1 when nothing registered (builds without -DRVC_X3P_CHECK)
+std::vector<int (*)()>& x3p_check_readers() { static std::vector<int (*)()> v; return v; }
+int conv_x3p_check_read() {
+  int n = x3p_check_readers().empty() ? -1 : 0;
+  for (auto read : x3p_check_readers()) n += read();
+  return n;
 }
-template <int T, int N, class F> __device__ __forceinline__ void static_for(F& f) {
-  if constexpr (T < N) { f(std::integral_constant<int, T>{}); static_for<T + 1, N>(f); }
-}
-#ifdef RVC_X3P_CHECK
-__device__ int g_x3p_bad;       // waits whose compile-time count exceeded the exact run-time one (must stay 0)
-int conv_x3p_check_read() { int v = 0, z = 0; (void)hipDeviceSynchronize(); (void)hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_x3p_bad), sizeof(int)); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_x3p_bad), &z, sizeof(int)); return v; }
-#define X3P_CHECK(N, exact) do { if ((N) > (exact) && (threadIdx.x & 63) == 0) atomicAdd(&g_x3p_bad, 1); } while (0)
-#else
-int conv_x3p_check_read() { return -1; }
-#define X3P_CHECK(N, exact) do {} while (0)
-#endif
-
-#ifdef RVC_CONV_TIMING
-__device__ unsigned long long g_x3p_timing[8];   // [0] tiles, [1] prologue, [2] compute between barriers, [3] weight wait, [4] barrier, [5] epilogue, [6] total
-void conv_x3p_timing_read(unsigned long long* out8, bool reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_x3p_timing), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_x3p_timing), z, sizeof(z)); }
-}
-#define XPTICK() ((long long)__builtin_readcyclecounter())
-#define XPACC(i, v) do { xpt[i] += (v); } while (0)
-#else
-void conv_x3p_timing_read(unsigned long long* out8, bool) { for (int i = 0; i < 8; ++i) out8[i] = 0; }
-#define XPTICK() 0ll
-#define XPACC(i, v) do {} while (0)
-#endif
 
 // KT = taps (compile-time: the units of a chunk are unrolled, so every vmcnt wait is an immediate - see the counting rules at the waits).
 // S2: stride 2 (HuBERT's feature encoder, k = 3): the staged input keeps one sub-plane per input phase (even / odd positions), tap t reads
@@ -112,11 +85,8 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3p_kernel(c
   const float pre_slope = p.pre_act == ACT_LRELU ? p.pre_slope : 1.f;
   const __amdgpu_buffer_rsrc_t xrs = make_rsrc(p.X, XSPLIT ? 0u : (unsigned)p.Ci * (unsigned)p.ldX * 4u);
 
-#ifdef RVC_CONV_TIMING
-  long long xpt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  const long long t_begin = XPTICK();
-  long long t_last = t_begin;
+  // [0] tiles, [1] prologue, [2] compute between barriers, [3] weight wait, [4] barrier, [5] epilogue, [6] total
+  PhaseTimer<PhaseClock::cycle> tm;
   // ---- accumulators: zero, or residual + bias when nothing but the scale follows the sum (the loads are the oldest VMEM operations of
   // the wave; their latency lies under the prologue's input loads and first weight slots)
   const bool r_init = !YSPLIT && p.R != nullptr && p.act == ACT_NONE;
@@ -146,9 +116,6 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3p_kernel(c
 
 #ifdef RVC_X3P_CHECK
   int issued = 0, mk_w[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mk_x[XS] = {0, 0, 0}, mk_xs = 0;   // exact bookkeeping (debug build only)
-#define X3P_ISSUED(n) (issued += (n))
-#else
-#define X3P_ISSUED(n) do {} while (0)
 #endif
 
   // ---- weights: unit u = (chunk, tap) is 2 * RB pieces of 1 KiB; consecutive units are consecutive planes of the image
@@ -286,7 +253,7 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3p_kernel(c
   }
 
   int sl = 0;                                                    // weight slot of the current unit
-  t_last = XPTICK(); XPACC(1, t_last - t_begin);
+  tm.lap(1);
   for (int c = 0; c < nck; ++c) {
     const int xb = c & 1;
     const bool tail2 = c + 2 >= nck, tail1 = c + 1 >= nck;       // no chunk c + 2 / c + 1
@@ -357,15 +324,14 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3p_kernel(c
 #ifdef RVC_X3P_CHECK
         const int exact = issued - mk_w[(c * KT + T + 1) & 7];
 #endif
-        const long long ta = XPTICK();
+        tm.lap(2);
         if (tail1) { X3P_CHECK(SL, exact); wait_vmcnt<SL>(); }
         else if (XSPLIT ? false : tail2) { X3P_CHECK(SL2, exact); wait_vmcnt<SL2>(); }
         else if (c == 0) { X3P_CHECK(S0, exact); wait_vmcnt<S0>(); }
         else { X3P_CHECK(SX, exact); wait_vmcnt<SX>(); }
-        const long long tb = XPTICK();
+        tm.lap(3);
         lds_barrier();
-        const long long tcc = XPTICK();
-        XPACC(2, ta - t_last); XPACC(3, tb - ta); XPACC(4, tcc - tb); t_last = tcc;
+        tm.lap(4);
         const int sn = sl + 1 == R ? 0 : sl + 1;
         if (XSPLIT && last_tap && x_edge) { zero_edges(xb ^ 1); lds_barrier(); }
         if (!(tail1 && T + R - 1 >= KT)) issue_w();               // unit u + R - 1 into the slot unit u - 1 was read from
@@ -394,8 +360,7 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3p_kernel(c
   }
 
   // ---- epilogue
-  const long long t_epi = XPTICK();
-  XPACC(2, t_epi - t_last);
+  tm.lap(2);
   if constexpr (YSPLIT) {
     ysplit_epilogue<WM, WN, AM, AN>(p, acc, co0, n0, wm, wn, li, lh);
   } else if (p.ostride != 1) {
@@ -452,10 +417,7 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3p_kernel(c
   } else {
     dense_epilogue<WM, WN, AM, AN, 4>(p, acc, 0, co0, n0, wm, wn, li, lh);
   }
-#ifdef RVC_CONV_TIMING
-  { const long long te = XPTICK(); XPACC(5, te - t_epi); XPACC(6, te - t_begin); XPACC(0, 1);
-    if (threadIdx.x == 0) for (int i = 0; i < 8; ++i) atomicAdd(&g_x3p_timing[i], (unsigned long long)xpt[i]); }
-#endif
+  tm.lap(5); tm.add(0, 1); tm.flush();
 }
 
 // ============================================================================ k = 1 (GEMM): the projections of HuBERT / the text encoder / the flow

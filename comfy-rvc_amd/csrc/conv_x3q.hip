@@ -22,46 +22,8 @@
 
 namespace rvc {
 
-template <int N> __device__ __forceinline__ void q_wait() {
-  static_assert(N >= 0, "vmcnt");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N > 63 ? 63 : N) : "memory");      // 6-bit counter: a smaller count than necessary only waits longer
-}
-template <int T, int N, class F> __device__ __forceinline__ void q_for(F& f) {
-  if constexpr (T < N) { f(std::integral_constant<int, T>{}); q_for<T + 1, N>(f); }
-}
-constexpr int q_mod(int t, int KT) { return ((t % KT) + KT) % KT; }
-// fp32 input: staging slot s (of XS) of the next chunk is converted during tap (s * KT) / XS
-constexpr int q_cv(int t, int KT, int XS) {
-  t = q_mod(t, KT);
-  for (int s = 0; s < XS; ++s) if ((s * KT) / XS == t) return 1;
-  return 0;
-}
-
-#ifdef RVC_X3P_CHECK
-__device__ int g_x3q_bad;
-int conv_x3q_check_read() { int v = 0, z = 0; (void)hipDeviceSynchronize(); (void)hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_x3q_bad), sizeof(int)); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_x3q_bad), &z, sizeof(int)); return v; }
-#define X3Q_CHECK(N, exact) do { if (((N) > 63 ? 63 : (N)) > (exact) && (threadIdx.x & 63) == 0) atomicAdd(&g_x3q_bad, 1); } while (0)
-#define X3Q_ISSUED(n) (issued += (n))
-#else
-int conv_x3q_check_read() { return -1; }
-#define X3Q_CHECK(N, exact) do {} while (0)
-#define X3Q_ISSUED(n) do {} while (0)
-#endif
-
-#ifdef RVC_CONV_TIMING
-__device__ unsigned long long g_x3q_timing[8];   // [0] tiles, [1] prologue (once per workgroup), [2] compute between barriers, [3] weight wait, [4] barrier, [5] epilogue, [6] total
-void conv_x3q_timing_read(unsigned long long* out8, bool reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_x3q_timing), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_x3q_timing), z, sizeof(z)); }
-}
-#define XQTICK() ((long long)__builtin_readcyclecounter())
-#define XQACC(i, v) do { xqt[i] += (v); } while (0)
-#else
-void conv_x3q_timing_read(unsigned long long* out8, bool) { for (int i = 0; i < 8; ++i) out8[i] = 0; }
-#define XQTICK() 0ll
-#define XQACC(i, v) do {} while (0)
-#endif
+RVC_PHASE_TABLE_REGISTER;
+RVC_X3P_CHECK_REGISTER;
 
 struct QTile { int co0, n0, bx; bool edge, valid; };
 // One 32 x 32 x 16 product.  SWAP = false: D[channel][position], a lane holds ONE position (its column) and 16 channels - what the split-image
@@ -98,9 +60,9 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
   // ---- operations a unit issues, in program order: A (fp32 refill of a converted slot) | C (weight unit) | D (split input chunk, last tap) |
   // E (residual block)
   struct Q {
-    static constexpr int nA(int t) { return XSPLIT ? 0 : 8 * q_cv(t, KT, XS); }
-    static constexpr int nD(int t) { return (XSPLIT && q_mod(t, KT) == KT - 1) ? NPX : 0; }
-    static constexpr int nE(int t) { return (RADD && q_mod(t, KT) == TR) ? 16 : 0; }
+    static constexpr int nA(int t) { return XSPLIT ? 0 : 8 * x3_cv(t, KT, XS); }
+    static constexpr int nD(int t) { return (XSPLIT && tap_mod(t, KT) == KT - 1) ? NPX : 0; }
+    static constexpr int nE(int t) { return (RADD && tap_mod(t, KT) == TR) ? 16 : 0; }
     static constexpr int tot(int t) { return nA(t) + NPW + nD(t) + nE(t); }
     static constexpr int sum() { int n = 0; for (int t = 0; t < KT; ++t) n += tot(t); return n; }
     // younger than the weight pieces of unit u + 1 (requested in step C of unit u - (R - 2)) at the wait of unit u (tap t), which follows step A
@@ -145,11 +107,8 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
   };
   const int nit = (int)((ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
 
-#ifdef RVC_CONV_TIMING
-  long long xqt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  const long long t_begin = XQTICK();
-  [[maybe_unused]] long long t_last = t_begin;
+  // [0] tiles, [1] prologue (once per workgroup), [2] compute between barriers, [3] weight wait, [4] barrier, [5] epilogue, [6] total (per workgroup)
+  PhaseTimer<PhaseClock::cycle> tm;
 #ifdef RVC_X3P_CHECK
   int issued = 0, mk_w[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mk_x[XS] = {0, 0, 0}, mk_r = 0, uwc = 0, mk_xs[2] = {0, 0};
 #endif
@@ -175,17 +134,17 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
       // (64-row tiles: the upper half-wave is switched off - the instruction still issues, so the counts below hold)
       unsigned char* dst = Ws + slw * wslot + wave * (RB == 4 ? 1024 : 512);
       if (RB == 4 || lane < 32)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void*)dst, 16, wvoff, (int)wsoff, 0, 0);
+        buf_dma(wrs, dst, wvoff, (int)wsoff);
     } else {
       unsigned char* dst = Ws + slw * wslot + wave * 1024;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void*)dst, 16, wvoff, (int)wsoff, 0, 0);
+      buf_dma(wrs, dst, wvoff, (int)wsoff);
       if constexpr (RB == 4)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void*)(dst + NW * 1024), 16, wvoff, (int)(wsoff + (unsigned)p.CoPx * 32u), 0, 0);
+        buf_dma(wrs, dst + NW * 1024, wvoff, (int)(wsoff + (unsigned)p.CoPx * 32u));
     }
     ++uw;
     if (uw == NU) { uw = 0; wsoff = (unsigned)wtile_co0_next * 16u; } else wsoff += wstep;
     slw = slw + 1 == R ? 0 : slw + 1;
-    X3Q_ISSUED(NPW);
+    X3P_ISSUED(NPW);
 #ifdef RVC_X3P_CHECK
     mk_w[uwc & 7] = issued; ++uwc;
 #endif
@@ -207,7 +166,7 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
     const unsigned c0 = (unsigned)(chunk * 16 + hb * 8);
 #pragma unroll
     for (int j = 0; j < 8; ++j) xr[s][j] = buf_load(xrs, voff, (c0 + j) * (unsigned)p.ldX * 4u);
-    X3Q_ISSUED(8);
+    X3P_ISSUED(8);
 #ifdef RVC_X3P_CHECK
     mk_x[s] = issued;
 #endif
@@ -241,9 +200,9 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
       unsigned char* dst = Xs + xb * xbuf + hp * xhalf + j * 1024;
       // (lanes past the half-plane's last row are switched off: the instruction still issues, so the counts below hold)
       if (j * 64 + lane < Pm)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(xsr, (__attribute__((address_space(3))) void*)dst, 16, lane * 16, (int)(row * 16u), 0, 0);
+        buf_dma(xsr, dst, lane * 16, (int)(row * 16u));
     }
-    X3Q_ISSUED(NPX);
+    X3P_ISSUED(NPX);
 #ifdef RVC_X3P_CHECK
     mk_xs[xb] = issued;
 #endif
@@ -269,7 +228,7 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
       const unsigned voff = (tl.valid && b < NBLK && n < p.Tout) ? ((unsigned)mb * (unsigned)p.ldR + (unsigned)n) * 4u : kOOB;
 #pragma unroll
       for (int r = 0; r < 16; ++r) rst[r] = buf_load(rrs, voff, (unsigned)((r & 3) + 8 * (r >> 2)) * (unsigned)p.ldR * 4u);
-      X3Q_ISSUED(16);
+      X3P_ISSUED(16);
 #ifdef RVC_X3P_CHECK
       mk_r = issued;
 #endif
@@ -288,7 +247,7 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
   } else {
 #pragma unroll
     for (int s = 0; s < XS; ++s) load_slot(s, cur, 0);
-    q_wait<0>();
+    wait_vmcnt<0>();
 #pragma unroll
     for (int s = 0; s < XS; ++s) store_slot(s, 0);
 #pragma unroll
@@ -297,7 +256,7 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
 #pragma unroll
   for (int i = 0; i < R - 1; ++i) issue_w();
   load_res(cur, 0);
-  q_wait<0>();
+  wait_vmcnt<0>();
 #pragma unroll
   for (int s = 0; s < XS; ++s)
 #pragma unroll
@@ -317,7 +276,7 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
   }
 
   int sl = 0, xb = 0;                                        // weight slot of the current unit, input buffer of the current chunk
-  t_last = XQTICK(); XQACC(1, t_last - t_begin);
+  tm.lap(1);
   for (int it = 0; it < nit; ++it) {
     // accumulators start at the bias where residual and bias join the sum inside the tile (RADD), at zero otherwise (bias in the epilogue)
 #pragma unroll
@@ -367,13 +326,13 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
             if constexpr ((s * KT) / XS == T) {
               constexpr int NS = Q::sum() - 8;                 // younger than this slot's loads (issued in step A one chunk ago)
               // (check build: waits whose target was issued in the prologue - first chunk of the first tile - are exempt: everything had landed there)
-              if (c0) { if (it > 0) X3Q_CHECK(NS + EP, issued - mk_x[s]); q_wait<NS + EP>(); }
-              else { X3Q_CHECK(NS, issued - mk_x[s]); q_wait<NS>(); }
+              if (c0) { if (it > 0) X3P_CHECK(vm6(NS + EP), issued - mk_x[s]); wait_vmcnt<vm6(NS + EP)>(); }
+              else { X3P_CHECK(vm6(NS), issued - mk_x[s]); wait_vmcnt<vm6(NS)>(); }
               store_slot(s, xb ^ 1);
               load_slot(s, t2, ch2);
             }
           };
-          q_for<0, XS>(stage);
+          static_for<0, XS>(stage);
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- group 2: hi_w * hi_x
@@ -389,17 +348,16 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
 #ifdef RVC_X3P_CHECK
           const int exact = issued - mk_w[(uwc - (R - 2)) & 7];
 #endif
-          [[maybe_unused]] const long long ta = XQTICK();
-          if (c0 && T < R - 2) { if (it > 0) X3Q_CHECK(NWT + EP, exact); q_wait<NWT + EP>(); }
-          else { X3Q_CHECK(NWT, exact); q_wait<NWT>(); }
+          tm.lap(2);
+          if (c0 && T < R - 2) { if (it > 0) X3P_CHECK(vm6(NWT + EP), exact); wait_vmcnt<vm6(NWT + EP)>(); }
+          else { X3P_CHECK(vm6(NWT), exact); wait_vmcnt<vm6(NWT)>(); }
           // the split-resident chunk this unit's tail starts to read (requested one chunk ago, right behind that unit's weight request) is covered by the
           // same wait as long as the weight request waited for is not older than it: R - 2 <= KT - 1 (conv_x3q_plan clamps the ring for 3-tap layers)
           static_assert(!XSPLIT || R - 2 <= KT - 1, "weight ring deeper than a chunk: the input chunk's DMA would not be covered by the weight wait");
-          if constexpr (XSPLIT && last_tap) { if (it > 0 || c > 0) X3Q_CHECK(NWT, issued - mk_xs[xb ^ 1]); }
-          [[maybe_unused]] const long long tb = XQTICK();
+          if constexpr (XSPLIT && last_tap) { if (it > 0 || c > 0) X3P_CHECK(vm6(NWT), issued - mk_xs[xb ^ 1]); }
+          tm.lap(3);
           lds_barrier();
-          [[maybe_unused]] const long long tcc = XQTICK();
-          XQACC(2, ta - t_last); XQACC(3, tb - ta); XQACC(4, tcc - tb); t_last = tcc;
+          tm.lap(4);
           const int sn = sl + 1 == R ? 0 : sl + 1;
           if (XSPLIT && last_tap && t1.edge) { zero_edges(t1, xb ^ 1); lds_barrier(); }
           issue_w();                                             // unit u + R - 1 into the slot unit u - 1 was read from
@@ -415,8 +373,8 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
         // ---- step E: residual + bias of block c join the sum; block c + 1 (the next tile's block 0 in a tile's last chunk) requested
         if constexpr (RADD && T == TR) {
           constexpr int NR = Q::sum() - 16;
-          if (c0) { if (it > 0) X3Q_CHECK(NR + EP, issued - mk_r); q_wait<NR + EP>(); }
-          else { X3Q_CHECK(NR, issued - mk_r); q_wait<NR>(); }
+          if (c0) { if (it > 0) X3P_CHECK(vm6(NR + EP), issued - mk_r); wait_vmcnt<vm6(NR + EP)>(); }
+          else { X3P_CHECK(vm6(NR), issued - mk_r); wait_vmcnt<vm6(NR)>(); }
           // The block that receives the residual is chosen at run time (block = chunk), its registers are not.  A branch the compiler can see
           // turns into copy-in / copy-out of the whole 16-register accumulator around every test (a phi of two 512-bit tuples: 256 v_mov per step
           // and 50 spilled registers), so the wave-uniform test lives INSIDE the asm statement: to the compiler every block is updated in place,
@@ -438,7 +396,7 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
             X3Q_ADD8(8);
 #undef X3Q_ADD8
           };
-          q_for<0, NBLK>(radd);
+          static_for<0, NBLK>(radd);
           load_res(t1, in1 ? c + 1 : 0);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -452,13 +410,12 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
               acc[am][an] = q_mfma<false>(al[am], bh[an], acc[am][an]);
         }
       };
-      q_for<0, KT>(unit);
+      static_for<0, KT>(unit);
       xb ^= 1;
     }
 
     // ---- epilogue of tile `cur` (the next tile's first chunks and weight units are already on their way)
-    [[maybe_unused]] const long long t_epi = XQTICK();
-    XQACC(2, t_epi - t_last);
+    tm.lap(2);
     if constexpr (YSPLIT) {
       // v = lrelu(acc + bias) as the bf16 (H2: fp16) hi / lo image the next layer stages by DMA (conv_x3_dev.h::ysplit_epilogue with the bias from LDS)
       const float sl2 = p.ys_slope;
@@ -502,7 +459,7 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
             __builtin_amdgcn_raw_buffer_store_b128(lo, ysr, (int)off, (int)(unsigned)(p.ysTp * 32), 0);
           }
         }
-      X3Q_ISSUED(4 * AM * AN);
+      X3P_ISSUED(4 * AM * AN);
     } else if constexpr (RADD) {
       // residual and bias are inside the sum: v = acc * scale [+ previous output].  The MFMA layout gives a lane ONE column: stored directly
       // that is 16 dword stores per accumulator (128 per tile) - and every store stands in the in-order vmcnt queue in front of the next tile's
@@ -544,25 +501,21 @@ __global__ __launch_bounds__(256, (AM * AN >= 8) ? 2 : 3) void conv_x3q_kernel(c
             }
 #ifdef RVC_X3P_CHECK
 #pragma unroll
-            for (int e = 0; e < 3; ++e) if (__ballot(n < p.Tout && n + 3 >= p.Tout && n + e < p.Tout)) X3Q_ISSUED(1);      // (an instruction issues when any lane is active)
+            for (int e = 0; e < 3; ++e) if (__ballot(n < p.Tout && n + 3 >= p.Tout && n + e < p.Tout)) X3P_ISSUED(1);      // (an instruction issues when any lane is active)
 #endif
           }
         }
-      X3Q_ISSUED(4 * AM * AN + (p.accumulate ? 4 * AM * AN : 0));
+      X3P_ISSUED(4 * AM * AN + (p.accumulate ? 4 * AM * AN : 0));
     } else {
       dense_epilogue<WM, WN, AM, AN, 4>(p, acc, 0, cur.co0, cur.n0, wm, wn, li, lh);
-      X3Q_ISSUED(EP);                                          // (a lower bound here: the check build only knows the stores)
+      X3P_ISSUED(EP);                                          // (a lower bound here: the check build only knows the stores)
     }
-    XQACC(5, XQTICK() - t_epi); XQACC(0, 1);
-    t_last = XQTICK();
+    tm.lap(5); tm.add(0, 1);
     cur = nxt; nxt = geom(it + 2);
     wtile_co0_next = nxt.valid ? nxt.co0 : cur.co0;
   }
-  q_wait<0>();                                                  // (requests past the end: nothing may land in LDS after the workgroup has gone)
-#ifdef RVC_CONV_TIMING
-  { XQACC(6, XQTICK() - t_begin);
-    if (threadIdx.x == 0) for (int i = 0; i < 8; ++i) atomicAdd(&g_x3q_timing[i], (unsigned long long)xqt[i]); }
-#endif
+  wait_vmcnt<0>();                                                  // (requests past the end: nothing may land in LDS after the workgroup has gone)
+  tm.flush();
 }
 
 

@@ -20,6 +20,7 @@
 //   * bias and residual are loaded into slice 0's accumulators at tile start (the oldest VMEM operations of the wave), so the epilogue is
 //     activation + store: fp32 rows, and / or the bf16 hi / lo image for the next GEMM (exact-erf GELU in fp32 before the split).
 #include "conv_x3_dev.h"
+#include "ops.h"
 
 namespace rvc {
 
@@ -53,39 +54,7 @@ struct GemmSArgs {
                                             // chunk: two products over one accumulator; INT_MAX: none
 };
 
-// exact-erf GELU (torch F.gelu default), branch-free: erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7 absolute, i.e. ~1e-7 of the
-// activation - far inside the fp32 noise of the 768-term sums that feed it; ocml's erff takes two divergent paths per element)
-__device__ __forceinline__ float x3s_gelu(float v) {
-  const float x = v * 0.70710678118654752440f, ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-  const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * x * x);
-  const float erf_abs = fmaf(-poly, e, 1.f);
-  return 0.5f * v * (1.f + copysignf(erf_abs, x));
-}
-// 1 KiB (16 B per lane) from a buffer straight into LDS: address = descriptor base + per-lane voffset + wave-uniform soffset
-__device__ __forceinline__ void x3s_dma(__amdgpu_buffer_rsrc_t rs, unsigned char* lds_dst, int voffset, int soffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
-template <int N> __device__ __forceinline__ void x3s_wait_vmcnt() {
-  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-#ifdef RVC_CONV_TIMING
-__device__ unsigned long long g_x3s_timing[8];   // [0] workgroups, [1] prologue (to the first barrier), [2] between barriers (operand reads + MFMA issue), [3] DMA wait, [4] barrier, [5] split-K + epilogue, [6] total
-void conv_x3s_timing_read(unsigned long long* out8, bool reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_x3s_timing), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_x3s_timing), z, sizeof(z)); }
-}
-#define XSTICK() ((long long)__builtin_readcyclecounter())
-#define XSACC(i, v) do { xst[i] += (v); } while (0)
-#else
-void conv_x3s_timing_read(unsigned long long* out8, bool) { for (int i = 0; i < 8; ++i) out8[i] = 0; }
-#define XSTICK() 0ll
-#define XSACC(i, v) do {} while (0)
-#endif
+RVC_PHASE_TABLE_REGISTER;
 
 // One (chunk, tap) unit per ring slot = per barrier.  Two units per barrier were measured in round 4 and not kept: the K loop of these grids is
 // bound by the L2 -> LDS latency per ring step, not by the barrier, and the doubled LDS footprint cost the three-lane bench 2.5 %.
@@ -120,11 +89,9 @@ __global__ __launch_bounds__(256, x3s_wgs(AM, AN, RS)) void conv_x3s_kernel(cons
   const int co0 = (tile_y - grp * p.rows_pg) * BM, n0 = tile_x * BN;      // first row INSIDE the group
   const int row0 = grp * p.co_g, CoG = p.co_g;              // global row = row0 + m for m < CoG
   const int U1 = p.nunits / S, u0 = ks * U1;                          // units of this slice
-#ifdef RVC_CONV_TIMING
-  long long xst[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  [[maybe_unused]] const long long xs_begin = XSTICK();
-  [[maybe_unused]] long long xs_last = xs_begin;
+  // [0] workgroups, [1] prologue (to the first barrier), [2] between barriers (operand reads + MFMA issue), [3] DMA wait, [4] barrier, [5] split-K + epilogue, [6] total
+  PhaseTimer<PhaseClock::cycle> tm;
+  tm.add(0, 1);
 
   // ---- accumulators: slice 0 starts from bias (+ residual unless an activation sits between the sum and the residual)
   const bool r_pre = p.R != nullptr && !(p.act_before_res && p.act != ACT_NONE);
@@ -186,8 +153,8 @@ __global__ __launch_bounds__(256, x3s_wgs(AM, AN, RS)) void conv_x3s_kernel(cons
     unsigned char* base = smem3s + slw * uslot;
 #pragma unroll
     for (int i = 0; i < NPW; ++i) {
-      if (i * NW < NPA) x3s_dma(ars, base + dsto[i], voff[i], soff_a);
-      else x3s_dma(brs, base + dsto[i], voff[i], soff_b);
+      if (i * NW < NPA) buf_dma(ars, base + dsto[i], voff[i], soff_a);
+      else buf_dma(brs, base + dsto[i], voff[i], soff_b);
     }
     ++uw;
     if (uw < U1) {
@@ -210,7 +177,7 @@ __global__ __launch_bounds__(256, x3s_wgs(AM, AN, RS)) void conv_x3s_kernel(cons
   // ---- prologue: [bias / residual] units 0 .. RS - 2
 #pragma unroll
   for (int i = 0; i < RS - 1; ++i) issue();
-  x3s_wait_vmcnt<(RS - 2) * NPW>();                          // slot 0 (younger: slots 1 .. RS - 2)
+  wait_vmcnt<(RS - 2) * NPW>();                          // slot 0 (younger: slots 1 .. RS - 2)
 #pragma unroll
   for (int am = 0; am < AM; ++am)
 #pragma unroll
@@ -249,12 +216,11 @@ __global__ __launch_bounds__(256, x3s_wgs(AM, AN, RS)) void conv_x3s_kernel(cons
   int sl = 0;
   auto body = [&](const Ops& cur, Ops& nxt) {
     // slot u + 1 was requested RS - 2 steps ago; younger: slots u + 2 .. u + RS - 2
-    [[maybe_unused]] const long long ta = XSTICK();
-    x3s_wait_vmcnt<(RS - 3) * NPW>();
-    [[maybe_unused]] const long long tb = XSTICK();
+    tm.lap(2);
+    wait_vmcnt<(RS - 3) * NPW>();
+    tm.lap(3);
     lds_barrier();
-    [[maybe_unused]] const long long tc = XSTICK();
-    XSACC(2, ta - xs_last); XSACC(3, tb - ta); XSACC(4, tc - tb); xs_last = tc;
+    tm.lap(4);
     issue();                                                 // slot u + RS - 1 over the one step u - 1 was read from (those reads fed step u - 1's MFMAs)
     sl = sl + 1 == RS ? 0 : sl + 1;
     read_ops(nxt, sl);
@@ -263,13 +229,13 @@ __global__ __launch_bounds__(256, x3s_wgs(AM, AN, RS)) void conv_x3s_kernel(cons
     __builtin_amdgcn_sched_barrier(0);
   };
   read_ops(o0, 0);
-  xs_last = XSTICK(); XSACC(1, xs_last - xs_begin);
+  tm.lap(1);
   int u = 0;
   for (; u + 1 < U1; u += 2) { body(o0, o1); body(o1, o0); }
   if (u < U1) body(o0, o1);
-  XSACC(2, XSTICK() - xs_last);
+  tm.lap(2);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (the requests past the end: nothing may land in LDS after the workgroup has gone)
-  [[maybe_unused]] const long long xs_epi = XSTICK();
+  tm.mark();
 
   // ---- K split: slabs in register order, write-through; the last slice to arrive sums them in slice order
   if (S > 1) {
@@ -300,13 +266,8 @@ __global__ __launch_bounds__(256, x3s_wgs(AM, AN, RS)) void conv_x3s_kernel(cons
       *flag = t;
     }
     __syncthreads();
-    if (*flag != (unsigned)S - 1u) {
-#ifdef RVC_CONV_TIMING
-    { const long long te = XSTICK(); XSACC(5, te - xs_epi); XSACC(6, te - xs_begin); XSACC(0, 1);
-      if (threadIdx.x == 0) for (int i = 0; i < 8; ++i) atomicAdd(&g_x3s_timing[i], (unsigned long long)xst[i]); }
-#endif
-      return;
-    }
+    tm.lap(5); tm.flush();                                   // (slices that end here; the last one goes on and flushes what follows at the end)
+    if (*flag != (unsigned)S - 1u) return;
 #pragma unroll
     for (int am = 0; am < AM; ++am)
 #pragma unroll
@@ -338,7 +299,7 @@ __global__ __launch_bounds__(256, x3s_wgs(AM, AN, RS)) void conv_x3s_kernel(cons
 #pragma unroll
       for (int an = 0; an < AN; ++an)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[am][an][r] = x3s_gelu(acc[am][an][r]);
+        for (int r = 0; r < 16; ++r) acc[am][an][r] = gelu_bf(acc[am][an][r]);
   } else if (p.act != ACT_NONE) {
     const float slope = p.act == ACT_RELU ? 0.f : p.act_slope;
 #pragma unroll
@@ -533,10 +494,7 @@ __global__ __launch_bounds__(256, x3s_wgs(AM, AN, RS)) void conv_x3s_kernel(cons
         }
       }
   }
-#ifdef RVC_CONV_TIMING
-  { const long long te = XSTICK(); XSACC(5, te - xs_epi); XSACC(6, te - xs_begin); XSACC(0, 1);
-    if (threadIdx.x == 0) for (int i = 0; i < 8; ++i) atomicAdd(&g_x3s_timing[i], (unsigned long long)xst[i]); }
-#endif
+  tm.lap(5); tm.flush();
 }
 
 // ---------------------------------------------------------------------------- fp32 [C][T] <-> split image (producers without an image epilogue, tests)

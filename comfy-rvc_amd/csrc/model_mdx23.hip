@@ -211,7 +211,6 @@ __global__ void inorm_fold_kernel(const double* __restrict__ part, int C, int P,
   const float a = gamma[c] * (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + (double)eps));
   sc[c] = a; sh[c] = beta[c] - (float)m * a;
 }
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
 // y = gelu(x * sc[c] + sh[c]) over [A][C][B]
 __global__ void inorm_apply_gelu_kernel(const float* __restrict__ x, float* __restrict__ y, int C, long long B, long long n, const float* __restrict__ sc,
                                         const float* __restrict__ sh) {
@@ -285,15 +284,6 @@ __global__ void ola_kernel(const float* __restrict__ fr, const float* __restrict
 
 
 // ---------------------------------------------------------------------------------------------- padded split-resident graph (round 4)
-// branch-free exact-erf GELU, the form conv_x3s.hip's epilogue evaluates (Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7 absolute): the image producers
-// below run at HBM rate only if the activation stays under ~20 VALU instructions per value (ocml's erff: two divergent paths)
-__device__ __forceinline__ float gelu_as(float v) {
-  const float x = v * 0.70710678118654752440f, ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-  const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * x * x);
-  return 0.5f * v * (1.f + copysignf(fmaf(-poly, e, 1.f), x));
-}
 // 8 values of one position -> one 16-byte row of the hi and of the lo plane; g = group of 8 rows = chunk * 2 + half, row = margin + position
 __device__ __forceinline__ void split8_store(const float (&v)[8], unsigned char* __restrict__ img, long long tp, long long row, int g) {
   u32x4 hi, lo;
@@ -385,7 +375,7 @@ __global__ __launch_bounds__(256) void inorm_apply_split_kernel(const float* __r
     if (!pad && row < rows) {
       if (RAW) { v[j] = x[(long long)row * ld + t]; continue; }
       if (!COLCH) { a = s_a[j]; b = s_b[j]; }
-      v[j] = gelu_as(fmaf(x[(long long)row * ld + t], a, b));
+      v[j] = gelu_bf(fmaf(x[(long long)row * ld + t], a, b));
     }
   }
   split8_store(v, img, tp, margin + t, g);
@@ -403,7 +393,7 @@ __global__ __launch_bounds__(256) void inorm_apply_tm_kernel(const float* __rest
   for (int i = 0; i < 8; ++i) {
     const int ri = i * 4 + (threadIdx.x >> 6), wi = threadIdx.x & 63, r = r0 + ri;
     float v = 0.f;
-    if (r < R && w0 + wi < W) { const int c = (hshift >= 0 ? (r >> hshift) : (r / H)) - cfirst; v = gelu_as(fmaf(x[(long long)r * Wp + 1 + w0 + wi], s_a[c], s_b[c])); }
+    if (r < R && w0 + wi < W) { const int c = (hshift >= 0 ? (r >> hshift) : (r / H)) - cfirst; v = gelu_bf(fmaf(x[(long long)r * Wp + 1 + w0 + wi], s_a[c], s_b[c])); }
     tile[ri][wi] = v;
   }
   __syncthreads();
@@ -434,8 +424,8 @@ __global__ __launch_bounds__(256) void inorm_apply_s2d_split_kernel(const float*
       if (ch < C) {
         const float a = s_a[cc], b = s_b[cc];
         const float* src = x + (long long)ch * TPin + (long long)(2 * y) * Wp + 1 + 2 * (xq - 1);
-        v[cc * 4 + 0] = gelu_as(fmaf(src[0], a, b)); v[cc * 4 + 1] = gelu_as(fmaf(src[1], a, b));
-        v[cc * 4 + 2] = gelu_as(fmaf(src[Wp], a, b)); v[cc * 4 + 3] = gelu_as(fmaf(src[Wp + 1], a, b));
+        v[cc * 4 + 0] = gelu_bf(fmaf(src[0], a, b)); v[cc * 4 + 1] = gelu_bf(fmaf(src[1], a, b));
+        v[cc * 4 + 2] = gelu_bf(fmaf(src[Wp], a, b)); v[cc * 4 + 3] = gelu_bf(fmaf(src[Wp + 1], a, b));
       }
     }
   }
@@ -470,7 +460,7 @@ __global__ void tr2d_in_kernel(const float* __restrict__ in, float* __restrict__
   for (int j = threadIdx.y; j < 32; j += blockDim.y) {
     const int r = r0 + j, c = c0 + threadIdx.x;
     float v = 0.f;
-    if (r < R && c < W) { const int ch = r / H; v = gelu_as(fmaf(in[(long long)r * Wp + 1 + c], sc[ch], sh[ch])); }
+    if (r < R && c < W) { const int ch = r / H; v = gelu_bf(fmaf(in[(long long)r * Wp + 1 + c], sc[ch], sh[ch])); }
     tile[j][threadIdx.x] = v;
   }
   __syncthreads();

@@ -1,8 +1,22 @@
-// Launch wrappers of the non-GEMM device ops (ops.hip).
+// Launch wrappers of the non-GEMM device ops (ops.hip), and the two GELU evaluations every kernel file shares.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace rvc {
+
+// exact-erf GELU (torch F.gelu default) through the library's erff: two divergent paths per element - for kernels that are not bound by it
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
+// exact-erf GELU (torch F.gelu default), branch-free: erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7 absolute, i.e. ~1e-7 of the
+// activation - far inside the fp32 noise of the 768-term sums that feed it; ocml's erff takes two divergent paths per element).  What
+// conv_x3s.hip's epilogue, HuBERT's fused layer 0 (ops.hip) and the image producers of model_mdx23.hip evaluate: those run at HBM rate
+// only if the activation stays under ~20 VALU instructions per value.
+__device__ __forceinline__ float gelu_bf(float v) {
+  const float x = v * 0.70710678118654752440f, ax = fabsf(x);
+  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));
+  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
+  const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * x * x);
+  return 0.5f * v * (1.f + copysignf(fmaf(-poly, e, 1.f), x));
+}
 
 // LayerNorm over channels that ALSO writes y as the split-resident image of conv_x3s.hip (y may be null: image only); margin = kSplitMargin
 void wn_gate_split(hipStream_t s, const float* a, const float* g, unsigned char* img, long long tp, int margin, int H, int T);   // WN gate -> split image only

@@ -21,7 +21,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
-__device__ __forceinline__ float gelu_f(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
 
 // ---------------------------------------------------------------------------------------------- LayerNorm over channels
 // y[c][t] = (x[c][t] (+ r[c][t]) - mean_t) * rstd_t * gamma[c] + beta[c];  block = 16 columns x 16 channel slices
@@ -195,7 +194,7 @@ __global__ __launch_bounds__(256) void groupnorm_t_gelu_kernel(float* __restrict
   const double var = (red[0] + red[1] + red[2] + red[3]) / (double)T;
   const float rstd = (float)(1.0 / sqrt(var + (double)eps));
   const float g = gamma[blockIdx.x], b = beta[blockIdx.x], mf = (float)mean;
-  for (int t = tid; t < T; t += 256) row[t] = gelu_f((row[t] - mf) * rstd * g + b);
+  for (int t = tid; t < T; t += 256) row[t] = gelu_erf((row[t] - mf) * rstd * g + b);
 }
 void groupnorm_t_gelu(hipStream_t s, float* x, const float* gamma, const float* beta, int C, int T, long long ld, float eps) {
   hipLaunchKernelGGL(groupnorm_t_gelu_kernel, dim3(C), dim3(256), 0, s, x, gamma, beta, T, ld, eps);
@@ -212,13 +211,6 @@ void groupnorm_t_gelu(hipStream_t s, float* x, const float* gamma, const float* 
 // wave-uniform weights (scalar loads).
 constexpr int kC0T = 1024, kC0C = 64, kC0K = 10, kC0S = 5;
 constexpr int kC0ST = 512;                                  // positions per statistics tile
-__device__ __forceinline__ float gelu_bf(float v) {        // exact-erf GELU, branch-free (Abramowitz & Stegun 7.1.26: |erf error| <= 1.5e-7)
-  const float x = v * 0.70710678118654752440f, ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-  const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * x * x);
-  return 0.5f * v * (1.f + copysignf(fmaf(-poly, e, 1.f), x));
-}
 // Statistics pass: a thread IS a channel (its 10 weights in registers) and walks the tile's positions - every thread reads the same audio
 // samples (LDS broadcast), so there is no cross-thread reduction at all: partial[tile][c] = {sum, sum of squares} over 512 positions,
 // accumulated in float64 in groups of 8 positions.

@@ -77,3 +77,59 @@ def test_pair_arithmetic_knob():
         e = dict(os.environ); e.pop("RVC_H2", None); e.update(env)
         out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT, env=e)
         assert out.returncode == 0 and out.stdout.strip().splitlines()[-1] == want, (env, out.stdout, out.stderr[-500:])
+
+
+CSRC = os.path.join(ROOT, "comfy-rvc_amd", "csrc")
+PER_FILE_FLAGS = {"attention_dma": "-amdgpu-mfma-vgpr-form=1", "audio_fx": "-ffp-contract=off"}
+
+
+def _compile_commands(*make_args):
+    """{stem: command} of `make -n -B` in csrc/ (nothing is compiled): every compile command names exactly one .hip, every .hip exactly one command."""
+    import subprocess
+    out = subprocess.run(["make", "-n", "-B", "-C", CSRC, *make_args], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-500:]
+    cmds = {}
+    for line in out.stdout.splitlines():
+        if " -c " not in line:
+            continue
+        stems = re.findall(r"(?<![\w/.-])(\w+)\.hip\b", line)
+        assert len(stems) == 1 and stems[0] not in cmds, line
+        cmds[stems[0]] = line
+    present = sorted(f[:-4] for f in os.listdir(CSRC) if f.endswith(".hip"))
+    assert sorted(cmds) == present, (sorted(set(present) - set(cmds)), sorted(set(cmds) - set(present)))
+    return cmds
+
+
+def test_one_source_list_for_the_product_and_the_variant_builds():
+    """csrc/Makefile is the only list of the .hip files and of their per-file flags: the plain build and a VARIANT build compile every .hip of csrc/ exactly
+    once, the variant with -DRVC_EXPERIMENTS and its EXTRA flags into variants/, the plain one with neither; tools/build_variant.sh names no source file."""
+    plain, variant = _compile_commands(), _compile_commands("VARIANT=t", "EXTRA=-DXYZ")
+    for stem in plain:
+        p, v = plain[stem].split(), variant[stem].split()
+        assert "-DRVC_EXPERIMENTS" not in p and "-DXYZ" not in p and not any("variants/" in w for w in p), plain[stem]
+        assert p[p.index("-o") + 1] == stem + ".o"
+        assert "-DRVC_EXPERIMENTS" in v and "-DXYZ" in v and v[v.index("-o") + 1] == f"variants/obj_t/{stem}.o", variant[stem]
+        for cmd in (p, v):
+            for owner, flag in PER_FILE_FLAGS.items():
+                assert (flag in cmd) == (stem == owner), (stem, flag)
+    script = open(os.path.join(ROOT, "tools", "build_variant.sh")).read()
+    assert not [s for s in plain if re.search(rf"\b{s}\b", script)]
+
+
+def test_shared_device_helpers_have_one_definition():
+    """The helpers the kernel files share exist once under csrc/ (comments do not count): the -DRVC_CONV_TIMING conditional (phase_timing.h), the immediate
+    vmcnt wait, the branch-free GELU (by its first constant) and the buffer-to-LDS DMA call."""
+    src = {}
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith((".hip", ".h")):
+            text = open(os.path.join(CSRC, f)).read()
+            src[f] = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    assert len(src) > 30
+
+    def files_with(pattern):
+        return [f for f, t in src.items() if re.search(pattern, t, flags=re.M)]
+
+    assert files_with(r"^[ \t]*#[ \t]*(if|ifdef|ifndef|elif)\b[^\n]*\bRVC_CONV_TIMING\b") == ["phase_timing.h"]
+    assert len(files_with(re.escape("s_waitcnt vmcnt(%0)"))) == 1
+    assert len(files_with(re.escape("0.3275911f"))) == 1
+    assert sum(len(re.findall(r"raw_ptr_buffer_load_lds\s*\(", t)) for t in src.values()) == 1
