@@ -373,10 +373,17 @@ void conv_timing_read(unsigned long long* out8, bool reset) {
     for (int i = 0; i < 8; ++i) out8[i] += t[i];
   }
 }
-float* dev_upload(const float* host, size_t n) {
-  float* d = nullptr;
-  RVC_HIP_CHECK(hipMalloc(&d, (n ? n : 1) * sizeof(float)));
-  if (n) RVC_HIP_CHECK(hipMemcpy(d, host, n * sizeof(float), hipMemcpyHostToDevice));
+void* dev_alloc(size_t bytes) {
+  void* d = nullptr;
+  RVC_HIP_CHECK(hipMalloc(&d, bytes));
+  return d;
+}
+void* dev_upload(const void* host, size_t bytes) {
+  void* d = dev_alloc(bytes ? bytes : sizeof(float));
+  if (bytes) {
+    const hipError_t e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { dev_free(d); RVC_HIP_CHECK(e); }
+  }
   return d;
 }
 void dev_free(void* p) { if (p) (void)hipFree(p); }
@@ -391,40 +398,30 @@ struct ScratchBuf { void* p = nullptr; size_t cap = 0; };
 using ScratchKey = std::tuple<int, hipStream_t, int>;
 std::map<ScratchKey, ScratchBuf>& scratch_pool() { static std::map<ScratchKey, ScratchBuf> pool; return pool; }
 std::mutex& scratch_mu() { static std::mutex mu; return mu; }
-}  // namespace
-void* stream_scratch(hipStream_t s, int slot, size_t bytes) {
+struct Scratch { void* p; bool grew; };
+// the buffer of (current device, s, slot) holding at least `bytes`; when it has to be (re)allocated it gets `grow_to` bytes (the caller's growth rule)
+Scratch scratch_get(hipStream_t s, int slot, size_t bytes, size_t grow_to) {
   int dev = 0;
   RVC_HIP_CHECK(hipGetDevice(&dev));
   ScratchBuf* b;
   { std::lock_guard<std::mutex> lk(scratch_mu()); b = &scratch_pool()[ScratchKey{dev, s, slot}]; }   // (std::map nodes are address-stable)
-  if (bytes > b->cap) {
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-    if (b->p) (void)hipFree(b->p);
-    b->p = nullptr; b->cap = 0;
-    const size_t want = bytes + bytes / 4 + (1 << 20);
-    RVC_HIP_CHECK(hipMalloc(&b->p, want));
-    b->cap = want;
-  }
-  return b->p;
+  if (bytes <= b->cap) return {b->p, false};
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  if (b->p) (void)hipFree(b->p);
+  b->p = nullptr; b->cap = 0;
+  RVC_HIP_CHECK(hipMalloc(&b->p, grow_to));
+  b->cap = grow_to;
+  return {b->p, true};
 }
-// Same pool; the buffer is zero-filled (on `s`, ahead of whatever the caller enqueues next) whenever it is (re)allocated, never otherwise:
+}  // namespace
+void* stream_scratch(hipStream_t s, int slot, size_t bytes) { return scratch_get(s, slot, bytes, bytes + bytes / 4 + (1 << 20)).p; }   // grows with headroom
+// Same pool; sized exactly and zero-filled (on `s`, ahead of whatever the caller enqueues next) whenever it is (re)allocated, never otherwise:
 // for words whose users leave them zero (the K-split tickets of conv_x3s_kernel).
 void* stream_scratch_zeroed(hipStream_t s, int slot, size_t bytes, bool* fresh) {
-  int dev = 0;
-  RVC_HIP_CHECK(hipGetDevice(&dev));
-  ScratchBuf* b;
-  { std::lock_guard<std::mutex> lk(scratch_mu()); b = &scratch_pool()[ScratchKey{dev, s, slot}]; }
-  if (fresh) *fresh = false;
-  if (bytes > b->cap) {
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-    if (b->p) (void)hipFree(b->p);
-    b->p = nullptr; b->cap = 0;
-    RVC_HIP_CHECK(hipMalloc(&b->p, bytes));
-    b->cap = bytes;
-    RVC_HIP_CHECK(hipMemsetAsync(b->p, 0, bytes, s));
-    if (fresh) *fresh = true;
-  }
-  return b->p;
+  const Scratch r = scratch_get(s, slot, bytes, bytes);
+  if (r.grew) RVC_HIP_CHECK(hipMemsetAsync(r.p, 0, bytes, s));
+  if (fresh) *fresh = r.grew;
+  return r.p;
 }
 void stream_scratch_release(int device) {
   std::lock_guard<std::mutex> lk(scratch_mu());
@@ -455,8 +452,6 @@ static void upload_layer(ConvLayer& L, const std::vector<float>& packed, const f
   L.Wd_ = dev_upload(packed.data(), packed.size());
   L.bd_ = bias ? dev_upload(bias, nbias) : nullptr;
 }
-
-void conv_layer_free(ConvLayer& L) { dev_free(L.Wd_); dev_free(L.bd_); dev_free(L.Wx_); dev_free(L.Wh_); dev_free(L.bd4_); L.Wd_ = L.bd_ = L.bd4_ = nullptr; L.Wx_ = L.Wh_ = nullptr; }
 
 // bf16x3 weight image (conv_x3.hip): every fp32 weight is split w = hi + lo (both bf16, round-to-nearest-even) and stored
 // [16-channel chunk][tap][hi|lo][8-channel half][CoPx rows][8 channels]: 16-B rows per half-plane, which is the layout the kernel

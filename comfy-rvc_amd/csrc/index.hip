@@ -18,16 +18,16 @@ namespace rvc {
 struct FeatIndex {
   Ctx* ctx = nullptr;
   long long N = 0; int D = 0;
-  float* rows = nullptr;      // big_npy [N][D] (gather source for the blend)
-  float* cols = nullptr;      // big_npy^T [D][N] (k-major GEMM operand)
-  float* nhalf = nullptr;     // -|b_j|^2 / 2
+  DevBuf<float> rows;         // big_npy [N][D] (gather source for the blend)
+  DevBuf<float> cols;         // big_npy^T [D][N] (k-major GEMM operand)
+  DevBuf<float> nhalf;        // -|b_j|^2 / 2
   // per 32768-row chunk: the rows as a k = 1 convolution layer (score = W f + bias) - on the bf16x3 kernel for large indices
   // (3-term split, fp32 accumulation: scores to ~1e-5 relative, i.e. ties closer than that may resolve to the other neighbour;
   // the reference's own IVF search with nprobe = 1 is far coarser), on the fp32 kernel for small ones
-  std::vector<ConvLayer> chunks;
+  std::vector<OwnedConvLayer> chunks;
   // IVF probe (nlist > 0): centroids as the k-major GEMM operand [D][nlist], -|c|^2/2, the list every row was added to
   int nlist = 0, nprobe = 0;
-  float* cen_cols = nullptr; float* cen_nhalf = nullptr; int* list_of = nullptr;
+  DevBuf<float> cen_cols, cen_nhalf; DevBuf<int> list_of;
 };
 
 __global__ void index_prep_kernel(const float* __restrict__ rows, float* __restrict__ cols, float* __restrict__ nhalf, long long N, int D) {
@@ -132,61 +132,47 @@ __global__ void index_blend_kernel(const float* __restrict__ f, const float* __r
 
 FeatIndex* index_create(Ctx* ctx, const float* big_npy, long long N, int D) {
   RVC_REQUIRE(big_npy && N > 0 && D > 0 && D <= 4096, "bad index shape");
-  FeatIndex* I = new FeatIndex(); I->ctx = ctx; I->N = N; I->D = D;
-  try {
-    RVC_HIP_CHECK(hipMalloc(&I->rows, (size_t)N * D * sizeof(float)));
-    RVC_HIP_CHECK(hipMalloc(&I->cols, (size_t)N * D * sizeof(float)));
-    RVC_HIP_CHECK(hipMalloc(&I->nhalf, (size_t)N * sizeof(float)));
-    RVC_HIP_CHECK(hipMemcpy(I->rows, big_npy, (size_t)N * D * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(index_prep_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, I->rows, I->cols, I->nhalf, N, D);
-    RVC_HIP_CHECK(hipDeviceSynchronize());
-    if (D % 16 == 0 && N >= 4096) {
-      std::vector<float> nh((size_t)N);
-      RVC_HIP_CHECK(hipMemcpy(nh.data(), I->nhalf, (size_t)N * sizeof(float), hipMemcpyDeviceToHost));   // the same bias values as the fp32 path
-      ConvBuildScope x3scope(ctx->precision);
-      const long long chunk = 32768;
-      I->chunks.resize((size_t)((N + chunk - 1) / chunk));
-      for (size_t c = 0; c < I->chunks.size(); ++c) {
-        const long long m0 = (long long)c * chunk;
-        const int M = (int)((N - m0) < chunk ? (N - m0) : chunk);
-        conv1d_layer_init(I->chunks[c], big_npy + m0 * D, nh.data() + m0, M, D, 1, 1, 0, 1, 1);
-      }
-      dev_free(I->cols); I->cols = nullptr;             // the k-major copy is only needed by the GEMM path
+  std::unique_ptr<FeatIndex> I(new FeatIndex()); I->ctx = ctx; I->N = N; I->D = D;
+  I->rows.alloc((size_t)N * D);
+  I->cols.alloc((size_t)N * D);
+  I->nhalf.alloc((size_t)N);
+  RVC_HIP_CHECK(hipMemcpy(I->rows.p, big_npy, (size_t)N * D * sizeof(float), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(index_prep_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, I->rows.p, I->cols.p, I->nhalf.p, N, D);
+  RVC_HIP_CHECK(hipDeviceSynchronize());
+  if (D % 16 == 0 && N >= 4096) {
+    std::vector<float> nh((size_t)N);
+    RVC_HIP_CHECK(hipMemcpy(nh.data(), I->nhalf.p, (size_t)N * sizeof(float), hipMemcpyDeviceToHost));   // the same bias values as the fp32 path
+    ConvBuildScope x3scope(ctx->precision);
+    const long long chunk = 32768;
+    I->chunks.resize((size_t)((N + chunk - 1) / chunk));
+    for (size_t c = 0; c < I->chunks.size(); ++c) {
+      const long long m0 = (long long)c * chunk;
+      const int M = (int)((N - m0) < chunk ? (N - m0) : chunk);
+      conv1d_layer_init(I->chunks[c], big_npy + m0 * D, nh.data() + m0, M, D, 1, 1, 0, 1, 1);
     }
-  } catch (...) { for (auto& L : I->chunks) conv_layer_free(L); dev_free(I->rows); dev_free(I->cols); dev_free(I->nhalf); delete I; throw; }
-  return I;
+    I->cols.reset();             // the k-major copy is only needed by the GEMM path
+  }
+  return I.release();
 }
 FeatIndex* index_create_ivf(Ctx* ctx, const float* big_npy, long long N, int D, const float* centroids, int nlist, const int* list_of, int nprobe) {
   RVC_REQUIRE(centroids && list_of && nlist > 0 && nprobe >= 1, "IVF index: centroids, list assignment, nlist >= 1 and nprobe >= 1 expected");
   RVC_REQUIRE(nprobe <= kMaxProbe || nprobe >= nlist, "IVF index: nprobe up to 16 (or >= nlist, which is the exact search)");
   for (long long j = 0; j < N; ++j) RVC_REQUIRE(list_of[j] >= 0 && list_of[j] < nlist, "IVF index: list assignment out of range");
-  FeatIndex* I = index_create(ctx, big_npy, N, D);
-  if (nprobe >= nlist) return I;                                   // every cell probed: the exact search
-  try {
-    std::vector<float> cc((size_t)D * nlist), nh((size_t)nlist);
-    for (int m = 0; m < nlist; ++m) {
-      float s = 0.f;
-      for (int c = 0; c < D; ++c) { const float v = centroids[(size_t)m * D + c]; cc[(size_t)c * nlist + m] = v; s = fmaf(v, v, s); }
-      nh[m] = -0.5f * s;
-    }
-    RVC_HIP_CHECK(hipMalloc(&I->cen_cols, cc.size() * sizeof(float)));
-    RVC_HIP_CHECK(hipMalloc(&I->cen_nhalf, nh.size() * sizeof(float)));
-    RVC_HIP_CHECK(hipMalloc(&I->list_of, (size_t)N * sizeof(int)));
-    RVC_HIP_CHECK(hipMemcpy(I->cen_cols, cc.data(), cc.size() * sizeof(float), hipMemcpyHostToDevice));
-    RVC_HIP_CHECK(hipMemcpy(I->cen_nhalf, nh.data(), nh.size() * sizeof(float), hipMemcpyHostToDevice));
-    RVC_HIP_CHECK(hipMemcpy(I->list_of, list_of, (size_t)N * sizeof(int), hipMemcpyHostToDevice));
-    I->nlist = nlist; I->nprobe = nprobe;
-  } catch (...) { index_destroy(I); throw; }
-  return I;
-}
-void index_destroy(FeatIndex* I) {
-  if (I) {
-    for (auto& L : I->chunks) conv_layer_free(L);
-    dev_free(I->rows); dev_free(I->cols); dev_free(I->nhalf); dev_free(I->cen_cols); dev_free(I->cen_nhalf);
-    if (I->list_of) (void)hipFree(I->list_of);
-    delete I;
+  std::unique_ptr<FeatIndex> I(index_create(ctx, big_npy, N, D));
+  if (nprobe >= nlist) return I.release();                         // every cell probed: the exact search
+  std::vector<float> cc((size_t)D * nlist), nh((size_t)nlist);
+  for (int m = 0; m < nlist; ++m) {
+    float s = 0.f;
+    for (int c = 0; c < D; ++c) { const float v = centroids[(size_t)m * D + c]; cc[(size_t)c * nlist + m] = v; s = fmaf(v, v, s); }
+    nh[m] = -0.5f * s;
   }
+  I->cen_cols.upload(cc);
+  I->cen_nhalf.upload(nh);
+  I->list_of.upload(list_of, (size_t)N);
+  I->nlist = nlist; I->nprobe = nprobe;
+  return I.release();
 }
+void index_destroy(FeatIndex* I) { delete I; }
 int index_nprobe(const FeatIndex* I) { return I->nlist > 0 ? I->nprobe : 0; }
 long long index_size(const FeatIndex* I) { return I->N; }
 int index_dim(const FeatIndex* I) { return I->D; }
@@ -204,22 +190,22 @@ void index_search(FeatIndex* I, hipStream_t s, const float* feats_cm, int T, lon
   ConvEpilogue E0;
   if (ivf) {
     // coarse quantiser (IndexFlatL2 over the centroids), fp32
-    gemm_tn_run(s, I->cen_cols, I->nlist, 0, feats_cm, T, 0, Y, T, 0, I->nlist, T, I->D, 1, I->cen_nhalf, 0, E0);
+    gemm_tn_run(s, I->cen_cols.p, I->nlist, 0, feats_cm, T, 0, Y, T, 0, I->nlist, T, I->D, 1, I->cen_nhalf.p, 0, E0);
     hipLaunchKernelGGL(index_topk_kernel, dim3((T + 127) / 128), dim3(128), 0, s, Y, I->nlist, T, I->nprobe, cells);
   }
   for (long long m0 = 0; m0 < I->N; m0 += chunk) {
     const int M = (int)((I->N - m0) < chunk ? (I->N - m0) : chunk);
     if (!I->chunks.empty()) conv1d_run(I->chunks[(size_t)(m0 / chunk)], s, feats_cm, T, T, Y, T, E0);
-    else gemm_tn_run(s, I->cols + m0, I->N, 0, feats_cm, T, 0, Y, T, 0, M, T, I->D, 1, I->nhalf + m0, 0, E0);
+    else gemm_tn_run(s, I->cols.p + m0, I->N, 0, feats_cm, T, 0, Y, T, 0, M, T, I->D, 1, I->nhalf.p + m0, 0, E0);
     hipLaunchKernelGGL(index_argmax_kernel, dim3((T + 63) / 64), dim3(1024), 0, s, Y, M, T, (long long)T, m0, best, idx, m0 == 0 ? 1 : 0,
-                       ivf ? I->list_of : nullptr, cells, ivf ? I->nprobe : 0);
+                       ivf ? I->list_of.p : nullptr, cells, ivf ? I->nprobe : 0);
   }
-  if (score) hipLaunchKernelGGL(index_score_kernel, dim3((T + 63) / 64), dim3(64), 0, s, feats_cm, I->rows, idx, score, I->D, T, I->N);
+  if (score) hipLaunchKernelGGL(index_score_kernel, dim3((T + 63) / 64), dim3(64), 0, s, feats_cm, I->rows.p, idx, score, I->D, T, I->N);
 }
 
 void index_blend(FeatIndex* I, hipStream_t s, const float* feats_cm, const long long* idx, int T, float rate, float* out_cm) {
   const long long n = (long long)I->D * T; int blocks = (int)((n + 255) / 256); if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(index_blend_kernel, dim3(blocks), dim3(256), 0, s, feats_cm, I->rows, idx, rate, out_cm, I->D, T, I->N);
+  hipLaunchKernelGGL(index_blend_kernel, dim3(blocks), dim3(256), 0, s, feats_cm, I->rows.p, idx, rate, out_cm, I->D, T, I->N);
 }
 
 }  // namespace rvc

@@ -43,16 +43,10 @@ struct Ctx {
   size_t workspace_bytes = 0;   // sum of the model arenas (informational)
   int precision = -1;           // conv arithmetic of the models built on this context: 0 fp32 MFMA only, 1 / 2 bf16x3 split where eligible,
                                 // -1 (default): the mode of the thread that finalizes the model (rvc_set_conv_precision, default 1)
-  struct SpecState* spec = nullptr;   // FFT tables per n_fft and mel filterbanks per (n_fft, n_mels), made on first use (spectrogram.hip); spec_state_free
+  struct SpecState* spec = nullptr;   // FFT tables per n_fft and mel filterbanks per (n_fft, n_mels), made on first use (spectrogram.hip); freed by spec_state_free
 };
 
-// device vector owned by a model
-struct DevVec {
-  float* p = nullptr; size_t n = 0;
-  void upload(const std::vector<float>& h) { dev_free(p); p = dev_upload(h.data(), h.size()); n = h.size(); }
-  void upload(const float* h, size_t cnt) { dev_free(p); p = dev_upload(h, cnt); n = cnt; }
-  void free_() { dev_free(p); p = nullptr; n = 0; }
-};
+using DevVec = DevBuf<float>;   // device vector owned by a model
 
 inline std::vector<float> transpose2d(const float* w, int R, int C) {   // [R][C] -> [C][R]
   std::vector<float> o((size_t)R * C);

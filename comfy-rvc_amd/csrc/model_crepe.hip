@@ -15,15 +15,17 @@
 
 namespace rvc {
 
-struct Crepe {
+struct CrepeWeights {            // what crepe_finalize builds
+  OwnedConvLayer conv[6], fc;
+  OwnedConvLayer gemm[6];        // layers 5 and 6 (L = 16, 8 positions per frame) as GEMMs over an explicit im2col (K = 64 C_in)
+  DevVec bn_a[6], bn_b[6];       // BatchNorm folded to y = a * x + b (applied after the ReLU, before the max-pool)
+};
+struct Crepe : CrepeWeights {
   Ctx* ctx = nullptr;
   Arena arena;
   TensorStore ts;
   bool ready = false, tiny = false;
   int ch[6] = {1024, 128, 128, 128, 256, 512};
-  ConvLayer conv[6], fc;
-  ConvLayer gemm[6];             // layers 5 and 6 (L = 16, 8 positions per frame) as GEMMs over an explicit im2col (K = 64 C_in)
-  DevVec bn_a[6], bn_b[6];       // BatchNorm folded to y = a * x + b (applied after the ReLU, before the max-pool)
 };
 
 static const int kCrepeFull[6] = {1024, 128, 128, 128, 256, 512};
@@ -35,15 +37,11 @@ Crepe* crepe_create(Ctx* ctx, int tiny) {
   return M;
 }
 void crepe_set_tensor(Crepe* M, const char* name, const float* d, const long long* shape, int ndim) { M->ts.set(name, d, shape, ndim); }
-static void crepe_free(Crepe& M) {
-  for (int i = 0; i < 6; ++i) { conv_layer_free(M.conv[i]); conv_layer_free(M.gemm[i]); M.bn_a[i].free_(); M.bn_b[i].free_(); }
-  conv_layer_free(M.fc);
-}
-void crepe_destroy(Crepe* M) { if (M) { crepe_free(*M); M->arena.release(); delete M; } }
+void crepe_destroy(Crepe* M) { delete M; }
 
 void crepe_finalize(Crepe* M) {
+  M->ready = false; static_cast<CrepeWeights&>(*M) = {};   // a finalize that throws leaves the handle not ready
   const TensorStore& ts = M->ts;
-  crepe_free(*M);
   ConvBuildScope x3scope(M->ctx->precision);
   int cin = 1;
   for (int i = 0; i < 6; ++i) {

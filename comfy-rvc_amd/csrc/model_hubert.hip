@@ -7,23 +7,25 @@
 namespace rvc {
 
 struct HubLayer {
-  ConvLayer qk;        // fused q (pre-scaled by head_dim^-0.5) and k projections: 768 -> 1536
+  OwnedConvLayer qk;   // fused q (pre-scaled by head_dim^-0.5) and k projections: 768 -> 1536
   DevVec bv;           // v projection bias, added after P.V (softmax rows sum to 1); the v rows are part of the qk layer (768 -> 2304)
-  ConvLayer o, ff1, ff2;
+  OwnedConvLayer o, ff1, ff2;
   DevVec g1, b1, g2, b2;
 };
 
-struct Hubert {
+struct HubertWeights {   // what hubert_finalize builds, and what the graph has learnt about it
+  const void* img_base = nullptr; unsigned img_gen = 0; size_t img_bytes = 0; int img_T = -1;   // image of the positional convolution's input: margins known to be zero
+  OwnedConvLayer conv[7];
+  DevVec gn_g, gn_b, fp_g, fp_b, enc_g, enc_b;
+  DevVec w0;            // conv_layers.0 raw [512][10]: the fused conv0 + GroupNorm + GELU kernels evaluate it from the audio
+  OwnedConvLayer proj, pos, final_proj;
+  std::vector<HubLayer> layers;
+};
+struct Hubert : HubertWeights {
   Ctx* ctx = nullptr;
   Arena arena;
   TensorStore ts;
   bool ready = false;
-  const void* img_base = nullptr; unsigned img_gen = 0; size_t img_bytes = 0; int img_T = -1;   // image of the positional convolution's input: margins known to be zero
-  ConvLayer conv[7];
-  DevVec gn_g, gn_b, fp_g, fp_b, enc_g, enc_b;
-  DevVec w0;            // conv_layers.0 raw [512][10]: the fused conv0 + GroupNorm + GELU kernels evaluate it from the audio
-  ConvLayer proj, pos, final_proj;
-  std::vector<HubLayer> layers;
 };
 
 static const int kKern[7] = {10, 3, 3, 3, 3, 2, 2};
@@ -38,23 +40,15 @@ long long hubert_num_frames(long long L) {
 Hubert* hubert_create(Ctx* ctx) { Hubert* H = new Hubert(); H->ctx = ctx; return H; }
 void hubert_set_tensor(Hubert* H, const char* name, const float* d, const long long* shape, int ndim) { H->ts.set(name, d, shape, ndim); }
 
-static void hubert_free(Hubert& H) {
-  for (auto& c : H.conv) conv_layer_free(c);
-  H.w0.free_(); H.gn_g.free_(); H.gn_b.free_(); H.fp_g.free_(); H.fp_b.free_(); H.enc_g.free_(); H.enc_b.free_();
-  conv_layer_free(H.proj); conv_layer_free(H.pos); conv_layer_free(H.final_proj);
-  for (auto& l : H.layers) { conv_layer_free(l.qk); l.bv.free_(); conv_layer_free(l.o); conv_layer_free(l.ff1); conv_layer_free(l.ff2); l.g1.free_(); l.b1.free_(); l.g2.free_(); l.b2.free_(); }
-  H.layers.clear();
-  H.img_base = nullptr; H.img_gen = 0; H.img_bytes = 0; H.img_T = -1;
-}
-void hubert_destroy(Hubert* H) { if (H) { hubert_free(*H); H->arena.release(); delete H; } }
+void hubert_destroy(Hubert* H) { delete H; }
 
 static void linear_layer(ConvLayer& L, const TensorStore& ts, const std::string& p, int out, int in) {
   conv1d_layer_init(L, ts.get(p + ".weight", {out, in}).data.data(), ts.get(p + ".bias", {out}).data.data(), out, in, 1, 1, 0, 1, 1);
 }
 
 void hubert_finalize(Hubert* H) {
+  H->ready = false; static_cast<HubertWeights&>(*H) = {};   // a finalize that throws leaves the handle not ready
   const TensorStore& ts = H->ts;
-  hubert_free(*H);
   // the k = 1 projections (feature projection, q/k, out, feed-forward, final_proj) also get a bf16x3 split weight image
   // (conv_x3.hip); strided / grouped convolutions and the activation x activation products of attention stay on the fp32 kernel
   ConvBuildScope x3scope(H->ctx->precision);

@@ -24,31 +24,45 @@ namespace rvc {
 struct TfcBlock {
   int in_c = 0, c = 0, f = 0;
   DevVec n1g, n1b, t0g, t0b, t3g, t3b, n2g, n2b;
-  ConvLayer tfc1, tfc2, shortcut, lin1, lin2;
+  OwnedConvLayer tfc1, tfc2, shortcut, lin1, lin2;
   bool fused_sc = false;    // padded graph: the shortcut's weight image is appended to tfc2's - tfc2(x2) + shortcut(x) is ONE product over two images
 };
 struct MdxScale {
   std::vector<TfcBlock> blocks;
   DevVec ng, nb;            // norm in front of the down / up convolution
-  ConvLayer rs;             // the 2x2 stride-2 (transposed) convolution as a k = 1 GEMM over re-arranged data
+  OwnedConvLayer rs;        // the 2x2 stride-2 (transposed) convolution as a k = 1 GEMM over re-arranged data
 };
-struct Mdx23 {
-  Ctx* ctx = nullptr;
-  // activations: one arena (+ the "images are zeroed" record) per chunk stream.  Lane 0 runs on the caller's stream; demix may alternate a clip's chunks over further
-  // lanes with streams of their own (they are independent until the overlap-add): the small launches of the deep levels of one chunk run beside the chip-filling ones of another
-  static constexpr int kMaxLanes = 4;
-  struct Lane { Arena arena; const char* img_base = nullptr; size_t img_bytes = 0; unsigned img_gen = 0; hipStream_t st = nullptr; hipEvent_t done = nullptr; float* acc = nullptr; size_t acc_n = 0; };
-  Lane lane[kMaxLanes];
-  hipEvent_t ev_start = nullptr;
-  int streams = 0;                           // chunk streams of demix (0: RVC_MDX_STREAMS or 1), mdx23_set_streams
-  TensorStore ts;
-  bool ready = false;
-  rvc_mdx23_config cfg{};
-  ConvLayer stft, istft, first, fin0, fin2;
+struct Mdx23Weights {   // what mdx23_finalize builds
+  OwnedConvLayer stft, istft, first, fin0, fin2;
   DevVec window;
   std::vector<MdxScale> enc, dec;
   MdxScale bott;
   bool pad_ok = false;                       // every 3x3 / 2x2 layer has its bf16x3 image: the padded split-resident graph (mdx23_graph_padded)
+};
+struct Mdx23 : Mdx23Weights {
+  Ctx* ctx = nullptr;
+  // activations: one arena (+ the "images are zeroed" record) per chunk stream.  Lane 0 runs on the caller's stream; demix may alternate a clip's chunks over further
+  // lanes with streams of their own (they are independent until the overlap-add): the small launches of the deep levels of one chunk run beside the chip-filling ones of another
+  static constexpr int kMaxLanes = 4;
+  struct Lane {
+    Arena arena; const char* img_base = nullptr; size_t img_bytes = 0; unsigned img_gen = 0; hipStream_t st = nullptr; hipEvent_t done = nullptr; DevBuf<float> acc;
+    Lane() = default;
+    ~Lane() {      // the stream's work is waited for before the stream, the accumulator and the arena go
+      if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+      if (done) (void)hipEventDestroy(done);
+    }
+  };
+  struct Event {      // declared ahead of the lanes: destroyed after their streams have been waited for and destroyed
+    hipEvent_t e = nullptr;
+    Event() = default;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    Event(const Event&) = delete; Event& operator=(const Event&) = delete;
+  } ev_start;
+  Lane lane[kMaxLanes];
+  int streams = 0;                           // chunk streams of demix (0: RVC_MDX_STREAMS or 1), mdx23_set_streams
+  TensorStore ts;
+  bool ready = false;
+  rvc_mdx23_config cfg{};
 };
 
 Mdx23* mdx23_create(Ctx* ctx, const rvc_mdx23_config& c) {
@@ -61,31 +75,7 @@ Mdx23* mdx23_create(Ctx* ctx, const rvc_mdx23_config& c) {
 }
 void mdx23_set_tensor(Mdx23* M, const char* name, const float* d, const long long* shape, int ndim) { M->ts.set(name, d, shape, ndim); }
 
-static void tfc_free(TfcBlock& b) {
-  b.n1g.free_(); b.n1b.free_(); b.t0g.free_(); b.t0b.free_(); b.t3g.free_(); b.t3b.free_(); b.n2g.free_(); b.n2b.free_();
-  conv_layer_free(b.tfc1); conv_layer_free(b.tfc2); conv_layer_free(b.shortcut); conv_layer_free(b.lin1); conv_layer_free(b.lin2);
-}
-static void scale_free(MdxScale& s) { for (auto& b : s.blocks) tfc_free(b); s.blocks.clear(); s.ng.free_(); s.nb.free_(); conv_layer_free(s.rs); }
-static void mdx23_free(Mdx23& M) {
-  conv_layer_free(M.stft); conv_layer_free(M.istft); conv_layer_free(M.first); conv_layer_free(M.fin0); conv_layer_free(M.fin2);
-  M.window.free_();
-  for (auto& s : M.enc) scale_free(s);
-  for (auto& s : M.dec) scale_free(s);
-  scale_free(M.bott);
-  M.enc.clear(); M.dec.clear();
-}
-void mdx23_destroy(Mdx23* M) {
-  if (!M) return;
-  mdx23_free(*M);
-  for (auto& Ln : M->lane) {
-    if (Ln.st) { (void)hipStreamSynchronize(Ln.st); (void)hipStreamDestroy(Ln.st); }
-    if (Ln.done) (void)hipEventDestroy(Ln.done);
-    if (Ln.acc) (void)hipFree(Ln.acc);
-    Ln.arena.release();
-  }
-  if (M->ev_start) (void)hipEventDestroy(M->ev_start);
-  delete M;
-}
+void mdx23_destroy(Mdx23* M) { delete M; }
 
 static void make_tfc(std::vector<TfcBlock>& out, const TensorStore& ts, const std::string& prefix, int in_c, int c, int f, int l, int bn) {
   out.resize((size_t)l);
@@ -107,9 +97,9 @@ static void make_tfc(std::vector<TfcBlock>& out, const TensorStore& ts, const st
 }
 
 void mdx23_finalize(Mdx23* M) {
+  M->ready = false; static_cast<Mdx23Weights&>(*M) = {};   // a finalize that throws leaves the handle not ready
   const TensorStore& ts = M->ts;
   const rvc_mdx23_config& c = M->cfg;
-  mdx23_free(*M);
   ConvBuildScope x3scope(M->ctx->precision);
   const int k = c.num_subbands, dim_c = k * c.audio_channels * 2, n = c.num_scales, l = c.blocks_per_scale, g = c.growth, bn = c.bottleneck;
   conv1d_layer_init(M->stft, ts.get("stft.basis", {2 * c.dim_f, c.n_fft}).data.data(), nullptr, 2 * c.dim_f, c.n_fft, 1, 1, 0, 1, 1);
@@ -870,20 +860,20 @@ void mdx23_demix(Mdx23* M, hipStream_t s, const float* mix, long long Lp, long l
   const size_t n = (size_t)M->cfg.num_targets * 2 * (size_t)Lp;
   RVC_HIP_CHECK(hipMemsetAsync(acc, 0, n * sizeof(float), s));
   if (K > 1) {
-    if (!M->ev_start) RVC_HIP_CHECK(hipEventCreateWithFlags(&M->ev_start, hipEventDisableTiming));
-    RVC_HIP_CHECK(hipEventRecord(M->ev_start, s));
+    if (!M->ev_start.e) RVC_HIP_CHECK(hipEventCreateWithFlags(&M->ev_start.e, hipEventDisableTiming));
+    RVC_HIP_CHECK(hipEventRecord(M->ev_start.e, s));
     for (int k = 1; k < K; ++k) {
       Mdx23::Lane& Ln = M->lane[k];
       if (!Ln.st) { RVC_HIP_CHECK(hipStreamCreateWithFlags(&Ln.st, hipStreamNonBlocking)); RVC_HIP_CHECK(hipEventCreateWithFlags(&Ln.done, hipEventDisableTiming)); }
-      if (Ln.acc_n < n) { if (Ln.acc) (void)hipFree(Ln.acc); Ln.acc = nullptr; Ln.acc_n = 0; RVC_HIP_CHECK(hipMalloc(&Ln.acc, n * sizeof(float))); Ln.acc_n = n; }
-      RVC_HIP_CHECK(hipStreamWaitEvent(Ln.st, M->ev_start, 0));          // (the mix is ready, the previous call's reads of this lane's accumulator are behind us)
-      RVC_HIP_CHECK(hipMemsetAsync(Ln.acc, 0, n * sizeof(float), Ln.st));
+      if (Ln.acc.n < n) Ln.acc.alloc(n);
+      RVC_HIP_CHECK(hipStreamWaitEvent(Ln.st, M->ev_start.e, 0));          // (the mix is ready, the previous call's reads of this lane's accumulator are behind us)
+      RVC_HIP_CHECK(hipMemsetAsync(Ln.acc.p, 0, n * sizeof(float), Ln.st));
     }
   }
   try {
     for (long long c = 0; c < n_chunks; ++c) {
       const int k = (int)(c % K);
-      mdx23_chunk(M, k, k == 0 ? s : M->lane[k].st, mix + c * step, C, (k == 0 ? acc : M->lane[k].acc) + c * step, MdxIO{Lp, Lp, 1});
+      mdx23_chunk(M, k, k == 0 ? s : M->lane[k].st, mix + c * step, C, (k == 0 ? acc : M->lane[k].acc.p) + c * step, MdxIO{Lp, Lp, 1});
     }
   } catch (...) {
     // a chunk failed to enqueue: the lane streams may still be reading `mix` / writing their accumulators - the caller's stream waits for them before the
@@ -894,7 +884,7 @@ void mdx23_demix(Mdx23* M, hipStream_t s, const float* mix, long long Lp, long l
   }
   for (int k = 1; k < K; ++k) {
     RVC_HIP_CHECK(hipEventRecord(M->lane[k].done, M->lane[k].st)); RVC_HIP_CHECK(hipStreamWaitEvent(s, M->lane[k].done, 0));
-    hipLaunchKernelGGL(add_kernel, dim3(gridn((long long)n)), dim3(256), 0, s, acc, M->lane[k].acc, (long long)n);
+    hipLaunchKernelGGL(add_kernel, dim3(gridn((long long)n)), dim3(256), 0, s, acc, M->lane[k].acc.p, (long long)n);
   }
   hipLaunchKernelGGL(div_kernel, dim3(gridn((long long)n)), dim3(256), 0, s, acc, (long long)n, overlap);
 }

@@ -7,46 +7,35 @@
 namespace rvc {
 
 struct CBR {           // ConvBlockRes with BatchNorm folded into both convs
-  ConvLayer c1, c2, sc; bool has_sc = false; int cin = 0, cout = 0;
-  ConvLayer c1sc;        // shallow levels: first convolution and 1 x 1 shortcut as ONE layer of 2 cout rows (the shortcut's weights at the centre tap) for conv3_small_run
+  OwnedConvLayer c1, c2, sc; bool has_sc = false; int cin = 0, cout = 0;
+  OwnedConvLayer c1sc;   // shallow levels: first convolution and 1 x 1 shortcut as ONE layer of 2 cout rows (the shortcut's weights at the centre tap) for conv3_small_run
 };
-struct Rmvpe {
+struct RmvpeWeights {    // what rmvpe_finalize builds, and what the graph has learnt about it
+  OwnedConvLayer stft, melproj;
+  float bn_a = 1.f, bn_b = 0.f;
+  CBR enc[5][4], inter[4][4], dec[5][4];
+  OwnedConvLayer dect[5];
+  OwnedConvLayer dect_t[4];   // the same transposed convolutions as 2 x 2-tap phase convolutions for the split-resident kernel (input levels 5 .. 2)
+  bool pad_ok = false;     // every layer of levels >= 2 has its bf16x3 image: those levels run on padded split-resident images (conv_x3s.hip)
+  const void* img_base = nullptr; unsigned img_gen = 0; size_t img_bytes = 0; int img_H1 = -1;   // image block whose margins are known to be zero (for this length)
+  OwnedConvLayer cnn;
+  DevVec wihT, b_ih, w_hh, w_hh_t, b_hh;
+  OwnedConvLayer fc;
+  OwnedConvLayer wih;      // GRU input projection [1536][384] (both directions) as a k = 1 layer: its weight image feeds the swapped split-resident product
+  DevBuf<unsigned long long> xbuf; DevBuf<int> gru_err;
+};
+struct Rmvpe : RmvpeWeights {
   Ctx* ctx = nullptr;
   Arena arena;
   TensorStore ts;
   bool ready = false;
-  ConvLayer stft, melproj;
-  float bn_a = 1.f, bn_b = 0.f;
-  CBR enc[5][4], inter[4][4], dec[5][4];
-  ConvLayer dect[5];
-  ConvLayer dect_t[4];     // the same transposed convolutions as 2 x 2-tap phase convolutions for the split-resident kernel (input levels 5 .. 2)
-  bool pad_ok = false;     // every layer of levels >= 2 has its bf16x3 image: those levels run on padded split-resident images (conv_x3s.hip)
-  const void* img_base = nullptr; unsigned img_gen = 0; size_t img_bytes = 0; int img_H1 = -1;   // image block whose margins are known to be zero (for this length)
-  ConvLayer cnn;
-  DevVec wihT, b_ih, w_hh, w_hh_t, b_hh;
-  ConvLayer fc;
-  ConvLayer wih;           // GRU input projection [1536][384] (both directions) as a k = 1 layer: its weight image feeds the swapped split-resident product
-  unsigned long long* xbuf = nullptr; int* gru_err = nullptr;
   int gru_fault = 0; unsigned gru_spin_limit = 0; bool gru_no_repair = false;   // test hooks (rmvpe_debug_fault)
 };
 
 Rmvpe* rmvpe_create(Ctx* ctx) { Rmvpe* R = new Rmvpe(); R->ctx = ctx; return R; }
 void rmvpe_set_tensor(Rmvpe* R, const char* name, const float* d, const long long* shape, int ndim) { R->ts.set(name, d, shape, ndim); }
 
-static void cbr_free(CBR& b) { conv_layer_free(b.c1); conv_layer_free(b.c2); conv_layer_free(b.sc); conv_layer_free(b.c1sc); }
-static void rmvpe_free(Rmvpe& R) {
-  conv_layer_free(R.stft); conv_layer_free(R.melproj);
-  for (auto& l : R.enc) for (auto& b : l) cbr_free(b);
-  for (auto& l : R.inter) for (auto& b : l) cbr_free(b);
-  for (auto& l : R.dec) for (auto& b : l) cbr_free(b);
-  for (auto& c : R.dect) conv_layer_free(c);
-  for (auto& c : R.dect_t) conv_layer_free(c);
-  R.pad_ok = false; R.img_base = nullptr; R.img_gen = 0; R.img_bytes = 0; R.img_H1 = -1;
-  conv_layer_free(R.cnn); conv_layer_free(R.fc); conv_layer_free(R.wih);
-  R.wihT.free_(); R.b_ih.free_(); R.w_hh.free_(); R.w_hh_t.free_(); R.b_hh.free_();
-  dev_free(R.xbuf); dev_free(R.gru_err); R.xbuf = nullptr; R.gru_err = nullptr;
-}
-void rmvpe_destroy(Rmvpe* R) { if (R) { rmvpe_free(*R); R->arena.release(); delete R; } }
+void rmvpe_destroy(Rmvpe* R) { delete R; }
 
 // BatchNorm2d (eval) folded into the preceding bias-free conv: w' = w * g / sqrt(var + eps), b' = beta - mean * g / sqrt(var + eps)
 static void bn_fold(const TensorStore& ts, const std::string& bn, int C, std::vector<float>& scale, std::vector<float>& shift) {
@@ -91,10 +80,10 @@ static void make_cbr(CBR& B, const TensorStore& ts, const std::string& p, int ci
 }
 
 void rmvpe_finalize(Rmvpe* R) {
+  R->ready = false; static_cast<RmvpeWeights&>(*R) = {};   // a finalize that throws leaves the handle not ready
   // 3x3 convolutions with Ci % 16 == 0 also get a bf16x3 split weight image (conv_x3.hip); Ci = 1 / transposed convs stay fp32
   ConvBuildScope x3scope(R->ctx->precision);
   const TensorStore& ts = R->ts;
-  rmvpe_free(*R);
   conv1d_layer_init(R->stft, ts.get("stft.forward_basis", {1026, 1024}).data.data(), nullptr, 1026, 1024, 1, 1, 0, 1, 1);
   conv1d_layer_init(R->melproj, ts.get("mel_basis", {128, 513}).data.data(), nullptr, 128, 513, 1, 1, 0, 1, 1);
   {
@@ -171,9 +160,9 @@ void rmvpe_finalize(Rmvpe* R) {
     for (int i = 0; i < 4; ++i) ok = ok && R->dect_t[i].Wx_ != nullptr && conv_x3s_eligible(R->dect_t[i]);
     R->pad_ok = ok;
   }
-  RVC_HIP_CHECK(hipMalloc(&R->xbuf, sizeof(unsigned long long) * 2 * 2 * 256));
-  RVC_HIP_CHECK(hipMalloc(&R->gru_err, 2 * sizeof(int)));      // [0] hand-off timed out, [1] directions repaired by the serial kernel
-  RVC_HIP_CHECK(hipMemset(R->gru_err, 0, 2 * sizeof(int)));
+  R->xbuf.alloc(2 * 2 * 256);
+  R->gru_err.alloc(2);      // [0] hand-off timed out, [1] directions repaired by the serial kernel
+  RVC_HIP_CHECK(hipMemset(R->gru_err.p, 0, 2 * sizeof(int)));
   R->ts.clear();
   R->ready = true;
 }
@@ -408,12 +397,12 @@ static void rmvpe_graph(Rmvpe* R, hipStream_t s, Arena& A, const float* audio, l
       transpose(s, c3, feat, Tr, 128, 128, Tr, 3, (long long)Tr * 128, 128LL * Tr);           // [c][t][m] -> [c*128+m][t]
       gemm_tn_run(s, feat, Tr, 0, R->wihT.p, 1536, 0, gi, 1536, 0, Tr, 1536, 384, 1, nullptr, 0, E0);
     }
-    gru_scan(s, gi, R->b_ih.p, R->w_hh.p, R->gru_no_repair ? nullptr : R->w_hh_t.p, R->b_hh.p, hid, R->xbuf, R->gru_err, Tr, R->gru_spin_limit, R->gru_fault);
+    gru_scan(s, gi, R->b_ih.p, R->w_hh.p, R->gru_no_repair ? nullptr : R->w_hh_t.p, R->b_hh.p, hid, R->xbuf.p, R->gru_err.p, Tr, R->gru_spin_limit, R->gru_fault);
     if (taps && taps->gru) RVC_HIP_CHECK(hipMemcpyAsync(taps->gru, hid, (size_t)512 * Tr * sizeof(float), hipMemcpyDeviceToDevice, s));
     ConvEpilogue Es; Es.act = ACT_SIGMOID;
     conv1d_run(R->fc, s, hid, Tr, Tr, sal, Tr, Es);
     if (sal_out) transpose(s, sal, sal_out, 360, n, Tr, 360, 1, 0, 0);
-    if (f0_out) rmvpe_decode(s, sal, f0_out, n, Tr, thred, R->gru_err);
+    if (f0_out) rmvpe_decode(s, sal, f0_out, n, Tr, thred, R->gru_err.p);
   }
 }
 
@@ -444,8 +433,8 @@ size_t rmvpe_workspace(const Rmvpe* M) { return M->arena.cap; }
 // 1: timed out and not repaired (f0 is NaN)
 int rmvpe_status(Rmvpe* R, hipStream_t s) {
   int flag[2] = {0, 0};
-  if (!R->gru_err) return 0;
-  RVC_HIP_CHECK(hipMemcpyAsync(flag, R->gru_err, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (!R->gru_err.p) return 0;
+  RVC_HIP_CHECK(hipMemcpyAsync(flag, R->gru_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
   RVC_HIP_CHECK(hipStreamSynchronize(s));
   return flag[0] ? (flag[1] >= 2 ? 2 : 1) : 0;
 }

@@ -8,7 +8,7 @@
 
 namespace rvc {
 
-static ConvLayer make_conv1d(const TensorStore& ts, const std::string& p, int stride, int pad, int dil, bool wn, bool bias = true,
+static OwnedConvLayer make_conv1d(const TensorStore& ts, const std::string& p, int stride, int pad, int dil, bool wn, bool bias = true,
                              float wscale = 1.f, int row0 = 0, int rows = -1) {
   std::vector<float> w; std::vector<long long> shape;
   if (wn) { const HostTensor& v = ts.get(p + ".weight_v"); w = weight_norm0(v, ts.get(p + ".weight_g")); shape = v.shape; }
@@ -23,32 +23,43 @@ static ConvLayer make_conv1d(const TensorStore& ts, const std::string& p, int st
   if (wscale != 1.f) for (auto& x : ws) x *= wscale;
   std::vector<float> bs;
   if (bias) { bs.assign(b.begin() + row0, b.begin() + row0 + rows); if (wscale != 1.f) for (auto& x : bs) x *= wscale; }
-  ConvLayer L;
+  OwnedConvLayer L;
   conv1d_layer_init(L, ws.data(), bias ? bs.data() : nullptr, rows, Ci, k, stride, pad, dil, 1);
   return L;
 }
 
 struct EncLayer {
-  ConvLayer qk;            // fused conv_q (pre-scaled by 1/sqrt(kc)) and conv_k: C -> 2C
+  OwnedConvLayer qk;       // fused conv_q (pre-scaled by 1/sqrt(kc)) and conv_k: C -> 2C
   DevVec bv;               // conv_v's bias, added after P.V; its rows are part of the qk layer (C -> 3 C)
-  ConvLayer relk, relv;    // emb_rel_k as a 21-row projection of Q; emb_rel_v as a 21 -> kc projection of banded P (unfused path)
+  OwnedConvLayer relk, relv;   // emb_rel_k as a 21-row projection of Q; emb_rel_v as a 21 -> kc projection of banded P (unfused path)
   DevVec ek, ev;           // the raw [21][kc] tables: the fused attention kernel does both projections itself
   DevVec rel_img;          // the same tables as the MFMA operand images of attention_split (kc = 96): E_k image, then E_v^T image (bf16 hi / lo)
   size_t evt_off = 0;      // byte offset of the E_v^T image
-  ConvLayer o, ffn1, ffn2;
+  OwnedConvLayer o, ffn1, ffn2;
   DevVec g1, b1, g2, b2;
 };
 struct FlowLayer {
-  ConvLayer pre, post, in[3], res[2], skip[3];
-  ConvLayer in_gate[3];    // in_layers with their 2 H rows in wn_gate_row_order: the gate runs in the split-resident GEMM's epilogue (conv_x3s.hip), the 2 H-row tensor is never stored
-  ConvLayer rs[2];         // res_skip_layers 0 / 1 whole (2 H rows: residual | skip) and
-  ConvLayer post_neg;      // post with negated weights (x1 - m as a plain residual add): the split-resident path (conv_x3s.hip)
+  OwnedConvLayer pre, post, in[3], res[2], skip[3];
+  OwnedConvLayer in_gate[3];   // in_layers with their 2 H rows in wn_gate_row_order: the gate runs in the split-resident GEMM's epilogue (conv_x3s.hip), the 2 H-row tensor is never stored
+  OwnedConvLayer rs[2];    // res_skip_layers 0 / 1 whole (2 H rows: residual | skip) and
+  OwnedConvLayer post_neg; // post with negated weights (x1 - m as a plain residual add): the split-resident path (conv_x3s.hip)
   DevVec cond_w, cond_b;   // weight-normed cond_layer [2*H*3][gin]
 };
-struct ResBlock { ConvLayer c1[3], c2[3]; };
-struct GenStage { ConvLayer up, noise; DevVec noise_w, noise_b; int u = 1, k = 1, noise_k = 1, noise_s = 1; ResBlock rb[3]; };   // noise_w / _b: raw [C][k] / [C] for the streaming kernel (k <= 8)
+struct ResBlock { OwnedConvLayer c1[3], c2[3]; };
+struct GenStage { OwnedConvLayer up, noise; DevVec noise_w, noise_b; int u = 1, k = 1, noise_k = 1, noise_s = 1; ResBlock rb[3]; };   // noise_w / _b: raw [C][k] / [C] for the streaming kernel (k <= 8)
 
-struct Synth {
+struct SynthWeights {    // what synth_finalize builds, and what the graph has learnt about it
+  DevVec emb_phone_wT, emb_phone_b, emb_pitch, emb_g;
+  std::vector<EncLayer> enc;
+  OwnedConvLayer proj;
+  FlowLayer flow[4];
+  OwnedConvLayer conv_pre;
+  DevVec dec_cond_w, dec_cond_b, conv_post_w;   // conv_post_w: raw [Ci][7] weights of the 1-channel output conv (ops.hip::conv_to1)
+  std::vector<GenStage> stages;
+  float lin_w = 1.f, lin_b = 0.f;
+  const void* img_base = nullptr; unsigned img_gen = 0; size_t img_bytes = 0; int img_T = -1, img_W = -1;   // split-resident image block whose margins are known to be zero (synth_graph); img_W: columns of the z image (the generator's window)
+};
+struct Synth : SynthWeights {
   Ctx* ctx = nullptr;
   Arena arena;           // activation workspace (grown on demand between launches)
   TensorStore ts;
@@ -57,31 +68,8 @@ struct Synth {
   int inter = 192, hidden = 192, filt = 768, n_heads = 2, n_layers = 6, ksz = 3, gin = 256, n_spk = 1, sr = 40000, feat_dim = 768;
   int up_init = 512; std::vector<int> rb_k, up_rates, up_k; std::vector<std::vector<int>> rb_d;
   int upp = 1;
-  // weights
-  DevVec emb_phone_wT, emb_phone_b, emb_pitch, emb_g;
-  std::vector<EncLayer> enc;
-  ConvLayer proj;
-  FlowLayer flow[4];
-  ConvLayer conv_pre;
-  DevVec dec_cond_w, dec_cond_b, conv_post_w;   // conv_post_w: raw [Ci][7] weights of the 1-channel output conv (ops.hip::conv_to1)
-  std::vector<GenStage> stages;
-  float lin_w = 1.f, lin_b = 0.f;
-  const void* img_base = nullptr; unsigned img_gen = 0; size_t img_bytes = 0; int img_T = -1, img_W = -1;   // split-resident image block whose margins are known to be zero (synth_graph); img_W: columns of the z image (the generator's window)
   bool f0 = true;        // false: the *_nono family (no pitch embedding, plain Generator: reference models.py:244-311,:812-1022)
 };
-
-static void synth_free(Synth& S) {
-  auto fl = [](ConvLayer& L) { conv_layer_free(L); };
-  S.emb_phone_wT.free_(); S.emb_phone_b.free_(); S.emb_pitch.free_(); S.emb_g.free_();
-  for (auto& e : S.enc) { fl(e.qk); e.bv.free_(); fl(e.relk); fl(e.relv); e.ek.free_(); e.ev.free_(); e.rel_img.free_(); fl(e.o); fl(e.ffn1); fl(e.ffn2); e.g1.free_(); e.b1.free_(); e.g2.free_(); e.b2.free_(); }
-  S.enc.clear();
-  fl(S.proj);
-  for (auto& f : S.flow) { fl(f.pre); fl(f.post); for (auto& c : f.in) fl(c); for (auto& c : f.in_gate) fl(c); for (auto& c : f.res) fl(c); for (auto& c : f.skip) fl(c); for (auto& c : f.rs) fl(c); fl(f.post_neg); f.cond_w.free_(); f.cond_b.free_(); }
-  fl(S.conv_pre); S.dec_cond_w.free_(); S.dec_cond_b.free_(); S.conv_post_w.free_();
-  for (auto& st : S.stages) { fl(st.up); fl(st.noise); st.noise_w.free_(); st.noise_b.free_(); for (auto& rb : st.rb) for (int m = 0; m < 3; ++m) { fl(rb.c1[m]); fl(rb.c2[m]); } }
-  S.stages.clear();
-  S.img_base = nullptr; S.img_gen = 0; S.img_bytes = 0; S.img_T = -1; S.img_W = -1;
-}
 
 Synth* synth_create(Ctx* ctx, const SynthConfig& c) {
   std::unique_ptr<Synth> S(new Synth());
@@ -96,7 +84,7 @@ Synth* synth_create(Ctx* ctx, const SynthConfig& c) {
   RVC_REQUIRE(S->hidden % S->n_heads == 0, "heads must divide hidden");
   return S.release();
 }
-void synth_destroy(Synth* S) { if (S) { synth_free(*S); S->arena.release(); delete S; } }
+void synth_destroy(Synth* S) { delete S; }
 void synth_set_tensor(Synth* S, const char* name, const float* d, const long long* shape, int ndim) { S->ts.set(name, d, shape, ndim); }
 int synth_upp(const Synth* S) { return S->upp; }
 int synth_feat_dim(const Synth* S) { return S->feat_dim; }
@@ -127,8 +115,8 @@ int synth_dec_halo_frames(const Synth* S) {
 }
 
 void synth_finalize(Synth* S) {
+  S->ready = false; static_cast<SynthWeights&>(*S) = {};   // a finalize that throws leaves the handle not ready
   const TensorStore& ts = S->ts;
-  synth_free(*S);
   // every eligible Conv1d (stride 1, groups 1, Ci % 16 == 0) also gets a bf16x3 split weight image: the generator ResBlocks
   // (70 % of a clip's FLOPs), flow WaveNet, enc_p projections; conv_x3.hip, ~1e-5 relative error per layer
   ConvBuildScope x3scope(S->ctx->precision);
@@ -363,7 +351,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
             ConvEpilogue Eqk; Eqk.ys_out = qk_s; Eqk.ys_tp = tp; Eqk.vt_out = vt_s; Eqk.vt_tp = attention_vt_tp(C); Eqk.vt_row0 = 2 * C;
             conv_x3s_run(e.qk, s, x_s, tp, T, nullptr, T, Eqk);
           } else {
-            ConvLayer qkL = e.qk; qkL.Co = 2 * C;                                 // the q and k rows of the 3 C-row projection -> image only
+            ConvLayer qkL = e.qk; qkL.Co = 2 * C;                                 // a VIEW (explicit copy of the owner's base, frees nothing): the q and k rows of the 3 C-row projection -> image only
             ConvEpilogue Eqk; Eqk.ys_out = qk_s; Eqk.ys_tp = tp;
             conv_x3s_run(qkL, s, x_s, tp, T, nullptr, T, Eqk);
             conv_x3s_run_swapped(e.qk, 2 * C, C, s, x_s, tp, T, vt_s, attention_vt_tp(C));

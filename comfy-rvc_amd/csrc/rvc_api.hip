@@ -16,7 +16,7 @@ static std::map<int, int> g_ctx_count;       // live contexts per device (the pe
 struct rvc_hubert { Hubert* m; rvc_ctx* ctx; };
 struct rvc_rmvpe { Rmvpe* m; rvc_ctx* ctx; };
 struct rvc_synth { Synth* m; rvc_ctx* ctx; };
-struct rvc_conv1d_plan { ConvLayer L; };
+struct rvc_conv1d_plan { OwnedConvLayer L; };
 
 #define RVC_TRY try {
 #define RVC_CATCH                                                            \
@@ -24,6 +24,44 @@ struct rvc_conv1d_plan { ConvLayer L; };
   }                                                                          \
   catch (const std::exception& e) { rvc::set_error(e.what()); return 1; }    \
   catch (...) { rvc::set_error("unknown error"); return 2; }
+
+// tests / benchmarks: the forced K split / tile (conv_x3s_force) and key split (attention_split_force_kz) of the calling thread last for one scope
+struct X3sForceScope {
+  X3sForceScope(int ksplit, int am, int an) { conv_x3s_force(ksplit, am, an); }
+  ~X3sForceScope() { conv_x3s_force(0, 0, 0); }
+  X3sForceScope(const X3sForceScope&) = delete; X3sForceScope& operator=(const X3sForceScope&) = delete;
+};
+struct AttentionKzScope {
+  explicit AttentionKzScope(int kz) { attention_split_force_kz(kz); }
+  ~AttentionKzScope() { attention_split_force_kz(0); }
+  AttentionKzScope(const AttentionKzScope&) = delete; AttentionKzScope& operator=(const AttentionKzScope&) = delete;
+};
+typedef DevBuf<unsigned char> DevBytes;
+// the split-resident image of x [C][T] for a single-op entry point: every byte `fill` (0: zero margins, the taps' zero padding; 0xff: NaN patterns wherever x does not
+// land, which must not reach a stored value), then x written into it - all on s
+static DevBytes image_from_f32(hipStream_t s, const float* x, int C, int T, int fill) {
+  DevBytes img;
+  img.alloc(split_image_bytes(C, T));
+  RVC_HIP_CHECK(hipMemsetAsync(img.p, fill, split_image_bytes(C, T), s));
+  split_image_from_f32(s, x, T, C, T, img.p, split_image_tp(T));
+  return img;
+}
+
+// the operand images of attention_split from fp32 q, k, v [C][T]: q | k in one image, V^T through a transposed fp32 copy (vtf); rows past T hold NaN patterns (masked
+// keys must not leak) except the V^T tail, which attention_vt_clear_tail zeroes
+static void attention_operand_images(hipStream_t s, const float* q, const float* k, const float* v, int C, int T, DevBytes& qk, DevBuf<float>& vtf, DevBytes& vt) {
+  const long long tp = split_image_tp(T), vtp = attention_vt_tp(C);
+  qk.alloc(split_image_bytes(2 * C, T));
+  RVC_HIP_CHECK(hipMemsetAsync(qk.p, 0xff, split_image_bytes(2 * C, T), s));
+  split_image_from_f32(s, q, T, C, T, qk.p, tp);
+  split_image_from_f32(s, k, T, C, T, qk.p + split_image_bytes(C, T), tp);
+  vtf.alloc((size_t)T * C);
+  transpose(s, v, vtf.p, C, T, T, C, 1, 0, 0);
+  vt.alloc(attention_vt_bytes(C, T));
+  RVC_HIP_CHECK(hipMemsetAsync(vt.p, 0xff, attention_vt_bytes(C, T), s));
+  split_image_from_f32(s, vtf.p, C, T, C, vt.p, vtp);                            // "channels" = keys, "positions" = model channels
+  attention_vt_clear_tail(s, vt.p, C, T);
+}
 
 static void check_launch() {
   hipError_t e = hipGetLastError();
@@ -84,7 +122,7 @@ int rvc_hubert_set_tensor(rvc_hubert* h, const char* name, const float* d, const
   hubert_set_tensor(h->m, name, d, sh, ndim);
   RVC_CATCH
 }
-int rvc_hubert_finalize(rvc_hubert* h) { RVC_TRY RVC_HIP_CHECK(hipSetDevice(h->ctx->c.device)); hubert_finalize(h->m); RVC_CATCH }
+int rvc_hubert_finalize(rvc_hubert* h) { RVC_TRY RVC_REQUIRE(h, "null argument"); RVC_HIP_CHECK(hipSetDevice(h->ctx->c.device)); hubert_finalize(h->m); RVC_CATCH }
 int rvc_hubert_destroy(rvc_hubert* h) { if (h) { hubert_destroy(h->m); delete h; } return 0; }
 int64_t rvc_hubert_num_frames(int64_t L) { return hubert_num_frames(L); }
 int rvc_hubert_forward(rvc_hubert* h, void* stream, const float* audio, int64_t L, int version, int n_layers, float* out_rm, float* out_cm,
@@ -111,7 +149,7 @@ int rvc_rmvpe_set_tensor(rvc_rmvpe* r, const char* name, const float* d, const i
   rmvpe_set_tensor(r->m, name, d, sh, ndim);
   RVC_CATCH
 }
-int rvc_rmvpe_finalize(rvc_rmvpe* r) { RVC_TRY RVC_HIP_CHECK(hipSetDevice(r->ctx->c.device)); rmvpe_finalize(r->m); RVC_CATCH }
+int rvc_rmvpe_finalize(rvc_rmvpe* r) { RVC_TRY RVC_REQUIRE(r, "null argument"); RVC_HIP_CHECK(hipSetDevice(r->ctx->c.device)); rmvpe_finalize(r->m); RVC_CATCH }
 int rvc_rmvpe_destroy(rvc_rmvpe* r) { if (r) { rmvpe_destroy(r->m); delete r; } return 0; }
 int rvc_rmvpe_forward(rvc_rmvpe* r, void* stream, const float* audio, int64_t L, float thred, float* mel, float* sal, double* f0,
                       const rvc_rmvpe_taps* taps) {
@@ -151,9 +189,8 @@ struct rvc_crepe { Crepe* m; rvc_ctx* ctx; };
 int rvc_crepe_create(rvc_ctx* ctx, int tiny, rvc_crepe** out) {
   RVC_TRY
   RVC_REQUIRE(ctx && out, "null argument");
-  rvc_crepe* c = new rvc_crepe(); c->ctx = ctx; c->m = nullptr;
-  try { c->m = crepe_create(&ctx->c, tiny); } catch (...) { delete c; throw; }
-  *out = c;
+  std::unique_ptr<rvc_crepe> c(new rvc_crepe()); c->ctx = ctx; c->m = crepe_create(&ctx->c, tiny);
+  *out = c.release();
   RVC_CATCH
 }
 int rvc_crepe_set_tensor(rvc_crepe* c, const char* name, const float* d, const int64_t* shape, int ndim) {
@@ -187,9 +224,8 @@ struct rvc_mdx23 { Mdx23* m; rvc_ctx* ctx; };
 int rvc_mdx23_create(rvc_ctx* ctx, const rvc_mdx23_config* cfg, rvc_mdx23** out) {
   RVC_TRY
   RVC_REQUIRE(ctx && cfg && out, "null argument");
-  rvc_mdx23* h = new rvc_mdx23(); h->ctx = ctx; h->m = nullptr;
-  try { h->m = mdx23_create(&ctx->c, *cfg); } catch (...) { delete h; throw; }
-  *out = h;
+  std::unique_ptr<rvc_mdx23> h(new rvc_mdx23()); h->ctx = ctx; h->m = mdx23_create(&ctx->c, *cfg);
+  *out = h.release();
   RVC_CATCH
 }
 int rvc_mdx23_set_tensor(rvc_mdx23* m, const char* name, const float* d, const int64_t* shape, int ndim) {
@@ -221,9 +257,8 @@ int rvc_mdx23_demix(rvc_mdx23* m, void* stream, const float* mix, int64_t Lp, in
 int rvc_synth_create(rvc_ctx* ctx, const rvc_synth_config* cfg, rvc_synth** out) {
   RVC_TRY
   RVC_REQUIRE(ctx && cfg && out, "null argument");
-  rvc_synth* s = new rvc_synth(); s->ctx = ctx; s->m = nullptr;
-  try { s->m = synth_create(&ctx->c, *cfg); } catch (...) { delete s; throw; }
-  *out = s;
+  std::unique_ptr<rvc_synth> s(new rvc_synth()); s->ctx = ctx; s->m = synth_create(&ctx->c, *cfg);
+  *out = s.release();
   RVC_CATCH
 }
 int rvc_synth_set_tensor(rvc_synth* s, const char* name, const float* d, const int64_t* shape, int ndim) {
@@ -233,7 +268,7 @@ int rvc_synth_set_tensor(rvc_synth* s, const char* name, const float* d, const i
   synth_set_tensor(s->m, name, d, sh, ndim);
   RVC_CATCH
 }
-int rvc_synth_finalize(rvc_synth* s) { RVC_TRY RVC_HIP_CHECK(hipSetDevice(s->ctx->c.device)); synth_finalize(s->m); RVC_CATCH }
+int rvc_synth_finalize(rvc_synth* s) { RVC_TRY RVC_REQUIRE(s, "null argument"); RVC_HIP_CHECK(hipSetDevice(s->ctx->c.device)); synth_finalize(s->m); RVC_CATCH }
 int rvc_synth_destroy(rvc_synth* s) { if (s) { synth_destroy(s->m); delete s; } return 0; }
 int rvc_synth_upp(rvc_synth* s) { return s ? synth_upp(s->m) : 0; }
 int rvc_synth_has_f0(rvc_synth* s) { return (s && synth_has_f0(s->m)) ? 1 : 0; }
@@ -336,9 +371,8 @@ struct rvc_index { FeatIndex* m; };
 int rvc_index_create(rvc_ctx* ctx, const float* big_npy, int64_t N, int D, rvc_index** out) {
   RVC_TRY
   RVC_REQUIRE(ctx && out, "null argument");
-  rvc_index* h = new rvc_index();
-  try { h->m = index_create(&ctx->c, big_npy, N, D); } catch (...) { delete h; throw; }
-  *out = h;
+  std::unique_ptr<rvc_index> h(new rvc_index()); h->m = index_create(&ctx->c, big_npy, N, D);
+  *out = h.release();
   RVC_CATCH
 }
 int rvc_index_destroy(rvc_index* h) { if (h) { index_destroy(h->m); delete h; } return 0; }
@@ -347,9 +381,8 @@ int rvc_index_create_ivf(rvc_ctx* ctx, const float* big_npy, int64_t N, int D, c
                          rvc_index** out) {
   RVC_TRY
   RVC_REQUIRE(ctx && out, "null argument");
-  rvc_index* h = new rvc_index();
-  try { h->m = index_create_ivf(&ctx->c, big_npy, N, D, centroids, nlist, (const int*)list_of, nprobe); } catch (...) { delete h; throw; }
-  *out = h;
+  std::unique_ptr<rvc_index> h(new rvc_index()); h->m = index_create_ivf(&ctx->c, big_npy, N, D, centroids, nlist, (const int*)list_of, nprobe);
+  *out = h.release();
   RVC_CATCH
 }
 int rvc_index_nprobe(const rvc_index* h) { return h && h->m ? index_nprobe(h->m) : 0; }
@@ -551,15 +584,15 @@ int rvc_op_conv1d(void* stream, const float* x, const float* w, const float* bia
                   int stride, int pad, int dil, int groups, int pre_act, float pre_slope, int act, float act_slope, int act_before_res,
                   float out_scale, int accumulate) {
   RVC_TRY
-  ConvLayer L;
+  OwnedConvLayer L;
   conv1d_layer_init(L, w, bias, Co, Ci, k, stride, pad, dil, groups);
   ConvEpilogue e; e.pre_act = pre_act; e.pre_slope = pre_slope; e.act = act; e.act_slope = act_slope; e.act_before_res = act_before_res;
   e.out_scale = out_scale; e.accumulate = accumulate;
   const int Tout = conv1d_out_len(L, Tin);
   e.R = res; e.ldR = Tout;
-  try { conv1d_run(L, (hipStream_t)stream, x, Tin, Tin, y, Tout, e); check_launch(); RVC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream)); }
-  catch (...) { conv_layer_free(L); throw; }
-  conv_layer_free(L);
+  conv1d_run(L, (hipStream_t)stream, x, Tin, Tin, y, Tout, e);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   RVC_CATCH
 }
 int rvc_op_gemm_split(void* stream, const float* x, const float* w, const float* bias, const float* res, float* y, float* ysplit_f32, int Ci, int Co,
@@ -567,51 +600,35 @@ int rvc_op_gemm_split(void* stream, const float* x, const float* w, const float*
   RVC_TRY
   RVC_REQUIRE(x && w && (y || ysplit_f32) && Ci > 0 && Co > 0 && T > 0 && k >= 1 && (k & 1) == 1 && dil >= 1, "bad argument");
   hipStream_t s = (hipStream_t)stream;
-  ConvLayer L;
+  OwnedConvLayer L;
   { ConvBuildScope scope(2); conv1d_layer_init(L, w, bias, Co, Ci, k, 1, (k - 1) / 2 * dil, dil, 1); }
-  unsigned char* xs = nullptr; unsigned char* ys = nullptr;
-  try {
-    RVC_REQUIRE(conv_x3s_eligible(L), "layer not eligible for the split-resident GEMM (Ci % 16 == 0, Ci k >= 64, Co >= 32, pad <= 64)");
-    const long long tp = split_image_tp(T);
-    RVC_HIP_CHECK(hipMalloc(&xs, split_image_bytes(Ci, T)));
-    RVC_HIP_CHECK(hipMemsetAsync(xs, 0, split_image_bytes(Ci, T), s));          // zero margins: the taps' zero padding
-    split_image_from_f32(s, x, T, Ci, T, xs, tp);
-    ConvEpilogue e; e.act = act; e.act_slope = act_slope; e.act_before_res = act_before_res; e.out_scale = out_scale; e.R = res; e.ldR = T;
-    if (ysplit_f32) { RVC_HIP_CHECK(hipMalloc(&ys, split_image_bytes(Co, T))); e.ys_out = ys; e.ys_tp = tp; }
-    conv_x3s_force(ksplit, am, an);
-    try { conv_x3s_run(L, s, xs, tp, T, y, T, e); } catch (...) { conv_x3s_force(0, 0, 0); throw; }
-    conv_x3s_force(0, 0, 0);
-    if (ysplit_f32) split_image_to_f32(s, ys, tp, Co, T, ysplit_f32, T);
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { if (xs) (void)hipFree(xs); if (ys) (void)hipFree(ys); conv_layer_free(L); throw; }
-  (void)hipFree(xs); if (ys) (void)hipFree(ys);
-  conv_layer_free(L);
+  RVC_REQUIRE(conv_x3s_eligible(L), "layer not eligible for the split-resident GEMM (Ci % 16 == 0, Ci k >= 64, Co >= 32, pad <= 64)");
+  const long long tp = split_image_tp(T);
+  DevBytes xs = image_from_f32(s, x, Ci, T, 0), ys;
+  ConvEpilogue e; e.act = act; e.act_slope = act_slope; e.act_before_res = act_before_res; e.out_scale = out_scale; e.R = res; e.ldR = T;
+  if (ysplit_f32) { ys.alloc(split_image_bytes(Co, T)); e.ys_out = ys.p; e.ys_tp = tp; }
+  { X3sForceScope force(ksplit, am, an); conv_x3s_run(L, s, xs.p, tp, T, y, T, e); }
+  if (ysplit_f32) split_image_to_f32(s, ys.p, tp, Co, T, ysplit_f32, T);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_gemm_split_swapped(void* stream, const float* x, const float* w, float* yt, int Ci, int Co, int T, int row0, int rows) {
   RVC_TRY
   RVC_REQUIRE(x && w && yt && Ci > 0 && Co > 0 && T > 0 && rows > 0, "bad argument");
   hipStream_t s = (hipStream_t)stream;
-  ConvLayer L;
+  OwnedConvLayer L;
   { ConvBuildScope scope(2); conv1d_layer_init(L, w, nullptr, Co, Ci, 1, 1, 0, 1, 1); }
-  unsigned char* xs = nullptr; unsigned char* ys = nullptr;
-  try {
-    const long long tp = split_image_tp(T), vtp = attention_vt_tp(rows);
-    const size_t vbytes = attention_vt_bytes(rows, T);
-    RVC_HIP_CHECK(hipMalloc(&xs, split_image_bytes(Ci, T)));
-    RVC_HIP_CHECK(hipMemsetAsync(xs, 0xff, split_image_bytes(Ci, T), s));       // NaN patterns past T: the tail rows must come out as zeros regardless
-    split_image_from_f32(s, x, T, Ci, T, xs, tp);
-    RVC_HIP_CHECK(hipMalloc(&ys, vbytes));
-    RVC_HIP_CHECK(hipMemsetAsync(ys, 0xff, vbytes, s));
-    conv_x3s_run_swapped(L, row0, rows, s, xs, tp, T, ys, vtp);
-    attention_vt_clear_tail(s, ys, rows, T);
-    split_image_to_f32(s, ys, vtp, (T + 63) / 64 * 64, rows, yt, rows);          // yt [ceil64(T)][rows]
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { if (xs) (void)hipFree(xs); if (ys) (void)hipFree(ys); conv_layer_free(L); throw; }
-  (void)hipFree(xs); (void)hipFree(ys);
-  conv_layer_free(L);
+  const long long tp = split_image_tp(T), vtp = attention_vt_tp(rows);
+  const size_t vbytes = attention_vt_bytes(rows, T);
+  DevBytes xs = image_from_f32(s, x, Ci, T, 0xff), ys;                          // NaN patterns past T: the tail rows must come out as zeros regardless
+  ys.alloc(vbytes);
+  RVC_HIP_CHECK(hipMemsetAsync(ys.p, 0xff, vbytes, s));
+  conv_x3s_run_swapped(L, row0, rows, s, xs.p, tp, T, ys.p, vtp);
+  attention_vt_clear_tail(s, ys.p, rows, T);
+  split_image_to_f32(s, ys.p, vtp, (T + 63) / 64 * 64, rows, yt, rows);          // yt [ceil64(T)][rows]
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_wn_in_gate_split(void* stream, const float* x, const float* w, const float* bias, const float* g_dev, float* y, int Ci, int H, int T, int k) {
@@ -625,54 +642,40 @@ int rvc_op_wn_in_gate_split(void* stream, const float* x, const float* w, const 
     std::copy(w + (size_t)src * Ci * k, w + (size_t)(src + 1) * Ci * k, wp.begin() + (size_t)r * Ci * k);
     if (bias) bp[r] = bias[src];
   }
-  ConvLayer L;
+  OwnedConvLayer L;
   { ConvBuildScope scope(2); conv1d_layer_init(L, wp.data(), bp.data(), 2 * H, Ci, k, 1, (k - 1) / 2, 1, 1); }
-  unsigned char* xs = nullptr; unsigned char* ys = nullptr;
-  try {
-    RVC_REQUIRE(conv_x3s_eligible(L), "layer not eligible for the split-resident kernel");
-    const long long tp = split_image_tp(T);
-    RVC_HIP_CHECK(hipMalloc(&xs, split_image_bytes(Ci, T)));
-    RVC_HIP_CHECK(hipMemsetAsync(xs, 0, split_image_bytes(Ci, T), s));
-    split_image_from_f32(s, x, T, Ci, T, xs, tp);
-    RVC_HIP_CHECK(hipMalloc(&ys, split_image_bytes(H, T)));
-    ConvEpilogue e; e.ys_out = ys; e.ys_tp = tp; e.gate_h = H; e.gate_g = g_dev;
-    conv_x3s_run(L, s, xs, tp, T, nullptr, T, e);
-    split_image_to_f32(s, ys, tp, H, T, y, T);
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { if (xs) (void)hipFree(xs); if (ys) (void)hipFree(ys); conv_layer_free(L); throw; }
-  (void)hipFree(xs); (void)hipFree(ys);
-  conv_layer_free(L);
+  RVC_REQUIRE(conv_x3s_eligible(L), "layer not eligible for the split-resident kernel");
+  const long long tp = split_image_tp(T);
+  DevBytes xs = image_from_f32(s, x, Ci, T, 0), ys;
+  ys.alloc(split_image_bytes(H, T));
+  ConvEpilogue e; e.ys_out = ys.p; e.ys_tp = tp; e.gate_h = H; e.gate_g = g_dev;
+  conv_x3s_run(L, s, xs.p, tp, T, nullptr, T, e);
+  split_image_to_f32(s, ys.p, tp, H, T, y, T);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_gemm_split_qkv(void* stream, const float* x, const float* w, const float* bias, float* y_img_f32, float* yt, int Ci, int Co, int T, int vt_row0) {
   RVC_TRY
   RVC_REQUIRE(x && w && y_img_f32 && yt && Ci > 0 && Co > 0 && T > 0 && vt_row0 > 0 && vt_row0 < Co, "bad argument");
   hipStream_t s = (hipStream_t)stream;
-  ConvLayer L;
+  OwnedConvLayer L;
   { ConvBuildScope scope(2); conv1d_layer_init(L, w, bias, Co, Ci, 1, 1, 0, 1, 1); }
-  unsigned char* xs = nullptr; unsigned char* ys = nullptr; unsigned char* vt = nullptr;
   const int rows = Co - vt_row0;
-  try {
-    RVC_REQUIRE(conv_x3s_eligible(L), "layer not eligible for the split-resident kernel");
-    const long long tp = split_image_tp(T), vtp = attention_vt_tp(rows);
-    const size_t vbytes = attention_vt_bytes(rows, T);
-    RVC_HIP_CHECK(hipMalloc(&xs, split_image_bytes(Ci, T)));
-    RVC_HIP_CHECK(hipMemsetAsync(xs, 0xff, split_image_bytes(Ci, T), s));       // NaN patterns past T: the transposed rows past T must come out as zeros regardless
-    split_image_from_f32(s, x, T, Ci, T, xs, tp);
-    RVC_HIP_CHECK(hipMalloc(&ys, split_image_bytes(vt_row0, T)));
-    RVC_HIP_CHECK(hipMalloc(&vt, vbytes));
-    RVC_HIP_CHECK(hipMemsetAsync(vt, 0xff, vbytes, s));
-    ConvEpilogue e; e.ys_out = ys; e.ys_tp = tp; e.vt_out = vt; e.vt_tp = vtp; e.vt_row0 = vt_row0;
-    conv_x3s_run(L, s, xs, tp, T, nullptr, T, e);
-    attention_vt_clear_tail(s, vt, rows, T);
-    split_image_to_f32(s, ys, tp, vt_row0, T, y_img_f32, T);                      // y_img_f32 [vt_row0][T]: the rows below vt_row0, from their image
-    split_image_to_f32(s, vt, vtp, (T + 63) / 64 * 64, rows, yt, rows);            // yt [ceil64(T)][rows]: the rows from vt_row0 on, transposed
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { if (xs) (void)hipFree(xs); if (ys) (void)hipFree(ys); if (vt) (void)hipFree(vt); conv_layer_free(L); throw; }
-  (void)hipFree(xs); (void)hipFree(ys); (void)hipFree(vt);
-  conv_layer_free(L);
+  RVC_REQUIRE(conv_x3s_eligible(L), "layer not eligible for the split-resident kernel");
+  const long long tp = split_image_tp(T), vtp = attention_vt_tp(rows);
+  const size_t vbytes = attention_vt_bytes(rows, T);
+  DevBytes xs = image_from_f32(s, x, Ci, T, 0xff), ys, vt;                      // NaN patterns past T: the transposed rows past T must come out as zeros regardless
+  ys.alloc(split_image_bytes(vt_row0, T));
+  vt.alloc(vbytes);
+  RVC_HIP_CHECK(hipMemsetAsync(vt.p, 0xff, vbytes, s));
+  ConvEpilogue e; e.ys_out = ys.p; e.ys_tp = tp; e.vt_out = vt.p; e.vt_tp = vtp; e.vt_row0 = vt_row0;
+  conv_x3s_run(L, s, xs.p, tp, T, nullptr, T, e);
+  attention_vt_clear_tail(s, vt.p, rows, T);
+  split_image_to_f32(s, ys.p, tp, vt_row0, T, y_img_f32, T);                    // y_img_f32 [vt_row0][T]: the rows below vt_row0, from their image
+  split_image_to_f32(s, vt.p, vtp, (T + 63) / 64 * 64, rows, yt, rows);          // yt [ceil64(T)][rows]: the rows from vt_row0 on, transposed
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_conv2d3x3_plus_1x1(void* stream, const float* x1, const float* w1, const float* x2, const float* w2, float* y, float* y_img_f32, int Ci1, int Ci2, int Co, int H, int W,
@@ -680,56 +683,42 @@ int rvc_op_conv2d3x3_plus_1x1(void* stream, const float* x1, const float* w1, co
   RVC_TRY
   RVC_REQUIRE(x1 && w1 && x2 && w2 && y && Ci1 > 0 && Ci2 > 0 && Co > 0 && H > 0 && W > 0, "bad argument");
   hipStream_t s = (hipStream_t)stream;
-  ConvLayer L1, L2;
+  OwnedConvLayer L1, L2;
   { ConvBuildScope scope(2); conv2d3x3_layer_init(L1, w1, nullptr, Co, Ci1); conv1d_layer_init(L2, w2, nullptr, Co, Ci2, 1, 1, 0, 1, 1); }
-  unsigned char* img = nullptr; unsigned char* yimg = nullptr; float* yp = nullptr;
-  try {
-    RVC_REQUIRE(conv_x3s_eligible(L1) && conv_x3s_eligible(L2), "layers not eligible for the split-resident GEMM (channels % 16, Co >= 32)");
-    conv_layer_append_x3(L1, L2);
-    SplitGeom g = split_geom_2d(W);
-    const long long TP = (long long)H * (W + 2), tp = ((long long)g.margin + TP + std::max(704, g.margin) + 63) & ~63LL;
-    const size_t b1 = (size_t)(Ci1 / 16) * 4 * (size_t)tp * 16, b2 = (size_t)(Ci2 / 16) * 4 * (size_t)tp * 16, bo = (size_t)((Co + 15) / 16) * 4 * (size_t)tp * 16;
-    RVC_HIP_CHECK(hipMalloc(&img, b1 + b2)); RVC_HIP_CHECK(hipMemsetAsync(img, 0, b1 + b2, s));      // zero margins: the vertical zero padding
-    RVC_HIP_CHECK(hipMalloc(&yp, (size_t)Co * TP * sizeof(float)));
-    if (y_img_f32) { RVC_HIP_CHECK(hipMalloc(&yimg, bo)); RVC_HIP_CHECK(hipMemsetAsync(yimg, 0xff, bo, s)); }
-    pad2d_split(s, x1, (long long)H * W, Ci1, H, W, nullptr, 0, img, tp, g.margin);
-    pad2d_split(s, x2, (long long)H * W, Ci2, H, W, nullptr, 0, img + b1, tp, g.margin);
-    g.seg2_off = (long long)b1;
-    ConvEpilogue e;
-    if (yimg) { e.ys_out = yimg; e.ys_tp = tp; }
-    conv_x3s_force(ksplit, 0, 0);
-    try { conv_x3s_run(L1, s, img, tp, (int)TP, yp, TP, e, &g); } catch (...) { conv_x3s_force(0, 0, 0); throw; }
-    conv_x3s_force(0, 0, 0);
-    unpad2d(s, yp, TP, Co, H, W, y, (long long)H * W);
-    if (yimg) {                                                 // the raw image of the output, read back through the padded layout
-      split_image_to_f32(s, yimg + (size_t)(g.margin - kSplitMargin) * 16, tp, Co, (int)TP, yp, TP);
-      unpad2d(s, yp, TP, Co, H, W, y_img_f32, (long long)H * W);
-    }
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { if (img) (void)hipFree(img); if (yimg) (void)hipFree(yimg); if (yp) (void)hipFree(yp); conv_layer_free(L1); conv_layer_free(L2); throw; }
-  (void)hipFree(img); if (yimg) (void)hipFree(yimg); (void)hipFree(yp);
-  conv_layer_free(L1); conv_layer_free(L2);
+  RVC_REQUIRE(conv_x3s_eligible(L1) && conv_x3s_eligible(L2), "layers not eligible for the split-resident GEMM (channels % 16, Co >= 32)");
+  conv_layer_append_x3(L1, L2);
+  SplitGeom g = split_geom_2d(W);
+  const long long TP = (long long)H * (W + 2), tp = ((long long)g.margin + TP + std::max(704, g.margin) + 63) & ~63LL;
+  const size_t b1 = (size_t)(Ci1 / 16) * 4 * (size_t)tp * 16, b2 = (size_t)(Ci2 / 16) * 4 * (size_t)tp * 16, bo = (size_t)((Co + 15) / 16) * 4 * (size_t)tp * 16;
+  DevBytes img, yimg; DevBuf<float> yp;
+  img.alloc(b1 + b2); RVC_HIP_CHECK(hipMemsetAsync(img.p, 0, b1 + b2, s));      // zero margins: the vertical zero padding
+  yp.alloc((size_t)Co * TP);
+  if (y_img_f32) { yimg.alloc(bo); RVC_HIP_CHECK(hipMemsetAsync(yimg.p, 0xff, bo, s)); }
+  pad2d_split(s, x1, (long long)H * W, Ci1, H, W, nullptr, 0, img.p, tp, g.margin);
+  pad2d_split(s, x2, (long long)H * W, Ci2, H, W, nullptr, 0, img.p + b1, tp, g.margin);
+  g.seg2_off = (long long)b1;
+  ConvEpilogue e;
+  if (yimg.p) { e.ys_out = yimg.p; e.ys_tp = tp; }
+  { X3sForceScope force(ksplit, 0, 0); conv_x3s_run(L1, s, img.p, tp, (int)TP, yp.p, TP, e, &g); }
+  unpad2d(s, yp.p, TP, Co, H, W, y, (long long)H * W);
+  if (yimg.p) {                                               // the raw image of the output, read back through the padded layout
+    split_image_to_f32(s, yimg.p + (size_t)(g.margin - kSplitMargin) * 16, tp, Co, (int)TP, yp.p, TP);
+    unpad2d(s, yp.p, TP, Co, H, W, y_img_f32, (long long)H * W);
+  }
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_gemm_split_swapped_res(void* stream, const float* x, const float* w, const float* res, float* y, int Ci, int Co, int T, int ld, int off) {
   RVC_TRY
   RVC_REQUIRE(x && w && res && y && Ci > 0 && Co > 0 && T > 0 && ld >= Co + off && off >= 0, "bad argument");
   hipStream_t s = (hipStream_t)stream;
-  ConvLayer L;
+  OwnedConvLayer L;
   { ConvBuildScope scope(2); conv1d_layer_init(L, w, nullptr, Co, Ci, 1, 1, 0, 1, 1); }
-  unsigned char* xs = nullptr;
-  try {
-    const long long tp = split_image_tp(T);
-    RVC_HIP_CHECK(hipMalloc(&xs, split_image_bytes(Ci, T)));
-    RVC_HIP_CHECK(hipMemsetAsync(xs, 0, split_image_bytes(Ci, T), s));
-    split_image_from_f32(s, x, T, Ci, T, xs, tp);
-    conv_x3s_run_swapped(L, 0, Co, s, xs, tp, T, nullptr, 0, y + off, ld, res + off, ld);      // y[t][off + j] = sum_c x[c][t] w[j][c] + res[t][off + j]
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { if (xs) (void)hipFree(xs); conv_layer_free(L); throw; }
-  (void)hipFree(xs);
-  conv_layer_free(L);
+  DevBytes xs = image_from_f32(s, x, Ci, T, 0);
+  conv_x3s_run_swapped(L, 0, Co, s, xs.p, split_image_tp(T), T, nullptr, 0, y + off, ld, res + off, ld);      // y[t][off + j] = sum_c x[c][t] w[j][c] + res[t][off + j]
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_attention_split(void* stream, const float* q, const float* k, const float* v, const float* bv, float* out, float* out_img_f32, int heads, int T) {
@@ -737,26 +726,14 @@ int rvc_op_attention_split(void* stream, const float* q, const float* k, const f
   RVC_REQUIRE(q && k && v && (out || out_img_f32) && heads > 0 && T > 0, "bad argument");
   hipStream_t s = (hipStream_t)stream;
   const int C = heads * 64;
-  unsigned char* qk = nullptr; unsigned char* vt = nullptr; unsigned char* oi = nullptr; float* vtf = nullptr;
-  try {
-    const long long tp = split_image_tp(T), vtp = attention_vt_tp(C);
-    RVC_HIP_CHECK(hipMalloc(&qk, split_image_bytes(2 * C, T)));
-    RVC_HIP_CHECK(hipMemsetAsync(qk, 0xff, split_image_bytes(2 * C, T), s));     // rows past T hold NaN patterns: masked keys must not leak
-    split_image_from_f32(s, q, T, C, T, qk, tp);
-    split_image_from_f32(s, k, T, C, T, qk + split_image_bytes(C, T), tp);
-    RVC_HIP_CHECK(hipMalloc(&vtf, (size_t)T * C * 4));
-    transpose((hipStream_t)s, v, vtf, C, T, T, C, 1, 0, 0);
-    RVC_HIP_CHECK(hipMalloc(&vt, attention_vt_bytes(C, T)));
-    RVC_HIP_CHECK(hipMemsetAsync(vt, 0xff, attention_vt_bytes(C, T), s));
-    split_image_from_f32(s, vtf, C, T, C, vt, vtp);                              // "channels" = keys, "positions" = model channels
-    attention_vt_clear_tail(s, vt, C, T);
-    if (out_img_f32) { RVC_HIP_CHECK(hipMalloc(&oi, split_image_bytes(C, T))); }
-    attention_split(s, qk, tp, 2 * C, 0, C / 16, vt, heads, 64, T, 1.f, bv, out, T, oi, tp);
-    if (out_img_f32) split_image_to_f32(s, oi, tp, C, T, out_img_f32, T);
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { (void)hipFree(qk); (void)hipFree(vt); (void)hipFree(oi); (void)hipFree(vtf); throw; }
-  (void)hipFree(qk); (void)hipFree(vt); (void)hipFree(oi); (void)hipFree(vtf);
+  DevBytes qk, vt, oi; DevBuf<float> vtf;
+  const long long tp = split_image_tp(T);
+  attention_operand_images(s, q, k, v, C, T, qk, vtf, vt);
+  if (out_img_f32) oi.alloc(split_image_bytes(C, T));
+  attention_split(s, qk.p, tp, 2 * C, 0, C / 16, vt.p, heads, 64, T, 1.f, bv, out, T, oi.p, tp);
+  if (out_img_f32) split_image_to_f32(s, oi.p, tp, C, T, out_img_f32, T);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_attention_split_rel(void* stream, const float* q, const float* k, const float* v, const float* bv, const float* ek_host, const float* ev_host,
@@ -765,47 +742,31 @@ int rvc_op_attention_split_rel(void* stream, const float* q, const float* k, con
   RVC_REQUIRE(q && k && v && ek_host && ev_host && (out || out_img_f32) && heads > 0 && T > 0, "bad argument");
   hipStream_t s = (hipStream_t)stream;
   const int C = heads * 96;
-  unsigned char* qk = nullptr; unsigned char* vt = nullptr; unsigned char* oi = nullptr; float* vtf = nullptr; unsigned char* tab = nullptr;
-  try {
-    std::vector<uint16_t> eki, evi;
-    attention_rel_images(ek_host, ev_host, 96, 10, eki, evi);
-    RVC_HIP_CHECK(hipMalloc(&tab, (eki.size() + evi.size()) * 2));
-    RVC_HIP_CHECK(hipMemcpy(tab, eki.data(), eki.size() * 2, hipMemcpyHostToDevice));
-    RVC_HIP_CHECK(hipMemcpy(tab + eki.size() * 2, evi.data(), evi.size() * 2, hipMemcpyHostToDevice));
-    const long long tp = split_image_tp(T), vtp = attention_vt_tp(C);
-    RVC_HIP_CHECK(hipMalloc(&qk, split_image_bytes(2 * C, T)));
-    RVC_HIP_CHECK(hipMemsetAsync(qk, 0xff, split_image_bytes(2 * C, T), s));
-    split_image_from_f32(s, q, T, C, T, qk, tp);
-    split_image_from_f32(s, k, T, C, T, qk + split_image_bytes(C, T), tp);
-    RVC_HIP_CHECK(hipMalloc(&vtf, (size_t)T * C * 4));
-    transpose((hipStream_t)s, v, vtf, C, T, T, C, 1, 0, 0);
-    RVC_HIP_CHECK(hipMalloc(&vt, attention_vt_bytes(C, T)));
-    RVC_HIP_CHECK(hipMemsetAsync(vt, 0xff, attention_vt_bytes(C, T), s));
-    split_image_from_f32(s, vtf, C, T, C, vt, vtp);
-    attention_vt_clear_tail(s, vt, C, T);
-    if (out_img_f32) { RVC_HIP_CHECK(hipMalloc(&oi, split_image_bytes(C, T))); }
-    attention_split_force_kz(kz);
-    try { attention_split(s, qk, tp, 2 * C, 0, C / 16, vt, heads, 96, T, 1.f, bv, out, T, oi, tp, 10, tab, tab + eki.size() * 2); } catch (...) { attention_split_force_kz(0); throw; }
-    attention_split_force_kz(0);
-    if (out_img_f32) split_image_to_f32(s, oi, tp, C, T, out_img_f32, T);
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { (void)hipFree(qk); (void)hipFree(vt); (void)hipFree(oi); (void)hipFree(vtf); (void)hipFree(tab); throw; }
-  (void)hipFree(qk); (void)hipFree(vt); (void)hipFree(oi); (void)hipFree(vtf); (void)hipFree(tab);
+  DevBytes qk, vt, oi, tab; DevBuf<float> vtf;
+  std::vector<uint16_t> eki, evi;
+  attention_rel_images(ek_host, ev_host, 96, 10, eki, evi);
+  const size_t evt_off = eki.size() * 2;                                         // E_k image, then E_v^T image
+  tab.alloc(evt_off + evi.size() * 2);
+  RVC_HIP_CHECK(hipMemcpy(tab.p, eki.data(), evt_off, hipMemcpyHostToDevice));
+  RVC_HIP_CHECK(hipMemcpy(tab.p + evt_off, evi.data(), evi.size() * 2, hipMemcpyHostToDevice));
+  const long long tp = split_image_tp(T);
+  attention_operand_images(s, q, k, v, C, T, qk, vtf, vt);
+  if (out_img_f32) oi.alloc(split_image_bytes(C, T));
+  { AttentionKzScope force(kz); attention_split(s, qk.p, tp, 2 * C, 0, C / 16, vt.p, heads, 96, T, 1.f, bv, out, T, oi.p, tp, 10, tab.p, tab.p + evt_off); }
+  if (out_img_f32) split_image_to_f32(s, oi.p, tp, C, T, out_img_f32, T);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_cbr2_small(void* stream, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y, int C, int H, int W) {
   RVC_TRY
   RVC_REQUIRE(x && w1 && b1 && w2 && b2 && y && (C == 16 || C == 32) && H > 0 && W > 0, "bad argument");
   hipStream_t s = (hipStream_t)stream;
-  ConvLayer c1, c2;
+  OwnedConvLayer c1, c2;
   { ConvBuildScope scope(2); conv2d3x3_layer_init(c1, w1, b1, C, C); conv2d3x3_layer_init(c2, w2, b2, C, C); }
-  try {
-    cbr2_small_run(c1, c2, s, x, H, W, y);
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { conv_layer_free(c1); conv_layer_free(c2); throw; }
-  conv_layer_free(c1); conv_layer_free(c2);
+  cbr2_small_run(c1, c2, s, x, H, W, y);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_conv3_small(void* stream, const float* x, const float* w, const float* b, const float* res, float* y, float* y2, int Ci, int Co, int H, int W, int split_row,
@@ -813,14 +774,11 @@ int rvc_op_conv3_small(void* stream, const float* x, const float* w, const float
   RVC_TRY
   RVC_REQUIRE(x && w && b && y && Ci > 0 && Co > 0 && H > 0 && W > 0, "bad argument");
   hipStream_t s = (hipStream_t)stream;
-  ConvLayer L;
+  OwnedConvLayer L;
   { ConvBuildScope scope(2); conv2d3x3_layer_init(L, w, b, Co, Ci); }
-  try {
-    conv3_small_run(L, s, x, H, W, y, y2, split_row, relu_rows, res);
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { conv_layer_free(L); throw; }
-  conv_layer_free(L);
+  conv3_small_run(L, s, x, H, W, y, y2, split_row, relu_rows, res);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_conv1d_split(void* stream, const float* x, const float* w, const float* bias, const float* res, float* y, int Ci, int Co, int T, int k, int pad,
@@ -828,50 +786,38 @@ int rvc_op_conv1d_split(void* stream, const float* x, const float* w, const floa
   RVC_TRY
   RVC_REQUIRE(x && w && y && Ci > 0 && Co > 0 && T > 0 && k >= 1 && groups >= 1, "bad argument");
   hipStream_t s = (hipStream_t)stream;
-  ConvLayer L;
+  OwnedConvLayer L;
   { ConvBuildScope scope(2); conv1d_layer_init(L, w, bias, Co, Ci, k, 1, pad, dil, groups); }
-  unsigned char* xs = nullptr;
-  try {
-    RVC_REQUIRE(conv_x3s_eligible(L), "layer not eligible for the split-resident kernel");
-    const long long tp = split_image_tp(T);
-    RVC_HIP_CHECK(hipMalloc(&xs, split_image_bytes(Ci, T)));
-    RVC_HIP_CHECK(hipMemsetAsync(xs, 0, split_image_bytes(Ci, T), s));
-    split_image_from_f32(s, x, T, Ci, T, xs, tp);
-    ConvEpilogue e; e.act = act; e.act_slope = 0.1f; e.act_before_res = act_before_res; e.R = res; e.ldR = T;
-    conv_x3s_run(L, s, xs, tp, T, y, T, e);
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { if (xs) (void)hipFree(xs); conv_layer_free(L); throw; }
-  (void)hipFree(xs);
-  conv_layer_free(L);
+  RVC_REQUIRE(conv_x3s_eligible(L), "layer not eligible for the split-resident kernel");
+  DevBytes xs = image_from_f32(s, x, Ci, T, 0);
+  ConvEpilogue e; e.act = act; e.act_slope = 0.1f; e.act_before_res = act_before_res; e.R = res; e.ldR = T;
+  conv_x3s_run(L, s, xs.p, split_image_tp(T), T, y, T, e);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_conv1d_s2_split(void* stream, const float* x, const float* w, const float* bias, float* y, float* y_img_f32, int Ci, int Co, int T, int k, int act) {
   RVC_TRY
   RVC_REQUIRE(x && w && y && Ci > 0 && Co > 0 && k >= 2 && T >= k, "bad argument");
   hipStream_t s = (hipStream_t)stream;
-  ConvLayer L;
+  OwnedConvLayer L;
   { ConvBuildScope scope(2); conv1d_layer_init(L, w, bias, Co, Ci, k, 2, 0, 1, 1); }
-  unsigned char* xs = nullptr; unsigned char* ys = nullptr;
-  try {
-    RVC_REQUIRE(conv_x3s_s2_eligible(L), "layer not eligible for the stride-2 path of the split-resident kernel (Ci, Co multiples of 16)");
-    const int Tout = (T - k) / 2 + 1;
-    const SplitGeom g = split_geom_s2(k, T);
-    RVC_HIP_CHECK(hipMalloc(&xs, split_s2_bytes(Ci, T)));
-    RVC_HIP_CHECK(hipMemsetAsync(xs, 0xff, split_s2_bytes(Ci, T), s));      // (NaN patterns wherever the producer does not write: what a consumer reads there must not reach a stored column)
-    split_image_deint_from_f32(s, x, T, Ci, T, xs, split_s2_tp(T), g.s2_h);
-    ConvEpilogue e; e.act = act; e.act_slope = 0.1f;
-    if (y_img_f32) {
-      RVC_HIP_CHECK(hipMalloc(&ys, split_s2_bytes(Co, Tout)));
-      e.ys_out = ys; e.ys_tp = split_s2_tp(Tout); e.ys_deint_h = split_s2_h(Tout);
-    }
-    conv_x3s_run(L, s, xs, split_s2_tp(T), Tout, y, Tout, e, &g);
-    if (y_img_f32) split_image_deint_to_f32(s, ys, split_s2_tp(Tout), split_s2_h(Tout), Co, Tout, y_img_f32, Tout);
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { if (xs) (void)hipFree(xs); if (ys) (void)hipFree(ys); conv_layer_free(L); throw; }
-  (void)hipFree(xs); if (ys) (void)hipFree(ys);
-  conv_layer_free(L);
+  RVC_REQUIRE(conv_x3s_s2_eligible(L), "layer not eligible for the stride-2 path of the split-resident kernel (Ci, Co multiples of 16)");
+  const int Tout = (T - k) / 2 + 1;
+  const SplitGeom g = split_geom_s2(k, T);
+  DevBytes xs, ys;
+  xs.alloc(split_s2_bytes(Ci, T));
+  RVC_HIP_CHECK(hipMemsetAsync(xs.p, 0xff, split_s2_bytes(Ci, T), s));      // (NaN patterns wherever the producer does not write: what a consumer reads there must not reach a stored column)
+  split_image_deint_from_f32(s, x, T, Ci, T, xs.p, split_s2_tp(T), g.s2_h);
+  ConvEpilogue e; e.act = act; e.act_slope = 0.1f;
+  if (y_img_f32) {
+    ys.alloc(split_s2_bytes(Co, Tout));
+    e.ys_out = ys.p; e.ys_tp = split_s2_tp(Tout); e.ys_deint_h = split_s2_h(Tout);
+  }
+  conv_x3s_run(L, s, xs.p, split_s2_tp(T), Tout, y, Tout, e, &g);
+  if (y_img_f32) split_image_deint_to_f32(s, ys.p, split_s2_tp(Tout), split_s2_h(Tout), Co, Tout, y_img_f32, Tout);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_conv2d_split(void* stream, const float* x, const float* w, const float* bias, const float* res, float* y, float* ysplit_f32, int Ci, int Co,
@@ -879,70 +825,64 @@ int rvc_op_conv2d_split(void* stream, const float* x, const float* w, const floa
   RVC_TRY
   RVC_REQUIRE(x && w && y && Ci > 0 && Co > 0 && H > 0 && W >= 2 && (W & 1) == 0, "bad argument");
   hipStream_t s = (hipStream_t)stream;
-  ConvLayer L;
+  OwnedConvLayer L;
   { ConvBuildScope scope(2); conv2d3x3_layer_init(L, w, bias, Co, Ci); }
-  unsigned char* xs = nullptr; unsigned char* ys = nullptr; float* rp = nullptr; float* yp = nullptr; float* t = nullptr;
-  auto cleanup = [&]() { if (xs) (void)hipFree(xs); if (ys) (void)hipFree(ys); if (rp) (void)hipFree(rp); if (yp) (void)hipFree(yp); if (t) (void)hipFree(t); conv_layer_free(L); };
-  try {
-    RVC_REQUIRE(conv_x3s_eligible(L), "layer not eligible for the split-resident kernel (Ci % 16 == 0)");
-    const SplitGeom g = split_geom_2d(W);
-    const int T = H * (W + 2);
-    const long long tp = g.margin + T + 704 + 64;
-    const size_t ib = (size_t)(Ci / 16) * 4 * tp * 16, ob = (size_t)((Co + 15) / 16) * 4 * tp * 16;
-    RVC_HIP_CHECK(hipMalloc(&xs, ib)); RVC_HIP_CHECK(hipMemsetAsync(xs, 0, ib, s));
-    RVC_HIP_CHECK(hipMalloc(&yp, (size_t)Co * T * 4));
-    pad2d_split(s, x, (long long)H * W, Ci, H, W, nullptr, 0, xs, tp, g.margin);
-    ConvEpilogue e; e.act = act; e.act_slope = 0.1f; e.act_before_res = act_before_res;
-    if (res) { RVC_HIP_CHECK(hipMalloc(&rp, (size_t)Co * T * 4)); pad2d_split(s, res, (long long)H * W, Co, H, W, rp, T, nullptr, 0, 0); e.R = rp; e.ldR = T; }
-    if (ysplit_f32) { RVC_HIP_CHECK(hipMalloc(&ys, ob)); RVC_HIP_CHECK(hipMemsetAsync(ys, 0, ob, s)); e.ys_out = ys; e.ys_tp = tp; }
-    conv_x3s_force(ksplit, am, an);
-    try { conv_x3s_run(L, s, xs, tp, T, yp, T, e, &g); } catch (...) { conv_x3s_force(0, 0, 0); throw; }
-    conv_x3s_force(0, 0, 0);
-    unpad2d(s, yp, T, Co, H, W, y, (long long)H * W);
-    if (ysplit_f32) {
-      RVC_REQUIRE((Co & 15) == 0, "split output needs Co % 16 == 0");
-      RVC_HIP_CHECK(hipMalloc(&t, (size_t)Co * T * 4));
-      // (the image's rows start at its own margin: hand the reader the plane origin shifted so that its fixed 64-row margin lands on position 0)
-      split_image_to_f32(s, ys + (size_t)(g.margin - kSplitMargin) * 16, tp, Co, T, t, T);
-      unpad2d(s, t, T, Co, H, W, ysplit_f32, (long long)H * W);
-    }
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { cleanup(); throw; }
-  cleanup();
+  RVC_REQUIRE(conv_x3s_eligible(L), "layer not eligible for the split-resident kernel (Ci % 16 == 0)");
+  const SplitGeom g = split_geom_2d(W);
+  const int T = H * (W + 2);
+  const long long tp = g.margin + T + 704 + 64;
+  const size_t ib = (size_t)(Ci / 16) * 4 * tp * 16, ob = (size_t)((Co + 15) / 16) * 4 * tp * 16;
+  DevBytes xs, ys; DevBuf<float> rp, yp, t;
+  xs.alloc(ib); RVC_HIP_CHECK(hipMemsetAsync(xs.p, 0, ib, s));
+  yp.alloc((size_t)Co * T);
+  pad2d_split(s, x, (long long)H * W, Ci, H, W, nullptr, 0, xs.p, tp, g.margin);
+  ConvEpilogue e; e.act = act; e.act_slope = 0.1f; e.act_before_res = act_before_res;
+  if (res) { rp.alloc((size_t)Co * T); pad2d_split(s, res, (long long)H * W, Co, H, W, rp.p, T, nullptr, 0, 0); e.R = rp.p; e.ldR = T; }
+  if (ysplit_f32) { ys.alloc(ob); RVC_HIP_CHECK(hipMemsetAsync(ys.p, 0, ob, s)); e.ys_out = ys.p; e.ys_tp = tp; }
+  { X3sForceScope force(ksplit, am, an); conv_x3s_run(L, s, xs.p, tp, T, yp.p, T, e, &g); }
+  unpad2d(s, yp.p, T, Co, H, W, y, (long long)H * W);
+  if (ysplit_f32) {
+    RVC_REQUIRE((Co & 15) == 0, "split output needs Co % 16 == 0");
+    t.alloc((size_t)Co * T);
+    // (the image's rows start at its own margin: hand the reader the plane origin shifted so that its fixed 64-row margin lands on position 0)
+    split_image_to_f32(s, ys.p + (size_t)(g.margin - kSplitMargin) * 16, tp, Co, T, t.p, T);
+    unpad2d(s, t.p, T, Co, H, W, ysplit_f32, (long long)H * W);
+  }
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_conv_transpose1d(void* stream, const float* x, const float* w, const float* bias, float* y, int Ci, int Co, int Tin, int k, int u,
                             int pad, int pre_act, float pre_slope, int accumulate) {
   RVC_TRY
-  ConvLayer L;
+  OwnedConvLayer L;
   tconv1d_layer_init(L, w, bias, Ci, Co, k, u, pad);
   ConvEpilogue e; e.pre_act = pre_act; e.pre_slope = pre_slope; e.accumulate = accumulate;
   const int Tout = conv1d_out_len(L, Tin);
-  try { conv1d_run(L, (hipStream_t)stream, x, Tin, Tin, y, Tout, e); check_launch(); RVC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream)); }
-  catch (...) { conv_layer_free(L); throw; }
-  conv_layer_free(L);
+  conv1d_run(L, (hipStream_t)stream, x, Tin, Tin, y, Tout, e);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   RVC_CATCH
 }
 int rvc_op_conv2d3x3(void* stream, const float* x, const float* w, const float* bias, const float* res, float* y, int Ci, int Co, int H, int W,
                      int relu) {
   RVC_TRY
-  ConvLayer L;
+  OwnedConvLayer L;
   conv2d3x3_layer_init(L, w, bias, Co, Ci);
   ConvEpilogue e; e.act = relu ? ACT_RELU : ACT_NONE; e.act_before_res = 1; e.R = res; e.ldR = (long long)H * W;
-  try { conv2d_run(L, (hipStream_t)stream, x, (long long)H * W, H, W, y, (long long)H * W, e); check_launch(); RVC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream)); }
-  catch (...) { conv_layer_free(L); throw; }
-  conv_layer_free(L);
+  conv2d_run(L, (hipStream_t)stream, x, (long long)H * W, H, W, y, (long long)H * W, e);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   RVC_CATCH
 }
 int rvc_op_conv_transpose2d(void* stream, const float* x, const float* w, const float* bias, float* y, int Ci, int Co, int H, int W, int relu) {
   RVC_TRY
-  ConvLayer L;
+  OwnedConvLayer L;
   tconv2d_layer_init(L, w, bias, Ci, Co);
   ConvEpilogue e; e.act = relu ? ACT_RELU : ACT_NONE;
-  try { conv2d_run(L, (hipStream_t)stream, x, (long long)H * W, H, W, y, 4LL * H * W, e); check_launch(); RVC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream)); }
-  catch (...) { conv_layer_free(L); throw; }
-  conv_layer_free(L);
+  conv2d_run(L, (hipStream_t)stream, x, (long long)H * W, H, W, y, 4LL * H * W, e);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   RVC_CATCH
 }
 int rvc_op_gemm_tn(void* stream, const float* a, const float* b, float* y, int M, int N, int K, int batch) {
@@ -955,14 +895,15 @@ int rvc_op_gemm_tn(void* stream, const float* a, const float* b, float* y, int M
 int rvc_conv1d_plan_create(const float* w, const float* bias, int Ci, int Co, int k, int stride, int pad, int dil, int groups,
                            rvc_conv1d_plan** out) {
   RVC_TRY
-  rvc_conv1d_plan* p = new rvc_conv1d_plan();
-  try { conv1d_layer_init(p->L, w, bias, Co, Ci, k, stride, pad, dil, groups); } catch (...) { delete p; throw; }
-  *out = p;
+  std::unique_ptr<rvc_conv1d_plan> p(new rvc_conv1d_plan());
+  conv1d_layer_init(p->L, w, bias, Co, Ci, k, stride, pad, dil, groups);
+  *out = p.release();
   RVC_CATCH
 }
 int rvc_conv1d_plan_run(rvc_conv1d_plan* p, void* stream, const float* x, int Tin, const float* res, float* y, int pre_act, float pre_slope,
                         int act, float act_slope) {
   RVC_TRY
+  RVC_REQUIRE(p, "null argument");
   ConvEpilogue e; e.pre_act = pre_act; e.pre_slope = pre_slope; e.act = act; e.act_slope = act_slope;
   const int Tout = conv1d_out_len(p->L, Tin);
   e.R = res; e.ldR = Tout;
@@ -1024,7 +965,7 @@ int rvc_conv1d_plan_pair_arithmetic(rvc_conv1d_plan* c1, rvc_conv1d_plan* c2, in
     return conv_x3_pair_plan(c1->L, c2->L, nullptr, T, T, T, nullptr, T, e, h2, p) && p.a.h2 ? 1 : 0;
   } catch (...) { return -1; }
 }
-int rvc_conv1d_plan_destroy(rvc_conv1d_plan* p) { if (p) { conv_layer_free(p->L); delete p; } return 0; }
+int rvc_conv1d_plan_destroy(rvc_conv1d_plan* p) { delete p; return 0; }
 int rvc_op_attention(void* stream, const float* q, const float* k, const float* v_rm, const float* bv, float* out, int heads, int T) {
   RVC_TRY
   attention_fused((hipStream_t)stream, q, k, T, v_rm, (long long)heads * 64, bv, out, T, heads, 64, T);
@@ -1048,16 +989,13 @@ int rvc_op_layernorm_c_split(void* stream, const float* x, const float* gamma, c
   RVC_TRY
   RVC_REQUIRE(x && gamma && beta && y_img_f32 && C > 0 && (C & 15) == 0 && T > 0, "bad argument");
   hipStream_t s = (hipStream_t)stream;
-  unsigned char* img = nullptr;
-  try {
-    const long long tp = split_image_tp(T);
-    RVC_HIP_CHECK(hipMalloc(&img, split_image_bytes(C, T)));
-    layernorm_c_split(s, x, gamma, beta, y, img, tp, kSplitMargin, C, T, T, 1e-5f);
-    split_image_to_f32(s, img, tp, C, T, y_img_f32, T);
-    check_launch();
-    RVC_HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) { (void)hipFree(img); throw; }
-  (void)hipFree(img);
+  DevBytes img;
+  const long long tp = split_image_tp(T);
+  img.alloc(split_image_bytes(C, T));
+  layernorm_c_split(s, x, gamma, beta, y, img.p, tp, kSplitMargin, C, T, T, 1e-5f);
+  split_image_to_f32(s, img.p, tp, C, T, y_img_f32, T);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
   RVC_CATCH
 }
 int rvc_op_sine_source(void* stream, const float* f0, const float* noise, float* har, float* sine, int T, int upp, float sr, float lw, float lb,
@@ -1120,44 +1058,35 @@ int rvc_debug_gemm_split_bench(void* stream, int Ci, int Co, int T, int ksplit, 
   const int kt = w2d > 0 ? 9 : 1;
   std::vector<float> w((size_t)Co * Ci * kt), b((size_t)Co, 0.01f);
   uint32_t st = 12345u;
-  std::vector<ConvLayer> Ls((size_t)nlayers);
-  float* x = nullptr; float* r = nullptr; float* y = nullptr; unsigned char* xs = nullptr; unsigned char* ys = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  auto cleanup = [&]() {
-    conv_x3s_force(0, 0, 0);
-    if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1);
-    dev_free(x); if (r) (void)hipFree(r); if (y) (void)hipFree(y); if (xs) (void)hipFree(xs); if (ys) (void)hipFree(ys);
-    for (auto& L : Ls) conv_layer_free(L);
-  };
-  try {
-    for (auto& L : Ls) {      // distinct weights per layer: cycled through, they come from HBM like a model's layers do
-      for (auto& v : w) { st = st * 1664525u + 1013904223u; v = ((float)(st >> 8) / 8388608.f - 1.f) * 0.05f; }
-      ConvBuildScope scope(2);
-      if (w2d > 0) conv2d3x3_layer_init(L, w.data(), b.data(), Co, Ci); else conv1d_layer_init(L, w.data(), b.data(), Co, Ci, 1, 1, 0, 1, 1);
-    }
-    SplitGeom g; if (w2d > 0) g = split_geom_2d(w2d);
-    const long long tp = ((long long)g.margin + T + 704 + 63) & ~63LL;
-    std::vector<float> hx((size_t)Ci * T);
-    for (auto& v : hx) { st = st * 1664525u + 1013904223u; v = (float)(st >> 8) / 8388608.f - 1.f; }
-    x = dev_upload(hx.data(), hx.size());
-    RVC_HIP_CHECK(hipMalloc(&r, (size_t)Co * T * 4)); RVC_HIP_CHECK(hipMemset(r, 0, (size_t)Co * T * 4));
-    RVC_HIP_CHECK(hipMalloc(&y, (size_t)Co * T * 4));
-    const size_t ib = (size_t)(Ci / 16) * 4 * tp * 16, ob = (size_t)((Co + 15) / 16) * 4 * tp * 16;
-    RVC_HIP_CHECK(hipMalloc(&xs, ib)); RVC_HIP_CHECK(hipMemset(xs, 0, ib)); RVC_HIP_CHECK(hipMalloc(&ys, ob)); RVC_HIP_CHECK(hipMemset(ys, 0, ob));
-    split_image_from_f32(s, x, T, Ci, T, xs + (size_t)(g.margin - kSplitMargin) * 16, tp);
-    ConvEpilogue e;
-    if (split_out) { e.act = ACT_GELU; e.ys_out = ys; e.ys_tp = tp; } else { e.R = r; e.ldR = T; }
-    conv_x3s_force(ksplit, am, an);
-    for (auto& L : Ls) conv_x3s_run(L, s, xs, tp, T, split_out ? nullptr : y, T, e, w2d > 0 ? &g : nullptr);
-    RVC_HIP_CHECK(hipEventCreate(&e0)); RVC_HIP_CHECK(hipEventCreate(&e1));
-    RVC_HIP_CHECK(hipEventRecord(e0, s));
-    for (int i = 0; i < reps; ++i) conv_x3s_run(Ls[(size_t)(i % nlayers)], s, xs, tp, T, split_out ? nullptr : y, T, e, w2d > 0 ? &g : nullptr);
-    RVC_HIP_CHECK(hipEventRecord(e1, s));
-    RVC_HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0.f; RVC_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    *us_out = ms * 1e3f / (float)reps;
-  } catch (...) { cleanup(); throw; }
-  cleanup();
+  std::vector<OwnedConvLayer> Ls((size_t)nlayers);
+  DevBuf<float> x, r, y; DevBytes xs, ys;
+  struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void)hipEventDestroy(e); } } e0, e1;
+  for (auto& L : Ls) {      // distinct weights per layer: cycled through, they come from HBM like a model's layers do
+    for (auto& v : w) { st = st * 1664525u + 1013904223u; v = ((float)(st >> 8) / 8388608.f - 1.f) * 0.05f; }
+    ConvBuildScope scope(2);
+    if (w2d > 0) conv2d3x3_layer_init(L, w.data(), b.data(), Co, Ci); else conv1d_layer_init(L, w.data(), b.data(), Co, Ci, 1, 1, 0, 1, 1);
+  }
+  SplitGeom g; if (w2d > 0) g = split_geom_2d(w2d);
+  const long long tp = ((long long)g.margin + T + 704 + 63) & ~63LL;
+  std::vector<float> hx((size_t)Ci * T);
+  for (auto& v : hx) { st = st * 1664525u + 1013904223u; v = (float)(st >> 8) / 8388608.f - 1.f; }
+  x.upload(hx);
+  r.alloc((size_t)Co * T); RVC_HIP_CHECK(hipMemset(r.p, 0, (size_t)Co * T * 4));
+  y.alloc((size_t)Co * T);
+  const size_t ib = (size_t)(Ci / 16) * 4 * tp * 16, ob = (size_t)((Co + 15) / 16) * 4 * tp * 16;
+  xs.alloc(ib); RVC_HIP_CHECK(hipMemset(xs.p, 0, ib)); ys.alloc(ob); RVC_HIP_CHECK(hipMemset(ys.p, 0, ob));
+  split_image_from_f32(s, x.p, T, Ci, T, xs.p + (size_t)(g.margin - kSplitMargin) * 16, tp);
+  ConvEpilogue e;
+  if (split_out) { e.act = ACT_GELU; e.ys_out = ys.p; e.ys_tp = tp; } else { e.R = r.p; e.ldR = T; }
+  X3sForceScope force(ksplit, am, an);
+  for (auto& L : Ls) conv_x3s_run(L, s, xs.p, tp, T, split_out ? nullptr : y.p, T, e, w2d > 0 ? &g : nullptr);
+  RVC_HIP_CHECK(hipEventCreate(&e0.e)); RVC_HIP_CHECK(hipEventCreate(&e1.e));
+  RVC_HIP_CHECK(hipEventRecord(e0.e, s));
+  for (int i = 0; i < reps; ++i) conv_x3s_run(Ls[(size_t)(i % nlayers)], s, xs.p, tp, T, split_out ? nullptr : y.p, T, e, w2d > 0 ? &g : nullptr);
+  RVC_HIP_CHECK(hipEventRecord(e1.e, s));
+  RVC_HIP_CHECK(hipEventSynchronize(e1.e));
+  float ms = 0.f; RVC_HIP_CHECK(hipEventElapsedTime(&ms, e0.e, e1.e));
+  *us_out = ms * 1e3f / (float)reps;
   RVC_CATCH
 }
 

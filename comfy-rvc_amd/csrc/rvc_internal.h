@@ -160,7 +160,6 @@ void conv2d1x1_layer_init(ConvLayer& L, const float* w /*[Co][Ci]*/, const float
 void tconv2d_layer_init(ConvLayer& L, const float* w /*[Ci][Co][3][3]*/, const float* bias, int Ci, int Co);
 // general KH x KW window with asymmetric zero padding, bf16x3 image only (no fp32 twin): the layers run on conv_x3s_run
 void conv2d_kx_layer_init(ConvLayer& L, const float* w /*[Co][Ci][KH][KW]*/, const float* bias, int Co, int Ci, int KH, int KW, int PH, int PWL);
-void conv_layer_free(ConvLayer& L);
 // Layers initialised while this is on also get a bf16x3 split weight image and run on conv_x3_kernel when eligible
 // (stride 1, groups 1, Ci % 16 == 0): 3 bf16 MFMAs per fp32 product, fp32 accumulate, ~1e-5 relative error.
 // Both switches are THREAD-LOCAL (a model is built by the thread that calls *_finalize; two threads building models at the same time
@@ -259,11 +258,46 @@ const char* conv_prof_cfg_name(int i);
 void conv_timing_read(unsigned long long* out8, bool reset);   // debug builds (-DRVC_CONV_TIMING): per-phase cycle sums
 
 // ----------------------------------------------------------------------------- device memory
-float* dev_upload(const float* host, size_t n);
+// Ownership: every device allocation has exactly one owner whose destructor frees it - DevBuf (a vector), OwnedConvLayer (a layer's weight images), Arena (a model's
+// activation block), Mdx23::Lane (stream, event, accumulator).  Owners are move-only members of heap objects (models, indices, plans) or locals; none has static
+// storage duration, so no destructor runs after the HIP runtime has shut down.  The per-stream scratch pool is the one process-wide holder: raw pointers, released
+// by stream_scratch_release.  DevBuf and OwnedConvLayer reach the device only through dev_alloc / dev_upload / dev_free (a host-only program may define its own).
+void* dev_alloc(size_t bytes);
+void* dev_upload(const void* host, size_t bytes);   // dev_alloc + blocking copy (at least one byte is allocated: the result is never null)
+template <typename T> T* dev_upload(const T* host, size_t n) { return static_cast<T*>(dev_upload(static_cast<const void*>(host), n * sizeof(T))); }
+void dev_free(void* p);                             // null is a no-op
 void* stream_scratch(hipStream_t s, int slot, size_t bytes);   // persistent per-(device, stream) scratch (grows on demand)
 void* stream_scratch_zeroed(hipStream_t s, int slot, size_t bytes, bool* fresh = nullptr);   // zero-filled when (re)allocated; users leave it zero
 void stream_scratch_release(int device);                        // frees the scratch of one device (last context of the device destroyed)
-void dev_free(void* p);
+
+// move-only owner of one device allocation of n elements; .p / .n are read by the graphs (never written from outside)
+template <typename T> struct DevBuf {
+  T* p = nullptr; size_t n = 0;
+  DevBuf() = default;
+  ~DevBuf() { dev_free(p); }
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { dev_free(p); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+  DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+  T* get() const { return p; }
+  void reset() { dev_free(p); p = nullptr; n = 0; }
+  void alloc(size_t cnt) { reset(); p = static_cast<T*>(dev_alloc(cnt * sizeof(T))); n = cnt; }   // uninitialised
+  void upload(const T* h, size_t cnt) { reset(); p = dev_upload(h, cnt); n = cnt; }
+  void upload(const std::vector<T>& h) { upload(h.data(), h.size()); }
+};
+
+// A layer that owns its five weight allocations.  Planners, eligibility questions and *_run take the plain `const ConvLayer&` it converts to; a non-owning VIEW
+// is an explicit copy of that base (`ConvLayer v = owner;`), valid while the owner lives and never freed.
+struct OwnedConvLayer : ConvLayer {
+  OwnedConvLayer() = default;
+  ~OwnedConvLayer() { free_weights(); }
+  OwnedConvLayer(OwnedConvLayer&& o) noexcept : ConvLayer(o) { o.disown(); }
+  OwnedConvLayer& operator=(OwnedConvLayer&& o) noexcept { if (this != &o) { free_weights(); ConvLayer::operator=(o); o.disown(); } return *this; }
+  OwnedConvLayer(const OwnedConvLayer&) = delete; OwnedConvLayer& operator=(const OwnedConvLayer&) = delete;
+  OwnedConvLayer(const ConvLayer&) = delete; OwnedConvLayer& operator=(const ConvLayer&) = delete;
+ private:
+  void disown() { Wd_ = bd_ = bd4_ = nullptr; Wx_ = Wh_ = nullptr; }
+  void free_weights() { dev_free(Wd_); dev_free(bd_); dev_free(bd4_); dev_free(Wx_); dev_free(Wh_); }
+};
 
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to a device's copy of the kernel: set it once per (call site = kernel instantiation, device),
 // not once per process - rvc_ctx_create takes a device id, and a second GPU driven from the same process would otherwise launch with the default
@@ -293,6 +327,9 @@ struct Arena {
   }
   void ensure(size_t bytes);
   void release();
+  Arena() = default;
+  ~Arena() { release(); }
+  Arena(const Arena&) = delete; Arena& operator=(const Arena&) = delete;
 };
 
 }  // namespace rvc

@@ -16,8 +16,8 @@ constexpr int kSpecRowPad = 2;        // complex values between the frames' LDS 
                                       // per half-wave fall on 32 distinct even banks
 constexpr int kMelCols = 64;          // frames per workgroup of mel_project_kernel
 
-struct SpecTables { float2* tw = nullptr; float* win = nullptr; };                     // tw [3 n_fft / 4 + 1] = exp(-2 pi i t / n_fft), win [n_fft]
-struct MelBank { int n_fft = 0, n_mels = 0; int* rows = nullptr; float* w = nullptr; };   // rows [n_mels][3] = (first bin, count, offset into w)
+struct SpecTables { DevBuf<float2> tw; DevBuf<float> win; };                     // tw [3 n_fft / 4 + 1] = exp(-2 pi i t / n_fft), win [n_fft]
+struct MelBank { int n_fft = 0, n_mels = 0; DevBuf<int> rows; DevBuf<float> w; };   // rows [n_mels][3] = (first bin, count, offset into w)
 struct SpecState {
   std::mutex mu;
   std::map<int, SpecTables> tables;
@@ -30,15 +30,9 @@ static SpecState* spec_state(Ctx* ctx) {
   if (!ctx->spec) ctx->spec = new SpecState();
   return ctx->spec;
 }
-void spec_state_free(Ctx* ctx) {
-  if (!ctx->spec) return;
-  for (auto& kv : ctx->spec->tables) { dev_free(kv.second.tw); dev_free(kv.second.win); }
-  for (auto& kv : ctx->spec->banks) { dev_free(kv.second.rows); dev_free(kv.second.w); }
-  delete ctx->spec;
-  ctx->spec = nullptr;
-}
+void spec_state_free(Ctx* ctx) { delete ctx->spec; ctx->spec = nullptr; }
 
-static SpecTables spec_tables(Ctx* ctx, int n_fft) {
+static const SpecTables& spec_tables(Ctx* ctx, int n_fft) {   // (std::map nodes are address-stable and a table is never replaced)
   SpecState* st = spec_state(ctx);
   std::lock_guard<std::mutex> lk(st->mu);
   auto it = st->tables.find(n_fft);
@@ -56,10 +50,9 @@ static SpecTables spec_tables(Ctx* ctx, int n_fft) {
   }
   for (int n = 0; n < n_fft; ++n) win[n] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)n / (double)n_fft));   // torch.hann_window(n_fft), periodic
   SpecTables T;
-  T.tw = (float2*)dev_upload(tw.data(), tw.size());
-  T.win = dev_upload(win.data(), win.size());
-  st->tables[n_fft] = T;
-  return T;
+  T.tw.upload(reinterpret_cast<const float2*>(tw.data()), (size_t)nt);
+  T.win.upload(win);
+  return st->tables[n_fft] = std::move(T);
 }
 
 // Clip tables in device memory, int64 [n_clips][4]: (sample offset, samples, first output column, first workgroup of the clip).  The workgroup finds
@@ -209,9 +202,9 @@ void spectrogram_batch(Ctx* ctx, hipStream_t s, const float* audio, long long n_
   }
   RVC_REQUIRE(blocks < (1LL << 31), "too many frames for one call");
   if (blocks == 0) return;
-  const SpecTables T = spec_tables(ctx, n_fft);
+  const SpecTables& T = spec_tables(ctx, n_fft);
   SpecArgs a;
-  a.audio = audio; a.n_clips = n_clips; a.hop = hop; a.pad = pad; a.eps = eps; a.clamp = clamp; a.tw = T.tw; a.win = T.win; a.out = out; a.pitch = pitch;
+  a.audio = audio; a.n_clips = n_clips; a.hop = hop; a.pad = pad; a.eps = eps; a.clamp = clamp; a.tw = T.tw.p; a.win = T.win.p; a.out = out; a.pitch = pitch;
   upload_clips(s, 20, rows, n_clips, &a.clips);
   const int M = n_fft / 2;
   const size_t lds = ((size_t)kSpecFrames * (M + kSpecRowPad) + 3 * M / 2 + 1) * sizeof(float2);
@@ -238,11 +231,11 @@ void mel_filterbank_set(Ctx* ctx, int n_fft, int n_mels, const int* first, const
   SpecState* st = spec_state(ctx);
   std::lock_guard<std::mutex> lk(st->mu);
   MelBank& B = st->banks[std::make_pair(n_fft, n_mels)];
-  if (B.rows) RVC_HIP_CHECK(hipDeviceSynchronize());      // a replaced bank may still be read by an earlier call
-  dev_free(B.rows); dev_free(B.w);
+  if (B.rows.p) RVC_HIP_CHECK(hipDeviceSynchronize());      // a replaced bank may still be read by an earlier call
+  B.rows.reset(); B.w.reset();
   B.n_fft = n_fft; B.n_mels = n_mels;
-  B.rows = (int*)dev_upload((const float*)rows.data(), rows.size());        // (a 4-byte copy: the helper does not look at the values)
-  B.w = dev_upload(weights, (size_t)total);
+  B.rows.upload(rows);
+  B.w.upload(weights, (size_t)total);
 }
 
 struct MelArgs {
@@ -274,12 +267,12 @@ void spec_to_mel_batch(Ctx* ctx, hipStream_t s, const float* spec, long long spe
                        float* mel, long long mel_pitch) {
   RVC_REQUIRE(n_clips >= 0 && spec_pitch >= 0 && mel_pitch >= 0, "bad argument");
   SpecState* st = spec_state(ctx);
-  MelBank B;
+  const int* bank_rows; const float* bank_w;
   {
     std::lock_guard<std::mutex> lk(st->mu);
     auto it = st->banks.find(std::make_pair(n_fft, n_mels));
     RVC_REQUIRE(it != st->banks.end(), "no filterbank was set for this (n_fft, n_mels)");
-    B = it->second;
+    bank_rows = it->second.rows.p; bank_w = it->second.w.p;
   }
   std::vector<long long> rows((size_t)n_clips * 4);
   long long blocks = 0;
@@ -292,7 +285,7 @@ void spec_to_mel_batch(Ctx* ctx, hipStream_t s, const float* spec, long long spe
   RVC_REQUIRE(blocks < (1LL << 31), "too many frames for one call");
   if (blocks == 0) return;
   MelArgs a;
-  a.spec = spec; a.spec_pitch = spec_pitch; a.n_clips = n_clips; a.rows = B.rows; a.w = B.w; a.n_mels = n_mels; a.mel = mel; a.mel_pitch = mel_pitch;
+  a.spec = spec; a.spec_pitch = spec_pitch; a.n_clips = n_clips; a.rows = bank_rows; a.w = bank_w; a.n_mels = n_mels; a.mel = mel; a.mel_pitch = mel_pitch;
   upload_clips(s, 21, rows, n_clips, &a.clips);
   hipLaunchKernelGGL(mel_project_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
 }

@@ -39,6 +39,35 @@ def test_crepe_probabilities_match_oracle(nets, model, hop, pad, seconds):
     assert np.max(np.abs(p.T - ref)) < 1e-3                         # sigmoid outputs in [0, 1]; measured ~1e-5
 
 
+def test_finalize_lifecycle_leaves_a_failed_handle_not_ready(nets):
+    """A second rvc_crepe_finalize finds the tensor store empty (the first one cleared it): it fails, and the handle is NOT ready - the next forward is refused
+    before any launch (output untouched) instead of running on freed weights.  Feeding the tensors again and finalizing again restores the handle, bit for bit.
+    Smallest case of this file: "tiny", 0.5 s, hop 64, no padding."""
+    import ctypes as C
+    from comfy_rvc_amd import _lib
+    from comfy_rvc_amd.lib.crepe import Crepe
+    sd = {k: v for k, v in nets["tiny"][0].items() if "num_batches_tracked" not in k}
+    net = Crepe(sd, "tiny")                                          # create, set tensors, finalize
+    x = torch.from_numpy(S.synth_audio(0.5, seed=11)).to(net.device, torch.float32).contiguous()
+    p0 = net.probabilities(x, 64, pad=False).clone()
+    assert _lib.lib.rvc_crepe_finalize(net._h) == 1
+    out = torch.full_like(p0, -7.0)
+    with torch.cuda.device(net.device):
+        st = _lib.lib.rvc_crepe_forward(net._h, _lib.current_stream(), _lib.ptr(x), x.numel(), 64, 0, _lib.ptr(out), None)
+    assert st == 1 and b"finalize" in _lib.lib.rvc_last_error()
+    torch.cuda.synchronize()
+    assert bool((out == -7.0).all())
+    with torch.cuda.device(net.device):
+        _lib.set_tensors(_lib.lib.rvc_crepe_set_tensor, net._h, sd)
+        assert _lib.lib.rvc_crepe_finalize(net._h) == 0
+    assert torch.equal(net.probabilities(x, 64, pad=False), p0)
+    assert _lib.lib.rvc_crepe_destroy(net._h) == 0
+    net._h = None
+    h = C.c_void_p()
+    _lib.check(_lib.lib.rvc_crepe_create(_lib.get_ctx(net.device.index or 0), 1, C.byref(h)))
+    assert _lib.lib.rvc_crepe_destroy(h) == 0                        # never finalized: nothing to free but the handle
+
+
 def test_device_viterbi_matches_host_decoding(nets):
     """rvc_crepe_viterbi (masked softmax, banded Viterbi in float64, back-pointer walk, periodicity gather) against lib/crepe.py's host
     implementation (itself pinned to the oracle's literal librosa restatement in tests/test_host_logic.py), on flat network output
