@@ -50,12 +50,17 @@ class SynthConfig(C.Structure):
                 ("n_layers", c_int), ("kernel_size", c_int), ("n_resblock_kernels", c_int),
                 ("resblock_kernel_sizes", c_int * 3), ("resblock_dilations", (c_int * 3) * 3), ("n_upsamples", c_int),
                 ("upsample_rates", c_int * 8), ("upsample_kernel_sizes", c_int * 8), ("upsample_initial_channel", c_int),
-                ("spk_embed_dim", c_int), ("gin_channels", c_int), ("sr", c_int), ("feat_dim", c_int)]
+                ("spk_embed_dim", c_int), ("gin_channels", c_int), ("sr", c_int), ("feat_dim", c_int),
+                ("spec_channels", c_int), ("segment_size", c_int)]
 
 
 class SynthTaps(C.Structure):
     _fields_ = [(n, c_void_p) for n in ("enc_p_layer0", "m_p", "logs_p", "z_p", "z", "sine_waves", "har_source", "gen_ups0",
                                         "gen_last")]
+
+
+class SynthForwardTaps(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("z", "z_p", "m_p", "logs_p", "m_q", "logs_q")]
 
 
 # every symbol include/rvc_hip.h declares (tests check that the library exports all of them)
@@ -106,6 +111,11 @@ SIGNATURES = {
                                 c_void_p, P(SynthTaps)]),
     "rvc_synth_infer_window": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                        c_void_p, P(SynthTaps), c_int64, c_int64]),
+    "rvc_synth_has_posterior": (c_int, [c_void_p]),
+    "rvc_synth_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64,
+                                  c_void_p, P(SynthForwardTaps)]),
+    "rvc_kl_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
+    "rvc_l1_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "rvc_synth_dec_halo": (c_int, [c_void_p]),
     "rvc_synth_window_frames": (c_int, [c_void_p, c_int64, c_int64, c_int64, P(c_int64), P(c_int64)]),
     "rvc_synth_infer_window_halo": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,

@@ -5,6 +5,7 @@
 // dataset_prep.hip: every block reduces its tile, ONE block chains the tile totals through LDS, every block scans its tile again from its true offset.
 #include "rvc_internal.h"
 #include "ops.h"
+#include "signal_dev.h"
 
 namespace rvc {
 
@@ -316,14 +317,6 @@ void gate_apply(hipStream_t s, const float* x, float* y, long long n, const long
 }
 
 // ================================================================================================ reductions: normalise, peak limit
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 __device__ __forceinline__ float block_max(float v, float* red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));

@@ -38,12 +38,25 @@ struct EncLayer {
   OwnedConvLayer o, ffn1, ffn2;
   DevVec g1, b1, g2, b2;
 };
+// modules.WN (reference lib/infer_pack/modules.py:130-209) with dilation_rate 1: n layers; the flow's couplings hold 3, the posterior encoder 16
+struct WNStack {
+  int n = 0;
+  std::vector<OwnedConvLayer> in, res, skip;   // in_layers; res_skip_layers split into their residual (layers 0 .. n - 2) and skip rows: the plain path
+  std::vector<OwnedConvLayer> in_gate;   // in_layers with their 2 H rows in wn_gate_row_order: the gate runs in the split-resident GEMM's epilogue (conv_x3s.hip), the 2 H-row tensor is never stored
+  std::vector<OwnedConvLayer> rs;        // res_skip_layers 0 .. n - 2 whole (2 H rows: residual | skip): the split-resident path
+  DevVec cond_w, cond_b;   // weight-normed cond_layer [2*H*n][gin]
+};
 struct FlowLayer {
-  OwnedConvLayer pre, post, in[3], res[2], skip[3];
-  OwnedConvLayer in_gate[3];   // in_layers with their 2 H rows in wn_gate_row_order: the gate runs in the split-resident GEMM's epilogue (conv_x3s.hip), the 2 H-row tensor is never stored
-  OwnedConvLayer rs[2];    // res_skip_layers 0 / 1 whole (2 H rows: residual | skip) and
-  OwnedConvLayer post_neg; // post with negated weights (x1 - m as a plain residual add): the split-resident path (conv_x3s.hip)
-  DevVec cond_w, cond_b;   // weight-normed cond_layer [2*H*3][gin]
+  OwnedConvLayer pre, post;
+  OwnedConvLayer post_neg; // post with negated weights (x1 - m as a plain residual add): the split-resident path (conv_x3s.hip) in the reverse direction
+  WNStack wn;
+};
+// PosteriorEncoder (reference lib/infer_pack/models.py:199-238), built only when the checkpoint holds enc_q.*
+struct Posterior {
+  bool built = false;
+  int spec = 0, Kp = 0;    // spectrogram rows, and the same rounded up to 32: the rows pre reads (weight columns and operand rows past `spec` are zero)
+  OwnedConvLayer pre, proj;
+  WNStack wn;
 };
 struct ResBlock { OwnedConvLayer c1[3], c2[3]; };
 struct GenStage { OwnedConvLayer up, noise; DevVec noise_w, noise_b; int u = 1, k = 1, noise_k = 1, noise_s = 1; ResBlock rb[3]; };   // noise_w / _b: raw [C][k] / [C] for the streaming kernel (k <= 8)
@@ -53,6 +66,7 @@ struct SynthWeights {    // what synth_finalize builds, and what the graph has l
   std::vector<EncLayer> enc;
   OwnedConvLayer proj;
   FlowLayer flow[4];
+  Posterior post_enc;
   OwnedConvLayer conv_pre;
   DevVec dec_cond_w, dec_cond_b, conv_post_w;   // conv_post_w: raw [Ci][7] weights of the 1-channel output conv (ops.hip::conv_to1)
   std::vector<GenStage> stages;
@@ -68,6 +82,7 @@ struct Synth : SynthWeights {
   int inter = 192, hidden = 192, filt = 768, n_heads = 2, n_layers = 6, ksz = 3, gin = 256, n_spk = 1, sr = 40000, feat_dim = 768;
   int up_init = 512; std::vector<int> rb_k, up_rates, up_k; std::vector<std::vector<int>> rb_d;
   int upp = 1;
+  int spec_channels = 0, segment = 0;   // training forward: rows of the posterior's spectrogram, frames of the generator's slice
   bool f0 = true;        // false: the *_nono family (no pitch embedding, plain Generator: reference models.py:244-311,:812-1022)
 };
 
@@ -77,6 +92,7 @@ Synth* synth_create(Ctx* ctx, const SynthConfig& c) {
   S->inter = c.inter_channels; S->hidden = c.hidden_channels; S->filt = c.filter_channels; S->n_heads = c.n_heads;
   S->n_layers = c.n_layers; S->ksz = c.kernel_size; S->gin = c.gin_channels; S->n_spk = c.spk_embed_dim; S->sr = c.sr;
   S->feat_dim = c.feat_dim; S->up_init = c.upsample_initial_channel;
+  S->spec_channels = c.spec_channels; S->segment = c.segment_size;
   RVC_REQUIRE(c.n_resblock_kernels == 3, "ResBlock1 x3 expected");
   for (int i = 0; i < 3; ++i) { S->rb_k.push_back(c.resblock_kernel_sizes[i]); S->rb_d.push_back({c.resblock_dilations[i][0], c.resblock_dilations[i][1], c.resblock_dilations[i][2]}); }
   S->upp = 1;
@@ -89,6 +105,7 @@ void synth_set_tensor(Synth* S, const char* name, const float* d, const long lon
 int synth_upp(const Synth* S) { return S->upp; }
 int synth_feat_dim(const Synth* S) { return S->feat_dim; }
 bool synth_has_f0(const Synth* S) { return S->f0; }
+bool synth_has_posterior(const Synth* S) { return S->ready && S->post_enc.built; }
 
 // Frames of z on either side of a kept output window that the generator's result inside the window depends on (GeneratorNSF / Generator, reference
 // lib/infer_pack/models.py:460-566,:244-311): the layer table walked backwards from the waveform.  h = reach in samples at the current rate.
@@ -112,6 +129,41 @@ int synth_dec_halo_frames(const Synth* S) {
     h = std::max((h + ku - 1 - p) / u, (h + p + u - 1) / u);
   }
   return (int)(h + 3);
+}
+
+// the weight-normed layers of one modules.WN under prefix p ("flow.flows.0.enc." / "enc_q.enc."), kernel 5, dilation 1
+static void make_wn(const TensorStore& ts, const std::string& p, int n, int C, WNStack& W) {
+  W.n = n;
+  W.in.resize(n); W.in_gate.resize(n); W.skip.resize(n); W.res.resize(n - 1); W.rs.resize(n - 1);
+  for (int i = 0; i < n; ++i) {
+    W.in[i] = make_conv1d(ts, p + "in_layers." + std::to_string(i), 1, 2, 1, true);
+    if ((C & 15) == 0) {
+      const std::string q = p + "in_layers." + std::to_string(i);
+      const HostTensor& v = ts.get(q + ".weight_v");
+      const std::vector<float> w = weight_norm0(v, ts.get(q + ".weight_g"));
+      const std::vector<float>& b = ts.get(q + ".bias").data;
+      const int Ci = (int)v.shape[1], k = (int)v.shape[2];
+      RVC_REQUIRE((int)v.shape[0] == 2 * C, q + ": expected 2 H rows");
+      std::vector<float> wp(w.size()), bp(b.size());
+      for (int r = 0; r < 2 * C; ++r) {
+        const int src = wn_gate_row_order(r, C);
+        std::copy(w.begin() + (size_t)src * Ci * k, w.begin() + (size_t)(src + 1) * Ci * k, wp.begin() + (size_t)r * Ci * k);
+        bp[r] = b[src];
+      }
+      conv1d_layer_init(W.in_gate[i], wp.data(), bp.data(), 2 * C, Ci, k, 1, 2, 1, 1);
+    }
+    const std::string rs = p + "res_skip_layers." + std::to_string(i);
+    if (i < n - 1) {
+      W.res[i] = make_conv1d(ts, rs, 1, 0, 1, true, true, 1.f, 0, C);
+      W.skip[i] = make_conv1d(ts, rs, 1, 0, 1, true, true, 1.f, C, C);
+      W.rs[i] = make_conv1d(ts, rs, 1, 0, 1, true);
+    } else {
+      W.skip[i] = make_conv1d(ts, rs, 1, 0, 1, true);
+    }
+  }
+  W.cond_w.upload(weight_norm0(ts.get(p + "cond_layer.weight_v"), ts.get(p + "cond_layer.weight_g")));
+  W.cond_b.upload(ts.get(p + "cond_layer.bias").data);
+  RVC_REQUIRE(W.cond_b.n == (size_t)2 * C * n, p + "cond_layer: expected 2 H n rows");
 }
 
 void synth_finalize(Synth* S) {
@@ -176,34 +228,24 @@ void synth_finalize(Synth* S) {
     F.pre = make_conv1d(ts, p + "pre", 1, 0, 1, false);
     F.post = make_conv1d(ts, p + "post", 1, 0, 1, false);
     F.post_neg = make_conv1d(ts, p + "post", 1, 0, 1, false, true, -1.f);
-    for (int i = 0; i < 3; ++i) {
-      F.in[i] = make_conv1d(ts, p + "enc.in_layers." + std::to_string(i), 1, 2, 1, true);
-      if ((C & 15) == 0) {
-        const std::string q = p + "enc.in_layers." + std::to_string(i);
-        const HostTensor& v = ts.get(q + ".weight_v");
-        const std::vector<float> w = weight_norm0(v, ts.get(q + ".weight_g"));
-        const std::vector<float>& b = ts.get(q + ".bias").data;
-        const int Ci = (int)v.shape[1], k = (int)v.shape[2];
-        RVC_REQUIRE((int)v.shape[0] == 2 * C, q + ": expected 2 H rows");
-        std::vector<float> wp(w.size()), bp(b.size());
-        for (int r = 0; r < 2 * C; ++r) {
-          const int src = wn_gate_row_order(r, C);
-          std::copy(w.begin() + (size_t)src * Ci * k, w.begin() + (size_t)(src + 1) * Ci * k, wp.begin() + (size_t)r * Ci * k);
-          bp[r] = b[src];
-        }
-        conv1d_layer_init(F.in_gate[i], wp.data(), bp.data(), 2 * C, Ci, k, 1, 2, 1, 1);
-      }
-      const std::string rs = p + "enc.res_skip_layers." + std::to_string(i);
-      if (i < 2) {
-        F.res[i] = make_conv1d(ts, rs, 1, 0, 1, true, true, 1.f, 0, C);
-        F.skip[i] = make_conv1d(ts, rs, 1, 0, 1, true, true, 1.f, C, C);
-        F.rs[i] = make_conv1d(ts, rs, 1, 0, 1, true);
-      } else {
-        F.skip[i] = make_conv1d(ts, rs, 1, 0, 1, true);
-      }
-    }
-    F.cond_w.upload(weight_norm0(ts.get(p + "enc.cond_layer.weight_v"), ts.get(p + "enc.cond_layer.weight_g")));
-    F.cond_b.upload(ts.get(p + "enc.cond_layer.bias").data);
+    make_wn(ts, p + "enc.", 3, C, F.wn);
+  }
+  Posterior& Q = S->post_enc;
+  if (ts.has("enc_q.pre.weight")) {
+    // pre is a 1 x 1 projection with K = spec_channels (1025 / 513): no multiple of the 16 / 32 the GEMM family tiles K by.  The layer is built over Kp = K
+    // rounded up to 32 with ZERO weight columns behind K, and synth_forward hands it an operand whose rows behind K are zero too (0 * 0, never 0 * garbage)
+    const HostTensor& w = ts.get("enc_q.pre.weight");
+    RVC_REQUIRE(w.shape.size() == 3 && w.shape[0] == C && w.shape[2] == 1, "enc_q.pre.weight: expected [hidden][spec_channels][1]");
+    Q.spec = (int)w.shape[1];
+    RVC_REQUIRE(S->spec_channels == 0 || S->spec_channels == Q.spec, "enc_q.pre.weight does not have spec_channels input rows");
+    Q.Kp = (Q.spec + 31) & ~31;
+    std::vector<float> wp((size_t)C * Q.Kp, 0.f);
+    for (int r = 0; r < C; ++r) std::copy(w.data.begin() + (size_t)r * Q.spec, w.data.begin() + (size_t)(r + 1) * Q.spec, wp.begin() + (size_t)r * Q.Kp);
+    conv1d_layer_init(Q.pre, wp.data(), ts.get("enc_q.pre.bias", {C}).data.data(), C, Q.Kp, 1, 1, 0, 1, 1);
+    make_wn(ts, "enc_q.enc.", 16, C, Q.wn);
+    Q.proj = make_conv1d(ts, "enc_q.proj", 1, 0, 1, false);
+    RVC_REQUIRE(Q.proj.Co == 2 * S->inter && Q.proj.Ci == C, "enc_q.proj: expected [2 inter][hidden][1]");
+    Q.built = true;
   }
   S->conv_pre = make_conv1d(ts, "dec.conv_pre", 1, 3, 1, false);
   S->conv_post_w.upload(ts.get("dec.conv_post.weight").data);
@@ -269,20 +311,17 @@ static GenPairs gen_stage_pairs(const GenStage& st, int Tfull, int h2) {
   return g;
 }
 
-static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm, const long long* pitch, const float* pitchf, int sid,
-                        const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps, int g0, int g1) {
-  // [g0, g1): the frames the generator runs on (synth_infer: the keep window plus its halo; [0, T): the whole sequence).  Everything up to the flow is full length.
-  const int W = g1 - g0;
-  const int C = S->hidden, H = S->n_heads, kc = C / H, IC = S->inter;
-  const bool dry = A.dry;
-  const int h2 = conv_set_pair_arithmetic(-1);      // read once: the whole pass plans with the pair arithmetic it saw when it started
-  auto tap = [&](float* dst, const float* src, size_t n) {
-    if (!dry && dst) RVC_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  };
-  ConvEpilogue E0;
-  // ---- split-resident front (conv_x3s.hip): the activations that feed enc_p's / the flow's / conv_pre's projections live as bf16 hi / lo
-  // images written by their producers; k = 3 / 5 / 7 layers read them with taps as row offsets, so the images' margins (the zero padding)
-  // must stay zero: the block is the graph's first allocation (nothing else ever occupies it) and is zeroed once per layout.
+// The split-resident front (conv_x3s.hip): the activations that feed enc_p's / the flow's / conv_pre's projections live as bf16 hi / lo
+// images written by their producers; k = 3 / 5 / 7 layers read them with taps as row offsets, so the images' margins (the zero padding)
+// must stay zero: the block is the graph's first allocation (nothing else ever occupies it) and is zeroed once per layout.
+struct SplitImgs { unsigned char *x_s = nullptr, *attn_s = nullptr, *ff_s = nullptr, *x0_s = nullptr, *hw_s = nullptr, *acts_s = nullptr, *z_s = nullptr, *spec_s = nullptr; };
+static bool wn_split_eligible(const WNStack& W) {
+  bool ok = conv_x3s_eligible(W.skip[W.n - 1]);
+  for (int i = 0; i < W.n && ok; ++i) ok = conv_x3s_eligible(W.in[i]) && (i == W.n - 1 || conv_x3s_eligible(W.rs[i]));
+  return ok;
+}
+static bool synth_split_front(const Synth* S) {
+  const int C = S->hidden, IC = S->inter;
   bool gs = (C & 15) == 0 && (IC & 31) == 0 && conv_x3s_eligible(S->proj) && conv_x3s_eligible(S->conv_pre);
   for (int l = 0; l < S->n_layers && gs; ++l) {
     const EncLayer& e = S->enc[l];
@@ -290,34 +329,42 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
   }
   for (int f = 0; f < 4 && gs; ++f) {
     const FlowLayer& F = S->flow[f];
-    gs = conv_x3s_eligible(F.pre) && conv_x3s_eligible(F.post_neg) && conv_x3s_eligible(F.skip[2]);
-    for (int i = 0; i < 3 && gs; ++i) gs = conv_x3s_eligible(F.in[i]) && (i == 2 || conv_x3s_eligible(F.rs[i]));
+    gs = conv_x3s_eligible(F.pre) && conv_x3s_eligible(F.post_neg) && wn_split_eligible(F.wn);
   }
+  return gs;
+}
+// the image block: T columns up to the flow, W columns of z for the generator; spec_rows > 0: also the posterior's spectrogram operand.  Zeroed when the
+// layout is not the one known to be zero.
+static SplitImgs split_imgs_alloc(Synth* S, hipStream_t s, Arena& A, int T, int W, int spec_rows) {
+  const int C = S->hidden, IC = S->inter;
+  SplitImgs m;
+  const size_t img0 = A.off;
+  m.x_s = A.alloc<unsigned char>(split_image_bytes(C, T)); m.attn_s = A.alloc<unsigned char>(split_image_bytes(C, T));
+  m.ff_s = A.alloc<unsigned char>(split_image_bytes(S->filt, T));
+  m.x0_s = A.alloc<unsigned char>(split_image_bytes(IC / 2, T)); m.hw_s = A.alloc<unsigned char>(split_image_bytes(2 * C, T));
+  m.acts_s = A.alloc<unsigned char>(split_image_bytes(C, T)); m.z_s = A.alloc<unsigned char>(split_image_bytes(IC, W));
+  if (spec_rows > 0) m.spec_s = A.alloc<unsigned char>(split_image_bytes(spec_rows, T));
+  const size_t img_bytes = A.off - img0;
+  // (a shorter sequence in the same allocation leaves the longer one's rows behind its end: the length is part of the layout - both lengths: the z image
+  // holds the generator's W columns)
+  if (!A.dry && (S->img_base != A.base + img0 || S->img_gen != A.gen || S->img_bytes != img_bytes || S->img_T != T || S->img_W != W)) {
+    RVC_HIP_CHECK(hipMemsetAsync(A.base + img0, 0, img_bytes, s));
+    S->img_base = A.base + img0; S->img_gen = A.gen; S->img_bytes = img_bytes; S->img_T = T; S->img_W = W;
+  }
+  return m;
+}
+
+// TextEncoder{256,768} (reference models.py:43-58,:90-105) up to and including proj: returns stats = [m_p | logs_p], 2 inter rows of T columns
+static float* enc_p_stats(Synth* S, hipStream_t s, Arena& A, bool gs, const SplitImgs& im, const float* feat_cm, const long long* pitch, int T,
+                          float* enc_p_layer0) {
+  const int C = S->hidden, H = S->n_heads, kc = C / H, IC = S->inter;
+  const bool dry = A.dry;
   const long long tp = split_image_tp(T);
-  unsigned char *x_s = nullptr, *attn_s = nullptr, *ff_s = nullptr, *x0_s = nullptr, *hw_s = nullptr, *acts_s = nullptr, *z_s = nullptr;
-  if (gs) {
-    const size_t img0 = A.off;
-    x_s = A.alloc<unsigned char>(split_image_bytes(C, T)); attn_s = A.alloc<unsigned char>(split_image_bytes(C, T));
-    ff_s = A.alloc<unsigned char>(split_image_bytes(S->filt, T));
-    x0_s = A.alloc<unsigned char>(split_image_bytes(IC / 2, T)); hw_s = A.alloc<unsigned char>(split_image_bytes(2 * C, T));
-    acts_s = A.alloc<unsigned char>(split_image_bytes(C, T)); z_s = A.alloc<unsigned char>(split_image_bytes(IC, W));
-    const size_t img_bytes = A.off - img0;
-    // (a shorter sequence in the same allocation leaves the longer one's rows behind its end: the length is part of the layout - both lengths: the z image
-    // holds the generator's W columns)
-    if (!dry && (S->img_base != A.base + img0 || S->img_gen != A.gen || S->img_bytes != img_bytes || S->img_T != T || S->img_W != W)) {
-      RVC_HIP_CHECK(hipMemsetAsync(A.base + img0, 0, img_bytes, s));
-      S->img_base = A.base + img0; S->img_gen = A.gen; S->img_bytes = img_bytes; S->img_T = T; S->img_W = W;
-    }
-  }
-  // ---- speaker conditioning vectors
-  const float* g = S->emb_g.p + (size_t)sid * S->gin;
-  float* pre_bias = A.alloc<float>(S->up_init);
-  float* gcond[4];
-  for (int f = 0; f < 4; ++f) gcond[f] = A.alloc<float>(6 * C);
-  if (!dry) {
-    gemv(s, S->dec_cond_w.p, g, S->dec_cond_b.p, pre_bias, S->up_init, S->gin, S->conv_pre.bd_);
-    for (int f = 0; f < 4; ++f) gemv(s, S->flow[f].cond_w.p, g, S->flow[f].cond_b.p, gcond[f], 6 * C, S->gin, nullptr);
-  }
+  unsigned char *x_s = im.x_s, *attn_s = im.attn_s, *ff_s = im.ff_s;
+  auto tap = [&](float* dst, const float* src, size_t n) {
+    if (!dry && dst) RVC_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  };
+  ConvEpilogue E0;
   // ---- enc_p
   float* x = A.alloc<float>((size_t)C * T);
   float* xb = A.alloc<float>((size_t)C * T);
@@ -366,7 +413,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
           conv_x3s_run(e.ffn1, s, x_s, tp, T, nullptr, T, Ef);
           conv_x3s_run(e.ffn2, s, ff_s, tp, T, xb, T, Er);
           layernorm_c_split(s, xb, e.g2.p, e.b2.p, x, x_s, tp, kSplitMargin, C, T, T, 1e-5f);
-          if (l == 0 && taps) tap(taps->enc_p_layer0, x, (size_t)C * T);
+          if (l == 0) tap(enc_p_layer0, x, (size_t)C * T);
           continue;
         }
         if (gs) conv_x3s_run(e.qk, s, x_s, tp, T, qk, T, E0); else
@@ -393,7 +440,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
           conv_x3s_run(e.ffn1, s, x_s, tp, T, nullptr, T, Ef);                  // k = 3: taps are row offsets into the image
           conv_x3s_run(e.ffn2, s, ff_s, tp, T, xb, T, Er);
           layernorm_c_split(s, xb, e.g2.p, e.b2.p, x, x_s, tp, kSplitMargin, C, T, T, 1e-5f);
-          if (l == 0 && taps) tap(taps->enc_p_layer0, x, (size_t)C * T);
+          if (l == 0) tap(enc_p_layer0, x, (size_t)C * T);
           continue;
         }
         conv1d_run(e.o, s, attn, T, T, xb, T, Er);
@@ -402,87 +449,89 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
         conv1d_run(e.ffn1, s, x, T, T, ff, T, Ef);
         conv1d_run(e.ffn2, s, ff, T, T, xb, T, Er);
         layernorm_c(s, xb, nullptr, e.g2.p, e.b2.p, x, C, T, T, 1e-5f);
-        if (l == 0 && taps) tap(taps->enc_p_layer0, x, (size_t)C * T);
+        if (l == 0) tap(enc_p_layer0, x, (size_t)C * T);
       }
     }
     A.off = mark;
   }
   float* stats = A.alloc<float>((size_t)2 * IC * T);
-  float* z = A.alloc<float>((size_t)IC * T);
-  float* zf = A.alloc<float>((size_t)IC * T);
   if (!dry) {
     if (gs) conv_x3s_run(S->proj, s, x_s, tp, T, stats, T, E0); else
     conv1d_run(S->proj, s, x, T, T, stats, T, E0);
-    if (taps) { tap(taps->m_p, stats, (size_t)IC * T); tap(taps->logs_p, stats + (size_t)IC * T, (size_t)IC * T); }
-    zp_sample(s, stats, noise_z, z, IC, T);
-    if (taps) tap(taps->z_p, z, (size_t)IC * T);
   }
-  // ---- flow (reverse)
-  {
-    const size_t mark = A.off;
-    float* hw = A.alloc<float>((size_t)2 * C * T);               // [h | wo]: the WaveNet's residual stream and its skip sum, adjacent rows
-    float* h = hw; float* wo = hw + (size_t)C * T;
-    float* xin = A.alloc<float>((size_t)2 * C * T);
-    float* acts = gs ? nullptr : A.alloc<float>((size_t)C * T);
-    const int half = IC / 2;
-    if (!dry) {
-      float* cur = z; float* oth = zf;
-      for (int f = 3; f >= 0; --f) {
-        FlowLayer& F = S->flow[f];
-        flip_c(s, cur, oth, IC, T);
-        std::swap(cur, oth);
-        if (gs) {
-          // every layer one launch of the split-resident GEMM: the res / skip pair of a WaveNet layer is ONE 2 H-row layer accumulating in place
-          // onto [h | wo] (its image output is the next in-layer's input), post is packed negated (x1 - m = x1 + (-W) wo + (-b))
-          split_image_from_f32(s, cur, T, half, T, x0_s, tp);
-          unsigned char* wo_s = hw_s + split_image_bytes(C, T);
-          ConvEpilogue Eh; Eh.ys_out = hw_s; Eh.ys_tp = tp;
-          conv_x3s_run(F.pre, s, x0_s, tp, T, h, T, Eh);
-          fill(s, wo, 0.f, (long long)C * T);
-          for (int i = 0; i < 3; ++i) {
-            if (F.in_gate[i].Wx_ && conv_x3s_eligible(F.in_gate[i])) {
-              // k = 5 over the first H channels of the [h | wo] image, the gate in the epilogue: acts leaves as its image, the 2 H-row tensor is never stored
-              ConvEpilogue Eg; Eg.ys_out = acts_s; Eg.ys_tp = tp; Eg.gate_h = C; Eg.gate_g = gcond[f] + (size_t)i * 2 * C;
-              conv_x3s_run(F.in_gate[i], s, hw_s, tp, T, nullptr, T, Eg);
-            } else {
-              conv_x3s_run(F.in[i], s, hw_s, tp, T, xin, T, E0);                 // k = 5 over the first H channels of the [h | wo] image
-              wn_gate_split(s, xin, gcond[f] + (size_t)i * 2 * C, acts_s, tp, kSplitMargin, C, T);
-            }
-            if (i < 2) { ConvEpilogue Ea; Ea.R = hw; Ea.ldR = T; Ea.ys_out = hw_s; Ea.ys_tp = tp; conv_x3s_run(F.rs[i], s, acts_s, tp, T, hw, T, Ea); }
-            else { ConvEpilogue Ea; Ea.R = wo; Ea.ldR = T; Ea.ys_out = wo_s; Ea.ys_tp = tp; conv_x3s_run(F.skip[2], s, acts_s, tp, T, wo, T, Ea); }
-          }
-          ConvEpilogue Ep; Ep.R = cur + (size_t)half * T; Ep.ldR = T;
-          conv_x3s_run(F.post_neg, s, wo_s, tp, T, cur + (size_t)half * T, T, Ep);    // x1 = x1 - m
-          continue;
-        }
-        conv1d_run(F.pre, s, cur, T, T, h, T, E0);
-        for (int i = 0; i < 3; ++i) {
-          conv1d_run(F.in[i], s, h, T, T, xin, T, E0);
-          wn_gate(s, xin, gcond[f] + (size_t)i * 2 * C, acts, C, T);
-          ConvEpilogue Es; Es.accumulate = (i > 0);
-          conv1d_run(F.skip[i], s, acts, T, T, wo, T, Es);
-          if (i < 2) { ConvEpilogue Er; Er.R = h; Er.ldR = T; conv1d_run(F.res[i], s, acts, T, T, h, T, Er); }
-        }
-        ConvEpilogue Ep; Ep.out_scale = -1.f; Ep.accumulate = 1;
-        conv1d_run(F.post, s, wo, T, T, cur + (size_t)half * T, T, Ep);     // x1 = x1 - m
+  return stats;
+}
+
+// modules.WN.forward (reference lib/infer_pack/modules.py:184-209) over an n-layer stack, full mask: the one runner of the flow's couplings (n = 3) and of the
+// posterior encoder (n = 16).  In: the residual stream h = hw rows [0, H) (split-resident path: also its image, the first H channels of hw_s); out: the skip sum
+// wo = hw rows [H, 2 H) (and its image behind h's).  gcond: cond_layer(g), 2 H n values.
+struct WnBufs { float* hw; float* xin; float* acts; unsigned char* hw_s; unsigned char* acts_s; };
+static void wn_run(hipStream_t s, const WNStack& W, const float* gcond, bool gs, const WnBufs& b, int C, int T) {
+  const long long tp = split_image_tp(T);
+  float* h = b.hw; float* wo = b.hw + (size_t)C * T;
+  ConvEpilogue E0;
+  if (gs) {
+    // every layer one launch of the split-resident GEMM: the res / skip pair of a WaveNet layer is ONE 2 H-row layer accumulating in place
+    // onto [h | wo] (its image output is the next in-layer's input)
+    unsigned char* wo_s = b.hw_s + split_image_bytes(C, T);
+    fill(s, wo, 0.f, (long long)C * T);
+    for (int i = 0; i < W.n; ++i) {
+      if (W.in_gate[i].Wx_ && conv_x3s_eligible(W.in_gate[i])) {
+        // k = 5 over the first H channels of the [h | wo] image, the gate in the epilogue: acts leaves as its image, the 2 H-row tensor is never stored
+        ConvEpilogue Eg; Eg.ys_out = b.acts_s; Eg.ys_tp = tp; Eg.gate_h = C; Eg.gate_g = gcond + (size_t)i * 2 * C;
+        conv_x3s_run(W.in_gate[i], s, b.hw_s, tp, T, nullptr, T, Eg);
+      } else {
+        conv_x3s_run(W.in[i], s, b.hw_s, tp, T, b.xin, T, E0);                 // k = 5 over the first H channels of the [h | wo] image
+        wn_gate_split(s, b.xin, gcond + (size_t)i * 2 * C, b.acts_s, tp, kSplitMargin, C, T);
       }
-      if (cur != z) RVC_HIP_CHECK(hipMemcpyAsync(z, cur, (size_t)IC * T * sizeof(float), hipMemcpyDeviceToDevice, s));
-      if (taps) tap(taps->z, z, (size_t)IC * T);
+      if (i < W.n - 1) { ConvEpilogue Ea; Ea.R = b.hw; Ea.ldR = T; Ea.ys_out = b.hw_s; Ea.ys_tp = tp; conv_x3s_run(W.rs[i], s, b.acts_s, tp, T, b.hw, T, Ea); }
+      else { ConvEpilogue Ea; Ea.R = wo; Ea.ldR = T; Ea.ys_out = wo_s; Ea.ys_tp = tp; conv_x3s_run(W.skip[i], s, b.acts_s, tp, T, wo, T, Ea); }
     }
-    A.off = mark;
+    return;
   }
-  // ---- generator
-  const long long N = (long long)T * S->upp;
-  float* har = S->f0 ? A.alloc<float>((size_t)N) : nullptr;
-  if (S->f0) {
-    float* rad = A.alloc<float>((size_t)T);
-    float* tmp = A.alloc<float>((size_t)T);
-    double* bsum = A.alloc<double>((size_t)((N + 1023) / 1024));
-    if (!dry) {
-      sine_source(s, pitchf, noise_src, har, taps ? taps->sine_waves : nullptr, rad, tmp, bsum, T, S->upp, (float)S->sr, S->lin_w, S->lin_b);
-      if (taps) tap(taps->har_source, har, (size_t)N);
-    }
+  for (int i = 0; i < W.n; ++i) {
+    conv1d_run(W.in[i], s, h, T, T, b.xin, T, E0);
+    wn_gate(s, b.xin, gcond + (size_t)i * 2 * C, b.acts, C, T);
+    ConvEpilogue Es; Es.accumulate = (i > 0);
+    conv1d_run(W.skip[i], s, b.acts, T, T, wo, T, Es);
+    if (i < W.n - 1) { ConvEpilogue Er; Er.R = h; Er.ldR = T; conv1d_run(W.res[i], s, b.acts, T, T, h, T, Er); }
   }
+}
+
+// One ResidualCouplingLayer (reference lib/infer_pack/modules.py:436-455, mean_only) on cur [inter][T] in place: x1 -= m (reverse, infer) or x1 += m (forward,
+// training).  The split-resident path packs post with both signs (post_neg / post): either direction is a plain residual add in the GEMM's epilogue.
+static void coupling_run(Synth* S, hipStream_t s, FlowLayer& F, const float* gcond, bool gs, const SplitImgs& im, const WnBufs& b, float* cur, int T, bool reverse) {
+  const int C = S->hidden, half = S->inter / 2;
+  const long long tp = split_image_tp(T);
+  float* h = b.hw; float* wo = b.hw + (size_t)C * T;
+  float* x1 = cur + (size_t)half * T;
+  ConvEpilogue E0;
+  if (gs) {
+    split_image_from_f32(s, cur, T, half, T, im.x0_s, tp);
+    unsigned char* wo_s = b.hw_s + split_image_bytes(C, T);
+    ConvEpilogue Eh; Eh.ys_out = b.hw_s; Eh.ys_tp = tp;
+    conv_x3s_run(F.pre, s, im.x0_s, tp, T, h, T, Eh);
+    wn_run(s, F.wn, gcond, gs, b, C, T);
+    ConvEpilogue Ep; Ep.R = x1; Ep.ldR = T;
+    conv_x3s_run(reverse ? F.post_neg : F.post, s, wo_s, tp, T, x1, T, Ep);    // x1 = x1 -+ m
+    return;
+  }
+  conv1d_run(F.pre, s, cur, T, T, h, T, E0);
+  wn_run(s, F.wn, gcond, gs, b, C, T);
+  ConvEpilogue Ep; Ep.out_scale = reverse ? -1.f : 1.f; Ep.accumulate = 1;
+  conv1d_run(F.post, s, wo, T, T, x1, T, Ep);     // x1 = x1 -+ m
+}
+
+// GeneratorNSF / Generator (reference models.py:460-566,:244-311) from conv_pre on, on the W columns [g0, g0 + W) of z [inter][T] (a T-frame sequence); har: the
+// harmonic source of the whole sequence [T upp] (null: no-f0 family); out: the whole sequence's waveform, written at [g0 upp, (g0 + W) upp).  Shared by
+// synth_infer (keep window plus halo) and the training forward (the slice as a sequence of its own: T = W = segment, g0 = 0).
+static void gen_tail(Synth* S, hipStream_t s, Arena& A, bool gs, unsigned char* z_s, const float* z, const float* har, const float* pre_bias, int T, int g0, int W,
+                     int h2, float* out, const SynthTaps* taps) {
+  const int IC = S->inter;
+  const bool dry = A.dry;
+  auto tap = [&](float* dst, const float* src, size_t n) {
+    if (!dry && dst) RVC_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  };
   // From here on every tensor holds the W columns of the window; the three full-length operands are addressed at its start: z + g0 (pitch T), har + g0 upp,
   // out + g0 upp.  Every launch is planned for the whole sequence and sized for the window: beside a stage's window length (Tc, Tn) runs the whole sequence's
   // (Tfull_c, Tfull_n), handed to every planner and, as ConvEpilogue::plan_tin, to every *_run - a window's columns are computed by the kernels, tiles and K
@@ -591,6 +640,159 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
   if (!dry) conv_to1(s, cur, Tc, S->conv_post_w.p, S->up_init >> nu, 7, 3, Tc, 0.01f, 1, out + (size_t)g0 * S->upp);
 }
 
+static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm, const long long* pitch, const float* pitchf, int sid,
+                        const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps, int g0, int g1) {
+  // [g0, g1): the frames the generator runs on (synth_infer: the keep window plus its halo; [0, T): the whole sequence).  Everything up to the flow is full length.
+  const int W = g1 - g0;
+  const int C = S->hidden, IC = S->inter;
+  const bool dry = A.dry;
+  const int h2 = conv_set_pair_arithmetic(-1);      // read once: the whole pass plans with the pair arithmetic it saw when it started
+  auto tap = [&](float* dst, const float* src, size_t n) {
+    if (!dry && dst) RVC_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  };
+  const bool gs = synth_split_front(S);
+  SplitImgs im;
+  if (gs) im = split_imgs_alloc(S, s, A, T, W, 0);
+  // ---- speaker conditioning vectors
+  const float* g = S->emb_g.p + (size_t)sid * S->gin;
+  float* pre_bias = A.alloc<float>(S->up_init);
+  float* gcond[4];
+  for (int f = 0; f < 4; ++f) gcond[f] = A.alloc<float>(6 * C);
+  if (!dry) {
+    gemv(s, S->dec_cond_w.p, g, S->dec_cond_b.p, pre_bias, S->up_init, S->gin, S->conv_pre.bd_);
+    for (int f = 0; f < 4; ++f) gemv(s, S->flow[f].wn.cond_w.p, g, S->flow[f].wn.cond_b.p, gcond[f], 6 * C, S->gin, nullptr);
+  }
+  float* stats = enc_p_stats(S, s, A, gs, im, feat_cm, pitch, T, taps ? taps->enc_p_layer0 : nullptr);
+  float* z = A.alloc<float>((size_t)IC * T);
+  float* zf = A.alloc<float>((size_t)IC * T);
+  if (!dry) {
+    if (taps) { tap(taps->m_p, stats, (size_t)IC * T); tap(taps->logs_p, stats + (size_t)IC * T, (size_t)IC * T); }
+    zp_sample(s, stats, noise_z, z, IC, T);
+    if (taps) tap(taps->z_p, z, (size_t)IC * T);
+  }
+  // ---- flow (reverse)
+  {
+    const size_t mark = A.off;
+    WnBufs wb;
+    wb.hw = A.alloc<float>((size_t)2 * C * T);               // [h | wo]: the WaveNet's residual stream and its skip sum, adjacent rows
+    wb.xin = A.alloc<float>((size_t)2 * C * T);
+    wb.acts = gs ? nullptr : A.alloc<float>((size_t)C * T);
+    wb.hw_s = im.hw_s; wb.acts_s = im.acts_s;
+    if (!dry) {
+      float* cur = z; float* oth = zf;
+      for (int f = 3; f >= 0; --f) {
+        flip_c(s, cur, oth, IC, T);
+        std::swap(cur, oth);
+        coupling_run(S, s, S->flow[f], gcond[f], gs, im, wb, cur, T, true);
+      }
+      if (cur != z) RVC_HIP_CHECK(hipMemcpyAsync(z, cur, (size_t)IC * T * sizeof(float), hipMemcpyDeviceToDevice, s));
+      if (taps) tap(taps->z, z, (size_t)IC * T);
+    }
+    A.off = mark;
+  }
+  // ---- generator
+  const long long N = (long long)T * S->upp;
+  float* har = S->f0 ? A.alloc<float>((size_t)N) : nullptr;
+  if (S->f0) {
+    float* rad = A.alloc<float>((size_t)T);
+    float* tmp = A.alloc<float>((size_t)T);
+    double* bsum = A.alloc<double>((size_t)((N + 1023) / 1024));
+    if (!dry) {
+      sine_source(s, pitchf, noise_src, har, taps ? taps->sine_waves : nullptr, rad, tmp, bsum, T, S->upp, (float)S->sr, S->lin_w, S->lin_b);
+      if (taps) tap(taps->har_source, har, (size_t)N);
+    }
+  }
+  gen_tail(S, s, A, gs, im.z_s, z, har, pre_bias, T, g0, W, h2, out, taps);
+}
+
+// SynthesizerTrnMs{256,768}NSFsid[_nono].forward for one item at its own length (reference models.py:781-796,:894-903): every mask is all ones.
+static void synth_forward_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm, const long long* pitch, const float* pitchf, const float* spec, int sid,
+                                const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps) {
+  const int C = S->hidden, IC = S->inter, seg = S->segment;
+  Posterior& Q = S->post_enc;
+  const bool dry = A.dry;
+  const int h2 = conv_set_pair_arithmetic(-1);
+  const long long tp = split_image_tp(T);
+  auto tap = [&](float* dst, const float* src, size_t n) {
+    if (!dry && dst) RVC_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  };
+  ConvEpilogue E0;
+  bool gs = synth_split_front(S) && conv_x3s_eligible(Q.pre) && conv_x3s_eligible(Q.proj) && wn_split_eligible(Q.wn);
+  for (int f = 0; f < 4 && gs; ++f) gs = conv_x3s_eligible(S->flow[f].post);
+  SplitImgs im;
+  if (gs) im = split_imgs_alloc(S, s, A, T, seg, Q.Kp);
+  // ---- speaker conditioning vectors
+  const float* g = S->emb_g.p + (size_t)sid * S->gin;
+  float* pre_bias = A.alloc<float>(S->up_init);
+  float* gcond[4];
+  for (int f = 0; f < 4; ++f) gcond[f] = A.alloc<float>(6 * C);
+  float* gcond_q = A.alloc<float>((size_t)2 * C * Q.wn.n);
+  if (!dry) {
+    gemv(s, S->dec_cond_w.p, g, S->dec_cond_b.p, pre_bias, S->up_init, S->gin, S->conv_pre.bd_);
+    for (int f = 0; f < 4; ++f) gemv(s, S->flow[f].wn.cond_w.p, g, S->flow[f].wn.cond_b.p, gcond[f], 6 * C, S->gin, nullptr);
+    gemv(s, Q.wn.cond_w.p, g, Q.wn.cond_b.p, gcond_q, 2 * C * Q.wn.n, S->gin, nullptr);
+  }
+  // ---- enc_p -> m_p, logs_p
+  float* stats = enc_p_stats(S, s, A, gs, im, feat_cm, pitch, T, nullptr);
+  if (!dry && taps) { tap(taps->m_p, stats, (size_t)IC * T); tap(taps->logs_p, stats + (size_t)IC * T, (size_t)IC * T); }
+  // ---- enc_q -> z, m_q, logs_q
+  float* stats_q = A.alloc<float>((size_t)2 * IC * T);
+  float* z = A.alloc<float>((size_t)IC * T);
+  float* zp = A.alloc<float>((size_t)IC * T);
+  float* zf = A.alloc<float>((size_t)IC * T);
+  {
+    const size_t mark = A.off;
+    WnBufs wb;
+    wb.hw = A.alloc<float>((size_t)2 * C * T);
+    wb.xin = A.alloc<float>((size_t)2 * C * T);
+    wb.acts = gs ? nullptr : A.alloc<float>((size_t)C * T);
+    wb.hw_s = im.hw_s; wb.acts_s = im.acts_s;
+    // the operand of pre: Kp rows, the rows behind the spectrogram's zero (its weight columns there are zero too)
+    float* specp = A.alloc<float>((size_t)Q.Kp * T);
+    if (!dry) {
+      RVC_HIP_CHECK(hipMemcpyAsync(specp, spec, (size_t)Q.spec * T * sizeof(float), hipMemcpyDeviceToDevice, s));
+      if (Q.Kp > Q.spec) RVC_HIP_CHECK(hipMemsetAsync(specp + (size_t)Q.spec * T, 0, (size_t)(Q.Kp - Q.spec) * T * sizeof(float), s));
+      float* h = wb.hw; float* wo = wb.hw + (size_t)C * T;
+      if (gs) {
+        split_image_from_f32(s, specp, T, Q.Kp, T, im.spec_s, tp);
+        ConvEpilogue Eh; Eh.ys_out = wb.hw_s; Eh.ys_tp = tp;
+        conv_x3s_run(Q.pre, s, im.spec_s, tp, T, h, T, Eh);
+      } else conv1d_run(Q.pre, s, specp, T, T, h, T, E0);
+      wn_run(s, Q.wn, gcond_q, gs, wb, C, T);
+      if (gs) conv_x3s_run(Q.proj, s, wb.hw_s + split_image_bytes(C, T), tp, T, stats_q, T, E0);
+      else conv1d_run(Q.proj, s, wo, T, T, stats_q, T, E0);
+      posterior_sample(s, stats_q, noise_q, z, IC, T);
+      if (taps) { tap(taps->m_q, stats_q, (size_t)IC * T); tap(taps->logs_q, stats_q + (size_t)IC * T, (size_t)IC * T); tap(taps->z, z, (size_t)IC * T); }
+      // ---- flow (forward): coupling 0 .. 3, each followed by Flip (reference models.py:185-192)
+      RVC_HIP_CHECK(hipMemcpyAsync(zp, z, (size_t)IC * T * sizeof(float), hipMemcpyDeviceToDevice, s));
+      float* cur = zp; float* oth = zf;
+      for (int f = 0; f < 4; ++f) {
+        coupling_run(S, s, S->flow[f], gcond[f], gs, im, wb, cur, T, false);
+        flip_c(s, cur, oth, IC, T);
+        std::swap(cur, oth);
+      }
+      if (taps) tap(taps->z_p, cur, (size_t)IC * T);
+    }
+    A.off = mark;
+  }
+  // ---- the slice as a sequence of its own through the generator
+  float* zs = A.alloc<float>((size_t)IC * seg);
+  const long long N = (long long)seg * S->upp;
+  float* har = S->f0 ? A.alloc<float>((size_t)N) : nullptr;
+  if (!dry) segment_gather(s, z, IC, T, ids, seg, zs);
+  if (S->f0) {
+    float* pfs = A.alloc<float>((size_t)seg);
+    float* rad = A.alloc<float>((size_t)seg);
+    float* tmp = A.alloc<float>((size_t)seg);
+    double* bsum = A.alloc<double>((size_t)((N + 1023) / 1024));
+    if (!dry) {
+      segment_gather(s, pitchf, 1, T, ids, seg, pfs);
+      sine_source(s, pfs, noise_src, har, nullptr, rad, tmp, bsum, seg, S->upp, (float)S->sr, S->lin_w, S->lin_b);
+    }
+  }
+  gen_tail(S, s, A, gs, im.z_s, zs, har, pre_bias, seg, 0, seg, h2, out, nullptr);
+}
+
 // [keep0, keep1): the frames whose samples the caller keeps.  out[keep0 upp, keep1 upp) is defined, nothing else is promised: the generator (conv_pre on) runs on the
 // window widened by its halo, clamped to the sequence; enc_p, the flow and the harmonic source run at full length (global attention, a running phase sum, and the
 // caller's noise tensors keep their shapes).  halo < 0: synth_dec_halo_frames (anything else is for the test that shows the derived value is tight).
@@ -643,6 +845,29 @@ void synth_infer_window(Synth* S, hipStream_t s, const float* feat, int feat_cha
 void synth_infer(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, int sid,
                  const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps) {
   synth_infer_window(S, s, feat, feat_channel_major, pitch, pitchf, sid, noise_z, noise_src, T, out, taps, 0, T, -1);
+}
+
+void synth_forward(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, const float* spec, int sid,
+                   const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  RVC_REQUIRE(S->post_enc.built, "no posterior encoder loaded: the checkpoint had no enc_q.* tensors (an inference checkpoint)");
+  RVC_REQUIRE(S->segment > 0, "segment_size is not set in the configuration");
+  RVC_REQUIRE(T >= S->segment && T >= 11, "the sequence is shorter than the segment");
+  RVC_REQUIRE(ids >= 0 && ids <= T - S->segment, "slice start outside [0, T - segment]");
+  RVC_REQUIRE(sid >= 0 && sid < S->n_spk, "speaker id out of range");
+  Arena& A = S->arena;
+  for (int pass = 0; pass < 2; ++pass) {
+    A.dry = (pass == 0); A.reset(); if (pass == 0) A.peak = 0;
+    const float* fcm = feat;
+    if (!feat_channel_major) {
+      float* t = A.alloc<float>((size_t)S->feat_dim * T);
+      if (!A.dry) transpose(s, feat, t, T, S->feat_dim, S->feat_dim, T, 1, 0, 0);
+      fcm = t;
+    }
+    synth_forward_graph(S, s, A, fcm, pitch, pitchf, spec, sid, noise_q, noise_src, T, ids, out, taps);
+    if (pass == 0) A.ensure(A.peak);
+  }
+  A.dry = false;
 }
 
 size_t synth_workspace(const Synth* M) { return M->arena.cap; }

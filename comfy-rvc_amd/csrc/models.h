@@ -7,6 +7,7 @@ namespace rvc {
 
 typedef rvc_synth_config SynthConfig;
 typedef rvc_synth_taps SynthTaps;
+typedef rvc_synth_forward_taps SynthForwardTaps;
 typedef rvc_hubert_taps HubertTaps;
 typedef rvc_rmvpe_taps RmvpeTaps;
 typedef rvc_crepe_taps CrepeTaps;
@@ -26,6 +27,15 @@ void synth_infer(Synth* S, hipStream_t s, const float* feat, int feat_channel_ma
 void synth_infer_window(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, int sid,
                         const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps, long long keep0, long long keep1, int halo);
 void synth_window_frames(const Synth* S, int T, long long keep0, long long keep1, int halo, int* g0, int* g1);   // the frames the generator runs on for a keep window
+bool synth_has_posterior(const Synth* S); // enc_q.* were present at finalize
+// the training forward of one item (reference models.py:781-796; model_synth.hip): spec [spec_channels][T], noise_q [inter][T], noise_src [seg upp], out [seg upp]
+void synth_forward(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, const float* spec, int sid,
+                   const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps);
+// train_forward.hip: z = m + noise exp(logs) from stats [m | logs] (2 C rows); columns [ids, ids + seg) of x [C][T] -> y [C][seg]; the two loss reductions
+void posterior_sample(hipStream_t s, const float* stats, const float* noise, float* z, int C, int T);
+void segment_gather(hipStream_t s, const float* x, int C, int T, int ids, int seg, float* y);
+void kl_loss_sum(hipStream_t s, const float* z_p, const float* logs_q, const float* m_p, const float* logs_p, int C, long long ldT, long long len, double* out2);
+void l1_sum(hipStream_t s, const float* a, const float* b, long long n, double* out1);
 int synth_dec_halo_frames(const Synth* S);   // pure host: frames of z the generator's output depends on to either side
 
 struct Hubert;

@@ -280,6 +280,33 @@ static void check_pitch_args(rvc_synth* s, const void* pitch, const void* pitchf
     RVC_REQUIRE(!pitch && !pitchf && !noise_src && !do_protect, "no-f0 model: pitch, pitchf, source noise must be NULL and protect off");
   }
 }
+int rvc_synth_has_posterior(rvc_synth* s) { return (s && synth_has_posterior(s->m)) ? 1 : 0; }
+int rvc_synth_forward(rvc_synth* s, void* stream, const float* phone, int phone_cm, const int64_t* pitch, const float* pitchf, const float* spec, int sid,
+                      const float* noise_q, const float* noise_src, int64_t T, int64_t ids, float* out, const rvc_synth_forward_taps* taps) {
+  RVC_TRY
+  RVC_REQUIRE(s && phone && spec && noise_q && out, "null argument");
+  RVC_REQUIRE(T > 0 && T < (1LL << 24), "bad sequence length");
+  check_pitch_args(s, pitch, pitchf, noise_src, 0);
+  RVC_HIP_CHECK(hipSetDevice(s->ctx->c.device));
+  synth_forward(s->m, (hipStream_t)stream, phone, phone_cm, (const long long*)pitch, pitchf, spec, sid, noise_q, noise_src, (int)T,
+                (int)std::max<int64_t>(-1, std::min<int64_t>(ids, T)), out, taps);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_kl_loss(void* stream, const float* z_p, const float* logs_q, const float* m_p, const float* logs_p, int C, int64_t T_pitch, int64_t len, double* sum) {
+  RVC_TRY
+  RVC_REQUIRE(z_p && logs_q && m_p && logs_p && sum, "null argument");
+  kl_loss_sum((hipStream_t)stream, z_p, logs_q, m_p, logs_p, C, T_pitch, len, sum);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_l1_sum(void* stream, const float* a, const float* b, int64_t n, double* sum) {
+  RVC_TRY
+  RVC_REQUIRE(a && b && sum, "null argument");
+  l1_sum((hipStream_t)stream, a, b, n, sum);
+  check_launch();
+  RVC_CATCH
+}
 int rvc_synth_dec_halo(rvc_synth* s) { return s ? synth_dec_halo_frames(s->m) : 0; }
 int rvc_synth_window_frames(rvc_synth* s, int64_t T, int64_t keep0, int64_t keep1, int64_t* g0, int64_t* g1) {
   RVC_TRY

@@ -7,6 +7,16 @@
 
 namespace rvc {
 
+// float64 sum over a 256-thread block in a fixed order (red: 4 doubles of LDS): the block-partial reductions of audio_fx.hip and train_forward.hip
+__device__ __forceinline__ double block_sum(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 constexpr int kSosN = 6;      // states of the cascade: 2 per section, 3 sections (a 5th-order filter: the last section is first order, b2 = a2 = 0)
 
 // one sample through the cascade sos[k] = {b0, b1, b2, 1, a1, a2} (direct form II transposed per section, float64)

@@ -6,6 +6,11 @@ Drop-in for the inference surface of reference lib/infer_pack/models.py:580-809:
 The reference draws its noise from the global torch RNG inside `infer` (models.py:801 and :409); here the same two
 draws are made on the host with the same shapes and order - or supplied explicitly through `noise=(noise_z, noise_src)`
 (precedent: the reference's ONNX twin takes `rnd`, models_onnx.py:634-648).
+
+The training forward (reference :665-680,:781-796, `_nono` :894-903,:1000-1009) is there too, without a backward pass:
+`forward(phone, phone_lengths, pitch, pitchf, y, y_lengths, ds)` / `net_g(...)` returns
+`(o, ids_slice, x_mask, y_mask, (z, z_p, m_p, logs_p, m_q, logs_q))` when the loaded state dict held `enc_q.*`.  The library is batch-1: the items of
+a batch run one after the other on the current stream, each at its own length, into zero-filled padded outputs (what the reference's masks leave).
 """
 import ctypes as C
 
@@ -28,6 +33,7 @@ class _SynthesizerNSFsid:
         assert len(resblock_kernel_sizes) == 3 and all(len(d) == 3 for d in resblock_dilation_sizes)
         assert len(upsample_rates) <= 8
         self.inter_channels, self.hidden_channels, self.sr = inter_channels, hidden_channels, sr
+        self.spec_channels, self.segment_size, self.p_dropout = int(spec_channels), int(segment_size), float(p_dropout)
         self.upsample_rates = list(upsample_rates)
         self.upp = int(np.prod(upsample_rates))
         self.device = torch.device(device)
@@ -44,6 +50,7 @@ class _SynthesizerNSFsid:
             cfg.upsample_rates[i], cfg.upsample_kernel_sizes[i] = u, k
         cfg.upsample_initial_channel, cfg.spk_embed_dim, cfg.gin_channels, cfg.sr = upsample_initial_channel, spk_embed_dim, gin_channels, sr
         cfg.feat_dim = self.FEAT_DIM
+        cfg.spec_channels, cfg.segment_size = self.spec_channels, self.segment_size
         self._ctx = _lib.get_ctx(self.device.index or 0)
         h = C.c_void_p()
         _lib.check(_lib.lib.rvc_synth_create(self._ctx, C.byref(cfg), C.byref(h)))
@@ -58,7 +65,9 @@ class _SynthesizerNSFsid:
             self._h = None
 
     def load_state_dict(self, state_dict, strict=False):
-        sd = {k: v for k, v in state_dict.items() if not k.startswith("enc_q.")}
+        # the posterior encoder is loaded when the checkpoint has it and the caller has not deleted it (`del net_g.enc_q`, get_vc)
+        keep_q = hasattr(self, "enc_q")
+        sd = {k: v for k, v in state_dict.items() if keep_q or not k.startswith("enc_q.")}
         with torch.cuda.device(self.device):
             _lib.set_tensors(_lib.lib.rvc_synth_set_tensor, self._h, sd)
             _lib.check(_lib.lib.rvc_synth_finalize(self._h))
@@ -128,6 +137,76 @@ class _SynthesizerNSFsid:
         x_mask = torch.ones(1, 1, T, dtype=torch.float32, device=dev)
         return out, x_mask, (tbuf.get("z"), tbuf.get("z_p"), tbuf.get("m_p"), tbuf.get("logs_p"))
 
+    # ------------------------------------------------------------------------------------------- training forward
+    def _forward(self, phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise, ids_slice):
+        """SynthesizerTrnMs{256,768}NSFsid[_nono].forward (reference :781-796,:894-903).  noise=(noise_q [B,inter,T], noise_src [B,seg*upp,1]);
+        without it the draws are made on the host in the reference's order and shapes: enc_q's randn_like [B,inter,T] (:237), torch.rand([B]) of
+        rand_slice_segments (commons.py:173), SineGen's rand_ini torch.rand(B, 1) (:378-381, zeroed) and its randn_like [B,seg*upp,1] (:409)."""
+        assert self._loaded, "load_state_dict first"
+        if self.p_dropout != 0:
+            raise ValueError("the forward implements the dropout-free arithmetic: p_dropout must be 0 (it is in every shipped configuration)")
+        if not _lib.lib.rvc_synth_has_posterior(self._h):
+            raise RuntimeError("no posterior encoder: the loaded state dict had no enc_q.* tensors, or enc_q was deleted before loading")
+        dev, seg, IC, upp = self.device, self.segment_size, self.inter_channels, self.upp
+        pl = torch.as_tensor(phone_lengths).reshape(-1).to("cpu", torch.int64)
+        yl = torch.as_tensor(y_lengths).reshape(-1).to("cpu", torch.int64)
+        B = int(yl.numel())
+        if pl.numel() != B or not torch.equal(pl, yl):
+            raise ValueError("phone_lengths and y_lengths differ: the flow maps the posterior's frames onto the prior's one to one")
+        if int(yl.min()) < seg:
+            raise ValueError(f"an item is shorter than segment_size ({seg} frames)")
+        Tx, Ty = int(phone.shape[1]), int(y.shape[2])
+        assert phone.shape[0] == B and y.shape[0] == B and y.shape[1] == self.spec_channels and int(yl.max()) <= min(Tx, Ty)
+        f0 = self.HAS_F0
+        noise_q = noise_src = None
+        if noise is not None:
+            noise_q, noise_src = noise if isinstance(noise, (tuple, list)) else (noise, None)
+        if noise_q is None:
+            noise_q = torch.randn(B, IC, Ty)
+        if ids_slice is None:
+            ids_slice = (torch.rand([B]) * (yl - seg + 1)).to(dtype=torch.long)
+        elif noise is None:
+            torch.rand([B])
+        if f0 and noise_src is None:
+            torch.rand(B, 1)
+            noise_src = torch.randn(B, seg * upp, 1)
+        ids = torch.as_tensor(ids_slice).reshape(-1).to("cpu", torch.int64)
+        assert ids.numel() == B
+        ph = phone.to(dev, torch.float32)
+        yd = y.to(dev, torch.float32)
+        nq = torch.as_tensor(noise_q).to(dev, torch.float32)
+        sid = torch.as_tensor(ds).reshape(-1).to("cpu", torch.int64)
+        if f0:
+            pc, pf = pitch.to(dev, torch.int64), pitchf.to(dev, torch.float32)
+            ns = torch.as_tensor(noise_src).to(dev, torch.float32).reshape(B, seg * upp)
+        o = torch.zeros(B, 1, seg * upp, dtype=torch.float32, device=dev)
+        taps = [torch.zeros(B, IC, Ty, dtype=torch.float32, device=dev) for _ in range(6)]       # z, z_p, m_p, logs_p, m_q, logs_q
+        with torch.cuda.device(dev):
+            st = _lib.current_stream()
+            for b in range(B):
+                L = int(yl[b])
+                item = [torch.empty(IC, L, dtype=torch.float32, device=dev) for _ in range(6)]
+                tp = _lib.SynthForwardTaps(*[_lib.ptr(t) for t in item])
+                ph_b, y_b, nq_b = ph[b, :L].contiguous(), yd[b, :, :L].contiguous(), nq[b, :, :L].contiguous()
+                pc_b = pc[b, :L].contiguous() if f0 else None
+                pf_b = pf[b, :L].contiguous() if f0 else None
+                ns_b = ns[b].contiguous() if f0 else None
+                o_b = torch.empty(seg * upp, dtype=torch.float32, device=dev)
+                _lib.check(_lib.lib.rvc_synth_forward(self._h, st, _lib.ptr(ph_b), 0, _lib.ptr(pc_b), _lib.ptr(pf_b), _lib.ptr(y_b), int(sid[b]),
+                                                      _lib.ptr(nq_b), _lib.ptr(ns_b), L, int(ids[b]), _lib.ptr(o_b), C.byref(tp)))
+                o[b, 0] = o_b
+                for dst, src in zip(taps, item):
+                    dst[b, :, :L] = src
+        x_mask = (torch.arange(Tx)[None, :] < pl[:, None]).to(torch.float32).unsqueeze(1).to(dev)
+        y_mask = (torch.arange(Ty)[None, :] < yl[:, None]).to(torch.float32).unsqueeze(1).to(dev)
+        return o, ids.to(dev), x_mask, y_mask, tuple(taps)
+
+    def forward(self, phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise=None, ids_slice=None):
+        return self._forward(phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise, ids_slice)
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
 
 class _SynthesizerNSFsid_nono(_SynthesizerNSFsid):
     """No-f0 family (reference lib/infer_pack/models.py:812-1022): text encoder without pitch embedding, plain HiFi-GAN Generator.
@@ -164,6 +243,12 @@ class _SynthesizerNSFsid_nono(_SynthesizerNSFsid):
             taps.update(tbuf)
         x_mask = torch.ones(1, 1, T, dtype=torch.float32, device=dev)
         return out, x_mask, (tbuf.get("z"), tbuf.get("z_p"), tbuf.get("m_p"), tbuf.get("logs_p"))
+
+    def forward(self, phone, phone_lengths, y, y_lengths, ds, *extra, noise=None, ids_slice=None):
+        """Five arguments (reference :894,:1000): the no-f0 family has no pitch inputs; noise = noise_q alone (one randn_like, then the slice's rand)."""
+        if extra:
+            raise ValueError("no-f0 model: forward(phone, phone_lengths, y, y_lengths, ds) takes no pitch arguments")
+        return self._forward(phone, phone_lengths, None, None, y, y_lengths, ds, noise, ids_slice)
 
 
 class SynthesizerTrnMs768NSFsid_nono(_SynthesizerNSFsid_nono):

@@ -1,0 +1,87 @@
+"""loss/mel and loss/kl of a generator checkpoint over a prepared dataset - the two numbers watched to pick an epoch - from the training forward alone
+(no discriminator, no backward pass).  Formed as the trainer forms them (reference training_cli.py:505-545,:570-571)."""
+import numpy as np
+import torch
+
+from ..infer_pack import models
+from . import data_utils
+from .losses import kl_loss, l1_loss
+from .mel_processing import mel_spectrogram_torch, spec_to_mel_torch
+
+
+def _slice_segments(x, ids, size):
+    """commons.slice_segments (reference lib/infer_pack/commons.py:150-156)."""
+    return torch.stack([x[i, :, int(s):int(s) + size] for i, s in enumerate(ids.tolist())])
+
+
+def reconstruction_losses(net_g, batch, hps, generator=None, *, noise=None, ids_slice=None):
+    """One collated batch (TextAudioCollateMultiNSFsid's nine tensors, or TextAudioCollate's seven) -> {"loss_mel", "loss_kl": 0-dim float32 device tensors,
+    "ids_slice": int64 [B]}.  Noise and slice starts are drawn from `generator` (a CPU torch.Generator; None: the global one) in the forward's order;
+    noise / ids_slice given explicitly (as to the forward) replace the draws."""
+    d, seg = hps.data, hps.train.segment_size // hps.data.hop_length
+    if len(batch) == 9:
+        phone, phone_lengths, pitch, pitchf, spec, spec_lengths, _wave, _wl, sid = batch
+    else:
+        phone, phone_lengths, spec, spec_lengths, _wave, _wl, sid = batch
+        pitch = pitchf = None
+    B, T = spec.shape[0], spec.shape[2]
+    yl = torch.as_tensor(spec_lengths).reshape(-1).cpu()
+    if noise is not None:
+        noise_q, noise_src = noise if isinstance(noise, (tuple, list)) else (noise, None)
+        ids = ids_slice if ids_slice is not None else (torch.rand([B], generator=generator) * (yl - seg + 1)).to(dtype=torch.long)
+    else:
+        noise_q = torch.randn(B, net_g.inter_channels, T, generator=generator)
+        ids = (torch.rand([B], generator=generator) * (yl - seg + 1)).to(dtype=torch.long)
+        if pitch is not None:
+            torch.rand(B, 1, generator=generator)
+            noise_src = torch.randn(B, seg * net_g.upp, 1, generator=generator)
+        if ids_slice is not None:
+            ids = ids_slice
+    if pitch is not None:
+        y_hat, ids_slice, _, z_mask, (_z, z_p, m_p, logs_p, _m_q, logs_q) = net_g(phone, phone_lengths, pitch, pitchf, spec, spec_lengths, sid,
+                                                                                  noise=(noise_q, noise_src), ids_slice=ids)
+    else:
+        y_hat, ids_slice, _, z_mask, (_z, z_p, m_p, logs_p, _m_q, logs_q) = net_g(phone, phone_lengths, spec, spec_lengths, sid, noise=noise_q, ids_slice=ids)
+    dev = y_hat.device
+    mel = spec_to_mel_torch(spec.to(dev, torch.float32), d.filter_length, d.n_mel_channels, d.sampling_rate, d.mel_fmin, d.mel_fmax)
+    y_mel = _slice_segments(mel, ids_slice, seg)
+    y_hat_mel = mel_spectrogram_torch(y_hat, d.filter_length, d.n_mel_channels, d.sampling_rate, d.hop_length, d.win_length, d.mel_fmin, d.mel_fmax)
+    return {"loss_mel": l1_loss(y_mel, y_hat_mel), "loss_kl": kl_loss(z_p, logs_q, m_p, logs_p, z_mask), "ids_slice": ids_slice}
+
+
+def load_generator(ckpt, hps, version="v2", f0=True, device="cuda:0"):
+    """A trainer's G_*.pth ({"model": state_dict, "iteration", ...}, reference lib/train/utils.py:120-131) or a bare state dict -> the loaded synthesizer."""
+    cpt = torch.load(ckpt, map_location="cpu") if isinstance(ckpt, str) else ckpt
+    sd = cpt["model"] if isinstance(cpt, dict) and "model" in cpt else cpt
+    m = hps.model
+    cls = getattr(models, f"SynthesizerTrnMs{768 if version == 'v2' else 256}NSFsid" + ("" if f0 else "_nono"))
+    net = cls(hps.data.filter_length // 2 + 1, hps.train.segment_size // hps.data.hop_length, m.inter_channels, m.hidden_channels, m.filter_channels,
+              m.n_heads, m.n_layers, m.kernel_size, m.p_dropout, m.resblock, m.resblock_kernel_sizes, m.resblock_dilation_sizes, m.upsample_rates,
+              m.upsample_initial_channel, m.upsample_kernel_sizes, m.spk_embed_dim, m.gin_channels, hps.data.sampling_rate, device=device)
+    net.load_state_dict(sd)
+    return net
+
+
+def evaluate_checkpoint(ckpt, filelist, hps, seed=1337, batch_size=4, boundaries=(32, 100, 200, 300, 400, 500, 600, 700, 800, 900), version="v2", f0=True,
+                        device="cuda:0"):
+    """Walks `filelist` through the loader, the collate and the bucket sampler (unshuffled) and returns {"loss_mel", "loss_kl": means over the batches,
+    "batches": [{"loss_mel", "loss_kl", "ids_slice"}...]}.  The sampler buckets by file size (dataset.lengths), so a batch may still hold an item whose
+    labels are shorter than the segment: such a batch cannot be sliced and is left out.  The draws come from torch.Generator().manual_seed(seed): the same seed gives the same two numbers."""
+    net = ckpt if hasattr(ckpt, "forward") else load_generator(ckpt, hps, version, f0, device)
+    seg = hps.train.segment_size // hps.data.hop_length
+    ds = (data_utils.TextAudioLoaderMultiNSFsid if f0 else data_utils.TextAudioLoader)(filelist, hps.data)
+    collate = data_utils.TextAudioCollateMultiNSFsid() if f0 else data_utils.TextAudioCollate()
+    bounds = list(boundaries)
+    sampler = data_utils.BucketSampler(ds, batch_size, bounds, shuffle=False)
+    gen = torch.Generator().manual_seed(int(seed))
+    rows = []
+    for idx in sampler:
+        batch = collate([ds[i] for i in idx])
+        lens = batch[5 if f0 else 3]
+        if int(lens.min()) < seg:
+            continue
+        r = reconstruction_losses(net, batch, hps, gen)
+        rows.append({"loss_mel": float(r["loss_mel"]), "loss_kl": float(r["loss_kl"]), "ids_slice": r["ids_slice"].cpu().numpy()})
+    if not rows:
+        raise ValueError("no batch of the file list has every item at least segment_size long")
+    return {"loss_mel": float(np.mean([r["loss_mel"] for r in rows])), "loss_kl": float(np.mean([r["loss_kl"] for r in rows])), "batches": rows}

@@ -378,51 +378,104 @@ def synth_state_dict(config, version="v2", seed=0, fp16_round=True, f0=True, fam
     for name, shape in spec.items():
         if not f0 and name.startswith(F0_ONLY_KEYS):
             continue
-        if name.endswith("weight_g"):
-            vshape = spec[name[:-1] + "v"]
-            fan = int(np.prod(vshape[1:]))
-            gain = 1.0
-            if ".ups." in name:                    # ConvTranspose1d: only k/stride taps hit per output
-                gain = 1.2
-            # |v| per dim-0 slice is ~ sqrt(fan) for unit-normal v; g sets the effective row norm
-            v = _uniform(seed, name, shape, 0.8, 1.2) * np.float32(gain)
-            if ".ups." in name:
-                k = vshape[2]
-                v = v * np.float32(np.sqrt(vshape[1] * k) / np.sqrt(vshape[0] * 2.0))
-            elif "res_skip" in name or "cond_layer" in name:
-                v = v * np.float32(0.5)
-        elif name.endswith("weight_v"):
-            v = _normal(seed, name, shape, 1.0)
-        elif name.endswith("gamma"):
-            v = _uniform(seed, name, shape, 0.8, 1.2)
-        elif name.endswith("beta"):
-            v = _normal(seed, name, shape, 0.05)
-        elif "emb_rel" in name:
-            v = _normal(seed, name, shape, shape[-1] ** -0.5)
-        elif name == "enc_p.emb_pitch.weight":
-            v = _normal(seed, name, shape, 0.05)
-        elif name == "emb_g.weight":
-            v = _normal(seed, name, shape, 0.5)
-        elif name == "dec.m_source.l_linear.weight":
-            v = np.full(shape, 0.9, dtype=np.float32)
-        elif name == "dec.m_source.l_linear.bias":
-            v = np.full(shape, 0.01, dtype=np.float32)
-        elif name == "dec.conv_post.weight":
-            v = _normal(seed, name, shape, 0.4 / np.sqrt(_fan_in(shape)))
-        elif "noise_convs" in name and name.endswith("weight"):
-            v = _normal(seed, name, shape, 2.0 / np.sqrt(_fan_in(shape)))
-        elif "flow" in name and "post.weight" in name:
-            v = _normal(seed, name, shape, 0.3 / np.sqrt(_fan_in(shape)))
-        elif name == "enc_p.proj.weight":
-            v = _normal(seed, name, shape, 0.5 / np.sqrt(_fan_in(shape)))
-        elif name.endswith(".bias"):
-            v = _normal(seed, name, shape, 0.02)
-        else:
-            v = _normal(seed, name, shape, 1.0 / np.sqrt(_fan_in(shape)))
-        if fp16_round:                             # real RVC checkpoints store fp16 (training_cli.py:38-74)
-            v = v.astype(np.float16).astype(np.float32)
-        sd[name] = v
+        sd[name] = _synth_draw(seed, name, shape, spec, fp16_round)
     return sd
+
+
+def _synth_draw(seed, name, shape, spec, fp16_round):
+    """One tensor of a synthesizer state dict by the rules of its name (the values depend on (seed, name, shape) alone)."""
+    if name.endswith("weight_g"):
+        vshape = spec[name[:-1] + "v"]
+        fan = int(np.prod(vshape[1:]))
+        gain = 1.0
+        if ".ups." in name:                    # ConvTranspose1d: only k/stride taps hit per output
+            gain = 1.2
+        # |v| per dim-0 slice is ~ sqrt(fan) for unit-normal v; g sets the effective row norm
+        v = _uniform(seed, name, shape, 0.8, 1.2) * np.float32(gain)
+        if ".ups." in name:
+            k = vshape[2]
+            v = v * np.float32(np.sqrt(vshape[1] * k) / np.sqrt(vshape[0] * 2.0))
+        elif "res_skip" in name or "cond_layer" in name:
+            v = v * np.float32(0.5)
+    elif name.endswith("weight_v"):
+        v = _normal(seed, name, shape, 1.0)
+    elif name.endswith("gamma"):
+        v = _uniform(seed, name, shape, 0.8, 1.2)
+    elif name.endswith("beta"):
+        v = _normal(seed, name, shape, 0.05)
+    elif "emb_rel" in name:
+        v = _normal(seed, name, shape, shape[-1] ** -0.5)
+    elif name == "enc_p.emb_pitch.weight":
+        v = _normal(seed, name, shape, 0.05)
+    elif name == "emb_g.weight":
+        v = _normal(seed, name, shape, 0.5)
+    elif name == "dec.m_source.l_linear.weight":
+        v = np.full(shape, 0.9, dtype=np.float32)
+    elif name == "dec.m_source.l_linear.bias":
+        v = np.full(shape, 0.01, dtype=np.float32)
+    elif name == "dec.conv_post.weight":
+        v = _normal(seed, name, shape, 0.4 / np.sqrt(_fan_in(shape)))
+    elif "noise_convs" in name and name.endswith("weight"):
+        v = _normal(seed, name, shape, 2.0 / np.sqrt(_fan_in(shape)))
+    elif "flow" in name and "post.weight" in name:
+        v = _normal(seed, name, shape, 0.3 / np.sqrt(_fan_in(shape)))
+    elif name in ("enc_p.proj.weight", "enc_q.proj.weight"):      # (m | logs) heads: logs stays within a few units
+        v = _normal(seed, name, shape, 0.5 / np.sqrt(_fan_in(shape)))
+    elif name.endswith(".bias"):
+        v = _normal(seed, name, shape, 0.02)
+    else:
+        v = _normal(seed, name, shape, 1.0 / np.sqrt(_fan_in(shape)))
+    if fp16_round:                             # real RVC checkpoints store fp16 (training_cli.py:38-74)
+        v = v.astype(np.float16).astype(np.float32)
+    return v
+
+
+def synth_posterior_spec(config):
+    """name -> shape of the enc_q.* tensors (PosteriorEncoder(spec_channels, inter, hidden, 5, 1, 16, gin), reference lib/infer_pack/models.py:199-238,
+    :636-644) in the reference module's state_dict order."""
+    spec_ch, inter, hidden, gin = config[0], config[2], config[3], config[16]
+    s = OrderedDict()
+    s["enc_q.pre.weight"] = (hidden, spec_ch, 1)
+    s["enc_q.pre.bias"] = (hidden,)
+    for l in range(16):
+        s[f"enc_q.enc.in_layers.{l}.bias"] = (2 * hidden,)
+        s[f"enc_q.enc.in_layers.{l}.weight_g"] = (2 * hidden, 1, 1)
+        s[f"enc_q.enc.in_layers.{l}.weight_v"] = (2 * hidden, hidden, 5)
+    for l in range(16):
+        rs = 2 * hidden if l < 15 else hidden
+        s[f"enc_q.enc.res_skip_layers.{l}.bias"] = (rs,)
+        s[f"enc_q.enc.res_skip_layers.{l}.weight_g"] = (rs, 1, 1)
+        s[f"enc_q.enc.res_skip_layers.{l}.weight_v"] = (rs, hidden, 1)
+    s["enc_q.enc.cond_layer.bias"] = (2 * hidden * 16,)
+    s["enc_q.enc.cond_layer.weight_g"] = (2 * hidden * 16, 1, 1)
+    s["enc_q.enc.cond_layer.weight_v"] = (2 * hidden * 16, gin, 1)
+    s["enc_q.proj.weight"] = (inter * 2, hidden, 1)
+    s["enc_q.proj.bias"] = (inter * 2,)
+    return s
+
+
+def synth_train_state_dict(config, version="v2", seed=0, f0=True):
+    """synth_state_dict plus the posterior encoder's enc_q.*: what a trainer's G_*.pth holds under "model" (reference lib/train/utils.py)."""
+    sd = synth_state_dict(config, version, seed, f0=f0)
+    spec = synth_posterior_spec(config)
+    for name, shape in spec.items():
+        sd[name] = _synth_draw(seed, name, shape, spec, True)
+    return sd
+
+
+def synth_posterior_input(config, lengths, seed=0):
+    """A spectrogram-like batch for the posterior encoder: float32 [B, spec_channels, max(lengths)], non-negative, a harmonic comb under a falling
+    envelope with magnitudes up to ~100 (what |STFT| of a full-scale 2048-point frame reaches), exactly 0 beyond each length."""
+    spec_ch, T = config[0], int(max(lengths))
+    y = np.zeros((len(lengths), spec_ch, T), dtype=np.float32)
+    k = np.arange(spec_ch, dtype=np.float64)[:, None]
+    for b, L in enumerate(lengths):
+        rng = _rng(seed, f"posterior_input.{b}")
+        f = 8.0 + 30.0 * rng.random((1, L))
+        comb = 0.5 + 0.5 * np.cos(2 * np.pi * k / f)
+        env = 100.0 * np.exp(-k / (spec_ch / 8.0)) * (0.1 + 0.9 * rng.random((1, L)) ** 2)
+        y[b, :, :L] = (env * comb ** 4 + 0.05 * np.abs(rng.standard_normal((spec_ch, L)))).astype(np.float32)
+    return y
 
 
 def synth_checkpoint(config=None, version="v2", seed=0, f0=1, family="plain"):
@@ -433,6 +486,24 @@ def synth_checkpoint(config=None, version="v2", seed=0, f0=1, family="plain"):
 
 
 # ----------------------------------------------------------------------------------- inputs
+def synth_train_batch(config, version, lengths, seed=0, f0=True, sids=None):
+    """One collated training batch for the synthesizer's forward, as TextAudioCollateMultiNSFsid pads it (zeros beyond each length): dict of phone
+    float32 [B,T,D], lengths int64 [B], pitch int64 [B,T], pitchf float32 [B,T] (designed_f0: voiced and unvoiced stretches), spec float32
+    [B,spec,T] (synth_posterior_input) and sid int64 [B]; pitch / pitchf are None for the no-f0 family."""
+    B, T, D = len(lengths), int(max(lengths)), 768 if version == "v2" else 256
+    rng = _rng(seed, "train_batch")
+    phone = np.zeros((B, T, D), dtype=np.float32)
+    pitch = np.zeros((B, T), dtype=np.int64)
+    pitchf = np.zeros((B, T), dtype=np.float32)
+    for b, L in enumerate(lengths):
+        phone[b, :L] = (rng.standard_normal((L, D)) * 0.5).astype(np.float32)
+        pitch[b, :L] = rng.integers(1, 256, size=L)
+        pitchf[b, :L] = designed_f0(L + 60 * (b + 1))[60 * (b + 1) - 10:60 * (b + 1) - 10 + L]
+    sid = np.array(sids if sids is not None else [(3 + 17 * b) % config[15] for b in range(B)], dtype=np.int64)
+    return {"phone": phone, "lengths": np.array(lengths, dtype=np.int64), "pitch": pitch if f0 else None, "pitchf": pitchf if f0 else None,
+            "spec": synth_posterior_input(config, lengths, seed), "sid": sid}
+
+
 def synth_audio(seconds, seed=0, sr=16000):
     """SURVEY 8(d) synthetic clip: AM'd glide 110-440 Hz with 20 % silent gaps plus a little noise."""
     n = int(round(seconds * sr))

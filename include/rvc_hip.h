@@ -8,6 +8,9 @@
  *   rvc_rmvpe_forward    <- RMVPE.infer_from_audio / _with_pitch         lib/rmvpe.py:614-659 (mel :510-556, E2E :464-470,
  *                                                                        decode :607-612,:661-685)
  *   rvc_synth_infer      <- SynthesizerTrnMs{256,768}NSFsid.infer        lib/infer_pack/models.py:682-693,:798-809
+ *   rvc_synth_forward    <- SynthesizerTrnMs{256,768}NSFsid.forward      lib/infer_pack/models.py:665-680,:781-796 (PosteriorEncoder :199-238)
+ *   rvc_kl_loss          <- kl_loss                                      lib/train/losses.py:596-611
+ *   rvc_l1_sum           <- F.l1_loss(y_mel, y_hat_mel)                  training_cli.py:570
  *   rvc_vc_segment       <- VC.vc (features -> x2 upsample -> protect -> infer)   vc_infer_pipeline.py:25-114
  *   rvc_*_set_tensor     <- load_state_dict of the checkpoint tensors    vc_infer_pipeline.py:199-221,
  *                                                                        lib/infer_pack/loaders.py:19-31, lib/rmvpe.py:579-586
@@ -156,6 +159,9 @@ typedef struct rvc_synth_config {   /* the fields of cpt["config"] that the infe
   int n_upsamples; int upsample_rates[8]; int upsample_kernel_sizes[8];
   int upsample_initial_channel, spk_embed_dim, gin_channels, sr;
   int feat_dim;                    /* 768 (v2) or 256 (v1) */
+  /* training forward only (rvc_synth_forward); 0 in both: an inference-only handle */
+  int spec_channels;               /* rows of the linear spectrogram the posterior encoder reads (config[0]: 1025 / 513) */
+  int segment_size;                /* frames of the slice the generator runs on (config[1]: 32) */
 } rvc_synth_config;
 
 typedef struct rvc_synth_taps {
@@ -203,6 +209,31 @@ int rvc_synth_window_frames(rvc_synth* s, int64_t T, int64_t keep0, int64_t keep
 int rvc_synth_infer_window_halo(rvc_synth* s, void* stream, const float* phone_dev, int phone_channel_major, const int64_t* pitch_dev,
                                 const float* pitchf_dev, int sid, const float* noise_z_dev, const float* noise_src_dev, int64_t T,
                                 float* out_dev, const rvc_synth_taps* taps, int64_t keep0, int64_t keep1, int halo);
+
+/* ---- training forward (no backward pass): SynthesizerTrnMs{256,768}NSFsid[_nono].forward for ONE item at its own length
+ * (reference lib/infer_pack/models.py:665-680,:781-796,:894-903,:1000-1009): enc_p -> (m_p, logs_p); PosteriorEncoder (:199-238: pre 1x1,
+ * WN(hidden, 5, 1, 16, gin), proj 1x1) -> z = m_q + noise_q exp(logs_q); the four coupling layers in the FORWARD direction, flows 0 -> 3, each followed
+ * by Flip (lib/infer_pack/modules.py:436-451 with reverse=False, mean_only: x1 = m + x1) -> z_p; columns [ids, ids + seg) of z and pitchf
+ * (lib/infer_pack/commons.py:150-175 slice_segments / slice_segments2) through the generator as a sequence of its own (zero padding at both cut edges,
+ * the harmonic source's phase starts at the slice) -> out_dev [seg * upp].  Dropout-free arithmetic (p_dropout = 0 in every shipped configuration).
+ * rvc_synth_set_tensor takes the enc_q.* tensors like every other; rvc_synth_finalize builds the posterior only when they are present (a model finalized
+ * without them is what it always was and allocates nothing for it). */
+int rvc_synth_has_posterior(rvc_synth* s);
+typedef struct rvc_synth_forward_taps {   /* all [inter][T]; NULL = skip */
+  float* z; float* z_p; float* m_p; float* logs_p; float* m_q; float* logs_q;
+} rvc_synth_forward_taps;
+/* phone_dev / pitch_dev / pitchf_dev / sid as rvc_synth_infer (a no-f0 model takes NULL for pitch_dev, pitchf_dev and noise_src_dev); spec_dev
+ * [spec_channels][T]; noise_q_dev [inter][T] (enc_q's randn_like, models.py:237); noise_src_dev [seg * upp] (SineGen's randn_like on the slice, :409);
+ * ids: first frame of the slice, 0 <= ids <= T - seg.  Errors: no posterior loaded, T < seg, ids out of range, the f0 / no-f0 argument mismatches. */
+int rvc_synth_forward(rvc_synth* s, void* stream, const float* phone_dev, int phone_channel_major, const int64_t* pitch_dev, const float* pitchf_dev,
+                      const float* spec_dev, int sid, const float* noise_q_dev, const float* noise_src_dev, int64_t T, int64_t ids, float* out_dev,
+                      const rvc_synth_forward_taps* taps);
+/* kl_loss of one item (reference lib/train/losses.py:596-611): sum_dev[0] = sum over c < C, t < len of logs_p - logs_q - 0.5 + 0.5 (z_p - m_p)^2 exp(-2 logs_p)
+ * (float64 accumulation, fixed order: two calls give the same bits), sum_dev[1] = len (the mask's sum); rows have pitch T_pitch >= len. */
+int rvc_kl_loss(void* stream, const float* z_p_dev, const float* logs_q_dev, const float* m_p_dev, const float* logs_p_dev, int C, int64_t T_pitch,
+                int64_t len, double* sum_dev);
+/* sum_dev[0] = sum_i |a[i] - b[i]| over n elements, float64 accumulation in a fixed order (F.l1_loss = that / n, training_cli.py:570) */
+int rvc_l1_sum(void* stream, const float* a_dev, const float* b_dev, int64_t n, double* sum_dev);
 
 /* ------------------------------------------------------------------ fused segment: VC.vc without index retrieval */
 /* audio_dev [L] 16 kHz segment; pitch/pitchf as above with at least p_len = 2*T_h entries; out_dev [2*T_h*upp].
