@@ -1,4 +1,4 @@
-// Host-side helpers shared by the three network graphs (hubert / rmvpe / synth).
+// Host-side helpers shared by the network graphs.
 #pragma once
 #include "rvc_internal.h"
 #include "ops.h"
@@ -47,6 +47,11 @@ struct Ctx {
 };
 
 using DevVec = DevBuf<float>;   // device vector owned by a model
+
+// a graph's optional output: n floats copied device to device on the real pass when the caller gave a buffer
+inline void tap(const Arena& A, hipStream_t s, float* dst, const float* src, size_t n) {
+  if (!A.dry && dst) RVC_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+}
 
 inline std::vector<float> transpose2d(const float* w, int R, int C) {   // [R][C] -> [C][R]
   std::vector<float> o((size_t)R * C);

@@ -292,13 +292,7 @@ void crepe_forward(Crepe* M, hipStream_t s, const float* audio, long long L, int
   RVC_REQUIRE(M->ready, "crepe_finalize has not been called");
   const long long n = crepe_num_frames(L, hop, pad);
   RVC_REQUIRE(n > 0 && n < (1LL << 24), "no frames (audio shorter than one 1024-sample window without padding?)");
-  Arena& A = M->arena;
-  for (int pass = 0; pass < 2; ++pass) {
-    A.dry = (pass == 0); A.reset(); if (pass == 0) A.peak = 0;
-    crepe_graph(M, s, A, audio, L, hop, pad, probs, n, taps);
-    if (pass == 0) A.ensure(A.peak);
-  }
-  A.dry = false;
+  arena_passes(M->arena, [&] { crepe_graph(M, s, M->arena, audio, L, hop, pad, probs, n, taps); });
 }
 
 size_t crepe_workspace(const Crepe* M) { return M->arena.cap; }

@@ -1,25 +1,20 @@
 // HubertModelWithFinalProj.extract_features as a HIP kernel graph (reference lib/infer_pack/loaders.py:55-61 over
 // transformers/models/hubert/modeling_hubert.py:45-477,878-955): 7-layer conv feature encoder (GroupNorm on layer 0),
 // LayerNorm + projection, grouped k=128 positional conv, post-LN transformer layers.  Channel-major [C][T] throughout.
-#include "model_common.h"
+#include "model_encoder.h"
 #include "models.h"
 
 namespace rvc {
 
-struct HubLayer {
-  OwnedConvLayer qk;   // fused q (pre-scaled by head_dim^-0.5) and k projections: 768 -> 1536
-  DevVec bv;           // v projection bias, added after P.V (softmax rows sum to 1); the v rows are part of the qk layer (768 -> 2304)
-  OwnedConvLayer o, ff1, ff2;
-  DevVec g1, b1, g2, b2;
-};
+static const EncoderShape kHubEncoder = {768, 12, 64, 0, ACT_GELU, 3072};
 
 struct HubertWeights {   // what hubert_finalize builds, and what the graph has learnt about it
-  const void* img_base = nullptr; unsigned img_gen = 0; size_t img_bytes = 0; int img_T = -1;   // image of the positional convolution's input: margins known to be zero
+  ZeroedBlock pos_img;   // image of the positional convolution's input: margins known to be zero (key: T)
   OwnedConvLayer conv[7];
   DevVec gn_g, gn_b, fp_g, fp_b, enc_g, enc_b;
   DevVec w0;            // conv_layers.0 raw [512][10]: the fused conv0 + GroupNorm + GELU kernels evaluate it from the audio
   OwnedConvLayer proj, pos, final_proj;
-  std::vector<HubLayer> layers;
+  std::vector<EncoderLayer> layers;
 };
 struct Hubert : HubertWeights {
   Ctx* ctx = nullptr;
@@ -85,7 +80,7 @@ void hubert_finalize(Hubert* H) {
   H->layers.resize(nl);
   const float qs = 0.125f;   // head_dim^-0.5 = 64^-0.5, exact in fp32
   for (int l = 0; l < nl; ++l) {
-    HubLayer& Y = H->layers[l];
+    EncoderLayer& Y = H->layers[l];
     const std::string p = "encoder.layers." + std::to_string(l) + ".";
     const HostTensor& wq = ts.get(p + "attention.q_proj.weight", {768, 768});
     const HostTensor& wk = ts.get(p + "attention.k_proj.weight", {768, 768});
@@ -96,7 +91,7 @@ void hubert_finalize(Hubert* H) {
     std::vector<float> w(3 * (size_t)768 * 768), b(3 * 768, 0.f);
     for (size_t i = 0; i < (size_t)768 * 768; ++i) { w[i] = wq.data[i] * qs; w[(size_t)768 * 768 + i] = wk.data[i]; w[2 * (size_t)768 * 768 + i] = wv.data[i]; }
     for (int i = 0; i < 768; ++i) { b[i] = bq.data[i] * qs; b[768 + i] = bk.data[i]; }
-    conv1d_layer_init(Y.qk, w.data(), b.data(), 2304, 768, 1, 1, 0, 1, 1);
+    conv1d_layer_init(Y.qkv, w.data(), b.data(), 2304, 768, 1, 1, 0, 1, 1);
     Y.bv.upload(ts.get(p + "attention.v_proj.bias", {768}).data);
     linear_layer(Y.o, ts, p + "attention.out_proj", 768, 768);
     linear_layer(Y.ff1, ts, p + "feed_forward.intermediate_dense", 3072, 768);
@@ -112,9 +107,6 @@ void hubert_finalize(Hubert* H) {
 static void hubert_graph(Hubert* H, hipStream_t s, Arena& A, const float* audio, long long L, int version, int n_layers, float* out_rm,
                          float* out_cm, const HubertTaps* taps) {
   const bool dry = A.dry;
-  auto tap = [&](float* dst, const float* src, size_t n) {
-    if (!dry && dst) RVC_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  };
   ConvEpilogue E0;
   int Tc[8]; Tc[0] = (int)L;
   for (int i = 0; i < 7; ++i) Tc[i + 1] = (Tc[i] - kKern[i]) / kStride[i] + 1;
@@ -126,11 +118,7 @@ static void hubert_graph(Hubert* H, hipStream_t s, Arena& A, const float* audio,
   if (pos_s) {
     const size_t img0 = A.off;
     hpos_s = A.alloc<unsigned char>(split_image_bytes(768, T));
-    const size_t ib = A.off - img0;
-    if (!dry && (H->img_base != A.base + img0 || H->img_gen != A.gen || H->img_bytes != ib || H->img_T != T)) {
-      RVC_HIP_CHECK(hipMemsetAsync(A.base + img0, 0, ib, s));
-      H->img_base = A.base + img0; H->img_gen = A.gen; H->img_bytes = ib; H->img_T = T;
-    }
+    H->pos_img.ensure_zero(A, img0, A.off - img0, T, 0, s);
   }
   // ---- feature encoder
   // Layers 1 .. 6 (k = 3 / 2, stride 2, no padding) on the split-resident GEMM: every layer's output is written by its producer's epilogue as the bf16 hi / lo
@@ -170,7 +158,7 @@ static void hubert_graph(Hubert* H, hipStream_t s, Arena& A, const float* audio,
   feat = in;
   }
   // feat: [512][T]
-  if (taps) tap(taps->conv_stack, feat, (size_t)512 * T);
+  if (taps) tap(A, s, taps->conv_stack, feat, (size_t)512 * T);
   // Split-resident GEMM path (conv_x3s.hip): the activations that feed a k = 1 projection live as the bf16 hi / lo image the kernel stages,
   // written by their producers (LayerNorm, the attention's epilogue, FFN1's GELU epilogue); the fp32 copy is kept only where a residual or
   // the attention reads it.  Needs the bf16x3 weight images (context precision 1 / 2); without them the fp32-input kernels run.
@@ -179,8 +167,8 @@ static void hubert_graph(Hubert* H, hipStream_t s, Arena& A, const float* audio,
   RVC_REQUIRE(need <= (int)H->layers.size(), "not enough encoder layers loaded");
   bool gs = conv_x3s_eligible(H->proj) && (version != 1 || conv_x3s_eligible(H->final_proj));
   for (int l = 0; l < need && gs; ++l) {
-    const HubLayer& Y = H->layers[l];
-    gs = conv_x3s_eligible(Y.qk) && conv_x3s_eligible(Y.o) && conv_x3s_eligible(Y.ff1) && conv_x3s_eligible(Y.ff2);
+    const EncoderLayer& Y = H->layers[l];
+    gs = conv_x3s_eligible(Y.qkv) && conv_x3s_eligible(Y.o) && conv_x3s_eligible(Y.ff1) && conv_x3s_eligible(Y.ff2);
   }
   const long long tp = split_image_tp(T);
   float* ln = gs ? nullptr : A.alloc<float>((size_t)512 * T);
@@ -217,36 +205,15 @@ static void hubert_graph(Hubert* H, hipStream_t s, Arena& A, const float* audio,
     unsigned char* ff_s = gs ? A.alloc<unsigned char>(split_image_bytes(3072, T)) : nullptr;
     if (!dry) {
       if (gs) attention_vt_clear_tail(s, vt_s, 768, T);
+      const EncoderSplitBufs sb = {h, hb, hs, qk_s, vt_s, attn_s, ff_s};
+      const EncoderPlainBufs pb = {h, hb, qk, vr, attn, ff};
       for (int l = 0; l < need; ++l) {
-        HubLayer& Y = H->layers[l];
-        if (taps && l == 0) tap(taps->hidden_0, h, (size_t)768 * T);
-        if (taps && l == 8) tap(taps->hidden_8, h, (size_t)768 * T);
-        ConvEpilogue Er; Er.R = h; Er.ldR = T;
-        if (gs) {
-          // q | k | v in ONE launch: the q and k rows go to their image, the v rows through the transposing epilogue into the V^T image (v's bias after the attention)
-          ConvEpilogue Eqk; Eqk.ys_out = qk_s; Eqk.ys_tp = tp; Eqk.vt_out = vt_s; Eqk.vt_tp = attention_vt_tp(768); Eqk.vt_row0 = 1536;
-          conv_x3s_run(Y.qk, s, hs, tp, T, nullptr, T, Eqk);
-          attention_split(s, qk_s, tp, 1536, 0, 48, vt_s, 12, 64, T, 1.f, Y.bv.p, nullptr, T, attn_s, tp);
-          conv_x3s_run(Y.o, s, attn_s, tp, T, hb, T, Er);
-          layernorm_c_split(s, hb, Y.g1.p, Y.b1.p, h, hs, tp, kSplitMargin, 768, T, T, 1e-5f);
-          ConvEpilogue Eg; Eg.act = ACT_GELU; Eg.ys_out = ff_s; Eg.ys_tp = tp;
-          conv_x3s_run(Y.ff1, s, hs, tp, T, nullptr, T, Eg);                     // GELU in the epilogue, the 3072-channel tensor exists only as the image
-          conv_x3s_run(Y.ff2, s, ff_s, tp, T, hb, T, Er);
-          layernorm_c_split(s, hb, Y.g2.p, Y.b2.p, h, hs, tp, kSplitMargin, 768, T, T, 1e-5f);
-          continue;
-        }
-        conv1d_run(Y.qk, s, h, T, T, qk, T, E0);
-        transpose(s, qk + (size_t)1536 * T, vr, 768, T, T, 768, 1, 0, 0);      // V row-major [T][768] for the fused attention
-        // softmax(K^T Q) V + bv without materialising the [12][T][T] scores (attention.hip)
-        attention_fused(s, qk, qk + (size_t)768 * T, T, vr, 768, Y.bv.p, attn, T, 12, 64, T);
-        conv1d_run(Y.o, s, attn, T, T, hb, T, Er);
-        layernorm_c(s, hb, nullptr, Y.g1.p, Y.b1.p, h, 768, T, T, 1e-5f);
-        ConvEpilogue Eg; Eg.act = ACT_GELU;
-        conv1d_run(Y.ff1, s, h, T, T, ff, T, Eg);
-        conv1d_run(Y.ff2, s, ff, T, T, hb, T, Er);
-        layernorm_c(s, hb, nullptr, Y.g2.p, Y.b2.p, h, 768, T, T, 1e-5f);
+        if (taps && l == 0) tap(A, s, taps->hidden_0, h, (size_t)768 * T);
+        if (taps && l == 8) tap(A, s, taps->hidden_8, h, (size_t)768 * T);
+        if (gs) encoder_layer_run_split(s, H->layers[l], kHubEncoder, sb, T);
+        else encoder_layer_run_plain(s, H->layers[l], kHubEncoder, pb, T);
       }
-      if (taps && need == 8) tap(taps->hidden_8, h, (size_t)768 * T);
+      if (taps && need == 8) tap(A, s, taps->hidden_8, h, (size_t)768 * T);
     }
     A.off = mark;
   }
@@ -267,13 +234,7 @@ void hubert_forward(Hubert* H, hipStream_t s, const float* audio, long long L, i
   RVC_REQUIRE(H->ready, "hubert_finalize has not been called");
   RVC_REQUIRE(version == 1 || version == 2, "version must be 1 or 2");
   RVC_REQUIRE(hubert_num_frames(L) >= 2, "audio too short");
-  Arena& A = H->arena;
-  for (int pass = 0; pass < 2; ++pass) {
-    A.dry = (pass == 0); A.reset(); if (pass == 0) A.peak = 0;
-    hubert_graph(H, s, A, audio, L, version, n_layers, out_rm, out_cm, taps);
-    if (pass == 0) A.ensure(A.peak);
-  }
-  A.dry = false;
+  arena_passes(H->arena, [&] { hubert_graph(H, s, H->arena, audio, L, version, n_layers, out_rm, out_cm, taps); });
 }
 
 size_t hubert_workspace(const Hubert* M) { return M->arena.cap; }

@@ -45,7 +45,7 @@ struct Mdx23 : Mdx23Weights {
   // lanes with streams of their own (they are independent until the overlap-add): the small launches of the deep levels of one chunk run beside the chip-filling ones of another
   static constexpr int kMaxLanes = 4;
   struct Lane {
-    Arena arena; const char* img_base = nullptr; size_t img_bytes = 0; unsigned img_gen = 0; hipStream_t st = nullptr; hipEvent_t done = nullptr; DevBuf<float> acc;
+    Arena arena; ZeroedBlock imgs; hipStream_t st = nullptr; hipEvent_t done = nullptr; DevBuf<float> acc;
     Lane() = default;
     ~Lane() {      // the stream's work is waited for before the stream, the accumulator and the arena go
       if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
@@ -139,7 +139,7 @@ void mdx23_finalize(Mdx23* M) {
     for (auto& S : M->enc) { blocks_ok(S.blocks); ok = ok && conv_x3s_eligible(S.rs); }
     for (auto& S : M->dec) { blocks_ok(S.blocks); ok = ok && conv_x3s_eligible(S.rs); }
     blocks_ok(M->bott.blocks);
-    M->pad_ok = ok; for (auto& Ln : M->lane) Ln.img_base = nullptr;
+    M->pad_ok = ok; for (auto& Ln : M->lane) Ln.imgs.reset();
     static const bool fuse = (knob_int("RVC_MDX_FUSE_SC", 1) != 0);
     auto fuse_blocks = [&](std::vector<TfcBlock>& bs) {
       for (TfcBlock& B : bs)
@@ -732,11 +732,7 @@ static void mdx23_graph_padded(Mdx23* M, Mdx23::Lane& Ln, hipStream_t s, Arena& 
     P.ir = i < n ? A.alloc<unsigned char>(pad_img_bytes(2 * P.C, P)) : nullptr;
     RVC_REQUIRE((double)pad_img_bytes(chans, P) + 2.0 * (double)pad_img_bytes(P.C, P) + (double)pad_img_bytes(2 * P.C, P) < 2147483648.0, "a level's images exceed 32-bit buffer addressing");
   }
-  const size_t img_bytes = A.off - img0;
-  if (!dry && (Ln.img_base != A.base + img0 || Ln.img_gen != A.gen || Ln.img_bytes != img_bytes)) {
-    RVC_HIP_CHECK(hipMemsetAsync(A.base + img0, 0, img_bytes, s));
-    Ln.img_base = A.base + img0; Ln.img_gen = A.gen; Ln.img_bytes = img_bytes;
-  }
+  Ln.imgs.ensure_zero(A, img0, A.off - img0, 0, 0, s);      // (one chunk geometry per model: no length key)
   // ---- images of the TDF linears' inputs (k = 1 products: no taps, margins never multiplied into a kept column)
   size_t il_bytes = 0, im_bytes = 0;
   for (int i = 0; i <= n; ++i) {
@@ -823,12 +819,7 @@ static void mdx23_graph_padded(Mdx23* M, Mdx23::Lane& Ln, hipStream_t s, Arena& 
 static void mdx23_chunk(Mdx23* M, int lane, hipStream_t s, const float* audio, long long L, float* out, const MdxIO& io) {
   Mdx23::Lane& Ln = M->lane[lane];
   Arena& A = Ln.arena;
-  for (int pass = 0; pass < 2; ++pass) {
-    A.dry = (pass == 0); A.reset(); if (pass == 0) A.peak = 0;
-    if (M->pad_ok) mdx23_graph_padded(M, Ln, s, A, audio, L, out, io); else mdx23_graph_plain(M, s, A, audio, L, out, io);
-    if (pass == 0) A.ensure(A.peak);
-  }
-  A.dry = false;
+  arena_passes(A, [&] { if (M->pad_ok) mdx23_graph_padded(M, Ln, s, A, audio, L, out, io); else mdx23_graph_plain(M, s, A, audio, L, out, io); });
 }
 void mdx23_forward(Mdx23* M, hipStream_t s, const float* audio, long long L, float* out) {
   RVC_REQUIRE(M->ready, "mdx23_finalize has not been called");

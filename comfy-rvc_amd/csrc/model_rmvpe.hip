@@ -17,7 +17,7 @@ struct RmvpeWeights {    // what rmvpe_finalize builds, and what the graph has l
   OwnedConvLayer dect[5];
   OwnedConvLayer dect_t[4];   // the same transposed convolutions as 2 x 2-tap phase convolutions for the split-resident kernel (input levels 5 .. 2)
   bool pad_ok = false;     // every layer of levels >= 2 has its bf16x3 image: those levels run on padded split-resident images (conv_x3s.hip)
-  const void* img_base = nullptr; unsigned img_gen = 0; size_t img_bytes = 0; int img_H1 = -1;   // image block whose margins are known to be zero (for this length)
+  ZeroedBlock pad_imgs;   // image block whose margins are known to be zero (key: H1, the length)
   OwnedConvLayer cnn;
   DevVec wihT, b_ih, w_hh, w_hh_t, b_hh;
   OwnedConvLayer fc;
@@ -226,12 +226,8 @@ static void rmvpe_pad_plan(Rmvpe* R, hipStream_t s, Arena& A, int H1, PadPlan& P
     P.iy[l] = A.alloc<unsigned char>(pad_img_bytes(P.lv[l].C, P.lv[l]));
     P.icat[l] = l <= 4 ? A.alloc<unsigned char>(pad_img_bytes(2 * P.lv[l].C, P.lv[l])) : nullptr;              // [deconv out | encoder skip]
   }
-  const size_t img_bytes = A.off - img0;
   // (a shorter clip in the same allocation leaves the longer one's rows behind its end: the length is part of the layout)
-  if (!A.dry && (R->img_base != A.base + img0 || R->img_gen != A.gen || R->img_bytes != img_bytes || R->img_H1 != H1)) {
-    RVC_HIP_CHECK(hipMemsetAsync(A.base + img0, 0, img_bytes, s));
-    R->img_base = A.base + img0; R->img_gen = A.gen; R->img_bytes = img_bytes; R->img_H1 = H1;
-  }
+  R->pad_imgs.ensure_zero(A, img0, A.off - img0, H1, 0, s);
 }
 
 static void rmvpe_unet_padded(Rmvpe* R, hipStream_t s, Arena& A, const PadPlan& P, const float* skip1, int H1, float* up1) {
@@ -410,18 +406,12 @@ void rmvpe_forward(Rmvpe* R, hipStream_t s, const float* audio, long long L, flo
                    const RmvpeTaps* taps) {
   RVC_REQUIRE(R->ready, "rmvpe_finalize has not been called");
   RVC_REQUIRE(L >= 1024 && L / 160 + 1 >= 32, "audio too short for RMVPE (need >= 0.32 s)");
-  Arena& A = R->arena;
-  for (int pass = 0; pass < 2; ++pass) {
-    A.dry = (pass == 0); A.reset(); if (pass == 0) A.peak = 0;
-    rmvpe_graph(R, s, A, audio, L, thred, mel_out, salience_out, f0_out, taps);
-    if (pass == 0) A.ensure(A.peak);
-  }
-  A.dry = false;
+  arena_passes(R->arena, [&] { rmvpe_graph(R, s, R->arena, audio, L, thred, mel_out, salience_out, f0_out, taps); });
 }
 
 void rmvpe_decode_rm(Rmvpe* R, hipStream_t s, const float* sal_rm, long long n, float thred, double* f0) {
   Arena& A = R->arena;
-  A.dry = false; A.reset(); A.ensure((size_t)360 * n * sizeof(float) + 4096);
+  A.reset(); A.ensure((size_t)360 * n * sizeof(float) + 4096);      // one buffer of known size: a single real pass
   float* cm = A.alloc<float>((size_t)360 * n);
   transpose(s, sal_rm, cm, (int)n, 360, 360, n, 1, 0, 0);
   rmvpe_decode(s, cm, f0, (int)n, n, thred);

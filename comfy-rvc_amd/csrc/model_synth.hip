@@ -2,7 +2,7 @@
 // enc_p (TextEncoder + 6 relative-position attention layers) -> z_p sampling -> 4 reversed coupling layers (WN)
 // -> GeneratorNSF (SineGen source, ConvTranspose1d stages, 3x ResBlock1 per stage, conv_post, tanh).
 // Activations are channel-major [C][T]; weights arrive with the reference's state-dict names and are folded here.
-#include "model_common.h"
+#include "model_encoder.h"
 #include "models.h"
 #include "conv_kernels.h"
 
@@ -28,16 +28,6 @@ static OwnedConvLayer make_conv1d(const TensorStore& ts, const std::string& p, i
   return L;
 }
 
-struct EncLayer {
-  OwnedConvLayer qk;       // fused conv_q (pre-scaled by 1/sqrt(kc)) and conv_k: C -> 2C
-  DevVec bv;               // conv_v's bias, added after P.V; its rows are part of the qk layer (C -> 3 C)
-  OwnedConvLayer relk, relv;   // emb_rel_k as a 21-row projection of Q; emb_rel_v as a 21 -> kc projection of banded P (unfused path)
-  DevVec ek, ev;           // the raw [21][kc] tables: the fused attention kernel does both projections itself
-  DevVec rel_img;          // the same tables as the MFMA operand images of attention_split (kc = 96): E_k image, then E_v^T image (bf16 hi / lo)
-  size_t evt_off = 0;      // byte offset of the E_v^T image
-  OwnedConvLayer o, ffn1, ffn2;
-  DevVec g1, b1, g2, b2;
-};
 // modules.WN (reference lib/infer_pack/modules.py:130-209) with dilation_rate 1: n layers; the flow's couplings hold 3, the posterior encoder 16
 struct WNStack {
   int n = 0;
@@ -63,7 +53,7 @@ struct GenStage { OwnedConvLayer up, noise; DevVec noise_w, noise_b; int u = 1, 
 
 struct SynthWeights {    // what synth_finalize builds, and what the graph has learnt about it
   DevVec emb_phone_wT, emb_phone_b, emb_pitch, emb_g;
-  std::vector<EncLayer> enc;
+  std::vector<EncoderLayer> enc;
   OwnedConvLayer proj;
   FlowLayer flow[4];
   Posterior post_enc;
@@ -71,7 +61,7 @@ struct SynthWeights {    // what synth_finalize builds, and what the graph has l
   DevVec dec_cond_w, dec_cond_b, conv_post_w;   // conv_post_w: raw [Ci][7] weights of the 1-channel output conv (ops.hip::conv_to1)
   std::vector<GenStage> stages;
   float lin_w = 1.f, lin_b = 0.f;
-  const void* img_base = nullptr; unsigned img_gen = 0; size_t img_bytes = 0; int img_T = -1, img_W = -1;   // split-resident image block whose margins are known to be zero (synth_graph); img_W: columns of the z image (the generator's window)
+  ZeroedBlock imgs;      // split-resident image block whose margins are known to be zero (split_imgs_alloc; keys: T, and the columns of the z image = the generator's window)
 };
 struct Synth : SynthWeights {
   Ctx* ctx = nullptr;
@@ -98,6 +88,8 @@ Synth* synth_create(Ctx* ctx, const SynthConfig& c) {
   S->upp = 1;
   for (int i = 0; i < c.n_upsamples; ++i) { S->up_rates.push_back(c.upsample_rates[i]); S->up_k.push_back(c.upsample_kernel_sizes[i]); S->upp *= c.upsample_rates[i]; }
   RVC_REQUIRE(S->hidden % S->n_heads == 0, "heads must divide hidden");
+  // the text encoder's relative-position attention exists for head dimension 96: every configuration the reference ships has hidden_channels 192, n_heads 2
+  RVC_REQUIRE(S->hidden / S->n_heads == 96, "hidden_channels / n_heads must be 96, got " + std::to_string(S->hidden / S->n_heads));
   return S.release();
 }
 void synth_destroy(Synth* S) { delete S; }
@@ -186,7 +178,7 @@ void synth_finalize(Synth* S) {
   S->enc.resize(S->n_layers);
   const float qscale = 1.f / std::sqrt((float)kc);
   for (int l = 0; l < S->n_layers; ++l) {
-    EncLayer& e = S->enc[l];
+    EncoderLayer& e = S->enc[l];
     const std::string p = "enc_p.encoder.attn_layers." + std::to_string(l) + ".";
     const HostTensor& wq = ts.get(p + "conv_q.weight", {C, C, 1});
     const HostTensor& wk = ts.get(p + "conv_k.weight", {C, C, 1});
@@ -196,25 +188,20 @@ void synth_finalize(Synth* S) {
     for (size_t i = 0; i < (size_t)C * C; ++i) { w[i] = wq.data[i] * qscale; w[(size_t)C * C + i] = wk.data[i]; w[2 * (size_t)C * C + i] = wv.data[i]; }
     const HostTensor& bq = ts.get(p + "conv_q.bias", {C}); const HostTensor& bk = ts.get(p + "conv_k.bias", {C});
     for (int i = 0; i < C; ++i) { b[i] = bq.data[i] * qscale; b[C + i] = bk.data[i]; }
-    conv1d_layer_init(e.qk, w.data(), b.data(), 3 * C, C, 1, 1, 0, 1, 1);
+    conv1d_layer_init(e.qkv, w.data(), b.data(), 3 * C, C, 1, 1, 0, 1, 1);
     e.bv.upload(ts.get(p + "conv_v.bias", {C}).data);
     const HostTensor& rk = ts.get(p + "emb_rel_k", {1, 21, kc});
-    conv1d_layer_init(e.relk, rk.data.data(), nullptr, 21, kc, 1, 1, 0, 1, 1);            // [r][d]: out[r][q] = sum_d E_k[r][d] Q[d][q]
     const HostTensor& rv = ts.get(p + "emb_rel_v", {1, 21, kc});
-    std::vector<float> rvT = transpose2d(rv.data.data(), 21, kc);                           // [d][r]: out[d][q] = sum_r E_v[r][d] Pb[r][q]
-    conv1d_layer_init(e.relv, rvT.data(), nullptr, kc, 21, 1, 1, 0, 1, 1);
     e.ek.upload(rk.data); e.ev.upload(rv.data);
-    if (kc == 96) {
-      std::vector<uint16_t> eki, evi;
-      attention_rel_images(rk.data.data(), rv.data.data(), kc, 10, eki, evi);
-      e.evt_off = eki.size() * 2;
-      eki.insert(eki.end(), evi.begin(), evi.end());
-      e.rel_img.upload(reinterpret_cast<const float*>(eki.data()), eki.size() / 2);
-    }
+    std::vector<uint16_t> eki, evi;
+    attention_rel_images(rk.data.data(), rv.data.data(), kc, 10, eki, evi);
+    e.evt_off = eki.size() * 2;
+    eki.insert(eki.end(), evi.begin(), evi.end());
+    e.rel_img.upload(reinterpret_cast<const float*>(eki.data()), eki.size() / 2);
     e.o = make_conv1d(ts, p + "conv_o", 1, 0, 1, false);
     const std::string f = "enc_p.encoder.ffn_layers." + std::to_string(l) + ".";
-    e.ffn1 = make_conv1d(ts, f + "conv_1", 1, (S->ksz - 1) / 2, 1, false);
-    e.ffn2 = make_conv1d(ts, f + "conv_2", 1, (S->ksz - 1) / 2, 1, false);
+    e.ff1 = make_conv1d(ts, f + "conv_1", 1, (S->ksz - 1) / 2, 1, false);
+    e.ff2 = make_conv1d(ts, f + "conv_2", 1, (S->ksz - 1) / 2, 1, false);
     RVC_REQUIRE(S->ksz % 2 == 1, "enc_p FFN kernel must be odd (symmetric same-padding)");
     e.g1.upload(ts.get("enc_p.encoder.norm_layers_1." + std::to_string(l) + ".gamma", {C}).data);
     e.b1.upload(ts.get("enc_p.encoder.norm_layers_1." + std::to_string(l) + ".beta", {C}).data);
@@ -324,8 +311,8 @@ static bool synth_split_front(const Synth* S) {
   const int C = S->hidden, IC = S->inter;
   bool gs = (C & 15) == 0 && (IC & 31) == 0 && conv_x3s_eligible(S->proj) && conv_x3s_eligible(S->conv_pre);
   for (int l = 0; l < S->n_layers && gs; ++l) {
-    const EncLayer& e = S->enc[l];
-    gs = conv_x3s_eligible(e.qk) && conv_x3s_eligible(e.o) && conv_x3s_eligible(e.ffn1) && conv_x3s_eligible(e.ffn2);
+    const EncoderLayer& e = S->enc[l];
+    gs = conv_x3s_eligible(e.qkv) && conv_x3s_eligible(e.o) && conv_x3s_eligible(e.ff1) && conv_x3s_eligible(e.ff2);
   }
   for (int f = 0; f < 4 && gs; ++f) {
     const FlowLayer& F = S->flow[f];
@@ -344,26 +331,20 @@ static SplitImgs split_imgs_alloc(Synth* S, hipStream_t s, Arena& A, int T, int 
   m.x0_s = A.alloc<unsigned char>(split_image_bytes(IC / 2, T)); m.hw_s = A.alloc<unsigned char>(split_image_bytes(2 * C, T));
   m.acts_s = A.alloc<unsigned char>(split_image_bytes(C, T)); m.z_s = A.alloc<unsigned char>(split_image_bytes(IC, W));
   if (spec_rows > 0) m.spec_s = A.alloc<unsigned char>(split_image_bytes(spec_rows, T));
-  const size_t img_bytes = A.off - img0;
   // (a shorter sequence in the same allocation leaves the longer one's rows behind its end: the length is part of the layout - both lengths: the z image
   // holds the generator's W columns)
-  if (!A.dry && (S->img_base != A.base + img0 || S->img_gen != A.gen || S->img_bytes != img_bytes || S->img_T != T || S->img_W != W)) {
-    RVC_HIP_CHECK(hipMemsetAsync(A.base + img0, 0, img_bytes, s));
-    S->img_base = A.base + img0; S->img_gen = A.gen; S->img_bytes = img_bytes; S->img_T = T; S->img_W = W;
-  }
+  S->imgs.ensure_zero(A, img0, A.off - img0, T, W, s);
   return m;
 }
 
 // TextEncoder{256,768} (reference models.py:43-58,:90-105) up to and including proj: returns stats = [m_p | logs_p], 2 inter rows of T columns
 static float* enc_p_stats(Synth* S, hipStream_t s, Arena& A, bool gs, const SplitImgs& im, const float* feat_cm, const long long* pitch, int T,
                           float* enc_p_layer0) {
-  const int C = S->hidden, H = S->n_heads, kc = C / H, IC = S->inter;
+  const int C = S->hidden, IC = S->inter;
+  const EncoderShape sh = {C, S->n_heads, C / S->n_heads, 10, ACT_RELU, S->filt};
   const bool dry = A.dry;
   const long long tp = split_image_tp(T);
-  unsigned char *x_s = im.x_s, *attn_s = im.attn_s, *ff_s = im.ff_s;
-  auto tap = [&](float* dst, const float* src, size_t n) {
-    if (!dry && dst) RVC_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  };
+  unsigned char *x_s = im.x_s;
   ConvEpilogue E0;
   // ---- enc_p
   float* x = A.alloc<float>((size_t)C * T);
@@ -377,79 +358,20 @@ static float* enc_p_stats(Synth* S, hipStream_t s, Arena& A, bool gs, const Spli
     const size_t mark = A.off;
     // attention on split-resident operands (attention_dma_kernel.h): q / k as one image, V^T written by the q | k | v launch (or by the swapped product);
     // otherwise fp32 q / k / v
-    const bool ad = gs && kc == 96;
-    unsigned char* qk_s = ad ? A.alloc<unsigned char>(split_image_bytes(2 * C, T)) : nullptr;
-    unsigned char* vt_s = ad ? A.alloc<unsigned char>(attention_vt_bytes(C, T)) : nullptr;
-    float* qk = ad ? nullptr : A.alloc<float>((size_t)3 * C * T);
-    float* vr = ad ? nullptr : A.alloc<float>((size_t)T * C);
-    const bool fused_att = kc == 96;
-    float* Sc = fused_att ? nullptr : A.alloc<float>((size_t)H * T * T);
-    float* relk = ad ? nullptr : A.alloc<float>((size_t)H * 21 * T);
-    float* pb = ad ? nullptr : A.alloc<float>((size_t)H * 21 * T);
-    float* attn = ad ? nullptr : A.alloc<float>((size_t)C * T);
+    unsigned char* qk_s = gs ? A.alloc<unsigned char>(split_image_bytes(2 * C, T)) : nullptr;
+    unsigned char* vt_s = gs ? A.alloc<unsigned char>(attention_vt_bytes(C, T)) : nullptr;
+    float* qk = gs ? nullptr : A.alloc<float>((size_t)3 * C * T);
+    float* vr = gs ? nullptr : A.alloc<float>((size_t)T * C);
+    float* attn = gs ? nullptr : A.alloc<float>((size_t)C * T);
     float* ff = gs ? nullptr : A.alloc<float>((size_t)S->filt * T);
     if (!dry) {
-      if (ad) attention_vt_clear_tail(s, vt_s, C, T);
+      if (gs) attention_vt_clear_tail(s, vt_s, C, T);
+      const EncoderSplitBufs sb = {x, xb, x_s, qk_s, vt_s, im.attn_s, im.ff_s};
+      const EncoderPlainBufs pb = {x, xb, qk, vr, attn, ff};
       for (int l = 0; l < S->n_layers; ++l) {
-        EncLayer& e = S->enc[l];
-        if (ad) {
-          if (((2 * C) & 127) == 0) {
-            // q | k | v in ONE launch: q and k rows to their image, the v rows through the transposing epilogue into the V^T image
-            ConvEpilogue Eqk; Eqk.ys_out = qk_s; Eqk.ys_tp = tp; Eqk.vt_out = vt_s; Eqk.vt_tp = attention_vt_tp(C); Eqk.vt_row0 = 2 * C;
-            conv_x3s_run(e.qk, s, x_s, tp, T, nullptr, T, Eqk);
-          } else {
-            ConvLayer qkL = e.qk; qkL.Co = 2 * C;                                 // a VIEW (explicit copy of the owner's base, frees nothing): the q and k rows of the 3 C-row projection -> image only
-            ConvEpilogue Eqk; Eqk.ys_out = qk_s; Eqk.ys_tp = tp;
-            conv_x3s_run(qkL, s, x_s, tp, T, nullptr, T, Eqk);
-            conv_x3s_run_swapped(e.qk, 2 * C, C, s, x_s, tp, T, vt_s, attention_vt_tp(C));
-          }
-          const unsigned char* ri = reinterpret_cast<const unsigned char*>(e.rel_img.p);
-          // softmax(K^T Q + banded rel-k bias) V + bv + banded P . E_v, written as the image the out-projection stages
-          attention_split(s, qk_s, tp, 2 * C, 0, C / 16, vt_s, H, kc, T, 1.f, e.bv.p, nullptr, T, attn_s, tp, 10, ri, ri + e.evt_off);
-          ConvEpilogue Er; Er.R = x; Er.ldR = T;
-          conv_x3s_run(e.o, s, attn_s, tp, T, xb, T, Er);
-          layernorm_c_split(s, xb, e.g1.p, e.b1.p, x, x_s, tp, kSplitMargin, C, T, T, 1e-5f);
-          ConvEpilogue Ef; Ef.act = ACT_RELU; Ef.ys_out = ff_s; Ef.ys_tp = tp;
-          conv_x3s_run(e.ffn1, s, x_s, tp, T, nullptr, T, Ef);
-          conv_x3s_run(e.ffn2, s, ff_s, tp, T, xb, T, Er);
-          layernorm_c_split(s, xb, e.g2.p, e.b2.p, x, x_s, tp, kSplitMargin, C, T, T, 1e-5f);
-          if (l == 0) tap(enc_p_layer0, x, (size_t)C * T);
-          continue;
-        }
-        if (gs) conv_x3s_run(e.qk, s, x_s, tp, T, qk, T, E0); else
-        conv1d_run(e.qk, s, x, T, T, qk, T, E0);
-        transpose(s, qk + (size_t)2 * C * T, vr, C, T, T, C, 1, 0, 0);                                       // V row-major [T][C] (bias later)
-        if (fused_att) {
-          // softmax(K^T Q + banded rel-k bias) V + bv + banded P . E_v in ONE kernel: both relative-position projections included
-          attention_rel_fused(s, qk, qk + (size_t)C * T, T, vr, C, e.bv.p, nullptr, nullptr, 10, attn, T, H, kc, T, e.ek.p, e.ev.p);
-        } else {
-        for (int h = 0; h < H; ++h) conv1d_run(e.relk, s, qk + (size_t)h * kc * T, T, T, relk + (size_t)h * 21 * T, T, E0);
-        gemm_tn_run(s, qk + (size_t)C * T, T, (long long)kc * T, qk, T, (long long)kc * T, Sc, T, (long long)T * T, T, T, kc, H, nullptr, 0, E0);
-        fill(s, pb, 0.f, (long long)H * 21 * T);
-        softmax_cols(s, Sc, T, T, T, (long long)T * T, H, relk, 21LL * T, 10, pb, 21LL * T);
-        gemm_tn_run(s, vr, C, kc, Sc, T, (long long)T * T, attn, T, (long long)kc * T, kc, T, T, H, e.bv.p, kc, E0);
-        ConvEpilogue Ea; Ea.accumulate = 1;
-        for (int h = 0; h < H; ++h) conv1d_run(e.relv, s, pb + (size_t)h * 21 * T, T, T, attn + (size_t)h * kc * T, T, Ea);
-        }
-        ConvEpilogue Er; Er.R = x; Er.ldR = T;
-        if (gs) {
-          split_image_from_f32(s, attn, T, C, T, attn_s, tp);
-          conv_x3s_run(e.o, s, attn_s, tp, T, xb, T, Er);
-          layernorm_c_split(s, xb, e.g1.p, e.b1.p, x, x_s, tp, kSplitMargin, C, T, T, 1e-5f);
-          ConvEpilogue Ef; Ef.act = ACT_RELU; Ef.ys_out = ff_s; Ef.ys_tp = tp;
-          conv_x3s_run(e.ffn1, s, x_s, tp, T, nullptr, T, Ef);                  // k = 3: taps are row offsets into the image
-          conv_x3s_run(e.ffn2, s, ff_s, tp, T, xb, T, Er);
-          layernorm_c_split(s, xb, e.g2.p, e.b2.p, x, x_s, tp, kSplitMargin, C, T, T, 1e-5f);
-          if (l == 0) tap(enc_p_layer0, x, (size_t)C * T);
-          continue;
-        }
-        conv1d_run(e.o, s, attn, T, T, xb, T, Er);
-        layernorm_c(s, xb, nullptr, e.g1.p, e.b1.p, x, C, T, T, 1e-5f);
-        ConvEpilogue Ef; Ef.act = ACT_RELU;
-        conv1d_run(e.ffn1, s, x, T, T, ff, T, Ef);
-        conv1d_run(e.ffn2, s, ff, T, T, xb, T, Er);
-        layernorm_c(s, xb, nullptr, e.g2.p, e.b2.p, x, C, T, T, 1e-5f);
-        if (l == 0) tap(enc_p_layer0, x, (size_t)C * T);
+        if (gs) encoder_layer_run_split(s, S->enc[l], sh, sb, T);
+        else encoder_layer_run_plain(s, S->enc[l], sh, pb, T);
+        if (l == 0) tap(A, s, enc_p_layer0, x, (size_t)C * T);
       }
     }
     A.off = mark;
@@ -529,9 +451,6 @@ static void gen_tail(Synth* S, hipStream_t s, Arena& A, bool gs, unsigned char* 
                      int h2, float* out, const SynthTaps* taps) {
   const int IC = S->inter;
   const bool dry = A.dry;
-  auto tap = [&](float* dst, const float* src, size_t n) {
-    if (!dry && dst) RVC_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  };
   // From here on every tensor holds the W columns of the window; the three full-length operands are addressed at its start: z + g0 (pitch T), har + g0 upp,
   // out + g0 upp.  Every launch is planned for the whole sequence and sized for the window: beside a stage's window length (Tc, Tn) runs the whole sequence's
   // (Tfull_c, Tfull_n), handed to every planner and, as ConvEpilogue::plan_tin, to every *_run - a window's columns are computed by the kernels, tiles and K
@@ -606,7 +525,7 @@ static void gen_tail(Synth* S, hipStream_t s, Arena& A, bool gs, unsigned char* 
       } else {
         conv1d_run(st.noise, s, har_w, Tn, Tn, up, Tn, En);
       }
-      if (taps && i == 0) tap(taps->gen_ups0, up, (size_t)Cc * Tn);
+      if (taps && i == 0) tap(A, s, taps->gen_ups0, up, (size_t)Cc * Tn);
       for (int j = 0; j < 3; ++j) {
         const float* in = up;
         if (rb3_ok[j]) { conv_rb3_launch(rb3[j], s); continue; }
@@ -633,11 +552,19 @@ static void gen_tail(Synth* S, hipStream_t s, Arena& A, bool gs, unsigned char* 
           in = dst;
         }
       }
-      if (taps && i == nu - 1) tap(taps->gen_last, xs, (size_t)Cc * Tn);
+      if (taps && i == nu - 1) tap(A, s, taps->gen_last, xs, (size_t)Cc * Tn);
     }
     cur = xs; Tc = Tn; Tfull_c = Tfull_n;
   }
   if (!dry) conv_to1(s, cur, Tc, S->conv_post_w.p, S->up_init >> nu, 7, 3, Tc, 0.01f, 1, out + (size_t)g0 * S->upp);
+}
+
+// the phone features channel-major [feat_dim][T]: the caller's own tensor, or its transpose as the graph's first temporary
+static const float* feat_cm_of(const Synth* S, hipStream_t s, Arena& A, const float* feat, int feat_channel_major, int T) {
+  if (feat_channel_major) return feat;
+  float* t = A.alloc<float>((size_t)S->feat_dim * T);
+  if (!A.dry) transpose(s, feat, t, T, S->feat_dim, S->feat_dim, T, 1, 0, 0);
+  return t;
 }
 
 static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm, const long long* pitch, const float* pitchf, int sid,
@@ -647,9 +574,6 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
   const int C = S->hidden, IC = S->inter;
   const bool dry = A.dry;
   const int h2 = conv_set_pair_arithmetic(-1);      // read once: the whole pass plans with the pair arithmetic it saw when it started
-  auto tap = [&](float* dst, const float* src, size_t n) {
-    if (!dry && dst) RVC_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  };
   const bool gs = synth_split_front(S);
   SplitImgs im;
   if (gs) im = split_imgs_alloc(S, s, A, T, W, 0);
@@ -666,9 +590,9 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
   float* z = A.alloc<float>((size_t)IC * T);
   float* zf = A.alloc<float>((size_t)IC * T);
   if (!dry) {
-    if (taps) { tap(taps->m_p, stats, (size_t)IC * T); tap(taps->logs_p, stats + (size_t)IC * T, (size_t)IC * T); }
+    if (taps) { tap(A, s, taps->m_p, stats, (size_t)IC * T); tap(A, s, taps->logs_p, stats + (size_t)IC * T, (size_t)IC * T); }
     zp_sample(s, stats, noise_z, z, IC, T);
-    if (taps) tap(taps->z_p, z, (size_t)IC * T);
+    if (taps) tap(A, s, taps->z_p, z, (size_t)IC * T);
   }
   // ---- flow (reverse)
   {
@@ -686,7 +610,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
         coupling_run(S, s, S->flow[f], gcond[f], gs, im, wb, cur, T, true);
       }
       if (cur != z) RVC_HIP_CHECK(hipMemcpyAsync(z, cur, (size_t)IC * T * sizeof(float), hipMemcpyDeviceToDevice, s));
-      if (taps) tap(taps->z, z, (size_t)IC * T);
+      if (taps) tap(A, s, taps->z, z, (size_t)IC * T);
     }
     A.off = mark;
   }
@@ -699,7 +623,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
     double* bsum = A.alloc<double>((size_t)((N + 1023) / 1024));
     if (!dry) {
       sine_source(s, pitchf, noise_src, har, taps ? taps->sine_waves : nullptr, rad, tmp, bsum, T, S->upp, (float)S->sr, S->lin_w, S->lin_b);
-      if (taps) tap(taps->har_source, har, (size_t)N);
+      if (taps) tap(A, s, taps->har_source, har, (size_t)N);
     }
   }
   gen_tail(S, s, A, gs, im.z_s, z, har, pre_bias, T, g0, W, h2, out, taps);
@@ -713,9 +637,6 @@ static void synth_forward_graph(Synth* S, hipStream_t s, Arena& A, const float* 
   const bool dry = A.dry;
   const int h2 = conv_set_pair_arithmetic(-1);
   const long long tp = split_image_tp(T);
-  auto tap = [&](float* dst, const float* src, size_t n) {
-    if (!dry && dst) RVC_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  };
   ConvEpilogue E0;
   bool gs = synth_split_front(S) && conv_x3s_eligible(Q.pre) && conv_x3s_eligible(Q.proj) && wn_split_eligible(Q.wn);
   for (int f = 0; f < 4 && gs; ++f) gs = conv_x3s_eligible(S->flow[f].post);
@@ -734,7 +655,7 @@ static void synth_forward_graph(Synth* S, hipStream_t s, Arena& A, const float* 
   }
   // ---- enc_p -> m_p, logs_p
   float* stats = enc_p_stats(S, s, A, gs, im, feat_cm, pitch, T, nullptr);
-  if (!dry && taps) { tap(taps->m_p, stats, (size_t)IC * T); tap(taps->logs_p, stats + (size_t)IC * T, (size_t)IC * T); }
+  if (!dry && taps) { tap(A, s, taps->m_p, stats, (size_t)IC * T); tap(A, s, taps->logs_p, stats + (size_t)IC * T, (size_t)IC * T); }
   // ---- enc_q -> z, m_q, logs_q
   float* stats_q = A.alloc<float>((size_t)2 * IC * T);
   float* z = A.alloc<float>((size_t)IC * T);
@@ -762,7 +683,7 @@ static void synth_forward_graph(Synth* S, hipStream_t s, Arena& A, const float* 
       if (gs) conv_x3s_run(Q.proj, s, wb.hw_s + split_image_bytes(C, T), tp, T, stats_q, T, E0);
       else conv1d_run(Q.proj, s, wo, T, T, stats_q, T, E0);
       posterior_sample(s, stats_q, noise_q, z, IC, T);
-      if (taps) { tap(taps->m_q, stats_q, (size_t)IC * T); tap(taps->logs_q, stats_q + (size_t)IC * T, (size_t)IC * T); tap(taps->z, z, (size_t)IC * T); }
+      if (taps) { tap(A, s, taps->m_q, stats_q, (size_t)IC * T); tap(A, s, taps->logs_q, stats_q + (size_t)IC * T, (size_t)IC * T); tap(A, s, taps->z, z, (size_t)IC * T); }
       // ---- flow (forward): coupling 0 .. 3, each followed by Flip (reference models.py:185-192)
       RVC_HIP_CHECK(hipMemcpyAsync(zp, z, (size_t)IC * T * sizeof(float), hipMemcpyDeviceToDevice, s));
       float* cur = zp; float* oth = zf;
@@ -771,7 +692,7 @@ static void synth_forward_graph(Synth* S, hipStream_t s, Arena& A, const float* 
         flip_c(s, cur, oth, IC, T);
         std::swap(cur, oth);
       }
-      if (taps) tap(taps->z_p, cur, (size_t)IC * T);
+      if (taps) tap(A, s, taps->z_p, cur, (size_t)IC * T);
     }
     A.off = mark;
   }
@@ -829,18 +750,7 @@ void synth_infer_window(Synth* S, hipStream_t s, const float* feat, int feat_cha
   synth_window_frames(S, T, keep0, keep1, halo, &g0, &g1);
   if (taps) { g0 = 0; g1 = T; }                                  // (the generator's taps are whole tensors)
   Arena& A = S->arena;
-  for (int pass = 0; pass < 2; ++pass) {
-    A.dry = (pass == 0); A.reset(); if (pass == 0) A.peak = 0;
-    const float* fcm = feat;
-    if (!feat_channel_major) {
-      float* t = A.alloc<float>((size_t)S->feat_dim * T);
-      if (!A.dry) transpose(s, feat, t, T, S->feat_dim, S->feat_dim, T, 1, 0, 0);
-      fcm = t;
-    }
-    synth_graph(S, s, A, fcm, pitch, pitchf, sid, noise_z, noise_src, T, out, taps, g0, g1);
-    if (pass == 0) A.ensure(A.peak);
-  }
-  A.dry = false;
+  arena_passes(A, [&] { synth_graph(S, s, A, feat_cm_of(S, s, A, feat, feat_channel_major, T), pitch, pitchf, sid, noise_z, noise_src, T, out, taps, g0, g1); });
 }
 void synth_infer(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, int sid,
                  const float* noise_z, const float* noise_src, int T, float* out, const SynthTaps* taps) {
@@ -856,18 +766,7 @@ void synth_forward(Synth* S, hipStream_t s, const float* feat, int feat_channel_
   RVC_REQUIRE(ids >= 0 && ids <= T - S->segment, "slice start outside [0, T - segment]");
   RVC_REQUIRE(sid >= 0 && sid < S->n_spk, "speaker id out of range");
   Arena& A = S->arena;
-  for (int pass = 0; pass < 2; ++pass) {
-    A.dry = (pass == 0); A.reset(); if (pass == 0) A.peak = 0;
-    const float* fcm = feat;
-    if (!feat_channel_major) {
-      float* t = A.alloc<float>((size_t)S->feat_dim * T);
-      if (!A.dry) transpose(s, feat, t, T, S->feat_dim, S->feat_dim, T, 1, 0, 0);
-      fcm = t;
-    }
-    synth_forward_graph(S, s, A, fcm, pitch, pitchf, spec, sid, noise_q, noise_src, T, ids, out, taps);
-    if (pass == 0) A.ensure(A.peak);
-  }
-  A.dry = false;
+  arena_passes(A, [&] { synth_forward_graph(S, s, A, feat_cm_of(S, s, A, feat, feat_channel_major, T), pitch, pitchf, spec, sid, noise_q, noise_src, T, ids, out, taps); });
 }
 
 size_t synth_workspace(const Synth* M) { return M->arena.cap; }

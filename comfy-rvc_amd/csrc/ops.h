@@ -33,8 +33,6 @@ void layernorm_c_split(hipStream_t s, const float* x, const float* gamma, const 
 void layernorm_c(hipStream_t s, const float* x, const float* r, const float* gamma, const float* beta, float* y, int C, int T,
                  long long ld, float eps);
 void groupnorm_t_gelu(hipStream_t s, float* x, const float* gamma, const float* beta, int C, int T, long long ld, float eps);
-void softmax_cols(hipStream_t s, float* S, int Tk, int Tq, long long ld, long long batchS, int batch, const float* rel,
-                  long long batchRel, int win, float* pb, long long batchPb);
 void fill(hipStream_t s, float* p, float v, long long n);
 void wn_gate(hipStream_t s, const float* a, const float* g, float* out, int H, int T);
 void gemv(hipStream_t s, const float* W, const float* x, const float* b, float* y, int N, int K, const float* add);

@@ -364,78 +364,6 @@ void hubert_conv0_gn_gelu(hipStream_t s, const float* audio, long long L, const 
 }
 size_t hubert_conv0_scratch_doubles(int C, int T1) { return (size_t)((T1 + kC0ST - 1) / kC0ST) * C * 2; }
 
-// ---------------------------------------------------------------------------------------------- column softmax of S^T [Tk][Tq]
-// Softmax over the key axis (rows) for every query column; optional relative-position bias
-// rel[(k - q + win)][q] for |k - q| <= win (enc_p, reference attentions.py:230-239) and optional gather of the banded
-// probabilities pb[r][q] = P[q][q + r - win] (reference attentions.py:260-267).  Block = 64 columns x 16 row slices: every
-// wave touches 256 contiguous bytes of a row.  Two sweeps: online (max, sum) then normalise-and-store: 2 reads + 1 write of the
-// score matrix (the second read comes from the 256 MB memory-side cache).
-__global__ __launch_bounds__(1024) void softmax_cols_kernel(float* __restrict__ S, int Tk, int Tq, long long ld, long long batchS,
-                                                            const float* __restrict__ rel, long long batchRel, int win,
-                                                            float* __restrict__ pb, long long batchPb) {
-  __shared__ float s_m[16][64], s_s[16][64];
-  const int col = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const int q = blockIdx.x * 64 + col;
-  const bool ok = q < Tq;
-  float* Sb = S + (long long)blockIdx.y * batchS;
-  const float* relb = rel ? rel + (long long)blockIdx.y * batchRel : nullptr;
-  float mx = -3.0e38f, sum = 0.f;
-  if (ok) {
-    int k = sl;
-    for (; k + 48 < Tk; k += 64) {           // four rows in flight per thread
-      float v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = Sb[(long long)(k + 16 * j) * ld + q];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (relb) { const int d = k + 16 * j - q + win; if (d >= 0 && d <= 2 * win) v[j] += relb[(long long)d * Tq + q]; }
-        const float nm = fmaxf(mx, v[j]);
-        sum = sum * expf(mx - nm) + expf(v[j] - nm);
-        mx = nm;
-      }
-    }
-    for (; k < Tk; k += 16) {
-      float v = Sb[(long long)k * ld + q];
-      if (relb) { const int d = k - q + win; if (d >= 0 && d <= 2 * win) v += relb[(long long)d * Tq + q]; }
-      const float nm = fmaxf(mx, v);
-      sum = sum * expf(mx - nm) + expf(v - nm);
-      mx = nm;
-    }
-  }
-  s_m[sl][col] = mx; s_s[sl][col] = sum;
-  __syncthreads();
-  float gm = -3.0e38f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) gm = fmaxf(gm, s_m[i][col]);
-  float gs = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) gs += s_s[i][col] * expf(s_m[i][col] - gm);
-  const float inv = 1.f / gs;
-  if (!ok) return;
-  auto emit = [&](int k, float v) {
-    const int d = k - q + win;
-    const bool band = d >= 0 && d <= 2 * win;
-    if (relb && band) v += relb[(long long)d * Tq + q];
-    const float pv = expf(v - gm) * inv;
-    Sb[(long long)k * ld + q] = pv;
-    if (pb && band) pb[(long long)blockIdx.y * batchPb + (long long)d * Tq + q] = pv;
-  };
-  int k = sl;
-  for (; k + 48 < Tk; k += 64) {
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = Sb[(long long)(k + 16 * j) * ld + q];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) emit(k + 16 * j, v[j]);
-  }
-  for (; k < Tk; k += 16) emit(k, Sb[(long long)k * ld + q]);
-}
-void softmax_cols(hipStream_t s, float* S, int Tk, int Tq, long long ld, long long batchS, int batch, const float* rel,
-                  long long batchRel, int win, float* pb, long long batchPb) {
-  hipLaunchKernelGGL(softmax_cols_kernel, dim3((Tq + 63) / 64, batch), dim3(1024), 0, s, S, Tk, Tq, ld, batchS, rel, batchRel,
-                     win, pb, batchPb);
-}
-
 // ---------------------------------------------------------------------------------------------- small elementwise ops
 __global__ void fill_kernel(float* p, float v, long long n) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

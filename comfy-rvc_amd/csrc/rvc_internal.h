@@ -332,4 +332,32 @@ struct Arena {
   Arena(const Arena&) = delete; Arena& operator=(const Arena&) = delete;
 };
 
+// The two passes of a model graph over its arena: a dry pass that only measures (alloc hands out addresses nobody dereferences, the graph launches nothing),
+// ensure(peak), then the real pass.  `dry` is false again on every exit, a throw from either pass included.
+template <typename F> void arena_passes(Arena& A, F&& graph) {
+  struct Restore { Arena& a; ~Restore() { a.dry = false; } } restore{A};
+  A.dry = true; A.reset(); A.peak = 0;
+  graph();
+  A.ensure(A.peak);
+  A.dry = false; A.reset();
+  graph();
+}
+
+// A block of an arena that a graph needs zero wherever no kernel writes: the margins of split-resident images are the zero padding of the convolutions that
+// read them through row offsets.  The block is a graph's first allocation (nothing else ever occupies it) and is cleared only when it is not the block
+// remembered as cleared: another place, another arena generation, another size, or another layout inside it - up to two integer keys, the lengths the images
+// were laid out for (a shorter sequence in the same bytes leaves the longer one's rows behind its end).
+struct ZeroedBlock {
+  const void* base = nullptr; unsigned gen = 0; size_t bytes = 0; int key0 = -1, key1 = -1;
+  bool stale(const void* b, unsigned g, size_t n, int k0, int k1) const { return base != b || gen != g || bytes != n || key0 != k0 || key1 != k1; }
+  void remember(const void* b, unsigned g, size_t n, int k0, int k1) { base = b; gen = g; bytes = n; key0 = k0; key1 = k1; }
+  void reset() { base = nullptr; }
+  // real pass only: [start, start + n) of the arena is zero-filled on stream s when stale() says so
+  void ensure_zero(const Arena& A, size_t start, size_t n, int k0, int k1, hipStream_t s) {
+    if (A.dry || !stale(A.base + start, A.gen, n, k0, k1)) return;
+    RVC_HIP_CHECK(hipMemsetAsync(A.base + start, 0, n, s));
+    remember(A.base + start, A.gen, n, k0, k1);
+  }
+};
+
 }  // namespace rvc

@@ -1,5 +1,7 @@
 """GPU parity of the three HIP network graphs: against the golden vectors captured from the real reference and against
 the CPU oracle on fresh seeded inputs.  Gate: 1e-3 relative (BASELINE.json north_star), fp32."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -31,12 +33,24 @@ def make_synth(config, version):
     return net
 
 
+@contextlib.contextmanager
+def plain_fp32_build():
+    """Models built inside take the plain fp32 graph (rvc_set_conv_precision(0)): no bf16x3 weight images, so every split-resident
+    branch of the graph functions is off.  The default mode is back before the model runs."""
+    from comfy_rvc_amd import _lib as L
+    L.check(L.lib.rvc_set_conv_precision(0))
+    try:
+        yield
+    finally:
+        L.check(L.lib.rvc_set_conv_precision(1))
+
+
 def cm(x):
     """channel-major device tap [C][T] -> numpy [1,C,T]"""
     return x.cpu().numpy()[None]
 
 
-def test_hubert_matches_reference_golden(hubert):
+def check_hubert_golden(hubert):
     g = golden("hubert_1s.npz")
     audio = torch.from_numpy(g["audio"])
     Th = hubert.num_frames(audio.shape[1])
@@ -53,6 +67,17 @@ def test_hubert_matches_reference_golden(hubert):
     assert rel_err(v1.cpu(), g["out_v1"]) < TOL
     vcm = hubert.extract_features(audio, version="v2", channel_major=True)
     assert torch.equal(vcm.t()[None], v2)
+
+
+def test_hubert_matches_reference_golden(hubert):
+    check_hubert_golden(hubert)
+
+
+def test_hubert_plain_fp32_graph_matches_reference_golden():
+    from comfy_rvc_amd.lib.infer_pack.loaders import HubertModelWithFinalProj
+    with plain_fp32_build():
+        hub = HubertModelWithFinalProj(S.hubert_state_dict(0), S.HUBERT_CONFIG)
+    check_hubert_golden(hub)
 
 
 def test_heavy_family_hubert_and_synth_match_reference_golden(pair_arith):
@@ -94,7 +119,7 @@ def test_hubert_matches_oracle_other_length(hubert):
     assert rel_err(out.cpu(), ref) < TOL
 
 
-def test_rmvpe_matches_reference_golden(rmvpe):
+def check_rmvpe_golden(rmvpe):
     g = golden("rmvpe_1s.npz")
     r = rmvpe.infer(g["audio"], want_mel=True, want_salience=True)
     assert np.max(np.abs(r["mel"].cpu().numpy()[None] - g["mel"])) < 2e-3          # log-mel: absolute (values span [-11.5, 3])
@@ -106,6 +131,17 @@ def test_rmvpe_matches_reference_golden(rmvpe):
     dec = rmvpe.decode(g["syn_salience"])
     assert np.array_equal(dec == 0, g["syn_f0"] == 0)                     # voiced / unvoiced decisions are exact
     assert np.allclose(dec, g["syn_f0"], rtol=1e-6, atol=0), np.max(np.abs(dec / np.maximum(g["syn_f0"], 1e-30) - 1))
+
+
+def test_rmvpe_matches_reference_golden(rmvpe):
+    check_rmvpe_golden(rmvpe)
+
+
+def test_rmvpe_plain_fp32_graph_matches_reference_golden():
+    from comfy_rvc_amd.lib.rmvpe import RMVPE
+    with plain_fp32_build():
+        net = RMVPE(S.rmvpe_state_dict(0), is_half=False)
+    check_rmvpe_golden(net)
 
 
 def test_rmvpe_matches_oracle_other_length(rmvpe):
@@ -127,8 +163,17 @@ def test_rmvpe_matches_oracle_other_length(rmvpe):
                                                  ("synth_40k_v1.npz", S.CONFIG_40K_V1, "v1"), ("synth_32k_v1.npz", S.CONFIG_32K_V1, "v1"),
                                                  ("synth_48k_v1.npz", S.CONFIG_48K_V1, "v1"), ("synth_32k_v2.npz", S.CONFIG_32K_V2, "v2")])
 def test_synth_matches_reference_golden(name, config, version):
-    g = golden(name)
-    net = make_synth(config, version)
+    check_synth_golden(make_synth(config, version), golden(name))
+
+
+@pytest.mark.parametrize("name,config,version", [("synth_40k_v2.npz", S.CONFIG_40K_V2, "v2"), ("synth_32k_v1.npz", S.CONFIG_32K_V1, "v1")])
+def test_synth_plain_fp32_graph_matches_reference_golden(name, config, version):
+    with plain_fp32_build():
+        net = make_synth(config, version)
+    check_synth_golden(net, golden(name))
+
+
+def check_synth_golden(net, g):
     T = g["phone"].shape[1]
     taps = {k: None for k in ("enc_p_layer0", "m_p", "logs_p", "z_p", "z", "har_source", "sine_waves")}
     o, mask, (z, z_p, m_p, logs_p) = net.infer(torch.from_numpy(g["phone"]), torch.LongTensor([T]), torch.from_numpy(g["pitch"]),
@@ -152,12 +197,7 @@ def test_synth_nono_matches_reference_golden(name, config, version):
     net = cls(*config)                                                # reference call: the cpt["config"] list splatted, sr last
     net.load_state_dict(S.synth_state_dict(config, version, 0, f0=False))
     T = g["phone"].shape[1]
-    taps = {k: None for k in ("m_p", "logs_p", "z_p", "z")}
-    o, mask, _ = net.infer(torch.from_numpy(g["phone"]), torch.LongTensor([T]), torch.LongTensor([int(g["sid"])]), noise=g["noise_z"], taps=taps)
-    assert tuple(o.shape) == g["wav"].shape and tuple(mask.shape) == (1, 1, T)
-    for k in ("m_p", "logs_p", "z_p", "z"):
-        assert rel_err(cm(taps[k]), g[k]) < TOL, k
-    assert rel_err(o.cpu(), g["wav"]) < TOL
+    check_synth_nono_golden(net, g)
     # the two families do not accept each other's checkpoints or arguments
     with pytest.raises(ValueError, match="without f0"):
         cls(*config).load_state_dict(S.synth_state_dict(config, version, 0))
@@ -170,6 +210,38 @@ def test_synth_nono_matches_reference_golden(name, config, version):
     with pytest.raises(RuntimeError, match="no-f0 model"):            # ... and a no-f0 model with them
         pc = torch.ones(T, dtype=torch.int64, device="cuda"); pf = torch.ones(T, device="cuda"); ns = torch.zeros(T * net.upp, device="cuda")
         _lib.check(_lib.lib.rvc_synth_infer(net._h, None, _lib.ptr(ph), 0, _lib.ptr(pc), _lib.ptr(pf), 0, _lib.ptr(nz), _lib.ptr(ns), T, _lib.ptr(out), None))
+
+
+def check_synth_nono_golden(net, g):
+    T = g["phone"].shape[1]
+    taps = {k: None for k in ("m_p", "logs_p", "z_p", "z")}
+    o, mask, _ = net.infer(torch.from_numpy(g["phone"]), torch.LongTensor([T]), torch.LongTensor([int(g["sid"])]), noise=g["noise_z"], taps=taps)
+    assert tuple(o.shape) == g["wav"].shape and tuple(mask.shape) == (1, 1, T)
+    for k in ("m_p", "logs_p", "z_p", "z"):
+        assert rel_err(cm(taps[k]), g[k]) < TOL, k
+    assert rel_err(o.cpu(), g["wav"]) < TOL
+
+
+def test_synth_nono_plain_fp32_graph_matches_reference_golden():
+    from comfy_rvc_amd.lib.infer_pack.models import SynthesizerTrnMs768NSFsid_nono
+    with plain_fp32_build():
+        net = SynthesizerTrnMs768NSFsid_nono(*S.CONFIG_40K_V2)
+        net.load_state_dict(S.synth_state_dict(S.CONFIG_40K_V2, "v2", 0, f0=False))
+    check_synth_nono_golden(net, golden("synth_40k_v2_nono.npz"))
+
+
+def test_synth_create_refuses_a_head_dimension_other_than_96():
+    """hidden_channels / n_heads is 96 in every configuration the reference ships and the text encoder's attention exists for that head dimension only:
+    rvc_synth_create (called by the wrapper's constructor, which raises on a non-zero return) refuses hidden_channels 128, n_heads 2.  Nothing is launched."""
+    from comfy_rvc_amd import _lib as L
+    from comfy_rvc_amd.lib.infer_pack import models as M
+    config = list(S.CONFIG_40K_V2)
+    assert config[3] == 192 and config[5] == 2
+    config[3] = 128
+    with pytest.raises(L.RvcHipError, match="96"):
+        M.SynthesizerTrnMs768NSFsid(*config, is_half=False)
+    msg = L.lib.rvc_last_error()
+    assert b"96" in msg and b"64" in msg, msg
 
 
 def test_synth_matches_oracle_longer_sequence():

@@ -85,6 +85,32 @@ def test_forward_matches_reference_golden(tag, nets):
     check_against(tag, f"golden_{tag}", res, g, [int(x) for x in g["lengths"]], g["ids_slice"])
 
 
+def test_plain_fp32_graph_forward_and_losses_match_reference_golden():
+    """The training forward built at rvc_set_conv_precision(0) (the plain fp32 graph: no split-resident branch of synth_forward is taken): taps and wave against
+    train_forward_40k_v2 at the gate above, both losses against the reference's values within the tolerances stored in the golden."""
+    from comfy_rvc_amd import _lib as L
+    from comfy_rvc_amd.lib.train.evaluate import reconstruction_losses
+    L.check(L.lib.rvc_set_conv_precision(0))
+    try:
+        net = make_net("40k_v2")
+    finally:
+        L.check(L.lib.rvc_set_conv_precision(1))
+    config, sd, b, noise_q, noise_src, g = case_inputs("40k_v2")
+    res = call(net, True, b, noise=(noise_q, noise_src), ids=torch.from_numpy(g["ids_slice"]))
+    assert tuple(res[0].shape) == tuple(g["o"].shape)
+    check_against("40k_v2", "plain_fp32_40k_v2", res, g, [int(x) for x in g["lengths"]], g["ids_slice"])
+    e = golden("train_eval_cases.npz")
+    t = {k: torch.from_numpy(np.asarray(v)) for k, v in b.items()}
+    batch = (t["phone"], t["lengths"], t["pitch"], t["pitchf"], t["spec"], t["lengths"], None, None, t["sid"])
+    r = reconstruction_losses(net, batch, hps(), None, noise=(noise_q, noise_src), ids_slice=torch.from_numpy(g["ids_slice"]))
+    for k in ("loss_mel", "loss_kl"):
+        d, tol = abs(float(r[k]) - float(e[f"batch_{k}"])), float(e[f"{k}_tol"])
+        print("plain fp32", k, float(r[k]), "reference", float(e[f"batch_{k}"]), "delta", d, "tolerance", tol)
+        record(f"plain_fp32_batch.{k}", d, tol)
+    for k in ("loss_mel", "loss_kl"):
+        assert abs(float(r[k]) - float(e[f"batch_{k}"])) <= float(e[f"{k}_tol"]), k
+
+
 def test_forward_fresh_seeds_against_restatement(nets):
     """Lengths 47 / 32 and starts 13 / 0: shapes the golden does not hold."""
     config, version, f0 = CASES["40k_v2"]
