@@ -197,6 +197,19 @@ SIGNATURES = {
     "rvc_prof_collect_ex": (c_int, [P(C.c_double), C.c_double, C.c_double]),
     "rvc_prof_cfg_name": (c_char_p, [c_int]),
     "rvc_op_sine_source": (c_int, [c_void_p] * 5 + [c_int, c_int, c_float, c_float, c_float] + [c_void_p] * 3),
+    "rvc_op_hubert_conv0": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64]),
+    "rvc_op_conv_to1": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, P(c_int)]),
+    "rvc_op_noise_add": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, P(c_int)]),
+    "rvc_op_transpose": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_int64, c_int64]),
+    "rvc_op_frames": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6),
+    "rvc_op_mel_to_unet": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float]),
+    "rvc_op_feats_prepare": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_int]),
+    "rvc_op_wn_gate": (c_int, [c_void_p] * 5 + [c_int, c_int]),
+    "rvc_op_pool2_pad": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64]),
+    "rvc_op_interleave2_pad": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int64]),
+    "rvc_op_pad2d": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int64]),
+    "rvc_op_unpad2d": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64]),
+    "rvc_op_gru_scan": (c_int, [c_void_p] * 6 + [c_int, P(c_int)]),
 }
 
 # instrumentation hooks of -DRVC_EXPERIMENTS builds (include/rvc_hip.h, last section): bound when the loaded library has them (RVC_HIP_LIB=<variant build>),

@@ -489,15 +489,22 @@ __global__ __launch_bounds__(256) void conv_to1_kernel(const float* __restrict__
                                                        int pad, int T, float pre_slope, int act_tanh, float* __restrict__ y) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= T) return;
+  // the sum runs in groups of four channels (one FMA chain of 4 K terms each, the group sums added up): a single chain over all Ci K terms rounds
+  // every one of them at the magnitude of the whole running sum (tests: measured 4.7 - 6.4 x 2^-24 of sum |terms| at Ci = 32)
   float acc = 0.f;
-  for (int c = 0; c < Ci; ++c) {
-    const float* xr = x + (long long)c * ldx;
-    for (int j = 0; j < K; ++j) {
-      const int q = t + j - pad;
-      float v = (q >= 0 && q < T) ? xr[q] : 0.f;
-      v = fmaxf(v, v * pre_slope);
-      acc = fmaf(w[c * K + j], v, acc);
+  for (int c0 = 0; c0 < Ci; c0 += 4) {
+    float p = 0.f;
+    const int ce = min(c0 + 4, Ci);
+    for (int c = c0; c < ce; ++c) {
+      const float* xr = x + (long long)c * ldx;
+      for (int j = 0; j < K; ++j) {
+        const int q = t + j - pad;
+        float v = (q >= 0 && q < T) ? xr[q] : 0.f;
+        v = fmaxf(v, v * pre_slope);
+        p = fmaf(w[c * K + j], v, p);
+      }
     }
+    acc += p;
   }
   y[t] = act_tanh ? tanhf(acc) : acc;
 }
@@ -510,35 +517,41 @@ __global__ __launch_bounds__(256) void conv_to1x4_kernel(const float* __restrict
   if (t0 >= T) return;
   const bool inner = t0 >= 4 && t0 + 8 <= T;
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  for (int c = 0; c < Ci; ++c) {
-    const float* xr = x + (long long)c * ldx;
-    float v[12];
-    if (inner) {
-      const f4 l = *reinterpret_cast<const f4*>(xr + t0 - 4), m = *reinterpret_cast<const f4*>(xr + t0), r = *reinterpret_cast<const f4*>(xr + t0 + 4);
+  for (int c0 = 0; c0 < Ci; c0 += 4) {                          // groups of four channels, summed like conv_to1_kernel's: the two kernels agree bit for bit
+    float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+    const int ce = min(c0 + 4, Ci);
+    for (int c = c0; c < ce; ++c) {
+      const float* xr = x + (long long)c * ldx;
+      float v[12];
+      if (inner) {
+        const f4 l = *reinterpret_cast<const f4*>(xr + t0 - 4), m = *reinterpret_cast<const f4*>(xr + t0), r = *reinterpret_cast<const f4*>(xr + t0 + 4);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) { v[i] = l[i]; v[4 + i] = m[i]; v[8 + i] = r[i]; }
-    } else {
+        for (int i = 0; i < 4; ++i) { v[i] = l[i]; v[4 + i] = m[i]; v[8 + i] = r[i]; }
+      } else {
 #pragma unroll
-      for (int i = 0; i < 12; ++i) { const int q = t0 - 4 + i; v[i] = (q >= 0 && q < T) ? xr[q] : 0.f; }
+        for (int i = 0; i < 12; ++i) { const int q = t0 - 4 + i; v[i] = (q >= 0 && q < T) ? xr[q] : 0.f; }
+      }
+#pragma unroll
+      for (int i = 0; i < 12; ++i) v[i] = fmaxf(v[i], v[i] * pre_slope);
+      const float* wc = w + c * 7;                              // (k = 7, pad = 3: compile-time indices keep v[] in registers)
+#pragma unroll
+      for (int j = 0; j < 7; ++j) {                             // output t0 + o reads v[4 + o + j - 3]
+        const float wj = wc[j];
+        p0 = fmaf(wj, v[1 + j], p0); p1 = fmaf(wj, v[2 + j], p1); p2 = fmaf(wj, v[3 + j], p2); p3 = fmaf(wj, v[4 + j], p3);
+      }
     }
-#pragma unroll
-    for (int i = 0; i < 12; ++i) v[i] = fmaxf(v[i], v[i] * pre_slope);
-    const float* wc = w + c * 7;                                // (k = 7, pad = 3: compile-time indices keep v[] in registers)
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {                               // output t0 + o reads v[4 + o + j - 3]
-      const float wj = wc[j];
-      a0 = fmaf(wj, v[1 + j], a0); a1 = fmaf(wj, v[2 + j], a1); a2 = fmaf(wj, v[3 + j], a2); a3 = fmaf(wj, v[4 + j], a3);
-    }
+    a0 += p0; a1 += p1; a2 += p2; a3 += p3;
   }
   const float o[4] = {a0, a1, a2, a3};
 #pragma unroll
   for (int i = 0; i < 4; ++i) if (t0 + i < T) y[t0 + i] = act_tanh ? tanhf(o[i]) : o[i];
 }
-void conv_to1(hipStream_t s, const float* x, long long ldx, const float* w, int Ci, int K, int pad, int T, float pre_slope, int act_tanh,
-              float* y) {
+int conv_to1(hipStream_t s, const float* x, long long ldx, const float* w, int Ci, int K, int pad, int T, float pre_slope, int act_tanh,
+             float* y) {
   const bool x4 = K == 7 && pad == 3 && (ldx & 3) == 0 && ((uintptr_t)x & 15) == 0;
   if (x4) hipLaunchKernelGGL(conv_to1x4_kernel, dim3((T + 1023) / 1024), dim3(256), 0, s, x, ldx, w, Ci, K, pad, T, pre_slope, act_tanh, y);
   else hipLaunchKernelGGL(conv_to1_kernel, dim3((T + 255) / 256), dim3(256), 0, s, x, ldx, w, Ci, K, pad, T, pre_slope, act_tanh, y);
+  return x4 ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------- rational resampling

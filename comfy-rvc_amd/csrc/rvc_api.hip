@@ -1043,6 +1043,181 @@ int rvc_op_sine_source(void* stream, const float* f0, const float* noise, float*
   RVC_CATCH
 }
 
+// ------------------------------------------------------------------------------------------------ single-op entry points of the model-glue kernels (ops.hip, split2d.hip)
+// The image of a padded 2-D level as RMVPE's U-Net holds it: margin of split_geom_2d(W), every byte 0xff first (NaN patterns wherever the producer does not
+// write), read back as fp32 [C][ld] over the P = H (W + 2) positions.
+struct Image2d { DevBytes b; long long tp = 0; int margin = 0; };
+static Image2d image2d_alloc(hipStream_t s, int C, int H, int W) {
+  Image2d im;
+  im.margin = split_geom_2d(W).margin;
+  im.tp = im.margin + (long long)H * (W + 2) + 704 + 64;
+  const size_t bytes = (size_t)(C / 16) * 4 * im.tp * 16;
+  im.b.alloc(bytes);
+  RVC_HIP_CHECK(hipMemsetAsync(im.b.p, 0xff, bytes, s));
+  return im;
+}
+static void image2d_to_f32(hipStream_t s, const Image2d& im, int C, long long P, float* y, long long ld) {
+  // (the reader's margin is fixed at 64 rows: hand it the plane origin shifted so that position 0 lands there)
+  split_image_to_f32(s, im.b.p + (size_t)(im.margin - kSplitMargin) * 16, im.tp, C, (int)P, y, ld);
+}
+
+int rvc_op_hubert_conv0(void* stream, const float* audio, int64_t L, const float* w, const float* gamma, const float* beta, int C, int T1, float* out, float* out_img_f32,
+                        int64_t ld) {
+  RVC_TRY
+  RVC_REQUIRE(audio && w && gamma && beta && (out || out_img_f32) && C > 0 && T1 > 0 && L > 0 && ld >= T1, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf<double> partial; DevBuf<float> stat; DevBytes img;
+  partial.alloc(hubert_conv0_scratch_doubles(C, T1)); stat.alloc((size_t)2 * C);
+  if (out) hubert_conv0_gn_gelu(s, audio, L, w, gamma, beta, C, T1, 1e-5f, out, ld, partial.p, stat.p);
+  if (out_img_f32) {
+    RVC_REQUIRE((C & 15) == 0, "the image needs C % 16 == 0");
+    const long long tp = split_s2_tp(T1); const int H = split_s2_h(T1);
+    img.alloc(split_s2_bytes(C, T1));
+    RVC_HIP_CHECK(hipMemsetAsync(img.p, 0xff, split_s2_bytes(C, T1), s));
+    hubert_conv0_gn_gelu_img(s, audio, L, w, gamma, beta, C, T1, 1e-5f, img.p, tp, kSplitMargin, H, partial.p, stat.p);
+    split_image_deint_to_f32(s, img.p, tp, H, C, T1, out_img_f32, ld);
+  }
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  RVC_CATCH
+}
+int rvc_op_conv_to1(void* stream, const float* x, int64_t ldx, const float* w, int Ci, int K, int pad, int T, float pre_slope, int act_tanh, float* y, int* kernel_out) {
+  RVC_TRY
+  RVC_REQUIRE(x && w && y && kernel_out && Ci > 0 && K > 0 && pad >= 0 && T > 0 && ldx >= T, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  *kernel_out = conv_to1(s, x, ldx, w, Ci, K, pad, T, pre_slope, act_tanh, y);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  RVC_CATCH
+}
+int rvc_op_noise_add(void* stream, float* x, int64_t ld, int C, int T, const float* src, int64_t L, int k, int stride, int pad, const float* w, const float* b, int* ran_out) {
+  RVC_TRY
+  RVC_REQUIRE(x && src && w && b && ran_out && C > 0 && T > 0 && L > 0 && k > 0 && stride > 0 && pad >= 0 && ld >= T, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  *ran_out = noise_add(s, x, ld, C, T, src, L, k, stride, pad, w, b) ? 1 : 0;
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  RVC_CATCH
+}
+int rvc_op_transpose(void* stream, const float* in, float* out, int R, int C, int64_t ldin, int64_t ldout, int batch, int64_t bin, int64_t bout) {
+  RVC_TRY
+  RVC_REQUIRE(in && out && R > 0 && C > 0 && batch > 0 && ldin >= C && ldout >= R, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  transpose(s, in, out, R, C, ldin, ldout, batch, bin, bout);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  RVC_CATCH
+}
+int rvc_op_frames(void* stream, const float* src, float* out, int L, int k, int stride, int pad, int Tout, int reflect) {
+  RVC_TRY
+  RVC_REQUIRE(src && out && L > 0 && k > 0 && stride > 0 && pad >= 0 && Tout > 0, "bad argument");
+  RVC_REQUIRE(!reflect || (pad < L && (long long)(Tout - 1) * stride + k - 1 - pad <= 2LL * (L - 1)), "a reflected index must land inside the signal");
+  hipStream_t s = (hipStream_t)stream;
+  frames(s, src, out, L, k, stride, pad, Tout, reflect);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  RVC_CATCH
+}
+int rvc_op_mel_to_unet(void* stream, const float* mel, float* x, int n, int Tr, float a, float b) {
+  RVC_TRY
+  RVC_REQUIRE(mel && x && n > 0 && Tr >= n && Tr <= 2 * n - 1, "bad argument (the right reflection must land inside the n frames)");
+  hipStream_t s = (hipStream_t)stream;
+  mel_to_unet(s, mel, x, n, Tr, a, b);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  RVC_CATCH
+}
+int rvc_op_feats_prepare(void* stream, const float* f, const float* f0, const float* pitchf, float* out, int D, int Th, int T, float protect, int do_protect) {
+  RVC_TRY
+  RVC_REQUIRE(f && out && (pitchf || !do_protect) && D > 0 && Th > 0 && T > 0 && T <= 2 * Th, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  feats_prepare(s, f, f0, pitchf, out, D, Th, T, protect, do_protect);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  RVC_CATCH
+}
+int rvc_op_wn_gate(void* stream, const float* a, const float* g, float* out, float* out_img_f32, int H, int T) {
+  RVC_TRY
+  RVC_REQUIRE(a && g && (out || out_img_f32) && H > 0 && T > 0, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  DevBytes img;
+  if (out) wn_gate(s, a, g, out, H, T);
+  if (out_img_f32) {
+    const long long tp = split_image_tp(T);
+    img.alloc(split_image_bytes(H, T));
+    RVC_HIP_CHECK(hipMemsetAsync(img.p, 0xff, split_image_bytes(H, T), s));
+    wn_gate_split(s, a, g, img.p, tp, kSplitMargin, H, T);
+    split_image_to_f32(s, img.p, tp, H, T, out_img_f32, T);
+  }
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  RVC_CATCH
+}
+int rvc_op_pool2_pad(void* stream, const float* x, int64_t ldx, int x_padded, int C, int H, int W, float* y, float* y_img_f32, int64_t ldy) {
+  RVC_TRY
+  RVC_REQUIRE(x && (y || y_img_f32) && C > 0 && H >= 2 && W >= 2, "bad argument");
+  const int Ho = H / 2, Wo = W / 2; const long long P = (long long)Ho * (Wo + 2);
+  RVC_REQUIRE(ldx >= (long long)H * (x_padded ? W + 2 : W) && ldy >= P, "bad pitch");
+  hipStream_t s = (hipStream_t)stream;
+  Image2d im;
+  if (y_img_f32) im = image2d_alloc(s, C, Ho, Wo);
+  pool2_pad_split(s, x, ldx, x_padded != 0, C, H, W, y, ldy, im.b.p, im.tp, im.margin);
+  if (y_img_f32) image2d_to_f32(s, im, C, P, y_img_f32, ldy);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  RVC_CATCH
+}
+int rvc_op_interleave2_pad(void* stream, const float* ph, int64_t ldp, int Co, int H, int W, float* y, int y_padded, float* y_img_f32, int64_t ldy) {
+  RVC_TRY
+  RVC_REQUIRE(ph && (y || y_img_f32) && Co > 0 && H > 0 && W > 0 && ldp >= (long long)H * (W + 2), "bad argument");
+  const long long P = (long long)(2 * H) * (2 * W + 2);      // the image (and its read-back) is always the padded level
+  RVC_REQUIRE(ldy >= ((y_padded || y_img_f32) ? P : (long long)(2 * H) * (2 * W)), "bad pitch");
+  hipStream_t s = (hipStream_t)stream;
+  Image2d im;
+  if (y_img_f32) im = image2d_alloc(s, Co, 2 * H, 2 * W);
+  interleave2_pad_split(s, ph, ldp, Co, H, W, y, ldy, y_padded != 0, im.b.p, im.tp, im.margin);
+  if (y_img_f32) image2d_to_f32(s, im, Co, P, y_img_f32, ldy);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  RVC_CATCH
+}
+int rvc_op_pad2d(void* stream, const float* x, int64_t ldx, int C, int H, int W, float* y, float* y_img_f32, int64_t ldy) {
+  RVC_TRY
+  const long long P = (long long)H * (W + 2);
+  RVC_REQUIRE(x && (y || y_img_f32) && C > 0 && H > 0 && W > 0 && ldx >= (long long)H * W && ldy >= P, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  Image2d im;
+  if (y_img_f32) im = image2d_alloc(s, C, H, W);
+  pad2d_split(s, x, ldx, C, H, W, y, ldy, im.b.p, im.tp, im.margin);
+  if (y_img_f32) image2d_to_f32(s, im, C, P, y_img_f32, ldy);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  RVC_CATCH
+}
+int rvc_op_unpad2d(void* stream, const float* x, int64_t ldx, int C, int H, int W, float* y, int64_t ldy) {
+  RVC_TRY
+  RVC_REQUIRE(x && y && C > 0 && H > 0 && W > 0 && ldx >= (long long)H * (W + 2) && ldy >= (long long)H * W, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  unpad2d(s, x, ldx, C, H, W, y, ldy);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  RVC_CATCH
+}
+int rvc_op_gru_scan(void* stream, const float* gi, const float* b_ih, const float* w_hh, const float* b_hh, float* out, int T, int* err_out) {
+  RVC_TRY
+  RVC_REQUIRE(gi && b_ih && w_hh && b_hh && out && err_out && T > 0, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf<unsigned long long> xbuf; DevBuf<int> err;
+  xbuf.alloc((size_t)2 * 2 * 256); err.alloc(2);
+  gru_scan(s, gi, b_ih, w_hh, nullptr, b_hh, out, xbuf.p, err.p, T);      // no repair kernel; the product's default spin limit
+  check_launch();
+  int e[2] = {0, 0};
+  RVC_HIP_CHECK(hipMemcpyAsync(e, err.p, sizeof(e), hipMemcpyDeviceToHost, s));
+  RVC_HIP_CHECK(hipStreamSynchronize(s));
+  *err_out = e[0];
+  RVC_CATCH
+}
+
 int rvc_prof_enable(int on) { RVC_TRY conv_prof_enable(on != 0); RVC_CATCH }
 int rvc_set_conv_precision(int mode) {
   RVC_TRY

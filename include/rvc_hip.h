@@ -522,6 +522,48 @@ int rvc_op_layernorm_c(void* stream, const float* x_dev, const float* res_dev, c
 int rvc_op_sine_source(void* stream, const float* f0_dev, const float* noise_dev, float* har_dev, float* sine_dev, int T, int upp, float sr,
                        float lin_w, float lin_b, float* rad_dev, float* tmp_dev, float* phase_dev);
 
+/* ------------------------------------------------------------------ single-op entry points of the model-glue kernels (csrc/ops.hip, csrc/split2d.hip)
+ * What runs between the GEMMs, one op per call for tests/test_hip_glue_ops.py: device pointers in, scratch and images allocated inside, images handed back
+ * decoded to fp32 (every image byte is 0xff before the op runs, so a row the op does not write decodes as NaN), stream synchronised on return. */
+/* HuBERT feature-encoder layer 0, Conv1d(1, C, 10, stride 5, no bias) -> GroupNorm(C, C) -> GELU (eps 1e-5) from L samples of raw audio (zero beyond L):
+ * out_dev fp32 [C][ld] (T1 columns written) and / or the de-interleaved image of the stride-2 consumer read back into out_img_f32_dev [C][ld] (C % 16 == 0). */
+int rvc_op_hubert_conv0(void* stream, const float* audio_dev, int64_t L, const float* w_dev, const float* gamma_dev, const float* beta_dev, int C, int T1,
+                        float* out_dev, float* out_img_f32_dev, int64_t ld);
+/* y[t] = act(sum_c sum_j w[c][j] pre(x[c][t + j - pad])), pre = leaky ReLU of slope pre_slope, act = tanh or none; x_dev, ldx, K, pad reach the launcher
+ * unchanged, *kernel_out = 1 when the four-outputs-per-thread kernel ran (K = 7, pad = 3, x_dev 16-byte aligned, ldx % 4 == 0), 0 for the one-output kernel. */
+int rvc_op_conv_to1(void* stream, const float* x_dev, int64_t ldx, const float* w_dev, int Ci, int K, int pad, int T, float pre_slope, int act_tanh, float* y_dev,
+                    int* kernel_out);
+/* x[c][t] += b[c] + sum_j w[c][j] src[t stride + j - pad] (src zero outside [0, L)) in place; *ran_out = 0 and x untouched when the kernel declines the
+ * shape (k not 1 / 4 / 8, T or ld not a multiple of 4, x_dev not 16-byte aligned). */
+int rvc_op_noise_add(void* stream, float* x_dev, int64_t ld, int C, int T, const float* src_dev, int64_t L, int k, int stride, int pad, const float* w_dev,
+                     const float* b_dev, int* ran_out);
+/* out[b][c][r] = in[b][r][c]: row pitches ldin / ldout, batch strides bin / bout (elements) */
+int rvc_op_transpose(void* stream, const float* in_dev, float* out_dev, int R, int C, int64_t ldin, int64_t ldout, int batch, int64_t bin, int64_t bout);
+/* out[j][t] = src[t stride + j - pad], j < k, t < Tout; outside [0, L): zero, or reflected (reflect != 0) */
+int rvc_op_frames(void* stream, const float* src_dev, float* out_dev, int L, int k, int stride, int pad, int Tout, int reflect);
+/* RMVPE's U-Net input: x[t][m] = a mel[m][t'] + b for t < Tr, m < 128, t' = t reflected at the right end of the n frames; mel [128][n], x [Tr][128] */
+int rvc_op_mel_to_unet(void* stream, const float* mel_dev, float* x_dev, int n, int Tr, float a, float b);
+/* nearest x2 upsampling of f [D][Th] to T frames and the protect blend out = w f + (1 - w) f0 with w = 1 where pitchf >= 1, protect elsewhere
+ * (do_protect; f0_dev NULL: f0 = f) */
+int rvc_op_feats_prepare(void* stream, const float* f_dev, const float* f0_dev, const float* pitchf_dev, float* out_dev, int D, int Th, int T, float protect,
+                         int do_protect);
+/* WN gate out[c][t] = tanh(a[c][t] + g[c]) sigmoid(a[H + c][t] + g[H + c]); a [2 H][T], g [2 H]; out_dev fp32 [H][T] and / or the image form (H % 16 == 0)
+ * read back into out_img_f32_dev [H][T] */
+int rvc_op_wn_gate(void* stream, const float* a_dev, const float* g_dev, float* out_dev, float* out_img_f32_dev, int H, int T);
+/* The level changes of RMVPE's U-Net on padded planes (row pitch W + 2, a zero column on either side; channel pitches ldx / ldy in elements).  y_dev (fp32) and
+ * y_img_f32_dev (the image, read back with the same pitch ldy over the padded positions) are each optional; C % 8 == 0, % 16 for the image.
+ *   pool2_pad:       AvgPool2d(2) of x [C][H][W] (x_padded: [C][H][W + 2]) -> padded level (H / 2) x (W / 2)
+ *   interleave2_pad: out[c][2 h + a][2 w + b] = ph[(2 a + b) Co + c][h][w], ph padded at H x W -> level 2 H x 2 W, y padded or plain (y_padded), image padded
+ *   pad2d / unpad2d: plain [C][H][W] <-> padded [C][H][W + 2] */
+int rvc_op_pool2_pad(void* stream, const float* x_dev, int64_t ldx, int x_padded, int C, int H, int W, float* y_dev, float* y_img_f32_dev, int64_t ldy);
+int rvc_op_interleave2_pad(void* stream, const float* ph_dev, int64_t ldp, int Co, int H, int W, float* y_dev, int y_padded, float* y_img_f32_dev, int64_t ldy);
+int rvc_op_pad2d(void* stream, const float* x_dev, int64_t ldx, int C, int H, int W, float* y_dev, float* y_img_f32_dev, int64_t ldy);
+int rvc_op_unpad2d(void* stream, const float* x_dev, int64_t ldx, int C, int H, int W, float* y_dev, int64_t ldy);
+/* RMVPE's bidirectional GRU recurrence (hidden 256; nn.GRU gate order r, z, n) by the 16-workgroup scan alone, without the repair kernel and with the
+ * product's default spin limit: gi [T][1536] = W_ih x (no bias), b_ih / b_hh [2][768], w_hh [2][768][256], out channel-major [512][T].
+ * *err_out = the scan's time-out flag (0: every hand-off arrived). */
+int rvc_op_gru_scan(void* stream, const float* gi_dev, const float* b_ih_dev, const float* w_hh_dev, const float* b_hh_dev, float* out_dev, int T, int* err_out);
+
 /* Rational resampling by up/down (lowest terms): y_dev[n] = sum_m x_dev[m] * taps_dev[m*up - n*down + half], n < n_out, float64
  * accumulation, zero extension outside the input.  taps_dev: 2*half+1 float64 coefficients of a linear-phase low-pass on the
  * up-times up-sampled grid, DC gain `up`.  Replaces librosa.resample (soxr_hq) at lib/audio.py:150 (input -> 16 kHz) and
