@@ -116,6 +116,17 @@ SIGNATURES = {
                                   c_void_p, P(SynthForwardTaps)]),
     "rvc_kl_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "rvc_l1_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rvc_disc_create": (c_int, [c_void_p, c_int, P(c_void_p)]),
+    "rvc_disc_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, P(c_int64), c_int]),
+    "rvc_disc_finalize": (c_int, [c_void_p]),
+    "rvc_disc_release": (c_int, [c_void_p]),
+    "rvc_disc_count": (c_int, [c_void_p]),
+    "rvc_disc_num_taps": (c_int, [c_void_p, c_int]),
+    "rvc_disc_tap_shape": (c_int, [c_void_p, c_int, c_int, c_int64, P(c_int), P(c_int), P(c_int)]),
+    "rvc_disc_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, P(c_void_p), P(c_void_p)]),
+    "rvc_disc_launch_count": (c_int, [c_void_p, c_int, c_int64]),
+    "rvc_sqerr_sums": (c_int, [c_void_p, P(c_void_p), P(c_int64), P(c_float), c_int, c_void_p]),
+    "rvc_l1_sums": (c_int, [c_void_p, P(c_void_p), P(c_void_p), P(c_int64), c_int, c_void_p]),
     "rvc_synth_dec_halo": (c_int, [c_void_p]),
     "rvc_synth_window_frames": (c_int, [c_void_p, c_int64, c_int64, c_int64, P(c_int64), P(c_int64)]),
     "rvc_synth_infer_window_halo": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,

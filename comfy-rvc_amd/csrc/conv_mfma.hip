@@ -488,21 +488,25 @@ static void pack_x3_grouped(ConvLayer& L, const float* w /*[groups * Cog][Cig][k
   RVC_HIP_CHECK(hipMalloc(&L.Wx_, P.size() * sizeof(uint16_t)));
   RVC_HIP_CHECK(hipMemcpy(L.Wx_, P.data(), P.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
 }
-static void pack_x3(ConvLayer& L, const float* w, int Co, int Ci, int k) {
-  L.CoPx = (Co + 127) & ~127;
-  const int nch = Ci / 16;
-  L.wxBatch = (long long)nch * k * 2 * L.CoPx * 16;
-  std::vector<uint16_t> P((size_t)L.wxBatch, 0);
+void x3_weight_image(const float* w, int Co, int Ci, int k, int CoPx, std::vector<uint16_t>& P) {
+  P.assign((size_t)(Ci / 16) * k * 2 * CoPx * 16, 0);
   for (int co = 0; co < Co; ++co)
     for (int ci = 0; ci < Ci; ++ci)
       for (int u = 0; u < k; ++u) {
         const float v = w[((size_t)co * Ci + ci) * k + u];
         const uint16_t hi = bf16_rne(v), lo = bf16_rne(v - bf16_to_f32(hi));
         const int chunk = ci >> 4, c16 = ci & 15;
-        const size_t base = (((size_t)chunk * k + u) * 2 * 2 + (size_t)(c16 >> 3)) * L.CoPx + co;   // (chunk, tap, hi, half) plane, row co
+        const size_t base = (((size_t)chunk * k + u) * 2 * 2 + (size_t)(c16 >> 3)) * CoPx + co;   // (chunk, tap, hi, half) plane, row co
         P[base * 8 + (c16 & 7)] = hi;
-        P[(base + 2 * (size_t)L.CoPx) * 8 + (c16 & 7)] = lo;
+        P[(base + 2 * (size_t)CoPx) * 8 + (c16 & 7)] = lo;
       }
+}
+static void pack_x3(ConvLayer& L, const float* w, int Co, int Ci, int k) {
+  L.CoPx = (Co + 127) & ~127;
+  const int nch = Ci / 16;
+  L.wxBatch = (long long)nch * k * 2 * L.CoPx * 16;
+  std::vector<uint16_t> P;
+  x3_weight_image(w, Co, Ci, k, L.CoPx, P);
   RVC_HIP_CHECK(hipMalloc(&L.Wx_, P.size() * sizeof(uint16_t)));
   RVC_HIP_CHECK(hipMemcpy(L.Wx_, P.data(), P.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
 }

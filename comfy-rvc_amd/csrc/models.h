@@ -38,6 +38,23 @@ void kl_loss_sum(hipStream_t s, const float* z_p, const float* logs_q, const flo
 void l1_sum(hipStream_t s, const float* a, const float* b, long long n, double* out1);
 int synth_dec_halo_frames(const Synth* S);   // pure host: frames of z the generator's output depends on to either side
 
+// the trainer's discriminators, forward only (discriminator.hip): version 1 = MultiPeriodDiscriminator, 2 = MultiPeriodDiscriminatorV2.  signals [S][T] (the
+// real items, then the generated ones); fmaps: one device pointer per tap, discriminator-major, tap (i, l) = [S][C][H][p] of disc_tap_shape; scores (or its
+// entries) may be null: score i is the last tap of discriminator i, copied when a distinct buffer is given
+struct Disc;
+Disc* disc_create(Ctx* ctx, int version);
+void disc_destroy(Disc* D);
+void disc_set_tensor(Disc* D, const char* name, const float* d, const long long* shape, int ndim);
+void disc_finalize(Disc* D);
+int disc_count(const Disc* D);
+int disc_num_taps(const Disc* D, int i);
+void disc_tap_shape(const Disc* D, int i, int tap, long long T, int* C, int* H, int* p);
+int disc_launch_count(const Disc* D, int S, long long T);   // size of the plan the forward launches: pure, independent of S
+void disc_forward(Disc* D, hipStream_t s, const float* signals, int S, long long T, float* const* scores, float* const* fmaps);
+// K <= 64 segments per call, out [K] float64, fixed order: sum_j (c[k] - x[k][j])^2 and sum_j |a[k][j] - b[k][j]|; pointer / length / constant arrays on the host
+void sqerr_sums(hipStream_t s, const float* const* x, const long long* n, const float* c, int K, double* out);
+void l1_sums(hipStream_t s, const float* const* a, const float* const* b, const long long* n, int K, double* out);
+
 struct Hubert;
 Hubert* hubert_create(Ctx* ctx);
 void hubert_destroy(Hubert* H);

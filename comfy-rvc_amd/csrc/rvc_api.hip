@@ -307,6 +307,59 @@ int rvc_l1_sum(void* stream, const float* a, const float* b, int64_t n, double* 
   check_launch();
   RVC_CATCH
 }
+// ------------------------------------------------------------------------------------------------ discriminators
+struct rvc_disc { Disc* m; rvc_ctx* ctx; };
+int rvc_disc_create(rvc_ctx* ctx, int version, rvc_disc** out) {
+  RVC_TRY
+  RVC_REQUIRE(ctx && out, "null argument");
+  std::unique_ptr<rvc_disc> d(new rvc_disc()); d->ctx = ctx; d->m = disc_create(&ctx->c, version);
+  *out = d.release();
+  RVC_CATCH
+}
+int rvc_disc_set_tensor(rvc_disc* d, const char* name, const float* data, const int64_t* shape, int ndim) {
+  RVC_TRY
+  RVC_REQUIRE(d && name && data && ndim <= 8, "bad argument");
+  long long sh[8]; for (int i = 0; i < ndim; ++i) sh[i] = shape[i];
+  disc_set_tensor(d->m, name, data, sh, ndim);
+  RVC_CATCH
+}
+int rvc_disc_finalize(rvc_disc* d) { RVC_TRY RVC_REQUIRE(d, "null argument"); RVC_HIP_CHECK(hipSetDevice(d->ctx->c.device)); disc_finalize(d->m); RVC_CATCH }
+int rvc_disc_release(rvc_disc* d) { if (d) { disc_destroy(d->m); delete d; } return 0; }
+int rvc_disc_count(rvc_disc* d) { return d ? disc_count(d->m) : 0; }
+int rvc_disc_num_taps(rvc_disc* d, int i) { return d && i >= 0 && i < disc_count(d->m) ? disc_num_taps(d->m, i) : 0; }
+int rvc_disc_tap_shape(rvc_disc* d, int i, int tap, int64_t T, int* C, int* H, int* p) {
+  RVC_TRY
+  RVC_REQUIRE(d && C && H && p, "null argument");
+  disc_tap_shape(d->m, i, tap, T, C, H, p);
+  RVC_CATCH
+}
+int rvc_disc_launch_count(rvc_disc* d, int S, int64_t T) {
+  try { RVC_REQUIRE(d, "null argument"); return disc_launch_count(d->m, S, T); }
+  catch (const std::exception& e) { rvc::set_error(e.what()); return -1; }
+}
+int rvc_disc_forward(rvc_disc* d, void* stream, const float* signals, int S, int64_t T, float* const* scores, float* const* fmaps) {
+  RVC_TRY
+  RVC_REQUIRE(d && signals && fmaps, "null argument");
+  disc_forward(d->m, (hipStream_t)stream, signals, S, T, scores, fmaps);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_sqerr_sums(void* stream, const float* const* x, const int64_t* n, const float* c, int K, double* sums) {
+  RVC_TRY
+  RVC_REQUIRE(x && n && c && sums && K >= 1 && K <= 64, "1 <= K <= 64 segments, no null argument");
+  long long nn[64]; for (int k = 0; k < K; ++k) nn[k] = n[k];
+  sqerr_sums((hipStream_t)stream, x, nn, c, K, sums);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_l1_sums(void* stream, const float* const* a, const float* const* b, const int64_t* n, int K, double* sums) {
+  RVC_TRY
+  RVC_REQUIRE(a && b && n && sums && K >= 1 && K <= 64, "1 <= K <= 64 segments, no null argument");
+  long long nn[64]; for (int k = 0; k < K; ++k) nn[k] = n[k];
+  l1_sums((hipStream_t)stream, a, b, nn, K, sums);
+  check_launch();
+  RVC_CATCH
+}
 int rvc_synth_dec_halo(rvc_synth* s) { return s ? synth_dec_halo_frames(s->m) : 0; }
 int rvc_synth_window_frames(rvc_synth* s, int64_t T, int64_t keep0, int64_t keep1, int64_t* g0, int64_t* g1) {
   RVC_TRY

@@ -220,6 +220,18 @@ void conv_x3s_run_swapped(const ConvLayer& L, int row0, int rows, hipStream_t s,
                           const float* Rrm = nullptr, long long ldRrm = 0);  // Rrm: residual added to the product, laid out like Yrm (MDX23C's x + tdf(x))
 void split_image_from_tm(hipStream_t s, const float* x, int C, int T, int M, unsigned char* img, long long tp);      // x [C][T][M] -> image of the (C M) x T tensor
 void conv_x3s_force(int ksplit, int am, int an);      // tests / benchmarks: K split and tile of the calling thread's next launches (0 = automatic)
+// the bf16x3 weight image of a dense layer on the host: P[chunk][tap][hi | lo][half][CoPx rows][8 ch] from w [Co][Ci][k], Ci % 16 == 0, rows Co .. CoPx - 1 zero (conv_mfma.hip)
+void x3_weight_image(const float* w, int Co, int Ci, int k, int CoPx, std::vector<uint16_t>& P);
+// Strided k-tap convolution along H over S tensors [Ci][H][p] -> [Co][Hout][p] (both [S][C][H][p], contiguous) in one bf16x3 GEMM launch, bias and
+// leaky ReLU (slope 1: none) in the epilogue (conv_x3d.hip: the discriminators' dense layers).  Planned, then launched, like the split-MFMA family
+// (conv_kernels.h); the plan is pure and its launch count - one - does not depend on S.  Wx: x3_weight_image of the layer.
+struct ConvX3dArgs {
+  const float* X; const unsigned char* Wx; const float* bias; float* Y;
+  int Ci, Co, CoPx, H, Hout, p, k, stride, pad, S; float slope;
+};
+struct ConvX3dPlan { ConvX3dArgs a; dim3 grid; int units = 1; size_t lds = 0; double flops = 0.0; };   // units: (chunk, tap) units per pipeline stage (1, 2 or 4)
+bool conv_x3d_plan(const ConvX3dArgs& a, ConvX3dPlan& p);   // false: the layer does not fit the kernel (Ci % 16, Co % 128 with CoPx = Co, a bias, k <= 16, 32-bit offsets)
+void conv_x3d_launch(const ConvX3dPlan& p, hipStream_t s);
 // one ConvBlockRes of 16 or 32 channels (3 x 3, 3 x 3, + x) in one launch (conv_cbr2.hip): x, out fp32 [C][H W], distinct
 bool cbr2_small_eligible(const ConvLayer& c1, const ConvLayer& c2);
 void cbr2_small_run(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, const float* x, int H, int W, float* out);

@@ -267,3 +267,105 @@ class SynthesizerTrnMs768NSFsid(_SynthesizerNSFsid):
 class SynthesizerTrnMs256NSFsid(_SynthesizerNSFsid):
     """v1: 256-d final_proj features (reference lib/infer_pack/models.py:580-693)."""
     FEAT_DIM = 256
+
+
+# ------------------------------------------------------------------------------------------------- discriminators
+class _MultiPeriodDiscriminator:
+    """MultiPeriodDiscriminator / MultiPeriodDiscriminatorV2 (reference lib/infer_pack/models.py:1024-1145), forward only: DiscriminatorS plus one
+    DiscriminatorP per period.  `forward(y, y_hat)` / `net_d(y, y_hat)` returns `(y_d_rs, y_d_gs, fmap_rs, fmap_gs)` like the reference: per
+    sub-discriminator the score [B, H p] of the real and of the generated batch and the lists of feature maps ([B,C,H,p]; [B,C,T'] for
+    DiscriminatorS).  Both batches run through every layer in one launch (rvc_disc_forward on the 2 B signals); the returned tensors are views of
+    the buffers the layers wrote.  CUDA tensors only: there is no CPU path."""
+    VERSION = 1
+
+    def __init__(self, use_spectral_norm=False, device="cuda:0"):
+        if use_spectral_norm:
+            raise NotImplementedError("spectral norm is not implemented (use_spectral_norm is false in every shipped configuration)")
+        self.device = torch.device(device)
+        self._ctx = _lib.get_ctx(self.device.index or 0)
+        h = C.c_void_p()
+        _lib.check(_lib.lib.rvc_disc_create(self._ctx, self.VERSION, C.byref(h)))
+        self._h = h
+        self._loaded = False
+        self.periods = [2, 3, 5, 7, 11, 17] + ([23, 37] if self.VERSION == 2 else [])
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None and getattr(_lib, 'lib', None) is not None:
+            _lib.lib.rvc_disc_release(h)
+            self._h = None
+
+    def load_state_dict(self, state_dict, strict=False):
+        with torch.cuda.device(self.device):
+            _lib.set_tensors(_lib.lib.rvc_disc_set_tensor, self._h, state_dict)
+            _lib.check(_lib.lib.rvc_disc_finalize(self._h))
+        self._loaded = True
+        return self
+
+    def eval(self):
+        return self
+
+    def train(self, mode=True):
+        return self
+
+    def to(self, device):
+        return self
+
+    def launch_count(self, S, T):
+        """Kernel launches of one forward over S signals of T samples (rvc_disc_launch_count: the size of the plan; nothing is launched)."""
+        n = _lib.lib.rvc_disc_launch_count(self._h, int(S), int(T))
+        if n < 0:
+            raise _lib.RvcHipError(_lib.lib.rvc_last_error().decode("utf-8", "replace"))
+        return n
+
+    def tap_shapes(self, T):
+        """[[(C, H, p) per tap] per sub-discriminator] for signals of T samples."""
+        out = []
+        for i in range(_lib.lib.rvc_disc_count(self._h)):
+            rows = []
+            for l in range(_lib.lib.rvc_disc_num_taps(self._h, i)):
+                c, h, p = C.c_int(), C.c_int(), C.c_int()
+                _lib.check(_lib.lib.rvc_disc_tap_shape(self._h, i, l, int(T), C.byref(c), C.byref(h), C.byref(p)))
+                rows.append((c.value, h.value, p.value))
+            out.append(rows)
+        return out
+
+    def forward(self, y, y_hat):
+        assert self._loaded, "load_state_dict first"
+        for t in (y, y_hat):
+            if not (hasattr(t, "is_cuda") and t.is_cuda):
+                raise ValueError("the discriminators run on the device: pass CUDA tensors (there is no CPU path)")
+        if y.dim() != 3 or y.shape[1] != 1 or tuple(y.shape) != tuple(y_hat.shape):
+            raise ValueError(f"y and y_hat must both be [B, 1, T]: got {tuple(y.shape)} and {tuple(y_hat.shape)}")
+        B, T = int(y.shape[0]), int(y.shape[2])
+        for p in self.periods:
+            if (p - T % p) % p >= T:
+                raise ValueError(f"T = {T} is not longer than the reflect pad period {p} needs")
+        dev = y.device
+        sig = torch.cat([y.detach().to(torch.float32).reshape(B, T), y_hat.detach().to(torch.float32).reshape(B, T)]).contiguous()
+        shapes = self.tap_shapes(T)
+        bufs = [[torch.empty((2 * B, c, h, p) if i else (2 * B, c, h), dtype=torch.float32, device=dev) for (c, h, p) in rows] for i, rows in enumerate(shapes)]
+        flat = [t for rows in bufs for t in rows]
+        ptrs = (C.c_void_p * len(flat))(*[t.data_ptr() for t in flat])
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.rvc_disc_forward(self._h, _lib.current_stream(), _lib.ptr(sig), 2 * B, T, None, ptrs))
+        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
+        for rows in bufs:
+            fmap_rs.append([t[:B] for t in rows])
+            fmap_gs.append([t[B:] for t in rows])
+            y_d_rs.append(torch.flatten(rows[-1][:B], 1, -1))
+            y_d_gs.append(torch.flatten(rows[-1][B:], 1, -1))
+        return y_d_rs, y_d_gs, fmap_rs, fmap_gs
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
+
+class MultiPeriodDiscriminator(_MultiPeriodDiscriminator):
+    """v1: periods 2, 3, 5, 7, 11, 17 (reference lib/infer_pack/models.py:1024-1049)."""
+    VERSION = 1
+
+
+class MultiPeriodDiscriminatorV2(_MultiPeriodDiscriminator):
+    """v2: periods 2, 3, 5, 7, 11, 17, 23, 37 (reference lib/infer_pack/models.py:1052-1079)."""
+    VERSION = 2

@@ -1,11 +1,12 @@
 """loss/mel and loss/kl of a generator checkpoint over a prepared dataset - the two numbers watched to pick an epoch - from the training forward alone
-(no discriminator, no backward pass).  Formed as the trainer forms them (reference training_cli.py:505-545,:570-571)."""
+(no backward pass), formed as the trainer forms them (reference training_cli.py:505-545,:570-571).  With the discriminator checkpoint that the trainer
+writes next to it (D_*.pth) also the three adversarial numbers it logs, loss_disc, loss_gen and loss_fm (:545-553,:567-572,:585)."""
 import numpy as np
 import torch
 
 from ..infer_pack import models
 from . import data_utils
-from .losses import kl_loss, l1_loss
+from .losses import discriminator_loss, feature_loss, generator_loss, kl_loss, l1_loss
 from .mel_processing import mel_spectrogram_torch, spec_to_mel_torch
 
 
@@ -14,10 +15,10 @@ def _slice_segments(x, ids, size):
     return torch.stack([x[i, :, int(s):int(s) + size] for i, s in enumerate(ids.tolist())])
 
 
-def reconstruction_losses(net_g, batch, hps, generator=None, *, noise=None, ids_slice=None):
+def reconstruction_losses(net_g, batch, hps, generator=None, *, noise=None, ids_slice=None, return_y_hat=False):
     """One collated batch (TextAudioCollateMultiNSFsid's nine tensors, or TextAudioCollate's seven) -> {"loss_mel", "loss_kl": 0-dim float32 device tensors,
     "ids_slice": int64 [B]}.  Noise and slice starts are drawn from `generator` (a CPU torch.Generator; None: the global one) in the forward's order;
-    noise / ids_slice given explicitly (as to the forward) replace the draws."""
+    noise / ids_slice given explicitly (as to the forward) replace the draws.  return_y_hat: the generated segments [B,1,segment_size] are added as "y_hat"."""
     d, seg = hps.data, hps.train.segment_size // hps.data.hop_length
     if len(batch) == 9:
         phone, phone_lengths, pitch, pitchf, spec, spec_lengths, _wave, _wl, sid = batch
@@ -46,7 +47,24 @@ def reconstruction_losses(net_g, batch, hps, generator=None, *, noise=None, ids_
     mel = spec_to_mel_torch(spec.to(dev, torch.float32), d.filter_length, d.n_mel_channels, d.sampling_rate, d.mel_fmin, d.mel_fmax)
     y_mel = _slice_segments(mel, ids_slice, seg)
     y_hat_mel = mel_spectrogram_torch(y_hat, d.filter_length, d.n_mel_channels, d.sampling_rate, d.hop_length, d.win_length, d.mel_fmin, d.mel_fmax)
-    return {"loss_mel": l1_loss(y_mel, y_hat_mel), "loss_kl": kl_loss(z_p, logs_q, m_p, logs_p, z_mask), "ids_slice": ids_slice}
+    out = {"loss_mel": l1_loss(y_mel, y_hat_mel), "loss_kl": kl_loss(z_p, logs_q, m_p, logs_p, z_mask), "ids_slice": ids_slice}
+    if return_y_hat:
+        out["y_hat"] = y_hat
+    return out
+
+
+def adversarial_losses(net_d, wave, y_hat, ids_slice=None, hps=None):
+    """loss_disc, loss_gen, loss_fm of one batch as the trainer forms them (reference training_cli.py:545-553,:567-572,:585): wave [B,1,Tw] the real waves,
+    sliced to y_hat's segments at ids_slice * hop_length when ids_slice is given (wave already sliced otherwise), y_hat [B,1,segment_size].  One
+    net_d(wave, y_hat) serves all three: without a backward pass the trainer's two calls compute the same.  0-dim float32 device tensors."""
+    y_hat = y_hat.detach()
+    wave = torch.as_tensor(wave).to(y_hat.device, torch.float32)
+    if ids_slice is not None:
+        wave = _slice_segments(wave, torch.as_tensor(ids_slice).reshape(-1).cpu() * int(hps.data.hop_length), int(y_hat.shape[-1]))
+    y_d_r, y_d_g, fmap_r, fmap_g = net_d(wave, y_hat)
+    loss_disc, _ = discriminator_loss(y_d_r, y_d_g)
+    loss_gen, _ = generator_loss(y_d_g)
+    return {"loss_disc": loss_disc, "loss_gen": loss_gen, "loss_fm": feature_loss(fmap_r, fmap_g)}
 
 
 def load_generator(ckpt, hps, version="v2", f0=True, device="cuda:0"):
@@ -62,12 +80,23 @@ def load_generator(ckpt, hps, version="v2", f0=True, device="cuda:0"):
     return net
 
 
+def load_discriminator(ckpt, version="v2", device="cuda:0"):
+    """A trainer's D_*.pth ({"model": state_dict, ...}, reference lib/train/utils.py:120-131) or a bare state dict -> the loaded discriminators
+    (MultiPeriodDiscriminatorV2 for "v2", MultiPeriodDiscriminator for "v1": training_cli.py picks them by version)."""
+    cpt = torch.load(ckpt, map_location="cpu") if isinstance(ckpt, str) else ckpt
+    sd = cpt["model"] if isinstance(cpt, dict) and "model" in cpt else cpt
+    cls = models.MultiPeriodDiscriminatorV2 if version == "v2" else models.MultiPeriodDiscriminator
+    return cls(False, device=device).load_state_dict(sd)
+
+
 def evaluate_checkpoint(ckpt, filelist, hps, seed=1337, batch_size=4, boundaries=(32, 100, 200, 300, 400, 500, 600, 700, 800, 900), version="v2", f0=True,
-                        device="cuda:0"):
+                        device="cuda:0", ckpt_d=None):
     """Walks `filelist` through the loader, the collate and the bucket sampler (unshuffled) and returns {"loss_mel", "loss_kl": means over the batches,
     "batches": [{"loss_mel", "loss_kl", "ids_slice"}...]}.  The sampler buckets by file size (dataset.lengths), so a batch may still hold an item whose
-    labels are shorter than the segment: such a batch cannot be sliced and is left out.  The draws come from torch.Generator().manual_seed(seed): the same seed gives the same two numbers."""
+    labels are shorter than the segment: such a batch cannot be sliced and is left out.  The draws come from torch.Generator().manual_seed(seed): the same seed gives the same two numbers.
+    ckpt_d (a D_*.pth path, a state dict or loaded discriminators): loss_disc, loss_gen and loss_fm are added per batch and as means; None: nothing changes."""
     net = ckpt if hasattr(ckpt, "forward") else load_generator(ckpt, hps, version, f0, device)
+    net_d = None if ckpt_d is None else (ckpt_d if hasattr(ckpt_d, "forward") else load_discriminator(ckpt_d, version, device))
     seg = hps.train.segment_size // hps.data.hop_length
     ds = (data_utils.TextAudioLoaderMultiNSFsid if f0 else data_utils.TextAudioLoader)(filelist, hps.data)
     collate = data_utils.TextAudioCollateMultiNSFsid() if f0 else data_utils.TextAudioCollate()
@@ -80,8 +109,15 @@ def evaluate_checkpoint(ckpt, filelist, hps, seed=1337, batch_size=4, boundaries
         lens = batch[5 if f0 else 3]
         if int(lens.min()) < seg:
             continue
-        r = reconstruction_losses(net, batch, hps, gen)
-        rows.append({"loss_mel": float(r["loss_mel"]), "loss_kl": float(r["loss_kl"]), "ids_slice": r["ids_slice"].cpu().numpy()})
+        r = reconstruction_losses(net, batch, hps, gen, return_y_hat=net_d is not None)
+        row = {"loss_mel": float(r["loss_mel"]), "loss_kl": float(r["loss_kl"]), "ids_slice": r["ids_slice"].cpu().numpy()}
+        if net_d is not None:
+            adv = adversarial_losses(net_d, batch[6 if f0 else 4], r["y_hat"], r["ids_slice"], hps)
+            row.update({k: float(v) for k, v in adv.items()})
+        rows.append(row)
     if not rows:
         raise ValueError("no batch of the file list has every item at least segment_size long")
-    return {"loss_mel": float(np.mean([r["loss_mel"] for r in rows])), "loss_kl": float(np.mean([r["loss_kl"] for r in rows])), "batches": rows}
+    names = ["loss_mel", "loss_kl"] + (["loss_disc", "loss_gen", "loss_fm"] if net_d is not None else [])
+    out = {k: float(np.mean([r[k] for r in rows])) for k in names}
+    out["batches"] = rows
+    return out

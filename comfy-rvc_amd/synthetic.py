@@ -485,6 +485,66 @@ def synth_checkpoint(config=None, version="v2", seed=0, f0=1, family="plain"):
             "sr": {32000: "32k", 40000: "40k", 48000: "48k"}[config[-1]], "info": "synthetic"}
 
 
+# ----------------------------------------------------------------------------------- discriminators
+DISC_PERIODS = {"v1": (2, 3, 5, 7, 11, 17), "v2": (2, 3, 5, 7, 11, 17, 23, 37)}
+_DISC_S = [(16, 1, 15), (64, 4, 41), (256, 4, 41), (1024, 4, 41), (1024, 4, 41), (1024, 1024, 5), (1, 1024, 3)]       # (Co, Ci / groups, k), conv_post last
+_DISC_P = [(32, 1, 5), (128, 32, 5), (512, 128, 5), (1024, 512, 5), (1024, 1024, 5), (1, 1024, 3)]
+
+
+def disc_spec(version="v2"):
+    """name -> shape of MultiPeriodDiscriminator (v1) / MultiPeriodDiscriminatorV2 (reference lib/infer_pack/models.py:1024-1145) with weight norm, in the
+    reference module's state-dict order: per layer bias, weight_g [Co,1,1(,1)], weight_v [Co,Ci/groups,k(,1)]."""
+    spec = OrderedDict()
+    for i, period in enumerate((0,) + DISC_PERIODS[version]):
+        layers = _DISC_P if period else _DISC_S
+        for l, (co, ci, k) in enumerate(layers):
+            n = f"discriminators.{i}." + (f"convs.{l}" if l + 1 < len(layers) else "conv_post")
+            tail = (1,) if period else ()
+            spec[n + ".bias"] = (co,)
+            spec[n + ".weight_g"] = (co, 1, 1) + tail
+            spec[n + ".weight_v"] = (co, ci, k) + tail
+    return spec
+
+
+def disc_state_dict(version="v2", seed=0):
+    """Procedural discriminator weights: weight_v ~ N(0, 1), weight_g = ||v|| (per output channel) * 1.8 / sqrt(fan_in) * exp(0.25 N(0, 1)), bias ~ U(-0.05, 0.05):
+    every feature map of every sub-discriminator keeps a maximum between 0.06 and 20 on disc_waves inputs (tools/gen_golden_discriminator.py asserts it)."""
+    spec, sd = disc_spec(version), OrderedDict()
+    for name, shape in spec.items():
+        if name.endswith(".bias"):
+            sd[name] = _uniform(seed, name, shape, -0.05, 0.05)
+        elif name.endswith(".weight_v"):
+            sd[name] = _normal(seed, name, shape, 1.0)
+    for name, shape in spec.items():
+        if name.endswith(".weight_g"):
+            v = sd[name[:-1] + "v"].astype(np.float64)
+            norm = np.sqrt((v.reshape(v.shape[0], -1) ** 2).sum(axis=1))
+            g = norm * (1.8 / np.sqrt(_fan_in(v.shape))) * np.exp(0.25 * _rng(seed, name).standard_normal(v.shape[0]))
+            sd[name] = g.reshape(shape).astype(np.float32)
+    return OrderedDict((n, sd[n]) for n in spec)
+
+
+def disc_waves(B, T, seed=0):
+    """(y, y_hat), float32 [B,1,T] each: a real-looking segment (harmonics under a slow envelope plus noise, peak ~0.8) and a "generated" one - the same
+    tones slightly detuned with its own noise -, what net_d(wave, y_hat) sees (reference training_cli.py:545-549)."""
+    t = np.arange(T, dtype=np.float64)
+    out = []
+    for tag in ("y", "y_hat"):
+        w = np.zeros((B, 1, T), dtype=np.float32)
+        for b in range(B):
+            rng = _rng(seed, f"disc_wave.{b}")                # the tones of item b are shared by y and y_hat
+            f = 0.004 + 0.02 * rng.random()
+            ph = 2 * np.pi * rng.random(4)
+            amp = 0.5 / (1 + np.arange(4))
+            det = 1.0 if tag == "y" else 1.003
+            x = sum(amp[h] * np.sin(2 * np.pi * f * det * (h + 1) * t + ph[h]) for h in range(4))
+            x = x * (0.6 + 0.4 * np.sin(2 * np.pi * t / max(T, 1) * (1 + b)))
+            x = x + (0.02 if tag == "y" else 0.05) * _rng(seed, f"disc_wave.{tag}.{b}").standard_normal(T)
+            w[b, 0] = x.astype(np.float32)
+        out.append(w)
+    return out[0], out[1]
+
+
 # ----------------------------------------------------------------------------------- inputs
 def synth_train_batch(config, version, lengths, seed=0, f0=True, sids=None):
     """One collated training batch for the synthesizer's forward, as TextAudioCollateMultiNSFsid pads it (zeros beyond each length): dict of phone

@@ -11,6 +11,9 @@
  *   rvc_synth_forward    <- SynthesizerTrnMs{256,768}NSFsid.forward      lib/infer_pack/models.py:665-680,:781-796 (PosteriorEncoder :199-238)
  *   rvc_kl_loss          <- kl_loss                                      lib/train/losses.py:596-611
  *   rvc_l1_sum           <- F.l1_loss(y_mel, y_hat_mel)                  training_cli.py:570
+ *   rvc_disc_forward     <- MultiPeriodDiscriminator[V2].forward         lib/infer_pack/models.py:1024-1145 (net_d: training_cli.py:549,:567)
+ *   rvc_sqerr_sums       <- discriminator_loss / generator_loss          lib/train/losses.py:571-593
+ *   rvc_l1_sums          <- feature_loss                                 lib/train/losses.py:564-569
  *   rvc_vc_segment       <- VC.vc (features -> x2 upsample -> protect -> infer)   vc_infer_pipeline.py:25-114
  *   rvc_*_set_tensor     <- load_state_dict of the checkpoint tensors    vc_infer_pipeline.py:199-221,
  *                                                                        lib/infer_pack/loaders.py:19-31, lib/rmvpe.py:579-586
@@ -234,6 +237,37 @@ int rvc_kl_loss(void* stream, const float* z_p_dev, const float* logs_q_dev, con
                 int64_t len, double* sum_dev);
 /* sum_dev[0] = sum_i |a[i] - b[i]| over n elements, float64 accumulation in a fixed order (F.l1_loss = that / n, training_cli.py:570) */
 int rvc_l1_sum(void* stream, const float* a_dev, const float* b_dev, int64_t n, double* sum_dev);
+
+/* ------------------------------------------------------------------ discriminators (training, forward only) */
+/* version 1: MultiPeriodDiscriminator (DiscriminatorS + DiscriminatorP for periods 2, 3, 5, 7, 11, 17), 2: MultiPeriodDiscriminatorV2 (+ 23, 37);
+ * reference lib/infer_pack/models.py:1024-1145.  Tensor names are the reference state dict's: discriminators.<i>.convs.<l>.{weight_g, weight_v, bias} and
+ * discriminators.<i>.conv_post.* (weight norm over every dimension but the first, folded by finalize), or a plain .weight; spectral-norm tensors
+ * (weight_orig / weight_u) make finalize fail. */
+typedef struct rvc_disc rvc_disc;
+int rvc_disc_create(rvc_ctx* ctx, int version, rvc_disc** out);
+int rvc_disc_set_tensor(rvc_disc* d, const char* name, const float* host_data, const int64_t* shape, int ndim);
+int rvc_disc_finalize(rvc_disc* d);
+int rvc_disc_release(rvc_disc* d);
+/* shapes: sub-discriminators (7 or 9; 0 is DiscriminatorS), taps of sub-discriminator i (every layer's post-activation output and conv_post's output:
+ * 7 for DiscriminatorS, 6 for a DiscriminatorP), and tap (i, tap) for signals of T samples: [S][C][H][p] with p = 1 for DiscriminatorS.  The score
+ * of sub-discriminator i is its last tap flattened ([S][H p]).  Fails when T is not longer than the reflect pad a period needs. */
+int rvc_disc_count(rvc_disc* d);
+int rvc_disc_num_taps(rvc_disc* d, int i);
+int rvc_disc_tap_shape(rvc_disc* d, int i, int tap, int64_t T, int* C, int* H, int* p);
+/* signals_dev [S][T]: the trainer passes the B real items followed by the B generated ones (net_d(y, y_hat), training_cli.py:549,:567), so S = 2 B.
+ * fmaps_dev: HOST array of one device pointer per tap, sub-discriminator-major (sum of rvc_disc_num_taps entries), each [S][C][H][p]: a layer writes its
+ * tap and the next layer reads it there - the call owns no activation memory.  scores_dev: NULL, or a HOST array of rvc_disc_count device pointers
+ * [S][H p] (an entry may be NULL or the last tap itself: nothing is copied then).  Every layer is one launch for all S signals. */
+int rvc_disc_forward(rvc_disc* d, void* stream, const float* signals_dev, int S, int64_t T, float* const* scores_dev, float* const* fmaps_dev);
+/* number of kernel launches rvc_disc_forward makes for this shape (the size of its plan; touches no stream): 6 per DiscriminatorP, 7 for
+ * DiscriminatorS, whatever S; -1 on error. */
+int rvc_disc_launch_count(rvc_disc* d, int S, int64_t T);
+/* The GAN losses' reductions (reference lib/train/losses.py:564-593), K <= 64 tensors per call in ONE segmented float64 reduction of a fixed order (two
+ * calls give the same bits).  x_dev / a_dev / b_dev, n, c: HOST arrays of K device pointers, lengths and constants; sums_dev [K] float64 on the device.
+ *   rvc_sqerr_sums: sums[k] = sum_j (c[k] - x[k][j])^2     discriminator_loss (c = 1 on real scores, 0 on generated), generator_loss (c = 1)
+ *   rvc_l1_sums:    sums[k] = sum_j |a[k][j] - b[k][j]|     feature_loss (the real and generated halves of every tap) */
+int rvc_sqerr_sums(void* stream, const float* const* x_dev, const int64_t* n, const float* c, int K, double* sums_dev);
+int rvc_l1_sums(void* stream, const float* const* a_dev, const float* const* b_dev, const int64_t* n, int K, double* sums_dev);
 
 /* ------------------------------------------------------------------ fused segment: VC.vc without index retrieval */
 /* audio_dev [L] 16 kHz segment; pitch/pitchf as above with at least p_len = 2*T_h entries; out_dev [2*T_h*upp].
