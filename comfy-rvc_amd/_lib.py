@@ -168,6 +168,12 @@ SIGNATURES = {
     "rvc_spectrogram_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_int64]),
     "rvc_mel_filterbank_set": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rvc_spec_to_mel_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
+    "rvc_spectrogram_batch_ms": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_int64]),
+    "rvc_multiscale_mel_loss": (c_int, [c_void_p, c_void_p, c_int, P(c_void_p), P(c_int64), P(c_int64), c_int, c_int64, P(C.c_int32), P(C.c_int32), c_int, c_int,
+                                        c_void_p]),
+    "rvc_hpss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
+    "rvc_hpss_l1": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    "rvc_tsi_terms": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "rvc_op_gemm_split": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_float, c_int, c_float] + [c_int] * 5),
     "rvc_op_conv2d_split": (c_int, [c_void_p] * 7 + [c_int] * 9),
     "rvc_op_wn_in_gate_split": (c_int, [c_void_p] * 6 + [c_int] * 4),

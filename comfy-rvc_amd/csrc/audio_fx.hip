@@ -137,7 +137,6 @@ struct StoreRev { long long* p; long long n; __device__ __forceinline__ void ope
 
 // ================================================================================================ click removal
 // scipy.ndimage "reflect" (d c b a | a b c d | d c b a), one reflection: valid for -n <= j < 2 n
-__device__ __forceinline__ long long reflect_index(long long j, long long n) { return j < 0 ? -j - 1 : (j >= n ? 2 * n - 1 - j : j); }
 
 struct ClickArgs {
   const float* x; long long n;
@@ -174,12 +173,7 @@ __global__ __launch_bounds__(256) void click_mask_kernel(const ClickArgs p) {
   if (click) {
     float w[kMaxClickKernel];
     const int k = p.ksize, h = k / 2;
-    for (int j = 0; j < k; ++j) {                                     // insertion sort of the k neighbours
-      const float u = p.x[reflect_index(i - h + j, p.n)];
-      int q = j;
-      while (q > 0 && w[q - 1] > u) { w[q] = w[q - 1]; --q; }
-      w[q] = u;
-    }
+    for (int j = 0; j < k; ++j) sorted_insert(w, j, p.x[reflect_index(i - h + j, p.n)]);      // insertion sort of the k neighbours
     out = w[h];
   }
   p.y[i] = out;

@@ -104,6 +104,20 @@ void mel_filterbank_set(Ctx* ctx, int n_fft, int n_mels, const int* first, const
 void spec_to_mel_batch(Ctx* ctx, hipStream_t s, const float* spec, long long spec_pitch, const long long* clips, int n_clips, int n_fft, int n_mels,
                        float* mel, long long mel_pitch);
 void spec_state_free(Ctx* ctx);
+// the same for the multi-scale loss's geometries: n_fft 256 .. 4096, any hop with n_fft - hop even (hop > n_fft: frames centred in their hop, no reflection)
+void spectrogram_batch_ms(Ctx* ctx, hipStream_t s, const float* audio, long long n_audio, const long long* clips, int n_clips, int n_fft, int hop, float eps,
+                          int clamp, float* out, long long pitch);
+// K scales of MultiScaleMelSpectrogramLoss: spec[k] [n_fft[k] / 2 + 1][pitch[k]] holds 2 B rows of nf frames, row r at column r row_stride[k];
+// out [K][2] float64 = sums of the pointwise loss (0 l1, 1 l2, 2 smoothl1) on the log-mels and on exp(log-mel); K + 1 launches
+void multiscale_mel_loss(Ctx* ctx, hipStream_t s, int K, const float* const* spec, const long long* pitch, const long long* row_stride, int B, long long nf,
+                         const int* n_fft, const int* n_mels, int loss, int want_mag, double* out);
+
+// auxiliary losses (aux_losses.hip)
+constexpr int kSegSumMax = 16;
+void f64_segment_sums(hipStream_t s, const double* x, const long long* bounds, int K, double* out);      // out[k] = sum of x[bounds[k] .. bounds[k + 1]), fixed order
+void hpss_parts(hipStream_t s, const float* x, int B, int F, int T, float* h, float* p, int medians);
+void hpss_l1(hipStream_t s, const float* org, const float* gen, int B, int F, int T, float eps, double* out2);
+void tsi_terms(hipStream_t s, const float* org, const float* gen, int B, int F, int T, float eps, double* out);
 
 void rmvpe_decode_rm(Rmvpe* R, hipStream_t s, const float* sal_rm, long long n, float thred, double* f0);
 int rmvpe_status(Rmvpe* R, hipStream_t s);                 // waits for the stream; bit 0: the last forward's GRU scan timed out

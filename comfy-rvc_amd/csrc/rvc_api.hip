@@ -658,6 +658,43 @@ int rvc_spec_to_mel_batch(rvc_ctx* ctx, void* stream, const float* spec, int64_t
   check_launch();
   RVC_CATCH
 }
+int rvc_spectrogram_batch_ms(rvc_ctx* ctx, void* stream, const float* audio, int64_t n_audio, const int64_t* clips, int n_clips, int n_fft, int hop, float eps,
+                             int clamp, float* out, int64_t pitch) {
+  RVC_TRY
+  RVC_REQUIRE(ctx && audio && out && (clips || n_clips == 0), "null argument");
+  spectrogram_batch_ms(&ctx->c, (hipStream_t)stream, audio, n_audio, (const long long*)clips, n_clips, n_fft, hop, eps, clamp, out, pitch);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_multiscale_mel_loss(rvc_ctx* ctx, void* stream, int K, const float* const* spec, const int64_t* pitch, const int64_t* row_stride, int B, int64_t nf,
+                            const int32_t* n_fft, const int32_t* n_mels, int loss, int want_mag, double* out) {
+  RVC_TRY
+  RVC_REQUIRE(ctx && spec && pitch && row_stride && n_fft && n_mels && out, "null argument");
+  multiscale_mel_loss(&ctx->c, (hipStream_t)stream, K, spec, (const long long*)pitch, (const long long*)row_stride, B, nf, (const int*)n_fft, (const int*)n_mels,
+                      loss, want_mag, out);
+  check_launch();
+  RVC_CATCH
+}
+
+// ------------------------------------------------------------------------------------------------ auxiliary losses (aux_losses.hip)
+int rvc_hpss(void* stream, const float* x, int B, int F, int T, float* h, float* p, int medians) {
+  RVC_TRY
+  hpss_parts((hipStream_t)stream, x, B, F, T, h, p, medians);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_hpss_l1(void* stream, const float* org, const float* gen, int B, int F, int T, float eps, double* sums) {
+  RVC_TRY
+  hpss_l1((hipStream_t)stream, org, gen, B, F, T, eps, sums);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_tsi_terms(void* stream, const float* org, const float* gen, int B, int F, int T, float eps, double* out) {
+  RVC_TRY
+  tsi_terms((hipStream_t)stream, org, gen, B, F, T, eps, out);
+  check_launch();
+  RVC_CATCH
+}
 
 // ------------------------------------------------------------------------------------------------ single ops
 int rvc_op_conv1d(void* stream, const float* x, const float* w, const float* bias, const float* res, float* y, int Ci, int Co, int Tin, int k,

@@ -1,4 +1,4 @@
-// Arithmetic shared by the input high-pass of the conversion path (ops.hip: filtfilt) and the dataset preparation (dataset_prep.hip: lfilter,
+// Device helpers with ONE definition.  Arithmetic shared by the input high-pass of the conversion path (ops.hip: filtfilt) and the dataset preparation (dataset_prep.hip: lfilter,
 // windowed resampling): ONE definition each of the second-order-section step, of the state transition of a block and of the polyphase tap
 // sum, so the two users cannot drift apart (the dataset path is tested bit for bit against rvc_resample).
 #pragma once
@@ -15,6 +15,19 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// scipy.ndimage's "reflect" boundary (d c b a | a b c d | d c b a): the edge sample is repeated.  One reflection: -n <= j < 2 n
+__host__ __device__ __forceinline__ long long reflect_index(long long j, long long n) { return j < 0 ? -j - 1 : (j >= n ? 2 * n - 1 - j : j); }
+
+// w[0 .. j) ascending: u is inserted in order (step j of an insertion sort).  After k steps w[k / 2] is the median of the k values of an odd window -
+// one of its inputs, so the median filters of audio_fx.hip (declick) and aux_losses.hip (HPSS) are exact whatever the order of insertion.
+// STRIDE: elements between neighbours of the list (a per-thread list interleaved with the other threads' in LDS).
+template <int STRIDE = 1>
+__device__ __forceinline__ void sorted_insert(float* w, int j, float u) {
+  int q = j;
+  while (q > 0 && w[(q - 1) * STRIDE] > u) { w[q * STRIDE] = w[(q - 1) * STRIDE]; --q; }
+  w[q * STRIDE] = u;
 }
 
 constexpr int kSosN = 6;      // states of the cascade: 2 per section, 3 sections (a 5th-order filter: the last section is first order, b2 = a2 = 0)

@@ -1,12 +1,14 @@
 """loss/mel and loss/kl of a generator checkpoint over a prepared dataset - the two numbers watched to pick an epoch - from the training forward alone
 (no backward pass), formed as the trainer forms them (reference training_cli.py:505-545,:570-571).  With the discriminator checkpoint that the trainer
-writes next to it (D_*.pth) also the three adversarial numbers it logs, loss_disc, loss_gen and loss_fm (:545-553,:567-572,:585)."""
+writes next to it (D_*.pth) also the three adversarial numbers it logs, loss_disc, loss_gen and loss_fm (:545-553,:567-572,:585).  The trainer's
+switches are followed: with hps.train.use_multiscale loss_mel is MultiScaleMelSpectrogramLoss(y_hat, wave) (:569), with hps.train.c_hd / c_tsi > 0 the
+harmonic_loss / tsi_loss of combined_aux_loss (:573-584) are added."""
 import numpy as np
 import torch
 
 from ..infer_pack import models
 from . import data_utils
-from .losses import discriminator_loss, feature_loss, generator_loss, kl_loss, l1_loss
+from .losses import MultiScaleMelSpectrogramLoss, combined_aux_loss, discriminator_loss, feature_loss, generator_loss, kl_loss, l1_loss
 from .mel_processing import mel_spectrogram_torch, spec_to_mel_torch
 
 
@@ -15,10 +17,27 @@ def _slice_segments(x, ids, size):
     return torch.stack([x[i, :, int(s):int(s) + size] for i, s in enumerate(ids.tolist())])
 
 
-def reconstruction_losses(net_g, batch, hps, generator=None, *, noise=None, ids_slice=None, return_y_hat=False):
+def _train_get(hps, key, default=0.):
+    """hps.train.get(key, default) for an HParams or a plain namespace."""
+    tr = hps.train
+    return tr.get(key, default) if hasattr(tr, "get") else getattr(tr, key, default)
+
+
+def multiscale_state(hps, ckpt=None):
+    """The MultiScaleMelSpectrogramLoss an evaluation uses: the state the trainer saved with the generator (the checkpoint's "msml" entry, its mel_fmin /
+    mel_fmax as saved), else the trainer's fresh one (defaults, epsilon = hps.train.eps).  adjustment_factor is 0 in both: evaluation does not move the bands."""
+    saved = ckpt.get("msml") if isinstance(ckpt, dict) else None
+    if saved:
+        return MultiScaleMelSpectrogramLoss(**{**saved, "adjustment_factor": 0.0})
+    return MultiScaleMelSpectrogramLoss(hps.data.sampling_rate, epsilon=_train_get(hps, "eps", 1e-8), adjustment_factor=0.0)
+
+
+def reconstruction_losses(net_g, batch, hps, generator=None, *, noise=None, ids_slice=None, return_y_hat=False, msml=None):
     """One collated batch (TextAudioCollateMultiNSFsid's nine tensors, or TextAudioCollate's seven) -> {"loss_mel", "loss_kl": 0-dim float32 device tensors,
     "ids_slice": int64 [B]}.  Noise and slice starts are drawn from `generator` (a CPU torch.Generator; None: the global one) in the forward's order;
-    noise / ids_slice given explicitly (as to the forward) replace the draws.  return_y_hat: the generated segments [B,1,segment_size] are added as "y_hat"."""
+    noise / ids_slice given explicitly (as to the forward) replace the draws.  return_y_hat: the generated segments [B,1,segment_size] are added as "y_hat".
+    hps.train.use_multiscale: loss_mel is msml(y_hat, sliced wave) (msml None: multiscale_state(hps)); hps.train.c_hd / c_tsi > 0: "harmonic_loss" /
+    "tsi_loss" of combined_aux_loss(sliced wave, y_hat) are added.  With none of the three set nothing changes."""
     d, seg = hps.data, hps.train.segment_size // hps.data.hop_length
     if len(batch) == 9:
         phone, phone_lengths, pitch, pitchf, spec, spec_lengths, _wave, _wl, sid = batch
@@ -47,7 +66,23 @@ def reconstruction_losses(net_g, batch, hps, generator=None, *, noise=None, ids_
     mel = spec_to_mel_torch(spec.to(dev, torch.float32), d.filter_length, d.n_mel_channels, d.sampling_rate, d.mel_fmin, d.mel_fmax)
     y_mel = _slice_segments(mel, ids_slice, seg)
     y_hat_mel = mel_spectrogram_torch(y_hat, d.filter_length, d.n_mel_channels, d.sampling_rate, d.hop_length, d.win_length, d.mel_fmin, d.mel_fmax)
-    out = {"loss_mel": l1_loss(y_mel, y_hat_mel), "loss_kl": kl_loss(z_p, logs_q, m_p, logs_p, z_mask), "ids_slice": ids_slice}
+    multiscale, c_hd, c_tsi = bool(_train_get(hps, "use_multiscale", False)), _train_get(hps, "c_hd", 0.), _train_get(hps, "c_tsi", 0.)
+    if multiscale or c_hd > 0 or c_tsi > 0:
+        wave = _slice_segments(torch.as_tensor(_wave).to(dev, torch.float32), torch.as_tensor(ids_slice).reshape(-1).cpu() * int(d.hop_length),
+                               int(y_hat.shape[-1]))
+    if multiscale:
+        loss_mel = (msml if msml is not None else multiscale_state(hps))(y_hat, wave)
+    else:
+        loss_mel = l1_loss(y_mel, y_hat_mel)
+    out = {"loss_mel": loss_mel, "loss_kl": kl_loss(z_p, logs_q, m_p, logs_p, z_mask), "ids_slice": ids_slice}
+    if c_hd > 0 or c_tsi > 0:
+        harmonic, _, tsi = combined_aux_loss(wave, y_hat, c_tefs=0., c_hd=c_hd, c_tsi=c_tsi, n_mels=d.n_mel_channels, sample_rate=d.sampling_rate,
+                                             n_fft=d.filter_length, hop_length=d.hop_length, win_length=d.win_length, fmin=d.mel_fmin, fmax=d.mel_fmax,
+                                             eps=_train_get(hps, "eps", None))
+        if c_hd > 0:
+            out["harmonic_loss"] = harmonic
+        if c_tsi > 0:
+            out["tsi_loss"] = tsi
     if return_y_hat:
         out["y_hat"] = y_hat
     return out
@@ -94,8 +129,12 @@ def evaluate_checkpoint(ckpt, filelist, hps, seed=1337, batch_size=4, boundaries
     """Walks `filelist` through the loader, the collate and the bucket sampler (unshuffled) and returns {"loss_mel", "loss_kl": means over the batches,
     "batches": [{"loss_mel", "loss_kl", "ids_slice"}...]}.  The sampler buckets by file size (dataset.lengths), so a batch may still hold an item whose
     labels are shorter than the segment: such a batch cannot be sliced and is left out.  The draws come from torch.Generator().manual_seed(seed): the same seed gives the same two numbers.
-    ckpt_d (a D_*.pth path, a state dict or loaded discriminators): loss_disc, loss_gen and loss_fm are added per batch and as means; None: nothing changes."""
-    net = ckpt if hasattr(ckpt, "forward") else load_generator(ckpt, hps, version, f0, device)
+    ckpt_d (a D_*.pth path, a state dict or loaded discriminators): loss_disc, loss_gen and loss_fm are added per batch and as means; None: nothing changes.
+    hps.train.use_multiscale / c_hd / c_tsi as in reconstruction_losses; the multi-scale state is the checkpoint's "msml" entry when ckpt is a path or a
+    checkpoint dict that has one."""
+    cpt = torch.load(ckpt, map_location="cpu") if isinstance(ckpt, str) else ckpt
+    msml = multiscale_state(hps, cpt) if _train_get(hps, "use_multiscale", False) else None
+    net = cpt if hasattr(cpt, "forward") else load_generator(cpt, hps, version, f0, device)
     net_d = None if ckpt_d is None else (ckpt_d if hasattr(ckpt_d, "forward") else load_discriminator(ckpt_d, version, device))
     seg = hps.train.segment_size // hps.data.hop_length
     ds = (data_utils.TextAudioLoaderMultiNSFsid if f0 else data_utils.TextAudioLoader)(filelist, hps.data)
@@ -109,8 +148,9 @@ def evaluate_checkpoint(ckpt, filelist, hps, seed=1337, batch_size=4, boundaries
         lens = batch[5 if f0 else 3]
         if int(lens.min()) < seg:
             continue
-        r = reconstruction_losses(net, batch, hps, gen, return_y_hat=net_d is not None)
+        r = reconstruction_losses(net, batch, hps, gen, return_y_hat=net_d is not None, msml=msml)
         row = {"loss_mel": float(r["loss_mel"]), "loss_kl": float(r["loss_kl"]), "ids_slice": r["ids_slice"].cpu().numpy()}
+        row.update({k: float(r[k]) for k in ("harmonic_loss", "tsi_loss") if k in r})
         if net_d is not None:
             adv = adversarial_losses(net_d, batch[6 if f0 else 4], r["y_hat"], r["ids_slice"], hps)
             row.update({k: float(v) for k, v in adv.items()})
@@ -118,6 +158,7 @@ def evaluate_checkpoint(ckpt, filelist, hps, seed=1337, batch_size=4, boundaries
     if not rows:
         raise ValueError("no batch of the file list has every item at least segment_size long")
     names = ["loss_mel", "loss_kl"] + (["loss_disc", "loss_gen", "loss_fm"] if net_d is not None else [])
+    names += [k for k in ("harmonic_loss", "tsi_loss") if k in rows[0]]
     out = {k: float(np.mean([r[k] for r in rows])) for k in names}
     out["batches"] = rows
     return out

@@ -1,10 +1,19 @@
 """The trainer's losses on device tensors, forward only: the two reconstruction losses (reference lib/train/losses.py:596-611 kl_loss; F.l1_loss as
 training_cli.py:570 uses it) and the three GAN losses (:564-593 feature_loss, discriminator_loss, generator_loss).  Each is a fixed-order float64
 reduction on the device (rvc_kl_loss per item, rvc_l1_sum; rvc_sqerr_sums / rvc_l1_sums: one segmented reduction over all tensors of a loss) and
-returns 0-dim float32 tensors.  No backward pass."""
+returns 0-dim float32 tensors.  No backward pass.
+
+Also the two generator-side terms the trainer adds on request: MultiScaleMelSpectrogramLoss (:430-561, `hps.train.use_multiscale`) and combined_aux_loss
+(:344-399) with its parts compute_harmonics, compute_envelope and compute_tsi_loss.  compute_tefs (the temporal envelope / fine structure term) is not
+implemented: combined_aux_loss(c_tefs > 0) raises."""
+import ctypes
+from collections import namedtuple
+
+import numpy as np
 import torch
 
 from ... import _lib
+from . import mel_processing as MP
 
 
 def _dev(t):
@@ -93,3 +102,234 @@ def generator_loss(disc_outputs):
     """(sum_i L_i, [L_i]) with L_i = mean (1 - dg_i)^2; 0-dim float32 tensors."""
     per = _sqerr_means(list(disc_outputs), [1.0] * len(disc_outputs)).to(torch.float32)
     return per.sum(), [per[i] for i in range(len(disc_outputs))]
+
+
+# ------------------------------------------------------------------------------------------------- multi-scale mel loss (reference lib/train/losses.py:430-561)
+STFTParams = namedtuple("STFTParams", ["window_length", "hop_length"])
+_LOSS_KINDS = {"l1": 0, "l2": 1, "smoothl1": 2}
+
+
+class MultiScaleMelSpectrogramLoss:
+    """The reference's class on the device, forward only.  x and y go through each STFT together (2 B rows in one launch, one STFT per distinct window
+    length), then one kernel per scale projects both spectrograms, forms the pointwise loss and reduces it in float64; the log-mels are never stored.
+    Launches per call: (distinct window lengths) + (scales) + 1 = 4 + 6 + 1 = 11 with the default n_mels, whatever B and T."""
+
+    def __init__(self, sampling_rate, n_mels=[20, 64, 80, 128, 160, 256], loss="l1", epsilon=1e-8, mag_weight=0.0, log_weight=1.0, adjustment_factor=0.0,
+                 fmin=50., fmax=None, center=False, **kwargs):
+        if loss not in _LOSS_KINDS:
+            raise ValueError(f"loss must be one of {sorted(_LOSS_KINDS)}: {loss!r}")
+        self.sampling_rate = sampling_rate
+        window_lengths = [self.compute_window_length(mel, sampling_rate) for mel in n_mels]      # in the order GIVEN; n_mels itself is sorted (reference quirk)
+        self.stft_params = [STFTParams(window_length=w, hop_length=sampling_rate // 100) for w in window_lengths]
+        self.n_mels = sorted(n_mels)
+        self.loss = loss
+        self.epsilon = epsilon
+        self.log_weight = log_weight
+        self.mag_weight = mag_weight
+        self.center = center
+        if fmax is None:
+            fmax = sampling_rate // 2
+        self.fmax = fmax
+        self.fmin = fmin
+        self.mel_fmin = [fmin for _ in n_mels]
+        self.mel_fmax = [fmax for _ in n_mels]
+        self.adjustment_factor = adjustment_factor
+        self.frequency_buffer = int(sampling_rate * adjustment_factor) + 1
+        self.window_lengths = window_lengths
+        for k, v in kwargs.items():                  # a to_dict() result restores mel_fmin / mel_fmax here
+            setattr(self, k, v)
+        self.scale_losses = None                     # the last forward's per-scale losses (float32 device tensor [scales])
+
+    def to_dict(self):
+        return dict(sampling_rate=self.sampling_rate, n_mels=self.n_mels, loss=self.loss, epsilon=self.epsilon, mag_weight=self.mag_weight,
+                    log_weight=self.log_weight, adjustment_factor=self.adjustment_factor, fmin=self.fmin, fmax=self.fmax, center=self.center,
+                    mel_fmin=self.mel_fmin, mel_fmax=self.mel_fmax)
+
+    def show_freqs(self):
+        print("MultiScaleMelSpectrogramLoss:\n\tn_mels \twindow \tfmin \tfmax")
+        for i in range(len(self.mel_fmax)):
+            print(f"\t{self.n_mels[i]} \t{self.window_lengths[i]} \t{self.mel_fmin[i]:.0f} \t{self.mel_fmax[i]:.0f}")
+
+    @staticmethod
+    def compute_window_length(n_mels, sample_rate):
+        """The largest power of two not above 8 n_mels / (sample_rate / 2) seconds: 2^floor(log2(16 n_mels)) samples at every rate."""
+        window_length = int(8 * n_mels / (sample_rate / 2 - 0) * sample_rate)
+        return 2 ** (window_length.bit_length() - 1)
+
+    def adjust_fmin_fmax(self, scale_losses):
+        """Moves every scale's band by at most adjustment_factor, relatively: host arithmetic on the per-scale losses, step by step as the reference."""
+        median_loss = np.nanmedian(scale_losses)
+        cumloss = np.cumsum(scale_losses)
+        cutoff_index = np.argmax(cumloss >= median_loss * len(scale_losses))
+        median_low = np.nanmedian(scale_losses[:cutoff_index])
+        median_high = np.nanmedian(scale_losses[cutoff_index:])
+        for i, scale_loss in enumerate(scale_losses):
+            high = i >= cutoff_index
+            threshold = median_high if high else median_low
+            deviation = (scale_loss - threshold) / (threshold + self.epsilon)
+            adjustment = min(abs(self.adjustment_factor * deviation), self.adjustment_factor)
+            if high:
+                self.mel_fmax[i] = min(self.mel_fmax[i] * (1 + adjustment), self.fmax)
+                if deviation > self.epsilon:
+                    self.mel_fmin[i] = min(self.mel_fmin[i] * (1 + adjustment), self.mel_fmax[i] - self.frequency_buffer)
+                elif deviation < -self.epsilon:
+                    self.mel_fmin[i] = max(self.mel_fmin[i] * (1 - adjustment), self.fmin)
+            else:
+                self.mel_fmin[i] = max(self.mel_fmin[i] * (1 - adjustment), self.fmin)
+                if deviation > self.epsilon:
+                    self.mel_fmax[i] = min(self.mel_fmax[i] * (1 + adjustment), self.fmax)
+                elif deviation < -self.epsilon:
+                    self.mel_fmax[i] = max(self.mel_fmax[i] * (1 - adjustment), self.mel_fmin[i] + self.frequency_buffer)
+
+    def forward(self, x, y):
+        """x, y [B, 1, T] device tensors -> the mean over the scales of log_weight * loss(log-mels) + mag_weight * loss(exp(log-mels)), 0-dim float32."""
+        if self.center:
+            raise NotImplementedError("center=True is not implemented (the reference never passes it)")
+        x, y = _dev(x), _dev(y)
+        if x.shape != y.shape or x.dim() != 3:
+            raise ValueError(f"MultiScaleMelSpectrogramLoss: [B, C, T] tensors of one shape expected: {tuple(x.shape)} and {tuple(y.shape)}")
+        T = x.shape[-1]
+        both = torch.cat([x.reshape(-1, T), y.reshape(-1, T)], dim=0)
+        B, K = both.shape[0] // 2, len(self.n_mels)
+        hop = self.stft_params[0].hop_length
+        dev_index = MP._dev_index(both)
+        specs = {}
+        with torch.cuda.device(both.device):
+            for s in self.stft_params:
+                if s.window_length not in specs:
+                    specs[s.window_length] = MP.rows_spectrogram_packed(both, s.window_length, s.hop_length, 0.0, False)
+            for n_mels, fmin, fmax, s in zip(self.n_mels, self.mel_fmin, self.mel_fmax, self.stft_params):
+                MP.ensure_bank(dev_index, s.window_length, n_mels, self.sampling_rate, fmin, fmax)
+            nf = MP.frames_of(T, hop)
+            per = [specs[s.window_length] for s in self.stft_params]
+            ptrs = (_lib.c_void_p * K)(*[p[0].data_ptr() for p in per])
+            pitch = (_lib.c_int64 * K)(*[p[0].shape[1] for p in per])
+            stride = (_lib.c_int64 * K)(*[p[2] for p in per])
+            n_fft = (ctypes.c_int32 * K)(*[s.window_length for s in self.stft_params])
+            n_mel = (ctypes.c_int32 * K)(*self.n_mels)
+            sums = torch.zeros(K, 2, dtype=torch.float64, device=both.device)
+            _lib.check(_lib.lib.rvc_multiscale_mel_loss(_lib.get_ctx(dev_index), _lib.current_stream(), K, ptrs, pitch, stride, B, nf, n_fft, n_mel,
+                                                        _LOSS_KINDS[self.loss], int(self.mag_weight > 0), _lib.ptr(sums)))
+        count = torch.tensor([B * m * nf for m in self.n_mels], dtype=torch.float64, device=sums.device)
+        means = (sums / count[:, None]).to(torch.float32)                    # the reference's loss_fn results, float32
+        scale = torch.zeros(K, dtype=torch.float32, device=sums.device)
+        if self.log_weight > 0:
+            scale = scale + self.log_weight * means[:, 0]
+        if self.mag_weight > 0:
+            scale = scale + self.mag_weight * means[:, 1]
+        self.scale_losses = scale
+        if self.adjustment_factor > 0:
+            self.adjust_fmin_fmax([float(v) for v in scale.tolist()])
+        return scale.sum() / K
+
+    __call__ = forward
+
+
+# ------------------------------------------------------------------------------------------------- auxiliary losses (reference lib/train/losses.py:235-399)
+HPSS_KERNEL_SIZES = (3, 7, 13, 19, 29)
+
+
+def _mag3(t, name):
+    t = _dev(t)
+    if t.dim() != 3:
+        raise ValueError(f"{name}: a [B, n_mels, T] tensor expected, got {tuple(t.shape)}")
+    return t
+
+
+def _hpss_check(F, T):
+    if F <= 14 or T <= 14:
+        raise ValueError(f"compute_harmonics: both spectrogram axes must be longer than 14 (the largest median window is 29): got {F} x {T}")
+
+
+def hpss_parts(mag, medians=False):
+    """mag [B, n_mels, T] float32 device tensor -> (harmonic, percussive) [B, n_mels, 5 T] before the min-max scaling: |mag| times its soft masks for the
+    kernel sizes 3 | 7 | 13 | 19 | 29 side by side (rvc_hpss, one launch).  medians: the median along time and the median along mel instead."""
+    B, F, T = mag.shape
+    _hpss_check(F, T)
+    h = torch.empty(B, F, 5 * T, dtype=torch.float32, device=mag.device)
+    p = torch.empty_like(h)
+    with torch.cuda.device(mag.device):
+        _lib.check(_lib.lib.rvc_hpss(_lib.current_stream(), _lib.ptr(mag), B, F, T, _lib.ptr(h), _lib.ptr(p), int(bool(medians))))
+    return h, p
+
+
+def compute_harmonics(mag, kernel_sizes=HPSS_KERNEL_SIZES, eps=1e-8):
+    """mag [B, n_mels, T] -> (harmonic, percussive), each [B, n_mels, 5 T]: librosa.decompose.hpss(|mag|, kernel_size=k) for k = 3, 7, 13, 19, 29 side by
+    side along the last axis (rvc_hpss, one launch), then each tensor min-max scaled by its own global extremes and nan_to_num(eps)."""
+    if tuple(kernel_sizes) != HPSS_KERNEL_SIZES:
+        raise NotImplementedError(f"compute_harmonics: the kernel sizes are fixed to {HPSS_KERNEL_SIZES}")
+    h, p = hpss_parts(_mag3(mag, "compute_harmonics"))
+    out = []
+    for t in (h, p):
+        mn, mx = t.min(), t.max()
+        out.append(((t - mn) / (mx - mn + eps)).nan_to_num(eps))
+    return out[0], out[1]
+
+
+def harmonic_loss(org_mag, gen_mag, eps=1e-8):
+    """L1(gen harmonic, org harmonic) + L1(gen percussive, org percussive) of compute_harmonics' tensors without forming them (rvc_hpss_l1: one min / max
+    reduction, one scaled-L1 reduction in float64); 0-dim float32."""
+    org_mag, gen_mag = _mag3(org_mag, "harmonic_loss"), _mag3(gen_mag, "harmonic_loss")
+    if org_mag.shape != gen_mag.shape:
+        raise ValueError(f"harmonic_loss: shapes differ: {tuple(org_mag.shape)} and {tuple(gen_mag.shape)}")
+    B, F, T = org_mag.shape
+    _hpss_check(F, T)
+    sums = torch.zeros(2, dtype=torch.float64, device=org_mag.device)
+    with torch.cuda.device(org_mag.device):
+        _lib.check(_lib.lib.rvc_hpss_l1(_lib.current_stream(), _lib.ptr(org_mag), _lib.ptr(gen_mag), B, F, T, float(eps), _lib.ptr(sums)))
+    means = (sums / float(B * F * 5 * T)).to(torch.float32)
+    return means[0] + means[1]
+
+
+def compute_envelope(log_magnitude, dim=-1, kernel_size=3, eps=1e-8):
+    """[B, n_mels, T] -> the envelope summed along dim: L2-normalise along dim, max over three neighbours along the LAST axis (whatever dim is, as the
+    reference's max_pool1d), nan_to_num(eps), sum along dim.  Host-side plumbing of the public name only: compute_tsi_loss runs rvc_tsi_terms."""
+    if kernel_size != 3:
+        raise NotImplementedError("compute_envelope: kernel_size is fixed to 3")
+    x = _mag3(log_magnitude, "compute_envelope")
+    x = torch.nn.functional.normalize(x, dim=dim, eps=eps)
+    return torch.nn.functional.max_pool1d(x, kernel_size=3, stride=1, padding=1).nan_to_num(eps).sum(dim)
+
+
+def _tsi_terms(org, gen, eps):
+    org, gen = _mag3(org, "compute_tsi_loss"), _mag3(gen, "compute_tsi_loss")
+    if org.shape != gen.shape:
+        raise ValueError(f"compute_tsi_loss: shapes differ: {tuple(org.shape)} and {tuple(gen.shape)}")
+    B, F, T = org.shape
+    out = torch.zeros(2, B, dtype=torch.float64, device=org.device)
+    with torch.cuda.device(org.device):
+        _lib.check(_lib.lib.rvc_tsi_terms(_lib.current_stream(), _lib.ptr(org), _lib.ptr(gen), B, F, T, float(eps), _lib.ptr(out)))
+    return out.to(torch.float32).mean(dim=1)
+
+
+def compute_tsi_loss(original_log_magnitude, generated_log_magnitude, dim=-1, eps=1e-8):
+    """mean over the batch of 1 - Pearson correlation of the two envelopes (rvc_tsi_terms, one launch); 0-dim float32."""
+    if dim not in (-1, -2, 1, 2):
+        raise ValueError(f"compute_tsi_loss: dim must be -1 or -2: {dim}")
+    return _tsi_terms(original_log_magnitude, generated_log_magnitude, eps)[0 if dim in (-1, 2) else 1]
+
+
+def combined_aux_loss(original_audio, generated_audio, c_tefs=1., c_hd=1., c_tsi=1., n_mels=128, sample_rate=40000, n_fft=1024, hop_length=320,
+                      win_length=1024, fmin=0, fmax=None, eps=None):
+    """(harmonic_loss, tefs_loss, tsi_loss) of [B, 1, T] device waves as the trainer forms them; a term whose coefficient is 0 is the Python 0.  Both waves go
+    through ONE STFT and ONE mel projection.  The temporal envelope / fine structure term is not implemented: c_tefs > 0 raises."""
+    if c_tefs > 0:
+        raise NotImplementedError("tefs_loss (compute_tefs, the temporal envelope / fine structure term) is not implemented: pass c_tefs=0")
+    if eps is None:
+        eps = torch.finfo(original_audio.dtype).eps
+    harmonic, tsi = 0, 0
+    if c_hd + c_tsi > 0:
+        if not original_audio.is_cuda or not generated_audio.is_cuda:
+            raise ValueError("the losses run on the device: pass CUDA tensors (there is no CPU path)")
+        if original_audio.shape != generated_audio.shape or original_audio.dim() != 3:
+            raise ValueError("combined_aux_loss: [B, C, T] tensors of one shape expected")
+        both = torch.cat([_dev(original_audio), _dev(generated_audio)], dim=0)
+        mag = MP.mel_spectrogram_torch(both, n_fft, n_mels, sample_rate, hop_length, win_length, fmin, fmax)
+        R = mag.shape[0] // 2
+        org_mag, gen_mag = mag[:R].contiguous(), mag[R:].contiguous()
+        if c_hd > 0:
+            harmonic = harmonic_loss(org_mag, gen_mag, eps=eps)
+        if c_tsi > 0:
+            terms = _tsi_terms(org_mag, gen_mag, eps)
+            tsi = terms[0] + terms[1]
+    return harmonic, 0, tsi

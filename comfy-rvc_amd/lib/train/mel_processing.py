@@ -3,8 +3,10 @@
 `spectrogram_torch`, `spec_to_mel_torch` and `mel_spectrogram_torch` keep the reference's signatures; device tensors go in and come out.  The STFT is
 the LDS FFT of csrc/spectrogram.hip (rvc_spectrogram_batch), the projection its banded filterbank kernel (rvc_spec_to_mel_batch); this module is host
 plumbing only.  `spectrogram_batch` is the ragged entry the spectrogram cache uses: any number of clips of any lengths, one launch.
+`spectrogram_torch` and `mel_spectrogram_torch` send n_fft 1024 / 2048 with hop <= n_fft through rvc_spectrogram_batch and every other geometry (n_fft
+256 .. 4096, also hop > n_fft, where the reference's negative padding crops) through rvc_spectrogram_batch_ms.
 
-Differences from the reference: `center=True` raises (the reference never passes it); only n_fft 1024 / 2048 with win_size == n_fft; spectrogram_torch
+Differences from the reference: `center=True` raises (the reference never passes it); n_fft 256 .. 4096 with win_size == n_fft; spectrogram_torch
 does not print the reference's out-of-range warnings (they would cost a device round trip; the clamp to +-1.05 itself is applied); `mel_filterbank`
 restates librosa.filters.mel and is PARITY-UNPINNED (see its docstring).
 """
@@ -113,6 +115,17 @@ def spectrogram_packed(audio, table, n_fft, hop_size, eps, clamp, out):
     return out
 
 
+def spectrogram_packed_ms(audio, table, n_fft, hop_size, eps, clamp, out):
+    """spectrogram_packed through rvc_spectrogram_batch_ms: n_fft 256, 512, 1024, 2048 or 4096 and any hop with n_fft - hop even, also hop > n_fft."""
+    table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 3)
+    assert audio.is_cuda and out.is_cuda and audio.dtype == torch.float32 and out.dtype == torch.float32 and audio.is_contiguous() and out.is_contiguous()
+    assert out.dim() == 2 and out.shape[0] == n_fft // 2 + 1
+    with torch.cuda.device(audio.device):
+        _lib.check(_lib.lib.rvc_spectrogram_batch_ms(_lib.get_ctx(_dev_index(audio)), _lib.current_stream(), _lib.ptr(audio), audio.numel(), _lib.ptr(table),
+                                                     table.shape[0], int(n_fft), int(hop_size), float(eps), int(bool(clamp)), _lib.ptr(out), out.shape[1]))
+    return out
+
+
 def _check_geometry(n_fft, win_size, center):
     if center:
         raise NotImplementedError("center=True is not implemented (the reference never passes it)")
@@ -143,18 +156,31 @@ def spectrogram_batch(clips, n_fft, hop_size, win_size, center=False, eps=1e-8, 
     return out, cols
 
 
+def min_samples(n_fft, hop_size):
+    """The shortest signal the reference accepts: one more than the reflect padding, or - hop > n_fft, where it crops instead - one hop."""
+    return (n_fft - hop_size) // 2 + 1 if hop_size <= n_fft else hop_size
+
+
+def rows_spectrogram_packed(y, n_fft, hop_size, eps, clamp, align=True):
+    """y [R, T] on the device -> (packed [n_fft / 2 + 1, R * nfa], frames nf, columns per row nfa): row r fills columns [r nfa, r nfa + nf).  (1024 | 2048,
+    hop <= n_fft) run through rvc_spectrogram_batch, everything else through rvc_spectrogram_batch_ms.  One launch."""
+    R, T = y.shape
+    if T < min_samples(n_fft, hop_size):
+        raise ValueError(f"{T} samples: n_fft {n_fft} at hop {hop_size} needs at least {min_samples(n_fft, hop_size)}")
+    nf = frames_of(T, hop_size)
+    nfa = -(-nf // FRAME_ALIGN) * FRAME_ALIGN if align else nf
+    table = np.array([(r * T, T, r * nfa) for r in range(R)], dtype=np.int64).reshape(-1, 3)
+    x = y.detach().float().contiguous().reshape(-1)
+    out = torch.empty(n_fft // 2 + 1, max(R * nfa, 1), device=y.device, dtype=torch.float32)
+    first = n_fft in (1024, 2048) and hop_size <= n_fft
+    (spectrogram_packed if first else spectrogram_packed_ms)(x, table, n_fft, hop_size, eps, clamp, out)
+    return out, nf, nfa
+
+
 def _rows_spectrogram(y, n_fft, hop_size, eps, clamp):
     """y [B, T] on the device -> [B, n_fft / 2 + 1, T // hop] (contiguous)."""
-    B, T = y.shape
-    pad = (n_fft - hop_size) // 2
-    if T <= pad:
-        raise ValueError(f"{T} samples: the reflect padding of ({n_fft} - {hop_size}) / 2 needs more than {pad}")
-    nf = frames_of(T, hop_size)
-    nfa = nf if B == 1 else -(-nf // FRAME_ALIGN) * FRAME_ALIGN
-    table = np.array([(b * T, T, b * nfa) for b in range(B)], dtype=np.int64).reshape(-1, 3)
-    x = y.detach().float().contiguous().reshape(-1)
-    out = torch.empty(n_fft // 2 + 1, max(B * nfa, 1), device=y.device, dtype=torch.float32)
-    spectrogram_packed(x, table, n_fft, hop_size, eps, clamp, out)
+    B = y.shape[0]
+    out, nf, nfa = rows_spectrogram_packed(y, n_fft, hop_size, eps, clamp, align=B != 1)
     if B == 1:
         return out[:, :nf].reshape(1, n_fft // 2 + 1, nf)
     return out.view(n_fft // 2 + 1, B, nfa)[:, :, :nf].permute(1, 0, 2).contiguous()
@@ -170,6 +196,11 @@ def spectrogram_torch(y, n_fft, hop_size, win_size, center=False):
 
 
 _bank_on_device = {}      # (device index, n_fft, n_mels) -> (sr, fmin, fmax) of the bank the context holds
+
+
+def ensure_bank(dev_index, n_fft, n_mels, sr, fmin, fmax):
+    """The context's filterbank of (n_fft, n_mels) is the one of (sr, fmin, fmax): uploaded only when it is not."""
+    _ensure_bank(dev_index, n_fft, n_mels, sr, fmin, fmax)
 
 
 def _ensure_bank(dev_index, n_fft, n_mels, sr, fmin, fmax):

@@ -430,6 +430,35 @@ int rvc_mel_filterbank_set(rvc_ctx* ctx, int n_fft, int n_mels, const int32_t* f
  * frames); spec_dev [n_fft / 2 + 1][spec_pitch], mel_dev [n_mels][mel_pitch], same columns in both.  One launch. */
 int rvc_spec_to_mel_batch(rvc_ctx* ctx, void* stream, const float* spec_dev, int64_t spec_pitch, const int64_t* clips_host, int n_clips, int n_fft,
                           int n_mels, float* mel_dev, int64_t mel_pitch);
+/* rvc_spectrogram_batch at the geometries of the multi-scale mel loss (lib/train/losses.py:430-561: windows 256 .. 4096 at hop = rate / 100): same
+ * clip table, same output layout, same window, eps, clamp switch and magnitude.  n_fft 256, 512, 1024, 2048 or 4096; any hop > 0 with n_fft - hop even.
+ * hop <= n_fft: as above (N > (n_fft - hop) / 2).  hop > n_fft: the reference's negative padding crops, so frame f starts at sample
+ * f hop + (hop - n_fft) / 2, nothing is reflected and N >= hop (one frame) suffices.  N / hop frames per clip in every case.  One launch: a workgroup
+ * owns 16 frames (8 at n_fft 4096, where 16 would not fit the LDS); at 256 and 512 a wave transforms four frames. */
+int rvc_spectrogram_batch_ms(rvc_ctx* ctx, void* stream, const float* audio_dev, int64_t n_audio, const int64_t* clips_host, int n_clips, int n_fft, int hop,
+                             float eps, int clamp, float* out_dev, int64_t pitch);
+/* The K <= 8 per-scale terms of MultiScaleMelSpectrogramLoss.forward(x, y).  spec_dev[k] (HOST array of device pointers) is the magnitude spectrogram
+ * [n_fft[k] / 2 + 1][pitch[k]] of the 2 B signals x_0 .. x_{B-1}, y_0 .. y_{B-1}: signal r fills columns [r row_stride[k], r row_stride[k] + nf).  Per
+ * scale ONE launch projects both through the filterbank set for (n_fft[k], n_mels[k]) (log(max(., 1e-5)) as rvc_spec_to_mel_batch), forms the pointwise
+ * loss (0 l1, 1 l2, 2 smoothl1 with beta 1) in fp32 and sums it in float64 in a fixed order; the log-mels are never stored.  out_dev [K][2] float64 =
+ * (sum over the B n_mels nf elements of loss(log-mel x, log-mel y), the same of loss(exp(log-mel x), exp(log-mel y)) - zero unless want_mag).  K + 1 launches. */
+int rvc_multiscale_mel_loss(rvc_ctx* ctx, void* stream, int K, const float* const* spec_dev, const int64_t* pitch, const int64_t* row_stride, int B, int64_t nf,
+                            const int32_t* n_fft, const int32_t* n_mels, int loss, int want_mag, double* out_dev);
+
+/* ------------------------------------------------------------------ auxiliary losses (reference lib/train/losses.py:235-277,:324-390) */
+/* compute_harmonics before its min-max scaling: x_dev [B][F][T] (F, T > 14); with S = |x|, for the kernel sizes k = 3, 7, 13, 19, 29 the median of S
+ * along T (harmonic) and along F (percussive) over k values, scipy.ndimage "reflect" boundaries, soft masks of power 2 and margin 1 (0.5 where both
+ * medians vanish), S * mask; h_dev, p_dev [B][F][5 T] hold the five results side by side.  The medians are exact (one of the inputs); medians != 0
+ * stores them (along T in h_dev, along F in p_dev) instead of the masked parts.  One launch. */
+int rvc_hpss(void* stream, const float* x_dev, int B, int F, int T, float* h_dev, float* p_dev, int medians);
+/* The harmonic loss of combined_aux_loss without its 5 T tensors: each of the four tensors (harmonic, percussive of org_dev and of gen_dev, [B][F][T]
+ * each) is scaled by its own global min / max, (v - min) / (max - min + eps) with NaN -> eps, and sums_dev [2] float64 = (sum |gen_h - org_h|,
+ * sum |gen_p - org_p|) over the B F 5 T values (fixed order).  4 launches. */
+int rvc_hpss_l1(void* stream, const float* org_dev, const float* gen_dev, int B, int F, int T, float eps, double* sums_dev);
+/* compute_tsi_loss before its mean: out_dev [2][B] float64 = 1 - Pearson correlation of the envelopes of org_dev and gen_dev [B][F][T] per item, row 0 for
+ * dim = -1 (L2-normalise along T, max over t - 1 .. t + 1, NaN -> eps, sum along T; correlate along F), row 1 for dim = -2 (normalise and sum along
+ * F; the max still runs along T, as in the reference; correlate along T).  2 max(F, T) + 2 T floats must fit 48 KB.  One launch. */
+int rvc_tsi_terms(void* stream, const float* org_dev, const float* gen_dev, int B, int F, int T, float eps, double* out_dev);
 
 /* ------------------------------------------------------------------ single ops (parity tests / kernel benchmarks) */
 /* Conv1d: x_dev [Ci][Tin], w_host [Co][Ci/groups][k], y_dev [Co][Tout]; act codes: 0 none 1 lrelu 2 relu 3 gelu 4 tanh 5 sigmoid */
