@@ -127,6 +127,10 @@ SIGNATURES = {
     "rvc_disc_launch_count": (c_int, [c_void_p, c_int, c_int64]),
     "rvc_sqerr_sums": (c_int, [c_void_p, P(c_void_p), P(c_int64), P(c_float), c_int, c_void_p]),
     "rvc_l1_sums": (c_int, [c_void_p, P(c_void_p), P(c_void_p), P(c_int64), c_int, c_void_p]),
+    "rvc_disc_input_grad": (c_int, [c_void_p, c_void_p, c_int, c_int64, P(c_void_p), P(c_void_p), P(c_void_p), c_void_p]),
+    "rvc_disc_input_grad_launch_count": (c_int, [c_void_p, c_int, c_int64]),
+    "rvc_loss_cotangents": (c_int, [c_void_p, c_int, P(c_void_p), P(c_void_p), P(c_int64), P(c_float), c_int, P(c_void_p)]),
+    "rvc_interpolate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "rvc_synth_dec_halo": (c_int, [c_void_p]),
     "rvc_synth_window_frames": (c_int, [c_void_p, c_int64, c_int64, c_int64, P(c_int64), P(c_int64)]),
     "rvc_synth_infer_window_halo": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,

@@ -8,6 +8,8 @@
 //   DiscriminatorS:    Conv1d(1, 16, 15) in disc_first_kernel (p = 1, nothing to pad); the four grouped k = 41 stride-4 layers (4 input channels per
 //                      group) in disc_group_kernel; Conv1d(1024, 1024, 5) on the GEMM with p = 1; Conv1d(1024, 1, 3) in disc_post_kernel.        7 launches
 // The forward is PLANNED (disc_plan: pure, no stream) and the plan is launched; disc_launch_count is the size of that plan.
+// The input-gradient pass (disc_input_grad: the vector-Jacobian product from cotangents on the taps to the signals) walks the same layers backwards on
+// the feature maps the forward wrote - one launch per layer again, planned the same way; see "input gradient" below.
 #include "model_common.h"
 #include "models.h"
 #include "signal_dev.h"
@@ -115,6 +117,8 @@ struct DiscLayer {
   int Ci = 0, Co = 0, k = 0, stride = 1, pad = 0, groups = 1, CoPx = 0;
   DevVec w, b;                       // folded fp32 weights [Co][Ci / groups][k] (the VALU layers) and bias
   DevBuf<uint16_t> wx;               // bf16x3 image (the GEMM layers)
+  DevBuf<uint16_t> wxb[3];           // the GEMM layers' data gradient: one transposed image per phase of the input row (stride of them), rows Ci padded to CiPx
+  int CiPx = 0;
 };
 struct DiscNet { int period = 0; std::vector<DiscLayer> L; };   // period 0: DiscriminatorS; L.back() is conv_post
 struct DiscWeights { std::vector<DiscNet> nets; };
@@ -139,6 +143,28 @@ static std::vector<int> disc_periods(int version) {
   return p;
 }
 static bool disc_layer_is_gemm(const DiscLayer& l) { return l.groups == 1 && l.Ci % 16 == 0 && l.Co > 1; }
+
+// The transposed, phase-grouped images of a dense layer's data gradient (conv_x3d_bwd.hip).  Input row h = stride h' + j - pad: stride 1 is one product,
+// tap t (row h + t - pad of the gradient) carrying W[.][.][k - 1 - t]; stride 3 (k 5, pad 2) is one product per phase r = h mod 3, tap 0 (row j) carrying
+// W[.][.][r + 2] and - r > 0 - tap 1 (row j + 1) carrying W[.][.][r - 1].
+static void disc_bwd_images(DiscLayer& L, const std::vector<float>& w) {
+  RVC_REQUIRE(L.k == 5 && L.pad == 2 && (L.stride == 1 || L.stride == 3), "dense discriminator layer: k 5, pad 2, stride 1 or 3");
+  L.CiPx = (L.Ci + 127) & ~127;
+  for (int r = 0; r < L.stride; ++r) {
+    std::vector<int> taps;
+    if (L.stride == 1) taps = {4, 3, 2, 1, 0};
+    else if (r == 0) taps = {2};
+    else taps = {r + 2, r - 1};
+    const int nt = (int)taps.size();
+    std::vector<float> wt((size_t)L.Ci * L.Co * nt);
+    for (int co = 0; co < L.Co; ++co)
+      for (int ci = 0; ci < L.Ci; ++ci)
+        for (int t = 0; t < nt; ++t) wt[((size_t)ci * L.Co + co) * nt + t] = w[((size_t)co * L.Ci + ci) * L.k + taps[t]];
+    std::vector<uint16_t> img;
+    x3_weight_image(wt.data(), L.Ci, L.Co, nt, L.CiPx, img);
+    L.wxb[r].upload(img);
+  }
+}
 
 void disc_finalize(Disc* D) {
   D->ready = false; static_cast<DiscWeights&>(*D) = {};   // a finalize that throws leaves the handle not ready
@@ -175,6 +201,7 @@ void disc_finalize(Disc* D) {
         std::vector<uint16_t> img;
         x3_weight_image(w.data(), c.Co, c.Ci, c.k, L.CoPx, img);
         L.wx.upload(img);
+        disc_bwd_images(L, w);
       } else {
         L.w.upload(w);
       }
@@ -338,6 +365,215 @@ void l1_sums(hipStream_t s, const float* const* a, const float* const* b, const 
   L1Segs g{};
   for (int k = 0; k < K; ++k) { RVC_REQUIRE(a[k] && b[k] && n[k] > 0, "l1_sums: empty segment"); g.a[k] = a[k]; g.b[k] = b[k]; g.n[k] = n[k]; }
   seg_sums(s, g, K, out);
+}
+
+// ---------------------------------------------------------------------------------------------- input gradient
+// tap[l] = a_{l+1} = lrelu(z_l), the last tap the score z_last.  With cotangents c_l on the taps (null: zero) and delta_l = dL / dz_l:
+//   delta_last = c_last;   delta_l = (convT_{l+1}(delta_{l+1}) + c_l) * (tap[l] > 0 ? 1 : slope);   dA_0 = convT_0(delta_0), folded back onto the signal.
+// The mask comes from the saved post-activation (a > 0 <=> z > 0; torch's leaky_relu backward takes the slope at exactly 0), so given the forward's own
+// feature maps the pass is linear: the exact VJP of what the forward computed.  Every kernel is a gather (no atomics): two calls give the same bits.
+
+// conv_post transposed, fused with the mask of the layer below: Y[s][c][h][w] = (sum_j W[c][j] ds[s][h + 1 - j][w] + Cot) * mask(A).  One thread per element.
+struct DiscPostBwdArgs { const float* dS; const float* W; const float* Cot; const float* A; float* Y; int Ci, H, p; float slope; };
+__global__ __launch_bounds__(256) void disc_post_bwd_kernel(const DiscPostBwdArgs a) {
+  const long long N = (long long)a.H * a.p, i = (long long)blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+  if (i >= a.Ci * N) return;
+  const int c = (int)(i / N), n = (int)(i - c * N), h = n / a.p;
+  float v = 0.f;
+  if (a.dS) {
+    const float* dS = a.dS + s * N + n;
+    const float* W = a.W + c * 3;
+    if (h + 1 < a.H) v = fmaf(W[0], dS[a.p], v);
+    v = fmaf(W[1], dS[0], v);
+    if (h > 0) v = fmaf(W[2], dS[-a.p], v);
+  }
+  const long long idx = s * a.Ci * N + i;
+  if (a.Cot) v += a.Cot[idx];
+  a.Y[idx] = a.A[idx] > 0.f ? v : v * a.slope;
+}
+
+// DiscriminatorS's grouped layers transposed: input sample u of channel g 4 + ci gathers, from the opg output channels of its group, the taps
+// j = (u & 3) + 4 m <= 40 at output t = (u >> 2) + 5 - m (4 t + j - 20 = u): 10 or 11 taps.  One thread per input element.
+struct DiscGroupBwdArgs { const float* D; const float* W; const float* Cot; const float* A; float* Y; int Ci, Co, opg, Tin, Tout; float slope; };
+__global__ __launch_bounds__(256) void disc_group_bwd_kernel(const DiscGroupBwdArgs a) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+  if (i >= (long long)a.Ci * a.Tin) return;
+  const int cin = (int)(i / a.Tin), u = (int)(i - (long long)cin * a.Tin), g = cin / kGrpCin, ci = cin - g * kGrpCin;
+  const float* D = a.D + (s * a.Co + (long long)g * a.opg) * a.Tout;
+  const float* W = a.W + ((long long)g * a.opg * kGrpCin + ci) * kGrpK;
+  float v = 0.f;
+  for (int m = 0; (u & 3) + 4 * m < kGrpK; ++m) {
+    const int j = (u & 3) + 4 * m, t = (u >> 2) + kGrpPad / kGrpStride - m;
+    if (t < 0 || t >= a.Tout) continue;
+    for (int o = 0; o < a.opg; ++o) v = fmaf(W[(long long)o * kGrpCin * kGrpK + j], D[(long long)o * a.Tout + t], v);
+  }
+  const long long idx = s * a.Ci * a.Tin + i;
+  if (a.Cot) v += a.Cot[idx];
+  a.Y[idx] = a.A[idx] > 0.f ? v : v * a.slope;
+}
+
+// First layer transposed, fused with the un-fold and the reflect fold-back.  One thread per signal sample t: it gathers dA_0 at its own position t and, where
+// 2 (T - 1) - t lies in the reflect pad [T, H p), at that mirror position too (disc_first_kernel reads sig[2 (T - 1) - q] for q >= T).  dA_0[h][w] =
+// sum_c sum_j W[c][j] D[c][h'][w] over stride h' + j - pad = h.  add: the sub-discriminators add into dsig one after the other on the stream, in index order.
+struct DiscFirstBwdArgs { const float* D; const float* W; float* dsig; int T, H, Hout, p, Co, stride, pad, add; };
+template <int K>
+__global__ __launch_bounds__(256) void disc_first_bwd_kernel(const DiscFirstBwdArgs a) {
+  __shared__ float ws[32 * K];
+  for (int i = threadIdx.x; i < a.Co * K; i += 256) ws[i] = a.W[i];
+  __syncthreads();
+  const int t = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+  if (t >= a.T) return;
+  const long long N = (long long)a.Hout * a.p;
+  const float* D = a.D + (long long)s * a.Co * N;
+  float v = 0.f;
+  for (int side = 0; side < 2; ++side) {
+    const long long q = side ? 2LL * (a.T - 1) - t : t;
+    if (side && (q < a.T || q >= (long long)a.H * a.p)) break;
+    const int h = (int)(q / a.p), w = (int)(q - (long long)h * a.p);
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const int hh = h + a.pad - j;
+      if (hh < 0 || hh % a.stride != 0 || hh / a.stride >= a.Hout) continue;
+      const float* d = D + (long long)(hh / a.stride) * a.p + w;
+      for (int c = 0; c < a.Co; ++c) v = fmaf(ws[c * K + j], d[(long long)c * N], v);
+    }
+  }
+  float* o = a.dsig + (long long)s * a.T + t;
+  *o = a.add ? *o + v : v;
+}
+
+struct DiscBwdLaunch {
+  int kind = 0;                       // 0: first layer, 1: grouped, 2: GEMM, 3: conv_post
+  dim3 grid;
+  int K = 0;                          // kind 0: taps
+  DiscFirstBwdArgs f; DiscGroupBwdArgs g; ConvX3dBwdPlan x; DiscPostBwdArgs q;
+};
+// pure: no stream, no launch, no allocation.  fmaps / dtaps / work (all may be null: counting only): one pointer per tap, discriminator-major; launch `l` of
+// a sub-discriminator is layer l transposed: it reads delta_l (work[l]; the given cotangent of the score for the last layer) and writes delta_{l-1} (work[l-1]).
+static void disc_bwd_plan(const Disc* D, int S, long long T, const float* const* fmaps, const float* const* dtaps, float* const* work, float* dsignals,
+                          std::vector<DiscBwdLaunch>& plan) {
+  RVC_REQUIRE(D->ready, "finalize first");
+  RVC_REQUIRE(S >= 1 && S <= 65535, "1 <= S <= 65535 signals");
+  disc_check_T(D, T);
+  plan.clear();
+  const bool real = fmaps != nullptr;
+  int tap0 = 0;
+  for (size_t i = 0; i < D->nets.size(); ++i) {
+    const DiscNet& net = D->nets[i];
+    const int per = net.period ? net.period : 1, nl = (int)net.L.size();
+    std::vector<int> Hs(nl + 1);
+    Hs[0] = (int)((T + per - 1) / per);
+    for (int l = 0; l < nl; ++l) { Hs[l + 1] = conv_out(Hs[l], net.L[l].k, net.L[l].stride, net.L[l].pad); RVC_REQUIRE(Hs[l + 1] >= 1, "signal too short"); }
+    if (real) for (int l = 0; l < nl; ++l) RVC_REQUIRE(fmaps[tap0 + l] && work[tap0 + l], "null feature-map or work pointer");
+    for (int l = nl - 1; l >= 0; --l) {
+      const DiscLayer& L = net.L[l];
+      const int H = Hs[l], Ho = Hs[l + 1];
+      const float* delta = real ? (l + 1 == nl ? dtaps[tap0 + l] : work[tap0 + l]) : nullptr;     // conv_post reads the score's cotangent where it was given
+      const float* cot = real && l > 0 ? dtaps[tap0 + l - 1] : nullptr;
+      const float* act = real && l > 0 ? fmaps[tap0 + l - 1] : nullptr;
+      float* y = real && l > 0 ? work[tap0 + l - 1] : nullptr;
+      DiscBwdLaunch d;
+      if (l == 0) {
+        d.kind = 0; d.K = L.k;
+        d.f = DiscFirstBwdArgs{delta, L.w.p, dsignals, (int)T, H, Ho, per, L.Co, L.stride, L.pad, i > 0 ? 1 : 0};
+        d.grid = dim3((unsigned)((T + 255) / 256), (unsigned)S);
+      } else if (l + 1 == nl) {
+        d.kind = 3;
+        d.q = DiscPostBwdArgs{delta, L.w.p, cot, act, y, L.Ci, H, per, kDiscSlope};
+        d.grid = dim3((unsigned)(((long long)L.Ci * H * per + 255) / 256), (unsigned)S);
+      } else if (disc_layer_is_gemm(L)) {
+        d.kind = 2;
+        ConvX3dBwdArgs a{};
+        a.D = delta; a.Cot = cot; a.A = act; a.Y = y;
+        for (int r = 0; r < L.stride; ++r) { a.Wx[r] = reinterpret_cast<const unsigned char*>(L.wxb[r].p); a.nt[r] = L.stride == 1 ? L.k : (r == 0 ? 1 : 2); }
+        a.R = L.Ci; a.RPx = L.CiPx; a.Ck = L.Co; a.Hd = Ho; a.H = H; a.p = per; a.ostride = L.stride; a.off0 = L.stride == 1 ? -L.pad : 0; a.nph = L.stride;
+        a.S = S; a.slope = kDiscSlope;
+        RVC_REQUIRE(conv_x3d_bwd_plan(a, d.x), "discriminator layer does not fit the data-gradient kernel");
+      } else {
+        RVC_REQUIRE(L.k == kGrpK && L.stride == kGrpStride && L.pad == kGrpPad && L.Ci / L.groups == kGrpCin && per == 1, "grouped layer geometry");
+        d.kind = 1;
+        d.g = DiscGroupBwdArgs{delta, L.w.p, cot, act, y, L.Ci, L.Co, L.Co / L.groups, H, Ho, kDiscSlope};
+        d.grid = dim3((unsigned)(((long long)L.Ci * H + 255) / 256), (unsigned)S);
+      }
+      plan.push_back(d);
+    }
+    tap0 += nl;
+  }
+}
+int disc_input_grad_launch_count(const Disc* D, int S, long long T) {
+  std::vector<DiscBwdLaunch> plan;
+  disc_bwd_plan(D, S, T, nullptr, nullptr, nullptr, nullptr, plan);
+  return (int)plan.size();
+}
+void disc_input_grad(Disc* D, hipStream_t s, int S, long long T, const float* const* fmaps, const float* const* dtaps, float* const* work, float* dsignals) {
+  RVC_REQUIRE(fmaps && dtaps && work && dsignals, "null argument");
+  std::vector<DiscBwdLaunch> plan;
+  disc_bwd_plan(D, S, T, fmaps, dtaps, work, dsignals, plan);
+  int tap0 = 0;                       // delta of the last tap is its cotangent: work receives a copy (zeros where none was given)
+  for (size_t i = 0; i < D->nets.size(); ++i) {
+    const int last = tap0 + (int)D->nets[i].L.size() - 1;
+    int C, H, p; disc_tap_shape(D, (int)i, (int)D->nets[i].L.size() - 1, T, &C, &H, &p);
+    const size_t bytes = (size_t)S * C * H * p * sizeof(float);
+    if (!dtaps[last]) RVC_HIP_CHECK(hipMemsetAsync(work[last], 0, bytes, s));
+    else if (dtaps[last] != work[last]) RVC_HIP_CHECK(hipMemcpyAsync(work[last], dtaps[last], bytes, hipMemcpyDeviceToDevice, s));
+    tap0 = last + 1;
+  }
+  for (const DiscBwdLaunch& d : plan) {
+    switch (d.kind) {
+      case 0:
+        if (d.K == 5) hipLaunchKernelGGL(disc_first_bwd_kernel<5>, d.grid, dim3(256), 0, s, d.f);
+        else if (d.K == 15) hipLaunchKernelGGL(disc_first_bwd_kernel<15>, d.grid, dim3(256), 0, s, d.f);
+        else throw Error("first layer: 5 or 15 taps");
+        break;
+      case 1: hipLaunchKernelGGL(disc_group_bwd_kernel, d.grid, dim3(256), 0, s, d.g); break;
+      case 2: conv_x3d_bwd_launch(d.x, s); break;
+      default: hipLaunchKernelGGL(disc_post_bwd_kernel, d.grid, dim3(256), 0, s, d.q); break;
+    }
+  }
+}
+
+// The element-wise ends of the pass.  Cotangents of the trainer's losses, K tensors in one launch:
+//   kind 0: out = scale a              (d mean(s^2) / ds = 2 s / N: discriminator_loss on generated scores)
+//   kind 1: out = -scale (1 - a)       (d mean((1 - s)^2) / ds: generator_loss; discriminator_loss on real scores)
+//   kind 2: out = scale sign(a - b)    (d mean |r - g| / dg with a = g, b = r: feature_loss; sign(0) = 0)
+struct CotSegs { const float* a[kSegMax]; const float* b[kSegMax]; float* out[kSegMax]; long long n[kSegMax]; float scale[kSegMax]; };
+__global__ __launch_bounds__(256) void cotangent_kernel(const CotSegs g, int kind) {
+  const int k = blockIdx.y;
+  const long long n = g.n[k];
+  const float sc = g.scale[k];
+  for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < n; j += (long long)gridDim.x * 256) {
+    const float a = g.a[k][j];
+    float v;
+    if (kind == 0) v = sc * a;
+    else if (kind == 1) v = -sc * (1.f - a);
+    else { const float d = a - g.b[k][j]; v = d > 0.f ? sc : (d < 0.f ? -sc : 0.f); }
+    g.out[k][j] = v;
+  }
+}
+void loss_cotangents(hipStream_t s, int kind, const float* const* a, const float* const* b, const long long* n, const float* scale, int K, float* const* out) {
+  RVC_REQUIRE(a && n && scale && out && K >= 1 && K <= kSegMax && kind >= 0 && kind <= 2 && (kind != 2 || b), "loss_cotangents: 1 <= K <= 64 tensors, kind 0, 1 or 2");
+  CotSegs g{};
+  long long longest = 0;
+  for (int k = 0; k < K; ++k) {
+    RVC_REQUIRE(a[k] && out[k] && n[k] > 0 && (kind != 2 || b[k]), "loss_cotangents: empty tensor");
+    g.a[k] = a[k]; g.b[k] = kind == 2 ? b[k] : nullptr; g.out[k] = out[k]; g.n[k] = n[k]; g.scale[k] = scale[k];
+    longest = std::max(longest, n[k]);
+  }
+  const unsigned blocks = (unsigned)std::min<long long>((longest + 255) / 256, 1024);
+  hipLaunchKernelGGL(cotangent_kernel, dim3(blocks, K), dim3(256), 0, s, g, kind);
+}
+// gradient_norm_loss's interpolation, out[b][t] = alpha[b] y[b][t] + (1 - alpha[b]) y_hat[b][t], with the reference's roundings: 1 - alpha, the two products
+// and the sum are each rounded to float32 (no contraction into an fma)
+__global__ __launch_bounds__(256) void interpolate_kernel(const float* __restrict__ alpha, const float* __restrict__ y, const float* __restrict__ y_hat, long long T,
+                                                          float* __restrict__ out) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+  if (t >= T) return;
+  const float al = alpha[b];
+  out[b * T + t] = __fadd_rn(__fmul_rn(al, y[b * T + t]), __fmul_rn(__fsub_rn(1.f, al), y_hat[b * T + t]));
+}
+void interpolate_rows(hipStream_t s, const float* alpha, const float* y, const float* y_hat, int B, long long T, float* out) {
+  RVC_REQUIRE(alpha && y && y_hat && out && B >= 1 && B <= 65535 && T >= 1, "interpolate_rows: bad argument");
+  hipLaunchKernelGGL(interpolate_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0, s, alpha, y, y_hat, T, out);
 }
 
 }  // namespace rvc

@@ -51,6 +51,13 @@ int disc_num_taps(const Disc* D, int i);
 void disc_tap_shape(const Disc* D, int i, int tap, long long T, int* C, int* H, int* p);
 int disc_launch_count(const Disc* D, int S, long long T);   // size of the plan the forward launches: pure, independent of S
 void disc_forward(Disc* D, hipStream_t s, const float* signals, int S, long long T, float* const* scores, float* const* fmaps);
+// the vector-Jacobian product of that forward with respect to the signals: fmaps as the forward wrote them for these S signals, dtaps one cotangent per tap
+// (an entry may be null: zero), work one buffer per tap in the tap's shape (receives dL / d pre-activation of its layer), dsignals [S][T] fully written
+int disc_input_grad_launch_count(const Disc* D, int S, long long T);   // pure, independent of S and T
+void disc_input_grad(Disc* D, hipStream_t s, int S, long long T, const float* const* fmaps, const float* const* dtaps, float* const* work, float* dsignals);
+// cotangents of the GAN losses, K tensors per launch (kind 0: scale a; 1: -scale (1 - a); 2: scale sign(a - b)), and gradient_norm_loss's interpolation
+void loss_cotangents(hipStream_t s, int kind, const float* const* a, const float* const* b, const long long* n, const float* scale, int K, float* const* out);
+void interpolate_rows(hipStream_t s, const float* alpha, const float* y, const float* y_hat, int B, long long T, float* out);
 // K <= 64 segments per call, out [K] float64, fixed order: sum_j (c[k] - x[k][j])^2 and sum_j |a[k][j] - b[k][j]|; pointer / length / constant arrays on the host
 void sqerr_sums(hipStream_t s, const float* const* x, const long long* n, const float* c, int K, double* out);
 void l1_sums(hipStream_t s, const float* const* a, const float* const* b, const long long* n, int K, double* out);

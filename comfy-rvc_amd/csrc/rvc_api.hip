@@ -360,6 +360,31 @@ int rvc_l1_sums(void* stream, const float* const* a, const float* const* b, cons
   check_launch();
   RVC_CATCH
 }
+int rvc_disc_input_grad_launch_count(rvc_disc* d, int S, int64_t T) {
+  try { RVC_REQUIRE(d, "null argument"); return disc_input_grad_launch_count(d->m, S, T); }
+  catch (const std::exception& e) { rvc::set_error(e.what()); return -1; }
+}
+int rvc_disc_input_grad(rvc_disc* d, void* stream, int S, int64_t T, const float* const* fmaps, const float* const* dtaps, float* const* work, float* dsignals) {
+  RVC_TRY
+  RVC_REQUIRE(d && fmaps && dtaps && work && dsignals, "null argument");
+  disc_input_grad(d->m, (hipStream_t)stream, S, T, fmaps, dtaps, work, dsignals);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_loss_cotangents(void* stream, int kind, const float* const* a, const float* const* b, const int64_t* n, const float* scale, int K, float* const* out) {
+  RVC_TRY
+  RVC_REQUIRE(a && n && scale && out && K >= 1 && K <= 64, "1 <= K <= 64 tensors, no null argument");
+  long long nn[64]; for (int k = 0; k < K; ++k) nn[k] = n[k];
+  loss_cotangents((hipStream_t)stream, kind, a, b, nn, scale, K, out);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_interpolate(void* stream, const float* alpha, const float* y, const float* y_hat, int B, int64_t T, float* out) {
+  RVC_TRY
+  interpolate_rows((hipStream_t)stream, alpha, y, y_hat, B, T, out);
+  check_launch();
+  RVC_CATCH
+}
 int rvc_synth_dec_halo(rvc_synth* s) { return s ? synth_dec_halo_frames(s->m) : 0; }
 int rvc_synth_window_frames(rvc_synth* s, int64_t T, int64_t keep0, int64_t keep1, int64_t* g0, int64_t* g1) {
   RVC_TRY

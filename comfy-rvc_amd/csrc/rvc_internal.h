@@ -232,6 +232,17 @@ struct ConvX3dArgs {
 struct ConvX3dPlan { ConvX3dArgs a; dim3 grid; int units = 1; size_t lds = 0; double flops = 0.0; };   // units: (chunk, tap) units per pipeline stage (1, 2 or 4)
 bool conv_x3d_plan(const ConvX3dArgs& a, ConvX3dPlan& p);   // false: the layer does not fit the kernel (Ci % 16, Co % 128 with CoPx = Co, a bias, k <= 16, 32-bit offsets)
 void conv_x3d_launch(const ConvX3dPlan& p, hipStream_t s);
+// The data gradient of that convolution with the backward chain's epilogue (conv_x3d_bwd.hip):  Y = (convT(D) + Cot) * (A > 0 ? 1 : slope), Y / Cot / A
+// [S][R][H][p] (R = the forward's input channels), D [S][Ck][Hd][p] (Ck = the forward's output channels).  The output rows h = ostride j + ph form
+// nph = ostride phases; phase ph is a stride-1 product of nt[ph] taps, tap t reading row j + off0 + t of D, with its own x3_weight_image Wx[ph]
+// (rows R padded to RPx, channels Ck, nt[ph] taps).  Hj and tile0 are filled by the planner.  One launch for every phase and every signal.
+struct ConvX3dBwdArgs {
+  const float* D; const unsigned char* Wx[3]; const float* Cot; const float* A; float* Y;
+  int R, RPx, Ck, Hd, H, p, ostride, off0, nph, S; int nt[3]; int Hj[3]; int tile0[4]; float slope;
+};
+struct ConvX3dBwdPlan { ConvX3dBwdArgs a; dim3 grid; int units = 1; size_t lds = 0; double flops = 0.0; };
+bool conv_x3d_bwd_plan(const ConvX3dBwdArgs& a, ConvX3dBwdPlan& p);   // false: the layer does not fit the kernel
+void conv_x3d_bwd_launch(const ConvX3dBwdPlan& p, hipStream_t s);
 // one ConvBlockRes of 16 or 32 channels (3 x 3, 3 x 3, + x) in one launch (conv_cbr2.hip): x, out fp32 [C][H W], distinct
 bool cbr2_small_eligible(const ConvLayer& c1, const ConvLayer& c2);
 void cbr2_small_run(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, const float* x, int H, int W, float* out);

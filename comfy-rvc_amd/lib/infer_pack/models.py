@@ -271,10 +271,10 @@ class SynthesizerTrnMs256NSFsid(_SynthesizerNSFsid):
 
 # ------------------------------------------------------------------------------------------------- discriminators
 class _MultiPeriodDiscriminator:
-    """MultiPeriodDiscriminator / MultiPeriodDiscriminatorV2 (reference lib/infer_pack/models.py:1024-1145), forward only: DiscriminatorS plus one
+    """MultiPeriodDiscriminator / MultiPeriodDiscriminatorV2 (reference lib/infer_pack/models.py:1024-1145), forward and input gradient: DiscriminatorS plus one
     DiscriminatorP per period.  `forward(y, y_hat)` / `net_d(y, y_hat)` returns `(y_d_rs, y_d_gs, fmap_rs, fmap_gs)` like the reference: per
     sub-discriminator the score [B, H p] of the real and of the generated batch and the lists of feature maps ([B,C,H,p]; [B,C,T'] for
-    DiscriminatorS).  Both batches run through every layer in one launch (rvc_disc_forward on the 2 B signals); the returned tensors are views of
+    DiscriminatorS).  `input_grad(fmaps, tap_cotangents)` is the one backward pass: the gradient with respect to the input waveform (rvc_disc_input_grad).  Both batches run through every layer in one launch (rvc_disc_forward on the 2 B signals); the returned tensors are views of
     the buffers the layers wrote.  CUDA tensors only: there is no CPU path."""
     VERSION = 1
 
@@ -330,6 +330,31 @@ class _MultiPeriodDiscriminator:
             out.append(rows)
         return out
 
+    def _run(self, sig):
+        """sig [S, T] float32 contiguous on the device -> [[tap buffers [S,C,H,p] ([S,C,T'] for DiscriminatorS)] per sub-discriminator], one rvc_disc_forward"""
+        S_, T, dev = int(sig.shape[0]), int(sig.shape[1]), sig.device
+        shapes = self.tap_shapes(T)
+        bufs = [[torch.empty((S_, c, h, p) if i else (S_, c, h), dtype=torch.float32, device=dev) for (c, h, p) in rows] for i, rows in enumerate(shapes)]
+        flat = [t for rows in bufs for t in rows]
+        ptrs = (C.c_void_p * len(flat))(*[t.data_ptr() for t in flat])
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.rvc_disc_forward(self._h, _lib.current_stream(), _lib.ptr(sig), S_, T, None, ptrs))
+        return bufs
+
+    def forward_single(self, x):
+        """One batch x [B,1,T] alone through every sub-discriminator (S = B signals): the lists of feature maps, the score being the last of each list.
+        What input_grad needs when only one half matters (gradient_norm_loss)."""
+        assert self._loaded, "load_state_dict first"
+        if not (hasattr(x, "is_cuda") and x.is_cuda):
+            raise ValueError("the discriminators run on the device: pass CUDA tensors (there is no CPU path)")
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise ValueError(f"x must be [B, 1, T]: got {tuple(x.shape)}")
+        B, T = int(x.shape[0]), int(x.shape[2])
+        for p in self.periods:
+            if (p - T % p) % p >= T:
+                raise ValueError(f"T = {T} is not longer than the reflect pad period {p} needs")
+        return self._run(x.detach().to(torch.float32).reshape(B, T).contiguous())
+
     def forward(self, y, y_hat):
         assert self._loaded, "load_state_dict first"
         for t in (y, y_hat):
@@ -341,14 +366,8 @@ class _MultiPeriodDiscriminator:
         for p in self.periods:
             if (p - T % p) % p >= T:
                 raise ValueError(f"T = {T} is not longer than the reflect pad period {p} needs")
-        dev = y.device
         sig = torch.cat([y.detach().to(torch.float32).reshape(B, T), y_hat.detach().to(torch.float32).reshape(B, T)]).contiguous()
-        shapes = self.tap_shapes(T)
-        bufs = [[torch.empty((2 * B, c, h, p) if i else (2 * B, c, h), dtype=torch.float32, device=dev) for (c, h, p) in rows] for i, rows in enumerate(shapes)]
-        flat = [t for rows in bufs for t in rows]
-        ptrs = (C.c_void_p * len(flat))(*[t.data_ptr() for t in flat])
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib.rvc_disc_forward(self._h, _lib.current_stream(), _lib.ptr(sig), 2 * B, T, None, ptrs))
+        bufs = self._run(sig)
         y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
         for rows in bufs:
             fmap_rs.append([t[:B] for t in rows])
@@ -356,6 +375,62 @@ class _MultiPeriodDiscriminator:
             y_d_rs.append(torch.flatten(rows[-1][:B], 1, -1))
             y_d_gs.append(torch.flatten(rows[-1][B:], 1, -1))
         return y_d_rs, y_d_gs, fmap_rs, fmap_gs
+
+    def backward_launch_count(self, S, T):
+        """Kernel launches of one input_grad over S signals of T samples (rvc_disc_input_grad_launch_count: the size of the plan; nothing is launched)."""
+        n = _lib.lib.rvc_disc_input_grad_launch_count(self._h, int(S), int(T))
+        if n < 0:
+            raise _lib.RvcHipError(_lib.lib.rvc_last_error().decode("utf-8", "replace"))
+        return n
+
+    def input_grad(self, fmaps, tap_cotangents, return_deltas=False):
+        """The vector-Jacobian product of the forward with respect to its input (rvc_disc_input_grad).  fmaps: the lists of feature maps `forward` returned
+        for ONE half (fmap_rs or fmap_gs: leading-dimension slices, hence contiguous); tap_cotangents: the same structure, each entry the cotangent of that
+        feature map in its shape (the last of a sub-discriminator is dL/dscore, [B, H p] accepted) or None for zero.  Returns dL/dinput [B, 1, T] float32;
+        return_deltas: also the per-layer dL/d(pre-activation) buffers the pass wrote, in the taps' structure.  The leaky ReLU masks are read from the
+        feature maps, so the result is the exact gradient of what the forward computed."""
+        assert self._loaded, "load_state_dict first"
+        if len(fmaps) != len(self.periods) + 1 or len(tap_cotangents) != len(fmaps) or any(len(a) != len(b) for a, b in zip(fmaps, tap_cotangents)):
+            raise ValueError("input_grad: fmaps and tap_cotangents must both hold one list per sub-discriminator with one entry per tap")
+        first = fmaps[0][0] if len(fmaps[0]) else None
+        if first is None or not (hasattr(first, "is_cuda") and first.is_cuda) or first.dim() != 3:
+            raise ValueError("input_grad: device feature maps as forward returned them expected (there is no CPU path)")
+        B, T, dev = int(first.shape[0]), int(first.shape[2]), first.device
+        for p in self.periods:
+            if (p - T % p) % p >= T:
+                raise ValueError(f"T = {T} is not longer than the reflect pad period {p} needs")
+        shapes = self.tap_shapes(T)
+        if [len(r) for r in shapes] != [len(r) for r in fmaps]:
+            raise ValueError("input_grad: wrong number of feature maps")
+        flat_f, flat_c = [], []
+        for i, rows in enumerate(shapes):
+            for l, (c, h, p) in enumerate(rows):
+                want = (B, c, h, p) if i else (B, c, h)
+                f, ct = fmaps[i][l], tap_cotangents[i][l]
+                if f is None:
+                    raise ValueError(f"input_grad: feature map ({i}, {l}) is missing")
+                if not f.is_cuda or f.dtype != torch.float32 or tuple(f.shape) != want or not f.is_contiguous():
+                    raise ValueError(f"input_grad: feature map ({i}, {l}) must be a contiguous float32 device tensor of shape {want}: got {tuple(f.shape)}")
+                if ct is not None:
+                    if not (hasattr(ct, "is_cuda") and ct.is_cuda):
+                        raise ValueError(f"input_grad: cotangent ({i}, {l}) must be a device tensor (there is no CPU path)")
+                    if ct.numel() != f.numel() or int(ct.shape[0]) != B:
+                        raise ValueError(f"input_grad: cotangent ({i}, {l}) must have the shape of its feature map {want}: got {tuple(ct.shape)}")
+                    ct = ct.detach().to(torch.float32).contiguous()
+                flat_f.append(f)
+                flat_c.append(ct)
+        work = [torch.empty_like(f) for f in flat_f]
+        out = torch.empty(B, 1, T, dtype=torch.float32, device=dev)
+        n = len(flat_f)
+        pf = (C.c_void_p * n)(*[t.data_ptr() for t in flat_f])
+        pc = (C.c_void_p * n)(*[(t.data_ptr() if t is not None else None) for t in flat_c])
+        pw = (C.c_void_p * n)(*[t.data_ptr() for t in work])
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.rvc_disc_input_grad(self._h, _lib.current_stream(), B, T, pf, pc, pw, _lib.ptr(out)))
+        if return_deltas:
+            it = iter(work)
+            return out, [[next(it) for _ in rows] for rows in shapes]
+        return out
 
     def __call__(self, *args, **kwargs):
         return self.forward(*args, **kwargs)

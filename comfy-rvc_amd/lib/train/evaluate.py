@@ -2,13 +2,15 @@
 (no backward pass), formed as the trainer forms them (reference training_cli.py:505-545,:570-571).  With the discriminator checkpoint that the trainer
 writes next to it (D_*.pth) also the three adversarial numbers it logs, loss_disc, loss_gen and loss_fm (:545-553,:567-572,:585).  The trainer's
 switches are followed: with hps.train.use_multiscale loss_mel is MultiScaleMelSpectrogramLoss(y_hat, wave) (:569), with hps.train.c_hd / c_tsi > 0 the
-harmonic_loss / tsi_loss of combined_aux_loss (:573-584) are added."""
+harmonic_loss / tsi_loss of combined_aux_loss (:573-584) are added, with hps.train.c_gp > 0 and a discriminator the gradient penalty (:552), the one
+term here that needs a derivative (the discriminators' input gradient, losses.gradient_norm_loss)."""
 import numpy as np
 import torch
 
 from ..infer_pack import models
 from . import data_utils
-from .losses import MultiScaleMelSpectrogramLoss, combined_aux_loss, discriminator_loss, feature_loss, generator_loss, kl_loss, l1_loss
+from .losses import (MultiScaleMelSpectrogramLoss, combined_aux_loss, discriminator_loss, feature_loss, generator_loss, gradient_norm_loss, kl_loss,
+                     l1_loss)
 from .mel_processing import mel_spectrogram_torch, spec_to_mel_torch
 
 
@@ -88,10 +90,12 @@ def reconstruction_losses(net_g, batch, hps, generator=None, *, noise=None, ids_
     return out
 
 
-def adversarial_losses(net_d, wave, y_hat, ids_slice=None, hps=None):
+def adversarial_losses(net_d, wave, y_hat, ids_slice=None, hps=None, generator=None):
     """loss_disc, loss_gen, loss_fm of one batch as the trainer forms them (reference training_cli.py:545-553,:567-572,:585): wave [B,1,Tw] the real waves,
     sliced to y_hat's segments at ids_slice * hop_length when ids_slice is given (wave already sliced otherwise), y_hat [B,1,segment_size].  One
-    net_d(wave, y_hat) serves all three: without a backward pass the trainer's two calls compute the same.  0-dim float32 device tensors."""
+    net_d(wave, y_hat) serves all three: without a backward pass the trainer's two calls compute the same.  0-dim float32 device tensors.
+    hps.train.c_gp > 0: "gradient_penalty" = gradient_norm_loss(wave, y_hat, net_d) * c_gp is added, the term the trainer adds to loss_disc (:552), its alpha
+    drawn from `generator` (a CPU torch.Generator; None: the global one).  loss_disc itself stays the plain discriminator loss."""
     y_hat = y_hat.detach()
     wave = torch.as_tensor(wave).to(y_hat.device, torch.float32)
     if ids_slice is not None:
@@ -99,7 +103,11 @@ def adversarial_losses(net_d, wave, y_hat, ids_slice=None, hps=None):
     y_d_r, y_d_g, fmap_r, fmap_g = net_d(wave, y_hat)
     loss_disc, _ = discriminator_loss(y_d_r, y_d_g)
     loss_gen, _ = generator_loss(y_d_g)
-    return {"loss_disc": loss_disc, "loss_gen": loss_gen, "loss_fm": feature_loss(fmap_r, fmap_g)}
+    out = {"loss_disc": loss_disc, "loss_gen": loss_gen, "loss_fm": feature_loss(fmap_r, fmap_g)}
+    c_gp = _train_get(hps, "c_gp", 0.) if hps is not None else 0.
+    if c_gp > 0:
+        out["gradient_penalty"] = gradient_norm_loss(wave, y_hat, net_d, eps=_train_get(hps, "eps", 1e-8), generator=generator) * c_gp
+    return out
 
 
 def load_generator(ckpt, hps, version="v2", f0=True, device="cuda:0"):
@@ -130,6 +138,8 @@ def evaluate_checkpoint(ckpt, filelist, hps, seed=1337, batch_size=4, boundaries
     "batches": [{"loss_mel", "loss_kl", "ids_slice"}...]}.  The sampler buckets by file size (dataset.lengths), so a batch may still hold an item whose
     labels are shorter than the segment: such a batch cannot be sliced and is left out.  The draws come from torch.Generator().manual_seed(seed): the same seed gives the same two numbers.
     ckpt_d (a D_*.pth path, a state dict or loaded discriminators): loss_disc, loss_gen and loss_fm are added per batch and as means; None: nothing changes.
+    With ckpt_d and hps.train.c_gp > 0 also gradient_penalty (the penalty times c_gp, as the trainer adds it), its alpha drawn from the walk's generator after
+    the batch's forward draws; with c_gp absent or 0 no draw is made and the result is what it was.
     hps.train.use_multiscale / c_hd / c_tsi as in reconstruction_losses; the multi-scale state is the checkpoint's "msml" entry when ckpt is a path or a
     checkpoint dict that has one."""
     cpt = torch.load(ckpt, map_location="cpu") if isinstance(ckpt, str) else ckpt
@@ -152,13 +162,13 @@ def evaluate_checkpoint(ckpt, filelist, hps, seed=1337, batch_size=4, boundaries
         row = {"loss_mel": float(r["loss_mel"]), "loss_kl": float(r["loss_kl"]), "ids_slice": r["ids_slice"].cpu().numpy()}
         row.update({k: float(r[k]) for k in ("harmonic_loss", "tsi_loss") if k in r})
         if net_d is not None:
-            adv = adversarial_losses(net_d, batch[6 if f0 else 4], r["y_hat"], r["ids_slice"], hps)
+            adv = adversarial_losses(net_d, batch[6 if f0 else 4], r["y_hat"], r["ids_slice"], hps, generator=gen)
             row.update({k: float(v) for k, v in adv.items()})
         rows.append(row)
     if not rows:
         raise ValueError("no batch of the file list has every item at least segment_size long")
     names = ["loss_mel", "loss_kl"] + (["loss_disc", "loss_gen", "loss_fm"] if net_d is not None else [])
-    names += [k for k in ("harmonic_loss", "tsi_loss") if k in rows[0]]
+    names += [k for k in ("gradient_penalty", "harmonic_loss", "tsi_loss") if k in rows[0]]
     out = {k: float(np.mean([r[k] for r in rows])) for k in names}
     out["batches"] = rows
     return out

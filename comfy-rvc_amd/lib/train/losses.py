@@ -1,7 +1,12 @@
 """The trainer's losses on device tensors, forward only: the two reconstruction losses (reference lib/train/losses.py:596-611 kl_loss; F.l1_loss as
 training_cli.py:570 uses it) and the three GAN losses (:564-593 feature_loss, discriminator_loss, generator_loss).  Each is a fixed-order float64
 reduction on the device (rvc_kl_loss per item, rvc_l1_sum; rvc_sqerr_sums / rvc_l1_sums: one segmented reduction over all tensors of a loss) and
-returns 0-dim float32 tensors.  No backward pass.
+returns 0-dim float32 tensors.
+
+One derivative is formed: the gradient of a discriminator-side loss with respect to the input waveform (models._MultiPeriodDiscriminator.input_grad, a
+vector-Jacobian product through the discriminators on the device).  gradient_norm_loss (:401-426, the trainer's gradient penalty) and
+adversarial_input_grads (the gradients and norms LossBalancer.calculate_gradients reads for loss_gen and loss_fm, :76-92) are built on it.  No weight
+gradient, no optimizer, no generator backward; LossBalancer itself is not ported.
 
 Also the two generator-side terms the trainer adds on request: MultiScaleMelSpectrogramLoss (:430-561, `hps.train.use_multiscale`) and combined_aux_loss
 (:344-399) with its parts compute_harmonics, compute_envelope and compute_tsi_loss.  compute_tefs (the temporal envelope / fine structure term) is not
@@ -102,6 +107,72 @@ def generator_loss(disc_outputs):
     """(sum_i L_i, [L_i]) with L_i = mean (1 - dg_i)^2; 0-dim float32 tensors."""
     per = _sqerr_means(list(disc_outputs), [1.0] * len(disc_outputs)).to(torch.float32)
     return per.sum(), [per[i] for i in range(len(disc_outputs))]
+
+
+# ------------------------------------------------------------------------------------------------- input gradients (reference lib/train/losses.py:401-426,:76-92)
+def _cotangents(kind, a, b, scales):
+    """rvc_loss_cotangents over lists of device tensors: one launch, float32 tensors in the shapes of `a`."""
+    a, pa, n = _segments(a)
+    pb = None
+    if b is not None:
+        b, pb, _ = _segments(b)
+    out = [torch.empty_like(t) for t in a]
+    po = (_lib.c_void_p * len(a))(*[t.data_ptr() for t in out])
+    sc = (_lib.c_float * len(a))(*scales)
+    with torch.cuda.device(a[0].device):
+        _lib.check(_lib.lib.rvc_loss_cotangents(_lib.current_stream(), kind, pa, pb, n, sc, len(a), po))
+    return out
+
+
+def _score_cotangents(fmaps, kind):
+    """cotangent lists for input_grad with d loss / d score on the last tap of every sub-discriminator: kind 0 for sum mean(s^2), 1 for sum mean((1 - s)^2)"""
+    scores = [d[-1] for d in fmaps]
+    cots = _cotangents(kind, scores, None, [2.0 / t.numel() for t in scores])
+    return [[None] * (len(d) - 1) + [c] for d, c in zip(fmaps, cots)]
+
+
+def _item_sq_norms(g):
+    """float64 [B]: sum of squares of every item of g (rvc_sqerr_sums with c = 0, fixed order)"""
+    rows = [g[b] for b in range(g.shape[0])]
+    return _sqerr_means(rows, [0.0] * len(rows)) * float(g[0].numel())
+
+
+def gradient_norm_loss(original_audio, generated_audio, net_d, eps=1e-8, alpha=None, generator=None, return_gradient=False):
+    """The trainer's gradient penalty mean_b (||d loss_disc / d x_b||_2 - 1)^2 at x = alpha original + (1 - alpha) generated; 0-dim float32 device tensor.
+    alpha [B,1,1] uniform in [0, 1): given, or drawn from `generator` (a CPU torch.Generator; None: the global one - the reference draws it from the global
+    generator on the device).  Only the interpolated batch goes through net_d (S = B signals): the real half of the reference's net_d(original,
+    interpolated) has no path to the gradient.  eps is unused, as in the reference.  return_gradient: (loss, gradient [B,1,T])."""
+    y, y_hat = _dev(original_audio), _dev(generated_audio)
+    if y.dim() != 3 or y.shape[1] != 1 or y.shape != y_hat.shape:
+        raise ValueError(f"gradient_norm_loss: two [B, 1, T] tensors expected: {tuple(y.shape)} and {tuple(y_hat.shape)}")
+    B, T = int(y.shape[0]), int(y.shape[2])
+    if alpha is None:
+        alpha = torch.rand(B, 1, 1, generator=generator)
+    alpha = torch.as_tensor(alpha, dtype=torch.float32)
+    if alpha.numel() != B:
+        raise ValueError(f"gradient_norm_loss: alpha must be [B, 1, 1] = [{B}, 1, 1]: got {tuple(alpha.shape)}")
+    alpha = alpha.reshape(B).to(y.device).contiguous()
+    x = torch.empty_like(y)
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.lib.rvc_interpolate(_lib.current_stream(), _lib.ptr(alpha), _lib.ptr(y), _lib.ptr(y_hat), B, T, _lib.ptr(x)))
+    fmaps = net_d.forward_single(x)
+    g = net_d.input_grad(fmaps, _score_cotangents(fmaps, 0))
+    norms = _item_sq_norms(g).sqrt()
+    loss = ((norms - 1.0) ** 2).mean().to(torch.float32)
+    return (loss, g) if return_gradient else loss
+
+
+def adversarial_input_grads(net_d, wave, y_hat):
+    """({"loss_gen": d generator_loss / d y_hat, "loss_fm": d feature_loss / d y_hat}, each [B,1,T] float32, and {"loss_gen": norm, "loss_fm": norm}): the norms
+    as LossBalancer.calculate_gradients forms them (per-item 2-norm, mean over the batch), 0-dim float32 device tensors.  One net_d(wave, y_hat) serves both."""
+    _, _, fmap_r, fmap_g = net_d(wave, y_hat)
+    fmap_g = [[t.contiguous() for t in d] for d in fmap_g]
+    fr, fg = [t for d in fmap_r for t in d], [t for d in fmap_g for t in d]
+    it = iter(_cotangents(2, fg, fr, [1.0 / t.numel() for t in fg]))
+    grads = {"loss_gen": net_d.input_grad(fmap_g, _score_cotangents(fmap_g, 1)),
+             "loss_fm": net_d.input_grad(fmap_g, [[next(it) for _ in d] for d in fmap_g])}
+    norms = {k: _item_sq_norms(g).sqrt().mean().to(torch.float32) for k, g in grads.items()}
+    return grads, norms
 
 
 # ------------------------------------------------------------------------------------------------- multi-scale mel loss (reference lib/train/losses.py:430-561)

@@ -14,6 +14,9 @@
  *   rvc_disc_forward     <- MultiPeriodDiscriminator[V2].forward         lib/infer_pack/models.py:1024-1145 (net_d: training_cli.py:549,:567)
  *   rvc_sqerr_sums       <- discriminator_loss / generator_loss          lib/train/losses.py:571-593
  *   rvc_l1_sums          <- feature_loss                                 lib/train/losses.py:564-569
+ *   rvc_disc_input_grad  <- torch.autograd.grad(loss, [wave]) through net_d      lib/train/losses.py:401-426 (gradient_norm_loss), :76-92 (LossBalancer)
+ *   rvc_loss_cotangents  <- the backward of the three GAN losses                 lib/train/losses.py:564-593
+ *   rvc_interpolate      <- alpha * original + (1 - alpha) * generated            lib/train/losses.py:407
  *   rvc_vc_segment       <- VC.vc (features -> x2 upsample -> protect -> infer)   vc_infer_pipeline.py:25-114
  *   rvc_*_set_tensor     <- load_state_dict of the checkpoint tensors    vc_infer_pipeline.py:199-221,
  *                                                                        lib/infer_pack/loaders.py:19-31, lib/rmvpe.py:579-586
@@ -268,6 +271,25 @@ int rvc_disc_launch_count(rvc_disc* d, int S, int64_t T);
  *   rvc_l1_sums:    sums[k] = sum_j |a[k][j] - b[k][j]|     feature_loss (the real and generated halves of every tap) */
 int rvc_sqerr_sums(void* stream, const float* const* x_dev, const int64_t* n, const float* c, int K, double* sums_dev);
 int rvc_l1_sums(void* stream, const float* const* a_dev, const float* const* b_dev, const int64_t* n, int K, double* sums_dev);
+/* The input-gradient pass: the vector-Jacobian product of rvc_disc_forward with respect to the signals, on the feature maps that forward wrote.
+ * fmaps_dev: the forward's HOST array of device pointers for these S signals (each [S][C][H][p]).  dtaps_dev: HOST array of one device pointer per tap,
+ * the cotangent of that tap in the tap's shape, or NULL for zero; the last tap's is dL / dscore.  work_dev: HOST array of one device buffer per tap in
+ * the tap's shape; buffer (i, l) receives dL / d(pre-activation of layer l) - the call owns no activation memory.  dsignals_dev [S][T] is fully written:
+ * the sub-discriminators add into it one after the other on the stream, in index order.  The leaky ReLU's mask is taken from the saved post-activation
+ * tap (slope 0.1 at exactly 0, as torch), so the pass is linear in the cotangents and exact for what the forward computed.  The dense k = 5 layers run
+ * on the matrix cores (bf16x3, fp32 accumulation), one launch per layer whatever S and T; no atomics anywhere: two calls give the same bits.
+ * rvc_disc_input_grad_launch_count: the size of its plan (touches no stream): 6 per DiscriminatorP, 7 for DiscriminatorS; -1 on error. */
+int rvc_disc_input_grad(rvc_disc* d, void* stream, int S, int64_t T, const float* const* fmaps_dev, const float* const* dtaps_dev, float* const* work_dev,
+                        float* dsignals_dev);
+int rvc_disc_input_grad_launch_count(rvc_disc* d, int S, int64_t T);
+/* Cotangents of the GAN losses for K <= 64 tensors in one launch; a_dev / b_dev / out_dev, n, scale: HOST arrays of K device pointers, lengths, factors.
+ *   kind 0: out = scale a             d mean(s^2) / ds with scale = 2 / numel          (discriminator_loss, generated scores)
+ *   kind 1: out = -scale (1 - a)      d mean((1 - s)^2) / ds with scale = 2 / numel    (generator_loss; discriminator_loss, real scores)
+ *   kind 2: out = scale sign(a - b)   d mean|r - g| / dg with a = g, b = r, scale = 1 / numel, sign(0) = 0   (feature_loss; b_dev may be NULL otherwise) */
+int rvc_loss_cotangents(void* stream, int kind, const float* const* a_dev, const float* const* b_dev, const int64_t* n, const float* scale, int K,
+                        float* const* out_dev);
+/* out[b][t] = alpha[b] y[b][t] + (1 - alpha[b]) y_hat[b][t] (gradient_norm_loss's interpolation): every operation rounded to float32 on its own, as torch */
+int rvc_interpolate(void* stream, const float* alpha_dev, const float* y_dev, const float* y_hat_dev, int B, int64_t T, float* out_dev);
 
 /* ------------------------------------------------------------------ fused segment: VC.vc without index retrieval */
 /* audio_dev [L] 16 kHz segment; pitch/pitchf as above with at least p_len = 2*T_h entries; out_dev [2*T_h*upp].
