@@ -129,6 +129,11 @@ SIGNATURES = {
     "rvc_l1_sums": (c_int, [c_void_p, P(c_void_p), P(c_void_p), P(c_int64), c_int, c_void_p]),
     "rvc_disc_input_grad": (c_int, [c_void_p, c_void_p, c_int, c_int64, P(c_void_p), P(c_void_p), P(c_void_p), c_void_p]),
     "rvc_disc_input_grad_launch_count": (c_int, [c_void_p, c_int, c_int64]),
+    "rvc_disc_keep_parameters": (c_int, [c_void_p, c_int]),
+    "rvc_disc_param_count": (c_int, [c_void_p]),
+    "rvc_disc_param_info": (c_int, [c_void_p, c_int, c_char_p, c_int, P(c_int64), P(c_int)]),
+    "rvc_disc_weight_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, P(c_void_p), P(c_void_p), P(c_void_p)]),
+    "rvc_disc_weight_grad_launch_count": (c_int, [c_void_p, c_int, c_int64]),
     "rvc_loss_cotangents": (c_int, [c_void_p, c_int, P(c_void_p), P(c_void_p), P(c_int64), P(c_float), c_int, P(c_void_p)]),
     "rvc_interpolate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "rvc_synth_dec_halo": (c_int, [c_void_p]),

@@ -10,6 +10,8 @@
 // The forward is PLANNED (disc_plan: pure, no stream) and the plan is launched; disc_launch_count is the size of that plan.
 // The input-gradient pass (disc_input_grad: the vector-Jacobian product from cotangents on the taps to the signals) walks the same layers backwards on
 // the feature maps the forward wrote - one launch per layer again, planned the same way; see "input gradient" below.
+// The weight-gradient pass (disc_weight_grad: dL / d(weight_g, weight_v, bias) from the same feature maps and the deltas the input-gradient pass left) is two
+// launches per layer - gradient, finish -, opt-in through disc_keep_parameters; see "weight gradient" below.
 #include "model_common.h"
 #include "models.h"
 #include "signal_dev.h"
@@ -119,7 +121,10 @@ struct DiscLayer {
   DevBuf<uint16_t> wx;               // bf16x3 image (the GEMM layers)
   DevBuf<uint16_t> wxb[3];           // the GEMM layers' data gradient: one transposed image per phase of the input row (stride of them), rows Ci padded to CiPx
   int CiPx = 0;
+  DevVec pv, pg;                     // weight_v [Co][Ci / groups][k] and weight_g [Co] as loaded: only with disc_keep_parameters (the weight-norm chain of weight_grad)
+  int gi_w = -1, gi_g = -1, gi_b = -1;   // this layer's entries of the parameter list: weight_v (or the plain weight), weight_g (-1: plain weight), bias
 };
+struct DiscParam { std::string name; std::vector<long long> shape; };
 struct DiscNet { int period = 0; std::vector<DiscLayer> L; };   // period 0: DiscriminatorS; L.back() is conv_post
 struct DiscWeights { std::vector<DiscNet> nets; };
 struct Disc : DiscWeights {
@@ -127,6 +132,9 @@ struct Disc : DiscWeights {
   int version = 2;
   TensorStore ts;
   bool ready = false;
+  bool keep = false;                 // disc_keep_parameters: finalize keeps weight_v / weight_g on the device and weight_grad is allowed
+  bool kept = false;                 // what the finalized net was loaded with
+  std::vector<DiscParam> params;     // the parameter tensors in the reference module's state-dict order (per layer: bias, weight_g, weight_v; or weight, bias)
 };
 
 Disc* disc_create(Ctx* ctx, int version) {
@@ -166,8 +174,13 @@ static void disc_bwd_images(DiscLayer& L, const std::vector<float>& w) {
   }
 }
 
+void disc_keep_parameters(Disc* D, bool on) {
+  RVC_REQUIRE(!D->ready, "disc_keep_parameters: set the switch before finalize");
+  D->keep = on;
+}
 void disc_finalize(Disc* D) {
   D->ready = false; static_cast<DiscWeights&>(*D) = {};   // a finalize that throws leaves the handle not ready
+  D->params.clear(); D->kept = false;
   const TensorStore& ts = D->ts;
   const std::vector<int> periods = disc_periods(D->version);
   struct Spec { int Ci, Co, k, stride, pad, groups; };
@@ -196,6 +209,16 @@ void disc_finalize(Disc* D) {
       const HostTensor& b = ts.get(n + ".bias", {c.Co});
       DiscLayer L; L.Ci = c.Ci; L.Co = c.Co; L.k = c.k; L.stride = c.stride; L.pad = c.pad; L.groups = c.groups;
       L.b.upload(b.data);
+      if (ts.has(n + ".weight_v")) {
+        const HostTensor& v = ts.get(n + ".weight_v"); const HostTensor& g = ts.get(n + ".weight_g");
+        L.gi_b = (int)D->params.size(); D->params.push_back({n + ".bias", b.shape});
+        L.gi_g = (int)D->params.size(); D->params.push_back({n + ".weight_g", g.shape});
+        L.gi_w = (int)D->params.size(); D->params.push_back({n + ".weight_v", v.shape});
+        if (D->keep) { L.pv.upload(v.data); L.pg.upload(g.data); }
+      } else {
+        L.gi_w = (int)D->params.size(); D->params.push_back({n + ".weight", ts.get(n + ".weight").shape});
+        L.gi_b = (int)D->params.size(); D->params.push_back({n + ".bias", b.shape});
+      }
       if (disc_layer_is_gemm(L)) {
         L.CoPx = (c.Co + 127) & ~127;
         std::vector<uint16_t> img;
@@ -210,7 +233,14 @@ void disc_finalize(Disc* D) {
     D->nets.push_back(std::move(net));
   }
   D->ts.clear();
+  D->kept = D->keep;
   D->ready = true;
+}
+int disc_param_count(const Disc* D) { RVC_REQUIRE(D->ready, "finalize first"); return (int)D->params.size(); }
+void disc_param_info(const Disc* D, int k, std::string& name, std::vector<long long>& shape) {
+  RVC_REQUIRE(D->ready, "finalize first");
+  RVC_REQUIRE(k >= 0 && k < (int)D->params.size(), "no such parameter");
+  name = D->params[k].name; shape = D->params[k].shape;
 }
 
 int disc_count(const Disc* D) { return (int)disc_periods(D->version).size(); }
@@ -574,6 +604,151 @@ __global__ __launch_bounds__(256) void interpolate_kernel(const float* __restric
 void interpolate_rows(hipStream_t s, const float* alpha, const float* y, const float* y_hat, int B, long long T, float* out) {
   RVC_REQUIRE(alpha && y && y_hat && out && B >= 1 && B <= 65535 && T >= 1, "interpolate_rows: bad argument");
   hipLaunchKernelGGL(interpolate_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0, s, alpha, y, y_hat, T, out);
+}
+
+// ---------------------------------------------------------------------------------------------- weight gradient
+// With delta_l = dL / dz_l (work[l] of the input-gradient pass) and X_l the layer's input (the signal through the reflect rule for l = 0, tap[l - 1] otherwise):
+//   dW_l[m][c][j] = sum_s sum_n delta_l[s][m][n] X_l[s][c][stride h' + j - pad][w]  (n = h' p + w; rows outside [0, H) are zero),   db_l[m] = sum_s sum_n delta_l[s][m][n]
+// and through weight norm (dim 0), with n_m = |v_m| and d_m = <dW[m], v[m]>:  grad_g[m] = d_m / n_m,  grad_v[m] = (g_m / n_m) (dW[m] - (d_m / n_m^2) v[m]).
+// Two launches per layer whatever S and T: the gradient kernel writes `splits` partial images (each split owns a contiguous piece of the reduction), the
+// finishing kernel adds them in index order, forms db in float64 and applies the chain in one pass over a row.  No atomics: two calls give the same bits.
+// The dense k = 5 layers run on the matrix cores (conv_x3d_wgrad.hip); the first layer, the grouped layers and conv_post are direct gathers.
+
+// One thread per weight element (m, ci, j) and split: the sum over every signal and the split's run of n, in float64.  T > 0: X is the signal [S][T] seen
+// through disc_first_kernel's reflect rule; T = 0: X is a tap [S][Ci][H][p] and channel ci of group m / opg is row (m / opg) cig + ci.
+struct DiscWgradDirectArgs { const float* D; const float* X; float* part; int S, Ci, Co, cig, opg, k, stride, pad, H, Hout, p, T, chunk; };
+__global__ __launch_bounds__(256) void disc_wgrad_direct_kernel(const DiscWgradDirectArgs a) {
+  const int L = a.cig * a.k, total = a.Co * L, o = blockIdx.x * 256 + threadIdx.x, split = blockIdx.y;
+  if (o >= total) return;
+  const int m = o / L, r = o - m * L, ci = r / a.k, j = r - ci * a.k, c = (m / a.opg) * a.cig + ci;
+  const int N = a.Hout * a.p, n0 = split * a.chunk, n1 = min(n0 + a.chunk, N);
+  const long long HP = (long long)a.H * a.p;
+  double acc = 0.0;
+  for (int s = 0; s < a.S; ++s) {
+    const float* D = a.D + ((long long)s * a.Co + m) * N;
+    const float* X = a.T ? a.X + (long long)s * a.T : a.X + ((long long)s * a.Ci + c) * HP;
+    int h = n0 / a.p, w = n0 - h * a.p;
+    for (int n = n0; n < n1; ++n) {
+      const int row = a.stride * h + j - a.pad;
+      if (row >= 0 && row < a.H) {
+        long long t = (long long)row * a.p + w;
+        if (a.T && t >= a.T) t = 2LL * (a.T - 1) - t;
+        acc = fma((double)D[n], (double)X[t], acc);
+      }
+      if (++w == a.p) { w = 0; ++h; }
+    }
+  }
+  a.part[(long long)split * total + o] = (float)acc;
+}
+
+// One workgroup per output channel m: db[m] (float64, thread-strided then block_sum: a fixed order), dW[m] = the partials added in index order, and the
+// weight-norm chain where v is given (gw receives dW itself otherwise).  gw doubles as the row's store between the two passes: a thread re-reads only what
+// it wrote itself.
+struct DiscWgradFinishArgs { const float* part; const float* D; const float* v; const float* g; float* gw; float* gg; float* gb; long long pstride; int splits, S, Co, N, L; };
+__global__ __launch_bounds__(256) void disc_wgrad_finish_kernel(const DiscWgradFinishArgs a) {
+  __shared__ double red[4];
+  const int m = blockIdx.x;
+  double bs[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int s = 0; s < a.S; ++s) {
+    const float* D = a.D + ((long long)s * a.Co + m) * a.N;
+    for (int n = threadIdx.x; n < a.N; n += 1024) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) bs[u] += n + 256 * u < a.N ? (double)D[n + 256 * u] : 0.0;
+    }
+  }
+  const double b = block_sum((bs[0] + bs[1]) + (bs[2] + bs[3]), red);
+  if (threadIdx.x == 0) a.gb[m] = (float)b;
+  const float* P = a.part + (long long)m * a.L;
+  const float* v = a.v ? a.v + (long long)m * a.L : nullptr;
+  float* gw = a.gw + (long long)m * a.L;
+  double d = 0.0, vv = 0.0;
+  for (int q = threadIdx.x; q < a.L; q += 256) {
+    double w = 0.0;
+    for (int z = 0; z < a.splits; ++z) w += (double)P[(long long)z * a.pstride + q];
+    gw[q] = (float)w;
+    if (v) { const double x = (double)v[q]; d = fma((double)(float)w, x, d); vv = fma(x, x, vv); }
+  }
+  if (!v) return;                               // uniform: a plain weight's gradient is dW
+  d = block_sum(d, red);
+  vv = block_sum(vv, red);
+  const double nrm = sqrt(vv), coef = d / vv, sc = (double)a.g[m] / nrm;
+  if (threadIdx.x == 0) a.gg[m] = (float)(d / nrm);
+  for (int q = threadIdx.x; q < a.L; q += 256) gw[q] = (float)(sc * ((double)gw[q] - coef * (double)v[q]));
+}
+
+struct DiscWgradLaunch {
+  bool gemm = false;
+  ConvX3dWgradPlan x; DiscWgradDirectArgs d; dim3 dgrid; DiscWgradFinishArgs f;
+  size_t part_floats = 0;
+};
+// pure: no stream, no launch, no allocation.  signals / fmaps / deltas / grads (all may be null: counting only).  The partial images' pointer is set by the
+// caller once the largest part_floats of the plan is known.
+static void disc_wgrad_plan(const Disc* D, const float* signals, int S, long long T, const float* const* fmaps, const float* const* deltas, float* const* grads,
+                            std::vector<DiscWgradLaunch>& plan) {
+  RVC_REQUIRE(D->ready, "finalize first");
+  RVC_REQUIRE(D->kept, "weight_grad needs the parameters on the device: call rvc_disc_keep_parameters(d, 1) before finalize (trainable=True)");
+  RVC_REQUIRE(S >= 1 && S <= 65535, "1 <= S <= 65535 signals");
+  disc_check_T(D, T);
+  plan.clear();
+  const bool real = fmaps != nullptr;
+  if (real) for (size_t k = 0; k < D->params.size(); ++k) RVC_REQUIRE(grads[k], "null gradient pointer");
+  int tap0 = 0;
+  for (size_t i = 0; i < D->nets.size(); ++i) {
+    const DiscNet& net = D->nets[i];
+    const int per = net.period ? net.period : 1;
+    int H = (int)((T + per - 1) / per);
+    for (size_t l = 0; l < net.L.size(); ++l) {
+      const DiscLayer& L = net.L[l];
+      const int Ho = conv_out(H, L.k, L.stride, L.pad);
+      RVC_REQUIRE(Ho >= 1, "signal too short");
+      if (real) RVC_REQUIRE(fmaps[tap0 + l] && deltas[tap0 + l], "null feature-map or delta pointer");
+      const float* x = real ? (l == 0 ? signals : fmaps[tap0 + l - 1]) : nullptr;
+      const float* delta = real ? deltas[tap0 + l] : nullptr;
+      const long long N = (long long)Ho * per;
+      const int cig = L.Ci / L.groups, Lrow = cig * L.k;
+      RVC_REQUIRE((long long)L.Co * Lrow < (1LL << 31) && N < (1LL << 31), "layer too large");
+      DiscWgradLaunch d;
+      if (l > 0 && l + 1 < net.L.size() && disc_layer_is_gemm(L)) {
+        d.gemm = true;
+        const ConvX3dWgradArgs a{delta, x, nullptr, L.Ci, L.Co, H, Ho, per, L.k, L.stride, L.pad, S, 0, 0, 0};
+        RVC_REQUIRE(conv_x3d_wgrad_plan(a, d.x), "discriminator layer does not fit the weight-gradient kernel");
+        d.f.splits = d.x.splits; d.part_floats = d.x.part_floats;
+      } else {
+        const int blocks = (L.Co * Lrow + 255) / 256;
+        const long long most = std::min<long long>(64, (N + 15) / 16);                    // a split sums at least 16 columns of every signal
+        const long long splits0 = std::max<long long>(1, std::min<long long>((2048 + blocks - 1) / blocks, most));
+        const int chunk = (int)((N + splits0 - 1) / splits0), splits = (int)((N + chunk - 1) / chunk);
+        d.d = DiscWgradDirectArgs{delta, x, nullptr, S, L.Ci, L.Co, cig, L.Co / L.groups, L.k, L.stride, L.pad, H, Ho, per, l == 0 ? (int)T : 0, chunk};
+        d.dgrid = dim3((unsigned)blocks, (unsigned)splits);
+        d.f.splits = splits; d.part_floats = (size_t)splits * L.Co * Lrow;
+      }
+      d.f.part = nullptr; d.f.D = delta; d.f.v = L.gi_g >= 0 ? L.pv.p : nullptr; d.f.g = L.gi_g >= 0 ? L.pg.p : nullptr;
+      d.f.gw = real ? grads[L.gi_w] : nullptr; d.f.gg = real && L.gi_g >= 0 ? grads[L.gi_g] : nullptr; d.f.gb = real ? grads[L.gi_b] : nullptr;
+      d.f.pstride = (long long)L.Co * Lrow; d.f.S = S; d.f.Co = L.Co; d.f.N = (int)N; d.f.L = Lrow;
+      plan.push_back(d);
+      H = Ho;
+    }
+    tap0 += (int)net.L.size();
+  }
+}
+int disc_weight_grad_launch_count(const Disc* D, int S, long long T) {
+  std::vector<DiscWgradLaunch> plan;
+  disc_wgrad_plan(D, nullptr, S, T, nullptr, nullptr, nullptr, plan);
+  return 2 * (int)plan.size();
+}
+void disc_weight_grad(Disc* D, hipStream_t s, const float* signals, int S, long long T, const float* const* fmaps, const float* const* deltas, float* const* grads) {
+  RVC_REQUIRE(signals && fmaps && deltas && grads, "null argument");
+  std::vector<DiscWgradLaunch> plan;
+  disc_wgrad_plan(D, signals, S, T, fmaps, deltas, grads, plan);
+  size_t most = 0;
+  for (const DiscWgradLaunch& d : plan) most = std::max(most, d.part_floats);
+  float* part = (float*)stream_scratch(s, 24, most * sizeof(float));       // every layer's partial images in turn: the stream orders their uses
+  for (DiscWgradLaunch& d : plan) {
+    d.f.part = part;
+    if (d.gemm) { d.x.a.part = part; conv_x3d_wgrad_launch(d.x, s); }
+    else { d.d.part = part; hipLaunchKernelGGL(disc_wgrad_direct_kernel, d.dgrid, dim3(256), 0, s, d.d); }
+    hipLaunchKernelGGL(disc_wgrad_finish_kernel, dim3((unsigned)d.f.Co), dim3(256), 0, s, d.f);
+  }
 }
 
 }  // namespace rvc

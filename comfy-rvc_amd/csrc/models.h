@@ -55,6 +55,14 @@ void disc_forward(Disc* D, hipStream_t s, const float* signals, int S, long long
 // (an entry may be null: zero), work one buffer per tap in the tap's shape (receives dL / d pre-activation of its layer), dsignals [S][T] fully written
 int disc_input_grad_launch_count(const Disc* D, int S, long long T);   // pure, independent of S and T
 void disc_input_grad(Disc* D, hipStream_t s, int S, long long T, const float* const* fmaps, const float* const* dtaps, float* const* work, float* dsignals);
+// the gradient with respect to the parameters, from the same feature maps and the deltas (`work`) of disc_input_grad over the S signals the forward saw:
+// grads one device pointer per parameter tensor in disc_param_info's order (the reference module's state-dict order), each fully written.  Needs
+// disc_keep_parameters(D, true) before finalize: weight_v / weight_g stay on the device for the weight-norm chain (without it nothing of a loaded net changes)
+void disc_keep_parameters(Disc* D, bool on);
+int disc_param_count(const Disc* D);
+void disc_param_info(const Disc* D, int k, std::string& name, std::vector<long long>& shape);
+int disc_weight_grad_launch_count(const Disc* D, int S, long long T);   // pure, independent of S and T: two per layer
+void disc_weight_grad(Disc* D, hipStream_t s, const float* signals, int S, long long T, const float* const* fmaps, const float* const* deltas, float* const* grads);
 // cotangents of the GAN losses, K tensors per launch (kind 0: scale a; 1: -scale (1 - a); 2: scale sign(a - b)), and gradient_norm_loss's interpolation
 void loss_cotangents(hipStream_t s, int kind, const float* const* a, const float* const* b, const long long* n, const float* scale, int K, float* const* out);
 void interpolate_rows(hipStream_t s, const float* alpha, const float* y, const float* y_hat, int B, long long T, float* out);

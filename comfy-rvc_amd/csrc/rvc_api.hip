@@ -371,6 +371,34 @@ int rvc_disc_input_grad(rvc_disc* d, void* stream, int S, int64_t T, const float
   check_launch();
   RVC_CATCH
 }
+int rvc_disc_keep_parameters(rvc_disc* d, int on) { RVC_TRY RVC_REQUIRE(d, "null argument"); disc_keep_parameters(d->m, on != 0); RVC_CATCH }
+int rvc_disc_param_count(rvc_disc* d) {
+  try { RVC_REQUIRE(d, "null argument"); return disc_param_count(d->m); }
+  catch (const std::exception& e) { rvc::set_error(e.what()); return -1; }
+}
+int rvc_disc_param_info(rvc_disc* d, int k, char* name, int name_cap, int64_t* shape, int* ndim) {
+  RVC_TRY
+  RVC_REQUIRE(d && name && name_cap > 0 && shape && ndim, "null argument");
+  std::string n; std::vector<long long> sh;
+  disc_param_info(d->m, k, n, sh);
+  RVC_REQUIRE((int)n.size() < name_cap && sh.size() <= 8, "name buffer too small");
+  std::memcpy(name, n.c_str(), n.size() + 1);
+  for (size_t i = 0; i < sh.size(); ++i) shape[i] = sh[i];
+  *ndim = (int)sh.size();
+  RVC_CATCH
+}
+int rvc_disc_weight_grad_launch_count(rvc_disc* d, int S, int64_t T) {
+  try { RVC_REQUIRE(d, "null argument"); return disc_weight_grad_launch_count(d->m, S, T); }
+  catch (const std::exception& e) { rvc::set_error(e.what()); return -1; }
+}
+int rvc_disc_weight_grad(rvc_disc* d, void* stream, const float* signals, int S, int64_t T, const float* const* fmaps, const float* const* deltas,
+                         float* const* grads) {
+  RVC_TRY
+  RVC_REQUIRE(d && signals && fmaps && deltas && grads, "null argument");
+  disc_weight_grad(d->m, (hipStream_t)stream, signals, S, T, fmaps, deltas, grads);
+  check_launch();
+  RVC_CATCH
+}
 int rvc_loss_cotangents(void* stream, int kind, const float* const* a, const float* const* b, const int64_t* n, const float* scale, int K, float* const* out) {
   RVC_TRY
   RVC_REQUIRE(a && n && scale && out && K >= 1 && K <= 64, "1 <= K <= 64 tensors, no null argument");

@@ -243,6 +243,16 @@ struct ConvX3dBwdArgs {
 struct ConvX3dBwdPlan { ConvX3dBwdArgs a; dim3 grid; int units = 1; size_t lds = 0; double flops = 0.0; };
 bool conv_x3d_bwd_plan(const ConvX3dBwdArgs& a, ConvX3dBwdPlan& p);   // false: the layer does not fit the kernel
 void conv_x3d_bwd_launch(const ConvX3dBwdPlan& p, hipStream_t s);
+// The weight gradient of that convolution (conv_x3d_wgrad.hip):  dW[m][c][j] = sum_s sum_n D[s][m][n] X[s][c][stride n - (stride - 1) w + (j - pad) p], both
+// operands fp32 and split in the kernel, the reduction over (signal, n) cut into `splits` runs of stages (one signal, 128 columns each): split z writes the
+// partial image part[z][Co][Ci k]; the caller provides part_floats floats and adds the partials in index order.  cps / per / total: filled by the planner.
+struct ConvX3dWgradArgs {
+  const float* D; const float* X; float* part;
+  int Ci, Co, H, Hout, p, k, stride, pad, S; int cps, per, total;
+};
+struct ConvX3dWgradPlan { ConvX3dWgradArgs a; dim3 grid; int splits = 1; size_t lds = 0, part_floats = 0; double flops = 0.0; };
+bool conv_x3d_wgrad_plan(const ConvX3dWgradArgs& a, ConvX3dWgradPlan& p);   // false: the layer does not fit the kernel (Co % 128, k <= 16, 32-bit offsets)
+void conv_x3d_wgrad_launch(const ConvX3dWgradPlan& p, hipStream_t s);
 // one ConvBlockRes of 16 or 32 channels (3 x 3, 3 x 3, + x) in one launch (conv_cbr2.hip): x, out fp32 [C][H W], distinct
 bool cbr2_small_eligible(const ConvLayer& c1, const ConvLayer& c2);
 void cbr2_small_run(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, const float* x, int H, int W, float* out);

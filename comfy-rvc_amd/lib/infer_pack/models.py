@@ -13,6 +13,7 @@ The training forward (reference :665-680,:781-796, `_nono` :894-903,:1000-1009) 
 a batch run one after the other on the current stream, each at its own length, into zero-filled padded outputs (what the reference's masks leave).
 """
 import ctypes as C
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -275,10 +276,12 @@ class _MultiPeriodDiscriminator:
     DiscriminatorP per period.  `forward(y, y_hat)` / `net_d(y, y_hat)` returns `(y_d_rs, y_d_gs, fmap_rs, fmap_gs)` like the reference: per
     sub-discriminator the score [B, H p] of the real and of the generated batch and the lists of feature maps ([B,C,H,p]; [B,C,T'] for
     DiscriminatorS).  `input_grad(fmaps, tap_cotangents)` is the one backward pass: the gradient with respect to the input waveform (rvc_disc_input_grad).  Both batches run through every layer in one launch (rvc_disc_forward on the 2 B signals); the returned tensors are views of
-    the buffers the layers wrote.  CUDA tensors only: there is no CPU path."""
+    the buffers the layers wrote.  `trainable=True` keeps weight_v / weight_g on the device (about the weights' size again) and allows
+    `weight_grad(x, fmaps, deltas)`, the gradient with respect to every parameter (rvc_disc_weight_grad); without it a loaded net is what it was.
+    CUDA tensors only: there is no CPU path."""
     VERSION = 1
 
-    def __init__(self, use_spectral_norm=False, device="cuda:0"):
+    def __init__(self, use_spectral_norm=False, device="cuda:0", trainable=False):
         if use_spectral_norm:
             raise NotImplementedError("spectral norm is not implemented (use_spectral_norm is false in every shipped configuration)")
         self.device = torch.device(device)
@@ -286,6 +289,9 @@ class _MultiPeriodDiscriminator:
         h = C.c_void_p()
         _lib.check(_lib.lib.rvc_disc_create(self._ctx, self.VERSION, C.byref(h)))
         self._h = h
+        self.trainable = bool(trainable)
+        if self.trainable:                     # weight_v / weight_g stay on the device (about the weights' size again): what weight_grad needs
+            _lib.check(_lib.lib.rvc_disc_keep_parameters(self._h, 1))
         self._loaded = False
         self.periods = [2, 3, 5, 7, 11, 17] + ([23, 37] if self.VERSION == 2 else [])
 
@@ -432,8 +438,81 @@ class _MultiPeriodDiscriminator:
             return out, [[next(it) for _ in rows] for rows in shapes]
         return out
 
+    def weight_grad_launch_count(self, S, T):
+        """Kernel launches of one weight_grad over S signals of T samples (rvc_disc_weight_grad_launch_count: the size of the plan; nothing is launched):
+        two per layer (gradient, finish), whatever S and T."""
+        n = _lib.lib.rvc_disc_weight_grad_launch_count(self._h, int(S), int(T))
+        if n < 0:
+            raise _lib.RvcHipError(_lib.lib.rvc_last_error().decode("utf-8", "replace"))
+        return n
+
+    def parameter_shapes(self):
+        """OrderedDict name -> shape of the parameter tensors in the reference module's state-dict order (rvc_disc_param_info)."""
+        assert self._loaded, "load_state_dict first"
+        out = OrderedDict()
+        name, shape, ndim = C.create_string_buffer(128), (_lib.c_int64 * 8)(), C.c_int()
+        n = _lib.lib.rvc_disc_param_count(self._h)
+        if n < 0:
+            raise _lib.RvcHipError(_lib.lib.rvc_last_error().decode("utf-8", "replace"))
+        for k in range(n):
+            _lib.check(_lib.lib.rvc_disc_param_info(self._h, k, name, 128, shape, C.byref(ndim)))
+            out[name.value.decode()] = tuple(int(shape[i]) for i in range(ndim.value))
+        return out
+
+    def weight_grad(self, x, fmaps, deltas):
+        """The gradient with respect to every parameter (rvc_disc_weight_grad).  x [S,1,T]: the batch that produced `fmaps` (forward_single(x); for the
+        trainer torch.cat([y, y_hat])); fmaps: those feature maps; deltas: what input_grad(fmaps, cotangents, return_deltas=True) returned beside the input
+        gradient.  Returns an OrderedDict from state-dict name (per layer bias, weight_g, weight_v) to a float32 device tensor in the parameter's shape: views
+        of ONE contiguous buffer in that order (`.flat` of the result holds it), so an optimizer can walk a single buffer.  Needs trainable=True."""
+        assert self._loaded, "load_state_dict first"
+        if not self.trainable:
+            raise ValueError("weight_grad: the discriminators were built without trainable=True (weight_v / weight_g are not kept on the device)")
+        if not (hasattr(x, "is_cuda") and x.is_cuda):
+            raise ValueError("weight_grad: x must be a device tensor (there is no CPU path)")
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise ValueError(f"weight_grad: x must be [S, 1, T]: got {tuple(x.shape)}")
+        S_, T, dev = int(x.shape[0]), int(x.shape[2]), x.device
+        for p in self.periods:
+            if (p - T % p) % p >= T:
+                raise ValueError(f"T = {T} is not longer than the reflect pad period {p} needs")
+        shapes = self.tap_shapes(T)
+        for what, lists in (("feature map", fmaps), ("delta", deltas)):
+            if len(lists) != len(shapes) or [len(r) for r in lists] != [len(r) for r in shapes]:
+                raise ValueError(f"weight_grad: one {what} per tap of every sub-discriminator expected")
+        flat_f, flat_d = [], []
+        for i, rows in enumerate(shapes):
+            for l, (c, h, p) in enumerate(rows):
+                want = (S_, c, h, p) if i else (S_, c, h)
+                for what, t, dst in (("feature map", fmaps[i][l], flat_f), ("delta", deltas[i][l], flat_d)):
+                    if t is None or not (hasattr(t, "is_cuda") and t.is_cuda) or t.device != dev:
+                        raise ValueError(f"weight_grad: {what} ({i}, {l}) must be a tensor on {dev} (there is no CPU path)")
+                    if t.dtype != torch.float32 or tuple(t.shape) != want or not t.is_contiguous():
+                        raise ValueError(f"weight_grad: {what} ({i}, {l}) must be a contiguous float32 tensor of shape {want}: got {t.dtype} {tuple(t.shape)}")
+                    dst.append(t)
+        sig = x.detach().to(torch.float32).reshape(S_, T).contiguous()
+        params = self.parameter_shapes()
+        sizes = [int(np.prod(s)) for s in params.values()]
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        out, o = _GradDict(), 0
+        for (name, shape), n in zip(params.items(), sizes):
+            out[name] = flat[o:o + n].view(shape)
+            o += n
+        out.flat = flat
+        n = len(flat_f)
+        pf = (C.c_void_p * n)(*[t.data_ptr() for t in flat_f])
+        pd = (C.c_void_p * n)(*[t.data_ptr() for t in flat_d])
+        pg = (C.c_void_p * len(out))(*[t.data_ptr() for t in out.values()])
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.rvc_disc_weight_grad(self._h, _lib.current_stream(), _lib.ptr(sig), S_, T, pf, pd, pg))
+        return out
+
     def __call__(self, *args, **kwargs):
         return self.forward(*args, **kwargs)
+
+
+class _GradDict(OrderedDict):
+    """weight_grad's result: name -> gradient view; `.flat` is the one contiguous float32 buffer the views share, in the dict's order."""
+    flat = None
 
 
 class MultiPeriodDiscriminator(_MultiPeriodDiscriminator):

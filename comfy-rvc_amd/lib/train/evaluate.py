@@ -8,9 +8,10 @@ import numpy as np
 import torch
 
 from ..infer_pack import models
+from ..infer_pack.commons import clip_grad_value_
 from . import data_utils
-from .losses import (MultiScaleMelSpectrogramLoss, combined_aux_loss, discriminator_loss, feature_loss, generator_loss, gradient_norm_loss, kl_loss,
-                     l1_loss)
+from .losses import (MultiScaleMelSpectrogramLoss, combined_aux_loss, discriminator_grads, discriminator_loss, feature_loss, generator_loss,
+                     gradient_norm_loss, kl_loss, l1_loss)
 from .mel_processing import mel_spectrogram_torch, spec_to_mel_torch
 
 
@@ -90,12 +91,15 @@ def reconstruction_losses(net_g, batch, hps, generator=None, *, noise=None, ids_
     return out
 
 
-def adversarial_losses(net_d, wave, y_hat, ids_slice=None, hps=None, generator=None):
+def adversarial_losses(net_d, wave, y_hat, ids_slice=None, hps=None, generator=None, grad_norm=False):
     """loss_disc, loss_gen, loss_fm of one batch as the trainer forms them (reference training_cli.py:545-553,:567-572,:585): wave [B,1,Tw] the real waves,
     sliced to y_hat's segments at ids_slice * hop_length when ids_slice is given (wave already sliced otherwise), y_hat [B,1,segment_size].  One
     net_d(wave, y_hat) serves all three: without a backward pass the trainer's two calls compute the same.  0-dim float32 device tensors.
     hps.train.c_gp > 0: "gradient_penalty" = gradient_norm_loss(wave, y_hat, net_d) * c_gp is added, the term the trainer adds to loss_disc (:552), its alpha
-    drawn from `generator` (a CPU torch.Generator; None: the global one).  loss_disc itself stays the plain discriminator loss."""
+    drawn from `generator` (a CPU torch.Generator; None: the global one).  loss_disc itself stays the plain discriminator loss.
+    grad_norm: "grad_norm_d" is added, the number the trainer logs for the discriminator step (:562): clip_grad_value_ over d loss_disc / d(parameter)
+    (losses.discriminator_grads) with batch_size = hps.train.batch_size and no clipping, a Python float.  net_d must be trainable; with c_gp > 0 the
+    penalty's second-order term would be part of it, which is not built: NotImplementedError."""
     y_hat = y_hat.detach()
     wave = torch.as_tensor(wave).to(y_hat.device, torch.float32)
     if ids_slice is not None:
@@ -107,6 +111,9 @@ def adversarial_losses(net_d, wave, y_hat, ids_slice=None, hps=None, generator=N
     c_gp = _train_get(hps, "c_gp", 0.) if hps is not None else 0.
     if c_gp > 0:
         out["gradient_penalty"] = gradient_norm_loss(wave, y_hat, net_d, eps=_train_get(hps, "eps", 1e-8), generator=generator) * c_gp
+    if grad_norm:
+        _, grads = discriminator_grads(net_d, wave, y_hat, c_gp=c_gp)
+        out["grad_norm_d"] = clip_grad_value_(grads.values(), None, batch_size=int(_train_get(hps, "batch_size", 1)) if hps is not None else 1)
     return out
 
 
@@ -123,29 +130,32 @@ def load_generator(ckpt, hps, version="v2", f0=True, device="cuda:0"):
     return net
 
 
-def load_discriminator(ckpt, version="v2", device="cuda:0"):
+def load_discriminator(ckpt, version="v2", device="cuda:0", trainable=False):
     """A trainer's D_*.pth ({"model": state_dict, ...}, reference lib/train/utils.py:120-131) or a bare state dict -> the loaded discriminators
-    (MultiPeriodDiscriminatorV2 for "v2", MultiPeriodDiscriminator for "v1": training_cli.py picks them by version)."""
+    (MultiPeriodDiscriminatorV2 for "v2", MultiPeriodDiscriminator for "v1": training_cli.py picks them by version).  trainable: weight_v / weight_g stay
+    on the device, so that the parameter gradients can be formed (grad_norm_d)."""
     cpt = torch.load(ckpt, map_location="cpu") if isinstance(ckpt, str) else ckpt
     sd = cpt["model"] if isinstance(cpt, dict) and "model" in cpt else cpt
     cls = models.MultiPeriodDiscriminatorV2 if version == "v2" else models.MultiPeriodDiscriminator
-    return cls(False, device=device).load_state_dict(sd)
+    return cls(False, device=device, trainable=trainable).load_state_dict(sd)
 
 
 def evaluate_checkpoint(ckpt, filelist, hps, seed=1337, batch_size=4, boundaries=(32, 100, 200, 300, 400, 500, 600, 700, 800, 900), version="v2", f0=True,
-                        device="cuda:0", ckpt_d=None):
+                        device="cuda:0", ckpt_d=None, grad_norm=False):
     """Walks `filelist` through the loader, the collate and the bucket sampler (unshuffled) and returns {"loss_mel", "loss_kl": means over the batches,
     "batches": [{"loss_mel", "loss_kl", "ids_slice"}...]}.  The sampler buckets by file size (dataset.lengths), so a batch may still hold an item whose
     labels are shorter than the segment: such a batch cannot be sliced and is left out.  The draws come from torch.Generator().manual_seed(seed): the same seed gives the same two numbers.
     ckpt_d (a D_*.pth path, a state dict or loaded discriminators): loss_disc, loss_gen and loss_fm are added per batch and as means; None: nothing changes.
     With ckpt_d and hps.train.c_gp > 0 also gradient_penalty (the penalty times c_gp, as the trainer adds it), its alpha drawn from the walk's generator after
     the batch's forward draws; with c_gp absent or 0 no draw is made and the result is what it was.
+    grad_norm (needs ckpt_d): also grad_norm_d per batch and as a mean, the trainer's logged gradient norm of the discriminator step; the discriminators are
+    then loaded trainable (loaded ones must have been).
     hps.train.use_multiscale / c_hd / c_tsi as in reconstruction_losses; the multi-scale state is the checkpoint's "msml" entry when ckpt is a path or a
     checkpoint dict that has one."""
     cpt = torch.load(ckpt, map_location="cpu") if isinstance(ckpt, str) else ckpt
     msml = multiscale_state(hps, cpt) if _train_get(hps, "use_multiscale", False) else None
     net = cpt if hasattr(cpt, "forward") else load_generator(cpt, hps, version, f0, device)
-    net_d = None if ckpt_d is None else (ckpt_d if hasattr(ckpt_d, "forward") else load_discriminator(ckpt_d, version, device))
+    net_d = None if ckpt_d is None else (ckpt_d if hasattr(ckpt_d, "forward") else load_discriminator(ckpt_d, version, device, trainable=grad_norm))
     seg = hps.train.segment_size // hps.data.hop_length
     ds = (data_utils.TextAudioLoaderMultiNSFsid if f0 else data_utils.TextAudioLoader)(filelist, hps.data)
     collate = data_utils.TextAudioCollateMultiNSFsid() if f0 else data_utils.TextAudioCollate()
@@ -162,13 +172,13 @@ def evaluate_checkpoint(ckpt, filelist, hps, seed=1337, batch_size=4, boundaries
         row = {"loss_mel": float(r["loss_mel"]), "loss_kl": float(r["loss_kl"]), "ids_slice": r["ids_slice"].cpu().numpy()}
         row.update({k: float(r[k]) for k in ("harmonic_loss", "tsi_loss") if k in r})
         if net_d is not None:
-            adv = adversarial_losses(net_d, batch[6 if f0 else 4], r["y_hat"], r["ids_slice"], hps, generator=gen)
+            adv = adversarial_losses(net_d, batch[6 if f0 else 4], r["y_hat"], r["ids_slice"], hps, generator=gen, grad_norm=grad_norm)
             row.update({k: float(v) for k, v in adv.items()})
         rows.append(row)
     if not rows:
         raise ValueError("no batch of the file list has every item at least segment_size long")
     names = ["loss_mel", "loss_kl"] + (["loss_disc", "loss_gen", "loss_fm"] if net_d is not None else [])
-    names += [k for k in ("gradient_penalty", "harmonic_loss", "tsi_loss") if k in rows[0]]
+    names += [k for k in ("gradient_penalty", "grad_norm_d", "harmonic_loss", "tsi_loss") if k in rows[0]]
     out = {k: float(np.mean([r[k] for r in rows])) for k in names}
     out["batches"] = rows
     return out

@@ -5,8 +5,10 @@ returns 0-dim float32 tensors.
 
 One derivative is formed: the gradient of a discriminator-side loss with respect to the input waveform (models._MultiPeriodDiscriminator.input_grad, a
 vector-Jacobian product through the discriminators on the device).  gradient_norm_loss (:401-426, the trainer's gradient penalty) and
-adversarial_input_grads (the gradients and norms LossBalancer.calculate_gradients reads for loss_gen and loss_fm, :76-92) are built on it.  No weight
-gradient, no optimizer, no generator backward; LossBalancer itself is not ported.
+adversarial_input_grads (the gradients and norms LossBalancer.calculate_gradients reads for loss_gen and loss_fm, :76-92) are built on it.  The same pass
+leaves dL / d(pre-activation) of every layer, from which discriminator_grads forms the discriminator step's parameter gradients
+(models._MultiPeriodDiscriminator.weight_grad; without the gradient penalty's second-order term).  No optimizer, no generator backward; LossBalancer itself
+is not ported.
 
 Also the two generator-side terms the trainer adds on request: MultiScaleMelSpectrogramLoss (:430-561, `hps.train.use_multiscale`) and combined_aux_loss
 (:344-399) with its parts compute_harmonics, compute_envelope and compute_tsi_loss.  compute_tefs (the temporal envelope / fine structure term) is not
@@ -173,6 +175,31 @@ def adversarial_input_grads(net_d, wave, y_hat):
              "loss_fm": net_d.input_grad(fmap_g, [[next(it) for _ in d] for d in fmap_g])}
     norms = {k: _item_sq_norms(g).sqrt().mean().to(torch.float32) for k, g in grads.items()}
     return grads, norms
+
+
+def discriminator_grads(net_d, y, y_hat, c_gp=0.0):
+    """(loss_disc, grads): the discriminator step's loss (reference training_cli.py:549-553) and d loss_disc / d(parameter) for every parameter of net_d, what
+    loss_disc.backward() leaves in net_d.parameters() (:560).  y, y_hat [B,1,T] device tensors (y_hat is used detached, as the trainer's gen_wave).  ONE
+    forward over the 2 B signals, the scores' cotangents from rvc_loss_cotangents (kind 1 on the real rows, kind 0 on the generated rows, scale 2 / numel
+    of one half), one input_grad and one weight_grad.  loss_disc is discriminator_loss of those scores (bit-equal); grads is weight_grad's OrderedDict
+    (state-dict name -> float32 device tensor, views of one buffer).  net_d must be built with trainable=True.
+    The gradient penalty's contribution is NOT built (it needs the second-order term d/dtheta |d loss / d x|): c_gp > 0 raises NotImplementedError."""
+    if c_gp and c_gp > 0:
+        raise NotImplementedError("discriminator_grads: the gradient penalty's parameter gradient (a second-order term) is not implemented: c_gp must be 0")
+    y, y_hat = _dev(y), _dev(y_hat)
+    if y.dim() != 3 or y.shape[1] != 1 or y.shape != y_hat.shape:
+        raise ValueError(f"discriminator_grads: two [B, 1, T] tensors expected: {tuple(y.shape)} and {tuple(y_hat.shape)}")
+    B = int(y.shape[0])
+    x = torch.cat([y, y_hat]).contiguous()
+    fmaps = net_d.forward_single(x)
+    real = [torch.flatten(d[-1][:B], 1, -1) for d in fmaps]
+    fake = [torch.flatten(d[-1][B:], 1, -1) for d in fmaps]
+    loss_disc, _ = discriminator_loss(real, fake)
+    scale = [2.0 / t.numel() for t in real]
+    cr, cg = _cotangents(1, real, None, scale), _cotangents(0, fake, None, scale)
+    cots = [[None] * (len(d) - 1) + [torch.cat([r, g]).reshape(d[-1].shape)] for d, r, g in zip(fmaps, cr, cg)]
+    _, deltas = net_d.input_grad(fmaps, cots, return_deltas=True)
+    return loss_disc, net_d.weight_grad(x, fmaps, deltas)
 
 
 # ------------------------------------------------------------------------------------------------- multi-scale mel loss (reference lib/train/losses.py:430-561)

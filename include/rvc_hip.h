@@ -15,6 +15,7 @@
  *   rvc_sqerr_sums       <- discriminator_loss / generator_loss          lib/train/losses.py:571-593
  *   rvc_l1_sums          <- feature_loss                                 lib/train/losses.py:564-569
  *   rvc_disc_input_grad  <- torch.autograd.grad(loss, [wave]) through net_d      lib/train/losses.py:401-426 (gradient_norm_loss), :76-92 (LossBalancer)
+ *   rvc_disc_weight_grad <- loss_disc.backward() onto net_d.parameters()            training_cli.py:559-562 (optim_d's gradients; grad_norm_d)
  *   rvc_loss_cotangents  <- the backward of the three GAN losses                 lib/train/losses.py:564-593
  *   rvc_interpolate      <- alpha * original + (1 - alpha) * generated            lib/train/losses.py:407
  *   rvc_vc_segment       <- VC.vc (features -> x2 upsample -> protect -> infer)   vc_infer_pipeline.py:25-114
@@ -282,6 +283,23 @@ int rvc_l1_sums(void* stream, const float* const* a_dev, const float* const* b_d
 int rvc_disc_input_grad(rvc_disc* d, void* stream, int S, int64_t T, const float* const* fmaps_dev, const float* const* dtaps_dev, float* const* work_dev,
                         float* dsignals_dev);
 int rvc_disc_input_grad_launch_count(rvc_disc* d, int S, int64_t T);
+/* The weight-gradient pass: dL / d(parameter) of every weight_g, weight_v (or plain weight) and bias, from the feature maps of rvc_disc_forward and the
+ * per-layer deltas rvc_disc_input_grad left in work_dev for the same S signals.  OPT-IN: rvc_disc_keep_parameters(d, 1) BEFORE rvc_disc_finalize keeps
+ * weight_v / weight_g on the device (about the size of the weights again) for the chain through weight norm; without it a loaded net's device memory and
+ * plans are unchanged and rvc_disc_weight_grad fails.  rvc_disc_param_count / rvc_disc_param_info: the parameter tensors in the reference module's
+ * state-dict order (per layer bias, weight_g, weight_v; weight, bias for a plain-weight checkpoint), name (NUL-terminated, name_cap bytes) and shape
+ * (at most 8 dimensions).  grads_dev: HOST array of one device pointer per parameter tensor in that order, each fully written; the call owns no memory
+ * apart from stream scratch.  dW[m][c][j] = sum_s sum_n delta[s][m][n] X[s][c][stride h' + j - pad][w], db[m] = sum_s sum_n delta[s][m][n] (float64),
+ * grad_g[m] = <dW[m], v[m]> / |v[m]|, grad_v[m] = (g[m] / |v[m]|) (dW[m] - <dW[m], v[m]> / |v[m]|^2 v[m]) (torch's weight_norm(dim=0) backward).  The dense
+ * k = 5 layers run on the matrix cores (bf16x3, both operands split in the kernel); every reduction is split into partial images added in index order:
+ * no atomics, two calls give the same bits.  rvc_disc_weight_grad_launch_count: the size of its plan (touches no stream), two launches per layer
+ * whatever S and T; -1 on error. */
+int rvc_disc_keep_parameters(rvc_disc* d, int on);
+int rvc_disc_param_count(rvc_disc* d);
+int rvc_disc_param_info(rvc_disc* d, int k, char* name, int name_cap, int64_t* shape, int* ndim);
+int rvc_disc_weight_grad(rvc_disc* d, void* stream, const float* signals_dev, int S, int64_t T, const float* const* fmaps_dev,
+                         const float* const* deltas_dev, float* const* grads_dev);
+int rvc_disc_weight_grad_launch_count(rvc_disc* d, int S, int64_t T);
 /* Cotangents of the GAN losses for K <= 64 tensors in one launch; a_dev / b_dev / out_dev, n, scale: HOST arrays of K device pointers, lengths, factors.
  *   kind 0: out = scale a             d mean(s^2) / ds with scale = 2 / numel          (discriminator_loss, generated scores)
  *   kind 1: out = -scale (1 - a)      d mean((1 - s)^2) / ds with scale = 2 / numel    (generator_loss; discriminator_loss, real scores)
