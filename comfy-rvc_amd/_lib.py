@@ -63,6 +63,11 @@ class SynthForwardTaps(C.Structure):
     _fields_ = [(n, c_void_p) for n in ("z", "z_p", "m_p", "logs_p", "m_q", "logs_q")]
 
 
+class AdamwHyper(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("step", c_int64), ("has_clip", c_int), ("clip_value", C.c_double)]
+
+
 # every symbol include/rvc_hip.h declares (tests check that the library exports all of them)
 SIGNATURES = {
     "rvc_last_error": (c_char_p, []),
@@ -134,6 +139,12 @@ SIGNATURES = {
     "rvc_disc_param_info": (c_int, [c_void_p, c_int, c_char_p, c_int, P(c_int64), P(c_int)]),
     "rvc_disc_weight_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, P(c_void_p), P(c_void_p), P(c_void_p)]),
     "rvc_disc_weight_grad_launch_count": (c_int, [c_void_p, c_int, c_int64]),
+    "rvc_adamw_step": (c_int, [c_void_p, P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p), P(c_int64), c_int, P(AdamwHyper)]),
+    "rvc_disc_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P(AdamwHyper)]),
+    "rvc_disc_adamw_step_launch_count": (c_int, [c_void_p]),
+    "rvc_disc_param_total": (c_int64, [c_void_p]),
+    "rvc_disc_get_parameters": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "rvc_disc_set_parameters": (c_int, [c_void_p, c_void_p, c_void_p]),
     "rvc_loss_cotangents": (c_int, [c_void_p, c_int, P(c_void_p), P(c_void_p), P(c_int64), P(c_float), c_int, P(c_void_p)]),
     "rvc_interpolate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "rvc_synth_dec_halo": (c_int, [c_void_p]),

@@ -12,8 +12,8 @@
 // the feature maps the forward wrote - one launch per layer again, planned the same way; see "input gradient" below.
 // The weight-gradient pass (disc_weight_grad: dL / d(weight_g, weight_v, bias) from the same feature maps and the deltas the input-gradient pass left) is two
 // launches per layer - gradient, finish -, opt-in through disc_keep_parameters; see "weight gradient" below.
-#include "model_common.h"
-#include "models.h"
+// The optimizer step (AdamW on the kept parameters, then the folded weights and the images below re-derived on the device) is disc_optim.hip.
+#include "disc_model.h"
 #include "signal_dev.h"
 
 namespace rvc {
@@ -115,28 +115,6 @@ __global__ __launch_bounds__(256) void disc_post_kernel(const DiscPostArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- model
-struct DiscLayer {
-  int Ci = 0, Co = 0, k = 0, stride = 1, pad = 0, groups = 1, CoPx = 0;
-  DevVec w, b;                       // folded fp32 weights [Co][Ci / groups][k] (the VALU layers) and bias
-  DevBuf<uint16_t> wx;               // bf16x3 image (the GEMM layers)
-  DevBuf<uint16_t> wxb[3];           // the GEMM layers' data gradient: one transposed image per phase of the input row (stride of them), rows Ci padded to CiPx
-  int CiPx = 0;
-  DevVec pv, pg;                     // weight_v [Co][Ci / groups][k] and weight_g [Co] as loaded: only with disc_keep_parameters (the weight-norm chain of weight_grad)
-  int gi_w = -1, gi_g = -1, gi_b = -1;   // this layer's entries of the parameter list: weight_v (or the plain weight), weight_g (-1: plain weight), bias
-};
-struct DiscParam { std::string name; std::vector<long long> shape; };
-struct DiscNet { int period = 0; std::vector<DiscLayer> L; };   // period 0: DiscriminatorS; L.back() is conv_post
-struct DiscWeights { std::vector<DiscNet> nets; };
-struct Disc : DiscWeights {
-  Ctx* ctx = nullptr;
-  int version = 2;
-  TensorStore ts;
-  bool ready = false;
-  bool keep = false;                 // disc_keep_parameters: finalize keeps weight_v / weight_g on the device and weight_grad is allowed
-  bool kept = false;                 // what the finalized net was loaded with
-  std::vector<DiscParam> params;     // the parameter tensors in the reference module's state-dict order (per layer: bias, weight_g, weight_v; or weight, bias)
-};
-
 Disc* disc_create(Ctx* ctx, int version) {
   RVC_REQUIRE(version == 1 || version == 2, "discriminator version must be 1 (MultiPeriodDiscriminator) or 2 (MultiPeriodDiscriminatorV2)");
   Disc* D = new Disc(); D->ctx = ctx; D->version = version;
@@ -150,7 +128,6 @@ static std::vector<int> disc_periods(int version) {
   if (version == 2) { p.push_back(23); p.push_back(37); }
   return p;
 }
-static bool disc_layer_is_gemm(const DiscLayer& l) { return l.groups == 1 && l.Ci % 16 == 0 && l.Co > 1; }
 
 // The transposed, phase-grouped images of a dense layer's data gradient (conv_x3d_bwd.hip).  Input row h = stride h' + j - pad: stride 1 is one product,
 // tap t (row h + t - pad of the gradient) carrying W[.][.][k - 1 - t]; stride 3 (k 5, pad 2) is one product per phase r = h mod 3, tap 0 (row j) carrying
@@ -180,7 +157,7 @@ void disc_keep_parameters(Disc* D, bool on) {
 }
 void disc_finalize(Disc* D) {
   D->ready = false; static_cast<DiscWeights&>(*D) = {};   // a finalize that throws leaves the handle not ready
-  D->params.clear(); D->kept = false;
+  D->params.clear(); D->kept = false; D->optim.reset();
   const TensorStore& ts = D->ts;
   const std::vector<int> periods = disc_periods(D->version);
   struct Spec { int Ci, Co, k, stride, pad, groups; };
@@ -218,6 +195,7 @@ void disc_finalize(Disc* D) {
       } else {
         L.gi_w = (int)D->params.size(); D->params.push_back({n + ".weight", ts.get(n + ".weight").shape});
         L.gi_b = (int)D->params.size(); D->params.push_back({n + ".bias", b.shape});
+        if (D->keep && c.groups == 1 && c.Ci % 16 == 0 && c.Co > 1) L.pv.upload(w);   // a GEMM layer keeps only images: the optimizer's fp32 master copy
       }
       if (disc_layer_is_gemm(L)) {
         L.CoPx = (c.Co + 127) & ~127;

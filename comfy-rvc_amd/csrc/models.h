@@ -63,6 +63,16 @@ int disc_param_count(const Disc* D);
 void disc_param_info(const Disc* D, int k, std::string& name, std::vector<long long>& shape);
 int disc_weight_grad_launch_count(const Disc* D, int S, long long T);   // pure, independent of S and T: two per layer
 void disc_weight_grad(Disc* D, hipStream_t s, const float* signals, int S, long long T, const float* const* fmaps, const float* const* deltas, float* const* grads);
+// disc_optim.hip.  adamw_step: torch.optim.AdamW (amsgrad off, maximize off) on K <= 64 tensors in one launch, float32 per element; the arrays are on the host.
+// disc_adamw_step: that update on every parameter the handle holds (grads / exp_avg / exp_avg_sq: caller-owned flat buffers in disc_param_info's order), then the
+// folded weights and the weight images re-derived on the stream, bit for bit as finalize builds them.  Needs disc_keep_parameters.  The launch count is a constant
+// of the net (3; 2 for a plain-weight net).  get / set: the parameters as one flat buffer in the same order; set re-derives weights and images with the same kernels
+void adamw_step(hipStream_t s, float* const* p, const float* const* g, float* const* m, float* const* v, const long long* n, int K, const rvc_adamw_hyper& h);
+void disc_adamw_step(Disc* D, hipStream_t s, const float* grads, float* exp_avg, float* exp_avg_sq, const rvc_adamw_hyper& h);
+int disc_adamw_step_launch_count(Disc* D);
+long long disc_param_total(Disc* D);
+void disc_get_parameters(Disc* D, hipStream_t s, float* flat);
+void disc_set_parameters(Disc* D, hipStream_t s, const float* flat);
 // cotangents of the GAN losses, K tensors per launch (kind 0: scale a; 1: -scale (1 - a); 2: scale sign(a - b)), and gradient_norm_loss's interpolation
 void loss_cotangents(hipStream_t s, int kind, const float* const* a, const float* const* b, const long long* n, const float* scale, int K, float* const* out);
 void interpolate_rows(hipStream_t s, const float* alpha, const float* y, const float* y_hat, int B, long long T, float* out);

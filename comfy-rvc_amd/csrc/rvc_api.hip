@@ -399,6 +399,45 @@ int rvc_disc_weight_grad(rvc_disc* d, void* stream, const float* signals, int S,
   check_launch();
   RVC_CATCH
 }
+int rvc_adamw_step(void* stream, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n, int K, const rvc_adamw_hyper* hyper) {
+  RVC_TRY
+  RVC_REQUIRE(p && g && m && v && n && hyper && K >= 1 && K <= 64, "1 <= K <= 64 tensors, no null argument");
+  long long nn[64]; for (int k = 0; k < K; ++k) nn[k] = n[k];
+  adamw_step((hipStream_t)stream, p, g, m, v, nn, K, *hyper);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_disc_adamw_step(rvc_disc* d, void* stream, const float* grads, float* exp_avg, float* exp_avg_sq, const rvc_adamw_hyper* hyper) {
+  RVC_TRY
+  RVC_REQUIRE(d && grads && exp_avg && exp_avg_sq && hyper, "null argument");
+  RVC_HIP_CHECK(hipSetDevice(d->ctx->c.device));
+  disc_adamw_step(d->m, (hipStream_t)stream, grads, exp_avg, exp_avg_sq, *hyper);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_disc_adamw_step_launch_count(rvc_disc* d) {
+  try { RVC_REQUIRE(d, "null argument"); RVC_HIP_CHECK(hipSetDevice(d->ctx->c.device)); return disc_adamw_step_launch_count(d->m); }
+  catch (const std::exception& e) { rvc::set_error(e.what()); return -1; }
+}
+int64_t rvc_disc_param_total(rvc_disc* d) {
+  try { RVC_REQUIRE(d, "null argument"); RVC_HIP_CHECK(hipSetDevice(d->ctx->c.device)); return disc_param_total(d->m); }
+  catch (const std::exception& e) { rvc::set_error(e.what()); return -1; }
+}
+int rvc_disc_get_parameters(rvc_disc* d, void* stream, float* flat) {
+  RVC_TRY
+  RVC_REQUIRE(d && flat, "null argument");
+  RVC_HIP_CHECK(hipSetDevice(d->ctx->c.device));
+  disc_get_parameters(d->m, (hipStream_t)stream, flat);
+  RVC_CATCH
+}
+int rvc_disc_set_parameters(rvc_disc* d, void* stream, const float* flat) {
+  RVC_TRY
+  RVC_REQUIRE(d && flat, "null argument");
+  RVC_HIP_CHECK(hipSetDevice(d->ctx->c.device));
+  disc_set_parameters(d->m, (hipStream_t)stream, flat);
+  check_launch();
+  RVC_CATCH
+}
 int rvc_loss_cotangents(void* stream, int kind, const float* const* a, const float* const* b, const int64_t* n, const float* scale, int K, float* const* out) {
   RVC_TRY
   RVC_REQUIRE(a && n && scale && out && K >= 1 && K <= 64, "1 <= K <= 64 tensors, no null argument");

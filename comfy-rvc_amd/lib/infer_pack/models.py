@@ -277,7 +277,8 @@ class _MultiPeriodDiscriminator:
     sub-discriminator the score [B, H p] of the real and of the generated batch and the lists of feature maps ([B,C,H,p]; [B,C,T'] for
     DiscriminatorS).  `input_grad(fmaps, tap_cotangents)` is the one backward pass: the gradient with respect to the input waveform (rvc_disc_input_grad).  Both batches run through every layer in one launch (rvc_disc_forward on the 2 B signals); the returned tensors are views of
     the buffers the layers wrote.  `trainable=True` keeps weight_v / weight_g on the device (about the weights' size again) and allows
-    `weight_grad(x, fmaps, deltas)`, the gradient with respect to every parameter (rvc_disc_weight_grad); without it a loaded net is what it was.
+    `weight_grad(x, fmaps, deltas)`, the gradient with respect to every parameter (rvc_disc_weight_grad); without it a loaded net is what it was.  A trainable
+    net can be stepped (lib.train.optim.AdamW over rvc_disc_adamw_step) and read back: `state_dict()`, `get_parameters()`, `load_parameters(flat)`.
     CUDA tensors only: there is no CPU path."""
     VERSION = 1
 
@@ -505,6 +506,75 @@ class _MultiPeriodDiscriminator:
         with torch.cuda.device(dev):
             _lib.check(_lib.lib.rvc_disc_weight_grad(self._h, _lib.current_stream(), _lib.ptr(sig), S_, T, pf, pd, pg))
         return out
+
+    def _need_trainable(self, what):
+        assert self._loaded, "load_state_dict first"
+        if not self.trainable:
+            raise ValueError(f"{what}: the discriminators were built without trainable=True (the parameters are not kept on the device)")
+
+    def parameter_count(self):
+        """Elements of all parameter tensors together: the length of weight_grad(...).flat and of the optimizer's state buffers."""
+        self._need_trainable("parameter_count")
+        with torch.cuda.device(self.device):
+            n = _lib.lib.rvc_disc_param_total(self._h)
+        if n < 0:
+            raise _lib.RvcHipError(_lib.lib.rvc_last_error().decode("utf-8", "replace"))
+        return int(n)
+
+    def get_parameters(self):
+        """The parameters the handle holds as ONE flat float32 device tensor in parameter_shapes() order (rvc_disc_get_parameters)."""
+        self._need_trainable("get_parameters")
+        flat = torch.empty(self.parameter_count(), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.rvc_disc_get_parameters(self._h, _lib.current_stream(), _lib.ptr(flat)))
+        return flat
+
+    def load_parameters(self, flat):
+        """Replaces every parameter from one flat float32 tensor in parameter_shapes() order and re-derives the folded weights and the weight images on
+        the device (rvc_disc_set_parameters: the optimizer step's kernels, the bits rvc_disc_finalize would build)."""
+        self._need_trainable("load_parameters")
+        flat = torch.as_tensor(flat)
+        if flat.dim() != 1 or flat.numel() != self.parameter_count():
+            raise ValueError(f"load_parameters: a flat tensor of {self.parameter_count()} elements expected, got {tuple(flat.shape)}")
+        flat = flat.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.rvc_disc_set_parameters(self._h, _lib.current_stream(), _lib.ptr(flat)))
+            torch.cuda.current_stream().synchronize()          # `flat` may be a temporary of this call
+        return self
+
+    def state_dict(self):
+        """OrderedDict name -> host float32 tensor of every parameter as the handle holds it now, in parameter_shapes() order: what the reference module's
+        state_dict() gives (trainable nets only: a frozen net keeps no parameters)."""
+        self._need_trainable("state_dict")
+        flat = self.get_parameters().cpu()
+        out, o = OrderedDict(), 0
+        for name, shape in self.parameter_shapes().items():
+            n = int(np.prod(shape))
+            out[name] = flat[o:o + n].view(shape).clone()
+            o += n
+        return out
+
+    def adamw_step_launch_count(self):
+        """Kernel launches of one optimizer step (rvc_disc_adamw_step_launch_count): a constant of the net."""
+        self._need_trainable("adamw_step_launch_count")
+        with torch.cuda.device(self.device):
+            n = _lib.lib.rvc_disc_adamw_step_launch_count(self._h)
+        if n < 0:
+            raise _lib.RvcHipError(_lib.lib.rvc_last_error().decode("utf-8", "replace"))
+        return n
+
+    def adamw_step(self, grads_flat, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step, clip_value=None):
+        """One AdamW step on the parameters the handle holds (rvc_disc_adamw_step); lib.train.optim.AdamW is the public face.  The three flat float32
+        device tensors are in parameter_shapes() order; exp_avg / exp_avg_sq are updated in place, grads_flat is only read."""
+        self._need_trainable("adamw_step")
+        n = self.parameter_count()
+        for what, t in (("grads", grads_flat), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+            if not (hasattr(t, "is_cuda") and t.is_cuda) or t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+                raise ValueError(f"adamw_step: {what} must be a contiguous flat float32 device tensor of {n} elements")
+        h = _lib.AdamwHyper(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step), int(clip_value is not None),
+                            float(clip_value) if clip_value is not None else 0.0)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.rvc_disc_adamw_step(self._h, _lib.current_stream(), _lib.ptr(grads_flat), _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq), C.byref(h)))
 
     def __call__(self, *args, **kwargs):
         return self.forward(*args, **kwargs)

@@ -7,8 +7,8 @@ One derivative is formed: the gradient of a discriminator-side loss with respect
 vector-Jacobian product through the discriminators on the device).  gradient_norm_loss (:401-426, the trainer's gradient penalty) and
 adversarial_input_grads (the gradients and norms LossBalancer.calculate_gradients reads for loss_gen and loss_fm, :76-92) are built on it.  The same pass
 leaves dL / d(pre-activation) of every layer, from which discriminator_grads forms the discriminator step's parameter gradients
-(models._MultiPeriodDiscriminator.weight_grad; without the gradient penalty's second-order term).  No optimizer, no generator backward; LossBalancer itself
-is not ported.
+(models._MultiPeriodDiscriminator.weight_grad; without the gradient penalty's second-order term).  The optimizer step that consumes them is lib/train/optim.py
+(train_step.train_discriminator_step runs the whole discriminator half of an iteration).  No generator backward; LossBalancer itself is not ported.
 
 Also the two generator-side terms the trainer adds on request: MultiScaleMelSpectrogramLoss (:430-561, `hps.train.use_multiscale`) and combined_aux_loss
 (:344-399) with its parts compute_harmonics, compute_envelope and compute_tsi_loss.  compute_tefs (the temporal envelope / fine structure term) is not

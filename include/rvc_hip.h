@@ -16,6 +16,7 @@
  *   rvc_l1_sums          <- feature_loss                                 lib/train/losses.py:564-569
  *   rvc_disc_input_grad  <- torch.autograd.grad(loss, [wave]) through net_d      lib/train/losses.py:401-426 (gradient_norm_loss), :76-92 (LossBalancer)
  *   rvc_disc_weight_grad <- loss_disc.backward() onto net_d.parameters()            training_cli.py:559-562 (optim_d's gradients; grad_norm_d)
+ *   rvc_disc_adamw_step  <- clip_grad_value_'s clamp and optim_d.step()             training_cli.py:562-563 (torch.optim.AdamW)
  *   rvc_loss_cotangents  <- the backward of the three GAN losses                 lib/train/losses.py:564-593
  *   rvc_interpolate      <- alpha * original + (1 - alpha) * generated            lib/train/losses.py:407
  *   rvc_vc_segment       <- VC.vc (features -> x2 upsample -> protect -> infer)   vc_infer_pipeline.py:25-114
@@ -300,6 +301,34 @@ int rvc_disc_param_info(rvc_disc* d, int k, char* name, int name_cap, int64_t* s
 int rvc_disc_weight_grad(rvc_disc* d, void* stream, const float* signals_dev, int S, int64_t T, const float* const* fmaps_dev,
                          const float* const* deltas_dev, float* const* grads_dev);
 int rvc_disc_weight_grad_launch_count(rvc_disc* d, int S, int64_t T);
+/* The optimizer step: torch.optim.AdamW (amsgrad = False, maximize = False), float32 per element:
+ *   g' = clamp(g, +-clip_value) when has_clip;  p *= 1 - lr wd;  m += (g' - m)(1 - beta1);  v = v beta2 + (1 - beta2) g'^2;
+ *   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps),  bc_i = 1 - beta_i^step
+ * Every operation is rounded on its own (no fused contraction; IEEE sqrt and division); the scalars 1 - lr wd, lr / bc1 and sqrt(bc2) are formed in double on
+ * the host.  step is the step being taken (>= 1).  g is only read: the clamp happens on read.
+ * rvc_adamw_step: K <= 64 tensors in ONE launch; p_dev / g_dev / m_dev / v_dev and n are HOST arrays of K device pointers and lengths.  Pointers need 4-byte
+ * alignment only (a float4 body runs where the four pointers of a tensor share their offset from 16 bytes).  K > 64 fails and launches nothing. */
+typedef struct rvc_adamw_hyper {
+  double lr, beta1, beta2, eps, weight_decay;
+  int64_t step;
+  int has_clip;
+  double clip_value;
+} rvc_adamw_hyper;
+int rvc_adamw_step(void* stream, float* const* p_dev, const float* const* g_dev, float* const* m_dev, float* const* v_dev, const int64_t* n, int K,
+                   const rvc_adamw_hyper* hyper);
+/* The discriminators' step (reference training_cli.py:562-563).  grads_flat_dev / exp_avg_flat_dev / exp_avg_sq_flat_dev: caller-owned flat float32 buffers of
+ * rvc_disc_param_total elements in rvc_disc_param_info's order (the layout of weight_grad's buffer).  The call updates the parameters the handle holds (bias,
+ * weight_g, weight_v, or the plain weight) and then, on the same stream, re-derives what the three passes read: the folded fp32 weights of the VALU layers
+ * and, for the dense k = 5 layers, the forward image and the one or three transposed phase images - bit for bit what rvc_disc_finalize builds on the host from
+ * the same parameters (the row norm is summed in float64 in the host's order).  Needs rvc_disc_keep_parameters(d, 1) before finalize; a plain-weight net kept
+ * that way holds an fp32 master copy of its dense weights from finalize on.  rvc_disc_adamw_step_launch_count: kernel launches of one step, a constant of the
+ * net (3: update, fold, images; 2 for a plain-weight net); -1 on error.  rvc_disc_get_parameters / rvc_disc_set_parameters: the parameters as one flat device
+ * buffer in the same order; set re-derives weights and images with the step's kernels.  Nothing changes for a net that is never stepped. */
+int rvc_disc_adamw_step(rvc_disc* d, void* stream, const float* grads_flat_dev, float* exp_avg_flat_dev, float* exp_avg_sq_flat_dev, const rvc_adamw_hyper* hyper);
+int rvc_disc_adamw_step_launch_count(rvc_disc* d);
+int64_t rvc_disc_param_total(rvc_disc* d);
+int rvc_disc_get_parameters(rvc_disc* d, void* stream, float* flat_dev);
+int rvc_disc_set_parameters(rvc_disc* d, void* stream, const float* flat_dev);
 /* Cotangents of the GAN losses for K <= 64 tensors in one launch; a_dev / b_dev / out_dev, n, scale: HOST arrays of K device pointers, lengths, factors.
  *   kind 0: out = scale a             d mean(s^2) / ds with scale = 2 / numel          (discriminator_loss, generated scores)
  *   kind 1: out = -scale (1 - a)      d mean((1 - s)^2) / ds with scale = 2 / numel    (generator_loss; discriminator_loss, real scores)
