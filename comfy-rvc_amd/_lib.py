@@ -120,6 +120,7 @@ SIGNATURES = {
     "rvc_synth_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64,
                                   c_void_p, P(SynthForwardTaps)]),
     "rvc_kl_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
+    "rvc_kl_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rvc_l1_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "rvc_disc_create": (c_int, [c_void_p, c_int, P(c_void_p)]),
     "rvc_disc_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, P(c_int64), c_int]),
@@ -189,6 +190,10 @@ SIGNATURES = {
     "rvc_mel_filterbank_set": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rvc_spec_to_mel_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
     "rvc_spectrogram_batch_ms": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_int64]),
+    "rvc_mel_spectrogram_vjp": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_int64,
+                                        c_void_p]),
+    "rvc_mel_spectrogram_vjp_launch_count": (c_int, []),
+    "rvc_mel_loss_cotangents": (c_int, [c_void_p, c_int, P(c_void_p), P(c_void_p), P(c_int64), c_int, c_float, c_float, P(c_float), P(c_void_p)]),
     "rvc_multiscale_mel_loss": (c_int, [c_void_p, c_void_p, c_int, P(c_void_p), P(c_int64), P(c_int64), c_int, c_int64, P(C.c_int32), P(C.c_int32), c_int, c_int,
                                         c_void_p]),
     "rvc_hpss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),

@@ -34,6 +34,8 @@ void synth_forward(Synth* S, hipStream_t s, const float* feat, int feat_channel_
 // train_forward.hip: z = m + noise exp(logs) from stats [m | logs] (2 C rows); columns [ids, ids + seg) of x [C][T] -> y [C][seg]; the two loss reductions
 void posterior_sample(hipStream_t s, const float* stats, const float* noise, float* z, int C, int T);
 void segment_gather(hipStream_t s, const float* x, int C, int T, int ids, int seg, float* y);
+void kl_loss_grad(hipStream_t s, const float* z_p, const float* m_p, const float* logs_p, int C, long long ldT, long long len, float scale, float* dz_p,
+                  float* dlogs_q, float* dm_p, float* dlogs_p);
 void kl_loss_sum(hipStream_t s, const float* z_p, const float* logs_q, const float* m_p, const float* logs_p, int C, long long ldT, long long len, double* out2);
 void l1_sum(hipStream_t s, const float* a, const float* b, long long n, double* out1);
 int synth_dec_halo_frames(const Synth* S);   // pure host: frames of z the generator's output depends on to either side
@@ -129,6 +131,14 @@ void mel_filterbank_set(Ctx* ctx, int n_fft, int n_mels, const int* first, const
 void spec_to_mel_batch(Ctx* ctx, hipStream_t s, const float* spec, long long spec_pitch, const long long* clips, int n_clips, int n_fft, int n_mels,
                        float* mel, long long mel_pitch);
 void spec_state_free(Ctx* ctx);
+// the adjoint of spectrogram_batch_ms followed by spec_to_mel_batch: cot [n_mels][pitch] on the log-mel -> d_audio [n_audio] (every sample of every clip is
+// written); clips as spectrogram_batch, the column now the clip's first cotangent column; 2 launches
+void mel_spectrogram_vjp(Ctx* ctx, hipStream_t s, const float* audio, long long n_audio, const long long* clips, int n_clips, int n_fft, int hop, float eps,
+                         int clamp, int n_mels, const float* cot, long long pitch, float* d_audio);
+constexpr int kMelVjpLaunches = 2;
+// d(log_weight mean loss(a, b) + mag_weight mean loss(exp a, exp b)) / da times scale[k] for K <= 8 pairs of log-mels; one launch
+void mel_loss_cotangents(hipStream_t s, int K, const float* const* a, const float* const* b, const long long* n, int loss, float log_weight, float mag_weight,
+                         const float* scale, float* const* out);
 // the same for the multi-scale loss's geometries: n_fft 256 .. 4096, any hop with n_fft - hop even (hop > n_fft: frames centred in their hop, no reflection)
 void spectrogram_batch_ms(Ctx* ctx, hipStream_t s, const float* audio, long long n_audio, const long long* clips, int n_clips, int n_fft, int hop, float eps,
                           int clamp, float* out, long long pitch);

@@ -293,6 +293,14 @@ int rvc_synth_forward(rvc_synth* s, void* stream, const float* phone, int phone_
   check_launch();
   RVC_CATCH
 }
+int rvc_kl_loss_grad(void* stream, const float* z_p, const float* m_p, const float* logs_p, int C, int64_t T_pitch, int64_t len, float scale, float* dz_p,
+                     float* dlogs_q, float* dm_p, float* dlogs_p) {
+  RVC_TRY
+  RVC_REQUIRE(z_p && m_p && logs_p && dz_p && dlogs_q && dm_p && dlogs_p, "null argument");
+  kl_loss_grad((hipStream_t)stream, z_p, m_p, logs_p, C, T_pitch, len, scale, dz_p, dlogs_q, dm_p, dlogs_p);
+  check_launch();
+  RVC_CATCH
+}
 int rvc_kl_loss(void* stream, const float* z_p, const float* logs_q, const float* m_p, const float* logs_p, int C, int64_t T_pitch, int64_t len, double* sum) {
   RVC_TRY
   RVC_REQUIRE(z_p && logs_q && m_p && logs_p && sum, "null argument");
@@ -755,6 +763,22 @@ int rvc_spectrogram_batch_ms(rvc_ctx* ctx, void* stream, const float* audio, int
   RVC_TRY
   RVC_REQUIRE(ctx && audio && out && (clips || n_clips == 0), "null argument");
   spectrogram_batch_ms(&ctx->c, (hipStream_t)stream, audio, n_audio, (const long long*)clips, n_clips, n_fft, hop, eps, clamp, out, pitch);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_mel_spectrogram_vjp(rvc_ctx* ctx, void* stream, const float* audio, int64_t n_audio, const int64_t* clips, int n_clips, int n_fft, int hop, float eps,
+                            int clamp, int n_mels, const float* cot_mel, int64_t pitch, float* d_audio) {
+  RVC_TRY
+  RVC_REQUIRE(ctx && audio && cot_mel && d_audio && (clips || n_clips == 0), "null argument");
+  mel_spectrogram_vjp(&ctx->c, (hipStream_t)stream, audio, n_audio, (const long long*)clips, n_clips, n_fft, hop, eps, clamp, n_mels, cot_mel, pitch, d_audio);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_mel_spectrogram_vjp_launch_count(void) { return kMelVjpLaunches; }
+int rvc_mel_loss_cotangents(void* stream, int K, const float* const* a, const float* const* b, const int64_t* n, int loss, float log_weight, float mag_weight,
+                            const float* scale, float* const* out) {
+  RVC_TRY
+  mel_loss_cotangents((hipStream_t)stream, K, a, b, (const long long*)n, loss, log_weight, mag_weight, scale, out);
   check_launch();
   RVC_CATCH
 }

@@ -3,6 +3,7 @@
 //   segment gather      columns [ids, ids + seg) of a [C][T] tensor  (lib/infer_pack/commons.py:150-166 slice_segments / slice_segments2)
 //   kl_loss             sum of logs_p - logs_q - 0.5 + 0.5 (z_p - m_p)^2 exp(-2 logs_p) over the unmasked columns (lib/train/losses.py:596-611)
 //   l1 sum              sum |a - b|                                  (F.l1_loss, training_cli.py:570)
+//   kl_loss backward    the four cotangents of that sum, element-wise (what loss_gen_all.backward() sends into z_p, logs_q, m_p, logs_p)
 // The reductions accumulate in float64 in a fixed order: kLossParts blocks each sum a contiguous chunk (thread-strided, then block_sum), ONE block adds
 // the partials in index order.  No floating-point atomics: two calls give the same bits.
 #include "rvc_internal.h"
@@ -76,6 +77,28 @@ static void loss_sum(hipStream_t s, const Term& term, long long n, double* out, 
 void kl_loss_sum(hipStream_t s, const float* z_p, const float* logs_q, const float* m_p, const float* logs_p, int C, long long ldT, long long len, double* out2) {
   RVC_REQUIRE(C > 0 && len > 0 && len <= ldT, "kl_loss: 0 < len <= T_pitch expected");
   loss_sum(s, KlTerm{z_p, logs_q, m_p, logs_p, ldT, len}, (long long)C * len, out2, (double)len, 1);
+}
+// kl_loss's backward for one item: with r = (z_p - m_p) exp(-2 logs_p), d z_p = scale r, d m_p = -scale r, d logs_q = -scale,
+// d logs_p = scale (1 - (z_p - m_p) r) for t < len and exactly 0 behind; float64 from the float32 inputs, rounded once.
+__global__ __launch_bounds__(256) void kl_loss_grad_kernel(const float* __restrict__ z_p, const float* __restrict__ m_p, const float* __restrict__ logs_p, long long ldT,
+                                                           long long len, long long n, double scale, float* __restrict__ dz_p, float* __restrict__ dlogs_q,
+                                                           float* __restrict__ dm_p, float* __restrict__ dlogs_p) {
+  const long long st = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += st) {
+    float gz = 0.f, gq = 0.f, gm = 0.f, gp = 0.f;
+    if (i % ldT < len) {
+      const double d = (double)z_p[i] - (double)m_p[i], r = d * exp(-2.0 * (double)logs_p[i]);
+      gz = (float)(scale * r); gm = (float)(-(scale * r)); gq = (float)(-scale); gp = (float)(scale * (1.0 - d * r));
+    }
+    dz_p[i] = gz; dlogs_q[i] = gq; dm_p[i] = gm; dlogs_p[i] = gp;
+  }
+}
+void kl_loss_grad(hipStream_t s, const float* z_p, const float* m_p, const float* logs_p, int C, long long ldT, long long len, float scale, float* dz_p,
+                  float* dlogs_q, float* dm_p, float* dlogs_p) {
+  RVC_REQUIRE(C > 0 && ldT > 0 && len >= 0 && len <= ldT, "kl_loss_grad: 0 <= len <= T_pitch expected");
+  const long long n = (long long)C * ldT;
+  const int blocks = (int)std::min<long long>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(kl_loss_grad_kernel, dim3(blocks), dim3(256), 0, s, z_p, m_p, logs_p, ldT, len, n, (double)scale, dz_p, dlogs_q, dm_p, dlogs_p);
 }
 void l1_sum(hipStream_t s, const float* a, const float* b, long long n, double* out1) {
   RVC_REQUIRE(n > 0, "l1_sum: n > 0 expected");

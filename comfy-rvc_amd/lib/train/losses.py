@@ -1,4 +1,4 @@
-"""The trainer's losses on device tensors, forward only: the two reconstruction losses (reference lib/train/losses.py:596-611 kl_loss; F.l1_loss as
+"""The trainer's losses on device tensors: the two reconstruction losses (reference lib/train/losses.py:596-611 kl_loss; F.l1_loss as
 training_cli.py:570 uses it) and the three GAN losses (:564-593 feature_loss, discriminator_loss, generator_loss).  Each is a fixed-order float64
 reduction on the device (rvc_kl_loss per item, rvc_l1_sum; rvc_sqerr_sums / rvc_l1_sums: one segmented reduction over all tensors of a loss) and
 returns 0-dim float32 tensors.
@@ -8,7 +8,12 @@ vector-Jacobian product through the discriminators on the device).  gradient_nor
 adversarial_input_grads (the gradients and norms LossBalancer.calculate_gradients reads for loss_gen and loss_fm, :76-92) are built on it.  The same pass
 leaves dL / d(pre-activation) of every layer, from which discriminator_grads forms the discriminator step's parameter gradients
 (models._MultiPeriodDiscriminator.weight_grad; without the gradient penalty's second-order term).  The optimizer step that consumes them is lib/train/optim.py
-(train_step.train_discriminator_step runs the whole discriminator half of an iteration).  No generator backward; LossBalancer itself is not ported.
+(train_step.train_discriminator_step runs the whole discriminator half of an iteration).
+
+The generator half's loss is differentiated as far as the generator's outputs: mel_loss_grad and MultiScaleMelSpectrogramLoss.forward_and_grad return
+d loss_mel / d y_hat (mel_processing.mel_spectrogram_vjp behind rvc_mel_loss_cotangents), kl_loss_grads the four cotangents of loss_kl, and LossBalancer is
+the reference's class (:14-233) fed those per-loss gradients instead of an autograd graph (train_step.generator_loss_cotangents puts them together).  The
+generator's own backward and the gradients of the HPSS / TSI terms are not built.
 
 Also the two generator-side terms the trainer adds on request: MultiScaleMelSpectrogramLoss (:430-561, `hps.train.use_multiscale`) and combined_aux_loss
 (:344-399) with its parts compute_harmonics, compute_envelope and compute_tsi_loss.  compute_tefs (the temporal envelope / fine structure term) is not
@@ -29,15 +34,21 @@ def _dev(t):
     return t.detach().to(torch.float32).contiguous()
 
 
+def _mask_lengths(z_mask, B):
+    """int64 [B] on the host: the lengths of a sequence mask [B, 1, T]"""
+    mask = z_mask.detach().reshape(B, -1).to("cpu")
+    lengths = mask.sum(dim=1).to(torch.int64)
+    if not torch.equal(mask, (torch.arange(mask.shape[1])[None, :] < lengths[:, None]).to(mask.dtype)):
+        raise ValueError("z_mask must be a sequence mask (ones up to each length, zeros behind)")
+    return lengths
+
+
 def kl_loss(z_p, logs_q, m_p, logs_p, z_mask):
     """z_p, logs_q, m_p, logs_p [B, C, T]; z_mask [B, 1, T], a sequence mask (ones up to each item's length): sum over the unmasked elements of
     logs_p - logs_q - 0.5 + 0.5 (z_p - m_p)^2 exp(-2 logs_p), divided by sum(z_mask)."""
     z_p, logs_q, m_p, logs_p = (_dev(t) for t in (z_p, logs_q, m_p, logs_p))
     B, C, T = z_p.shape
-    mask = z_mask.detach().reshape(B, -1).to("cpu")
-    lengths = mask.sum(dim=1).to(torch.int64)
-    if not torch.equal(mask, (torch.arange(mask.shape[1])[None, :] < lengths[:, None]).to(mask.dtype)):
-        raise ValueError("z_mask must be a sequence mask (ones up to each length, zeros behind)")
+    lengths = _mask_lengths(z_mask, B)
     sums = torch.zeros(B, 2, dtype=torch.float64, device=z_p.device)
     with torch.cuda.device(z_p.device):
         st = _lib.current_stream()
@@ -47,6 +58,23 @@ def kl_loss(z_p, logs_q, m_p, logs_p, z_mask):
                                                 _lib.ptr(sums[b])))
     tot = sums.sum(dim=0)
     return (tot[0] / tot[1]).to(torch.float32)
+
+
+def kl_loss_grads(z_p, logs_q, m_p, logs_p, z_mask, scale=1.0):
+    """{"z_p", "logs_q", "m_p", "logs_p"} -> d (scale * kl_loss) / d that tensor, each [B, C, T] float32 on the device and exactly 0 behind an item's length
+    (rvc_kl_loss_grad, one launch per item)."""
+    z_p, logs_q, m_p, logs_p = (_dev(t) for t in (z_p, logs_q, m_p, logs_p))
+    B, C, T = z_p.shape
+    lengths = _mask_lengths(z_mask, B)
+    total = int(lengths.sum())
+    out = {k: torch.empty_like(z_p) for k in ("z_p", "logs_q", "m_p", "logs_p")}
+    with torch.cuda.device(z_p.device):
+        st = _lib.current_stream()
+        for b in range(B):
+            _lib.check(_lib.lib.rvc_kl_loss_grad(st, _lib.ptr(z_p[b]), _lib.ptr(m_p[b]), _lib.ptr(logs_p[b]), C, T, int(lengths[b]),
+                                                 float(scale) / total if total else 0.0, _lib.ptr(out["z_p"][b]), _lib.ptr(out["logs_q"][b]),
+                                                 _lib.ptr(out["m_p"][b]), _lib.ptr(out["logs_p"][b])))
+    return out
 
 
 def l1_loss(a, b):
@@ -164,17 +192,45 @@ def gradient_norm_loss(original_audio, generated_audio, net_d, eps=1e-8, alpha=N
     return (loss, g) if return_gradient else loss
 
 
-def adversarial_input_grads(net_d, wave, y_hat):
+def adversarial_input_grads(net_d, wave, y_hat, return_losses=False):
     """({"loss_gen": d generator_loss / d y_hat, "loss_fm": d feature_loss / d y_hat}, each [B,1,T] float32, and {"loss_gen": norm, "loss_fm": norm}): the norms
-    as LossBalancer.calculate_gradients forms them (per-item 2-norm, mean over the batch), 0-dim float32 device tensors.  One net_d(wave, y_hat) serves both."""
-    _, _, fmap_r, fmap_g = net_d(wave, y_hat)
+    as LossBalancer.calculate_gradients forms them (per-item 2-norm, mean over the batch), 0-dim float32 device tensors.  One net_d(wave, y_hat) serves both.
+    return_losses: a third dict {"loss_gen", "loss_fm"} with generator_loss and feature_loss of the same forward."""
+    _, y_d_g, fmap_r, fmap_g = net_d(wave, y_hat)
     fmap_g = [[t.contiguous() for t in d] for d in fmap_g]
     fr, fg = [t for d in fmap_r for t in d], [t for d in fmap_g for t in d]
     it = iter(_cotangents(2, fg, fr, [1.0 / t.numel() for t in fg]))
     grads = {"loss_gen": net_d.input_grad(fmap_g, _score_cotangents(fmap_g, 1)),
              "loss_fm": net_d.input_grad(fmap_g, [[next(it) for _ in d] for d in fmap_g])}
     norms = {k: _item_sq_norms(g).sqrt().mean().to(torch.float32) for k, g in grads.items()}
+    if return_losses:
+        return grads, norms, {"loss_gen": generator_loss(y_d_g)[0], "loss_fm": feature_loss(fmap_r, fmap_g)}
     return grads, norms
+
+
+def _mel_cotangents(kind, a, b, log_weight, mag_weight, scales):
+    """rvc_mel_loss_cotangents over lists of log-mels (a generated, b target): one launch, float32 tensors in the shapes of `a`."""
+    a, pa, n = _segments(a)
+    b, pb, _ = _segments(b)
+    if len(a) > 8 or any(x.shape != y.shape for x, y in zip(a, b)):
+        raise ValueError("mel cotangents: at most 8 pairs of log-mels, each pair of one shape")
+    out = [torch.empty_like(t) for t in a]
+    po = (_lib.c_void_p * len(a))(*[t.data_ptr() for t in out])
+    sc = (_lib.c_float * len(a))(*scales)
+    with torch.cuda.device(a[0].device):
+        _lib.check(_lib.lib.rvc_mel_loss_cotangents(_lib.current_stream(), len(a), pa, pb, n, _LOSS_KINDS[kind], float(log_weight), float(mag_weight), sc, po))
+    return out
+
+
+def mel_loss_grad(y_mel, y_hat, n_fft, n_mels, sampling_rate, hop_length, win_length, fmin, fmax, return_mel=False):
+    """(loss_mel, d loss_mel / d y_hat) for loss_mel = l1_loss(y_mel, mel_spectrogram_torch(y_hat, ...)) (training_cli.py:533-542,:570): y_mel [B, n_mels, frames],
+    y_hat [B, 1, T] device tensors; the loss is bit-equal to that expression, the gradient [B, 1, T] float32.  return_mel: also y_hat's log-mel."""
+    y_hat_mel = MP.mel_spectrogram_torch(y_hat, n_fft, n_mels, sampling_rate, hop_length, win_length, fmin, fmax)
+    loss = l1_loss(y_mel, y_hat_mel)
+    gen = _dev(y_hat_mel)
+    cot = _mel_cotangents("l1", [gen], [_dev(y_mel)], 1.0, 0.0, [1.0 / gen.numel()])[0]
+    grad = MP.mel_spectrogram_vjp(_dev(y_hat), cot, n_fft, n_mels, sampling_rate, hop_length, win_length, fmin, fmax)
+    return (loss, grad, y_hat_mel) if return_mel else (loss, grad)
 
 
 def discriminator_grads(net_d, y, y_hat, c_gp=0.0):
@@ -202,13 +258,163 @@ def discriminator_grads(net_d, y, y_hat, c_gp=0.0):
     return loss_disc, net_d.weight_grad(x, fmaps, deltas)
 
 
+# ------------------------------------------------------------------------------------------------- loss balancer (reference lib/train/losses.py:14-233)
+class LossBalancer:
+    """The reference's LossBalancer without an autograd graph: the weights of the generator's (or the discriminator's) loss terms, redistributed every batch
+    in proportion to each term's gradient norm at the model's output (use_norm) or to the relative change of the loss against its moving average, optionally
+    mixed with a Pareto weighting of the moving averages, and smoothed by a moving average of their own.  Host arithmetic on the loss VALUES, step by step as
+    the reference (float32 tensors times Python floats; the state dictionaries hold Python / NumPy floats), so a recorded trajectory is reproduced.
+
+    Where the reference differentiates each weighted loss with respect to `input`, on_train_batch_start takes the gradients: input_grads maps a key to
+    d(unweighted loss) / d input, [B, 1, T] on the device, or to None; the norm is the per-item 2-norm, mean over the batch, of nan_to_num(weight * gradient,
+    epsilon), formed on the device (_item_sq_norms).  grad_norms maps a key to that norm where the caller already holds it.  A key in neither has norm 0 and,
+    as every norm <= epsilon, falls back to the loss's relative change - what the reference's materialize_grads=True gives a loss without a path to `input`
+    (loss_kl).  With both None the reference's `input=None` path is taken.  `model` is kept for the signature and may be None.
+    last_weights: key -> float, the weights of the last balanced sum."""
+
+    def __init__(self, model=None, initial_weights={}, historical_losses={}, ema_weights={}, epsilon=1e-8, weights_decay=0., loss_decay=.0, active=True,
+                 use_pareto=True, use_norm=False):
+        self.model = model
+        self.epsilon = epsilon
+        self.weights_decay = weights_decay
+        self.loss_decay = loss_decay
+        self.initial_weights = initial_weights
+        self.ema_weights = ema_weights
+        self.historical_losses = historical_losses
+        self.active = active
+        self.use_pareto = use_pareto
+        self.use_norm = use_norm
+        self.last_weights = {}
+
+    def to_dict(self):
+        return dict(epsilon=self.epsilon, weights_decay=self.weights_decay, loss_decay=self.loss_decay, ema_weights=self.ema_weights,
+                    initial_weights=self.initial_weights, historical_losses=self.historical_losses, active=self.active, use_pareto=self.use_pareto,
+                    use_norm=self.use_norm)
+
+    def update_ema_weights(self, new_weights):
+        if not self.ema_weights:
+            self.ema_weights = dict(**new_weights)
+        else:
+            d = self.weights_decay
+            self.ema_weights = {k: np.nan_to_num(d * self.ema_weights.get(k, 1.) + (1 - d) * new_weights[k], nan=self.epsilon) for k in new_weights}
+        return dict(**self.ema_weights)
+
+    def update_historical_losses(self, new_losses):
+        if not self.historical_losses:
+            self.historical_losses = dict(**new_losses)
+        else:
+            d = self.loss_decay
+            for k, v in new_losses.items():
+                self.historical_losses[k] = np.nan_to_num(d * self.historical_losses.get(k, v) + (1 - d) * v, nan=self.epsilon)
+        return dict(**self.historical_losses)
+
+    def calculate_loss_slope(self, key, current_loss):
+        """|current - average| / average of a 0-dim tensor against the loss's moving average (itself when the key is new)"""
+        ema_loss = self.historical_losses.get(key, current_loss) + self.epsilon
+        return ((current_loss - ema_loss) / ema_loss).abs()
+
+    def calculate_gradients(self, key, current_loss, weight, grad, norm=None):
+        """The norm of weight * grad (or `norm`, or 0 without either) as a 0-dim float32 tensor; the loss's slope where that is <= epsilon."""
+        if norm is not None:
+            grad_norm = torch.tensor(float(norm), dtype=torch.float32)
+        elif grad is not None:
+            g = (_dev(grad) * weight).nan_to_num(self.epsilon)
+            g = g if g.dim() > 1 else g[None]
+            grad_norm = _item_sq_norms(g).sqrt().mean().to(torch.float32).cpu()
+        else:
+            grad_norm = torch.zeros((), dtype=torch.float32)
+        if grad_norm <= self.epsilon:
+            grad_norm = self.calculate_loss_slope(key, current_loss)
+        return grad_norm
+
+    def pareto_normalizer(self, loss_dict, weight=.8):
+        """The losses' shares with the largest contributors - those that reach `weight` of the total between them - counted len(losses) times."""
+        keys = list(loss_dict.keys())
+        losses = np.array(list(loss_dict.values()))
+        share = losses / np.sum(losses)
+        order = np.argsort(share)[::-1]
+        top = np.argmax(np.cumsum(share[order]) >= weight)
+        factor = np.ones_like(losses)
+        factor[order[:top + 1]] = len(losses)
+        out = losses * factor
+        out /= np.sum(out) + self.epsilon
+        return {keys[i]: out[i] for i in range(len(keys))}
+
+    def redistribute_weights(self, gradients):
+        pareto = self.pareto_normalizer(self.historical_losses) if self.use_pareto else {}
+        inverse_total = 1. / (sum(gradients.values()) + self.epsilon)
+        spare = sum(self.initial_weights.values()) - len(gradients)           # the weight to hand out above 1 per term
+        if spare < 0:
+            return {k: 1. for k in gradients}
+        out = {}
+        for k, g in gradients.items():
+            ratio = g * inverse_total
+            out[k] = 1. + spare * (pareto.get(k, ratio) * .5 + ratio * .5)
+        return out
+
+    def on_train_batch_start(self, losses, input_grads=None, grad_norms=None):
+        """losses: key -> 0-dim tensor (or a Python number, which is skipped) -> the balanced sum, a 0-dim float32 tensor on the losses' device."""
+        self.last_weights = {}
+        if len(losses) == 0:
+            return 0.
+        if not self.initial_weights:
+            self.initial_weights = {k: 1. for k in losses}
+        if not self.ema_weights:
+            self.ema_weights = {k: 1. for k in losses}
+        device = next((v.device for v in losses.values() if isinstance(v, torch.Tensor)), torch.device("cpu"))
+        host = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in losses.items()}
+        if not self.active:
+            self.update_historical_losses({k: v.item() * self.initial_weights.get(k, 1.) for k, v in host.items() if v > 0})
+            self.last_weights = {k: float(self.initial_weights.get(k, 1.)) for k in host}
+            total = sum(v * self.initial_weights.get(k, 1.) for k, v in host.items())
+            return total.to(device) if isinstance(total, torch.Tensor) else total
+        with_norm = self.use_norm and (input_grads is not None or grad_norms is not None)
+        gradients, valid = {}, {}
+        for key, loss in host.items():
+            weight = self.initial_weights.get(key, 1.)
+            if weight == 0 or loss == 0 or not isinstance(loss, torch.Tensor):
+                continue
+            weighted = loss * weight
+            if with_norm:
+                measure = self.calculate_gradients(key, weighted, weight, (input_grads or {}).get(key), (grad_norms or {}).get(key))
+            else:
+                measure = self.calculate_loss_slope(key, weighted)
+            gradients[key] = max(measure.item(), self.epsilon)
+            valid[key] = loss.nan_to_num(self.epsilon)
+        if not valid or not gradients:
+            return torch.tensor(0.0)
+        self.update_historical_losses({k: v.item() for k, v in valid.items()})
+        weights = self.redistribute_weights(gradients) if len(valid) > 1 else {k: self.initial_weights.get(k, 1.) for k in valid}
+        weights = self.update_ema_weights(weights)
+        balanced = 0
+        for k, v in valid.items():
+            balanced += weights.get(k, 1.) * v
+        self.last_weights = {k: float(weights.get(k, 1.)) for k in valid}
+        return balanced.to(device)
+
+    def on_epoch_end(self, weights_decay=None, loss_decay=None):
+        if weights_decay is not None:
+            self.weights_decay = weights_decay
+        if loss_decay is not None:
+            self.loss_decay = loss_decay
+        weights = dict(sorted(self.ema_weights.items(), key=lambda kv: kv[1], reverse=True))
+        losses = dict(sorted(self.historical_losses.items(), key=lambda kv: kv[1], reverse=True))
+        print(f"|| EMA weights: {weights} ({self.weights_decay=})")
+        print(f"|| EMA losses: {losses} ({self.loss_decay=})")
+        print(f"===> Weighted EMA loss: {self.weighted_ema_loss:.3f} <====")
+
+    @property
+    def weighted_ema_loss(self):
+        return sum(v * self.ema_weights.get(k, 1.) for k, v in self.historical_losses.items())
+
+
 # ------------------------------------------------------------------------------------------------- multi-scale mel loss (reference lib/train/losses.py:430-561)
 STFTParams = namedtuple("STFTParams", ["window_length", "hop_length"])
 _LOSS_KINDS = {"l1": 0, "l2": 1, "smoothl1": 2}
 
 
 class MultiScaleMelSpectrogramLoss:
-    """The reference's class on the device, forward only.  x and y go through each STFT together (2 B rows in one launch, one STFT per distinct window
+    """The reference's class on the device; forward_and_grad adds the gradient at its first argument.  x and y go through each STFT together (2 B rows in one launch, one STFT per distinct window
     length), then one kernel per scale projects both spectrograms, forms the pointwise loss and reduces it in float64; the log-mels are never stored.
     Launches per call: (distinct window lengths) + (scales) + 1 = 4 + 6 + 1 = 11 with the default n_mels, whatever B and T."""
 
@@ -279,8 +485,8 @@ class MultiScaleMelSpectrogramLoss:
                 elif deviation < -self.epsilon:
                     self.mel_fmax[i] = max(self.mel_fmax[i] * (1 - adjustment), self.mel_fmin[i] + self.frequency_buffer)
 
-    def forward(self, x, y):
-        """x, y [B, 1, T] device tensors -> the mean over the scales of log_weight * loss(log-mels) + mag_weight * loss(exp(log-mels)), 0-dim float32."""
+    def _scales(self, x, y):
+        """(per-scale losses [K] float32 on the device, the packed spectrograms per scale, both waves [2 B, T], frames): everything forward computes"""
         if self.center:
             raise NotImplementedError("center=True is not implemented (the reference never passes it)")
         x, y = _dev(x), _dev(y)
@@ -316,9 +522,46 @@ class MultiScaleMelSpectrogramLoss:
         if self.mag_weight > 0:
             scale = scale + self.mag_weight * means[:, 1]
         self.scale_losses = scale
+        return scale, per, both, nf
+
+    def forward(self, x, y):
+        """x, y [B, 1, T] device tensors -> the mean over the scales of log_weight * loss(log-mels) + mag_weight * loss(exp(log-mels)), 0-dim float32."""
+        scale = self._scales(x, y)[0]
         if self.adjustment_factor > 0:
             self.adjust_fmin_fmax([float(v) for v in scale.tolist()])
-        return scale.sum() / K
+        return scale.sum() / len(self.n_mels)
+
+    def forward_and_grad(self, x, y, return_mels=False):
+        """(loss, d loss / d x) with x the first argument, as the trainer calls MultiscaleMelLoss(y_hat, wave): loss is forward(x, y) bit for bit (the same
+        launches), the gradient has x's shape, float32.  adjust_fmin_fmax runs after both, so the gradient belongs to the bands the loss used.
+        On top of the forward's launches (one STFT per distinct window length W, K + 1 for the K scales' losses) the log-mels of both signals are stored -
+        they are small - and differentiated: K projections, K copies that split them into the two signals, 1 launch for all cotangents
+        (rvc_mel_loss_cotangents), 2 K for the vector-Jacobian products (rvc_mel_spectrogram_vjp per scale) and 1 sum over the scales:
+        W + 5 K + 3 = 37 launches with the default n_mels (W = 4, K = 6), whatever B and T.
+        return_mels: also [(log-mel of x, log-mel of y)] per scale, each [n_mels, B, frames]."""
+        scale, per, both, nf = self._scales(x, y)
+        B, K = both.shape[0] // 2, len(self.n_mels)
+        T = both.shape[1]
+        gen, tgt = [], []
+        with torch.cuda.device(both.device):
+            for n_mels, fmin, fmax, s, (spec, _, nfa) in zip(self.n_mels, self.mel_fmin, self.mel_fmax, self.stft_params, per):
+                cols = np.array([(r * nfa, nf) for r in range(2 * B)], dtype=np.int64)
+                mel = MP.mel_packed(spec, cols, s.window_length, n_mels, self.sampling_rate, fmin, fmax)      # (the alignment columns stay unwritten and unread)
+                halves = mel.view(n_mels, 2, B * nfa).permute(1, 0, 2).contiguous()
+                gen.append(halves[0])
+                tgt.append(halves[1])
+            cots = _mel_cotangents(self.loss, gen, tgt, self.log_weight, self.mag_weight, [1.0 / (K * B * m * nf) for m in self.n_mels])
+            grads = torch.empty(K, B, T, device=both.device, dtype=torch.float32)
+            for k, (n_mels, fmin, fmax, s, (_, _, nfa)) in enumerate(zip(self.n_mels, self.mel_fmin, self.mel_fmax, self.stft_params, per)):
+                MP.mel_vjp_packed(both[:B].reshape(-1), np.array([(r * T, T, r * nfa) for r in range(B)], dtype=np.int64), cots[k], s.window_length,
+                                  s.hop_length, 0.0, False, n_mels, self.sampling_rate, fmin, fmax, out=grads[k].view(-1))
+            grad = grads.sum(dim=0).view(x.shape)
+        if self.adjustment_factor > 0:
+            self.adjust_fmin_fmax([float(v) for v in scale.tolist()])
+        loss = scale.sum() / K
+        if return_mels:
+            return loss, grad, [(g.view(g.shape[0], B, -1)[:, :, :nf], t.view(t.shape[0], B, -1)[:, :, :nf]) for g, t in zip(gen, tgt)]
+        return loss, grad
 
     __call__ = forward
 

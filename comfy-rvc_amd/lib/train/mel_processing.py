@@ -6,6 +6,9 @@ plumbing only.  `spectrogram_batch` is the ragged entry the spectrogram cache us
 `spectrogram_torch` and `mel_spectrogram_torch` send n_fft 1024 / 2048 with hop <= n_fft through rvc_spectrogram_batch and every other geometry (n_fft
 256 .. 4096, also hop > n_fft, where the reference's negative padding crops) through rvc_spectrogram_batch_ms.
 
+`mel_spectrogram_vjp` is the backward of `mel_spectrogram_torch` with respect to the waveform (rvc_mel_spectrogram_vjp: the forward FFT redone in LDS, the
+filterbank's transpose, the inverse FFT, an overlap-add gather; 2 launches): what torch.autograd.grad sends into y_hat from a cotangent on its log-mel.
+
 Differences from the reference: `center=True` raises (the reference never passes it); n_fft 256 .. 4096 with win_size == n_fft; spectrogram_torch
 does not print the reference's out-of-range warnings (they would cost a device round trip; the clamp to +-1.05 itself is applied); `mel_filterbank`
 restates librosa.filters.mel and is PARITY-UNPINNED (see its docstring).
@@ -254,3 +257,46 @@ def mel_spectrogram_torch(wav, n_fft, n_mels, sampling_rate, hop_length, window_
     B, Cn, T = wav.shape
     spec = _rows_spectrogram(wav.reshape(-1, T), n_fft, hop_length, 0.0, False)
     return _rows_mel(spec, n_fft, n_mels, sampling_rate, fmin, fmax).to(dtype=wav.dtype)
+
+
+def mel_vjp_packed(audio, table, cot, n_fft, hop_size, eps, clamp, n_mels, sampling_rate, fmin, fmax, out=None):
+    """One rvc_mel_spectrogram_vjp (2 launches): audio = 1-D float32 device tensor, table = int64 [n, 3] numpy (sample offset, samples, first cotangent column),
+    cot = [n_mels, pitch] float32 device tensor on the log-mel -> d_audio in audio's shape; every sample of every listed clip is written."""
+    table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 3)
+    assert audio.is_cuda and cot.is_cuda and audio.dtype == torch.float32 and cot.dtype == torch.float32 and audio.is_contiguous() and cot.is_contiguous()
+    assert cot.dim() == 2 and cot.shape[0] == n_mels
+    if out is None:
+        out = torch.empty_like(audio)
+    with torch.cuda.device(audio.device):
+        _ensure_bank(_dev_index(audio), n_fft, n_mels, sampling_rate, fmin, fmax)
+        _lib.check(_lib.lib.rvc_mel_spectrogram_vjp(_lib.get_ctx(_dev_index(audio)), _lib.current_stream(), _lib.ptr(audio), audio.numel(), _lib.ptr(table),
+                                                    table.shape[0], int(n_fft), int(hop_size), float(eps), int(bool(clamp)), int(n_mels), _lib.ptr(cot), cot.shape[1],
+                                                    _lib.ptr(out)))
+    return out
+
+
+def rows_mel_vjp(y, cot, nfa, n_fft, hop_size, eps, clamp, n_mels, sampling_rate, fmin, fmax):
+    """y [R, T] on the device, cot [n_mels, >= R * nfa] with row r's frames from column r * nfa -> the gradient [R, T]."""
+    R, T = y.shape
+    if T < min_samples(n_fft, hop_size):
+        raise ValueError(f"{T} samples: n_fft {n_fft} at hop {hop_size} needs at least {min_samples(n_fft, hop_size)}")
+    table = np.array([(r * T, T, r * nfa) for r in range(R)], dtype=np.int64).reshape(-1, 3)
+    x = y.detach().float().contiguous().reshape(-1)
+    return mel_vjp_packed(x, table, cot, n_fft, hop_size, eps, clamp, n_mels, sampling_rate, fmin, fmax).view(R, T)
+
+
+def mel_spectrogram_vjp(wav, cot_mel, n_fft, n_mels, sampling_rate, hop_length, window_length, fmin, fmax, center=False):
+    """The vector-Jacobian product of mel_spectrogram_torch: wav [B, C, T] (device tensor), cot_mel [B * C, n_mels, T // hop_length] on its log-mel ->
+    d <cot_mel, mel_spectrogram_torch(wav, ...)> / d wav, [B, C, T] in wav's dtype.  2 launches behind one re-layout of the cotangent."""
+    _check_geometry(n_fft, window_length, center)
+    if not wav.is_cuda or not cot_mel.is_cuda:
+        raise ValueError("mel_spectrogram_vjp runs on the device: pass CUDA tensors (there is no CPU path)")
+    B, Cn, T = wav.shape
+    nf = frames_of(T, hop_length)
+    if tuple(cot_mel.shape) != (B * Cn, n_mels, nf):
+        raise ValueError(f"mel_spectrogram_vjp: cot_mel must be [{B * Cn}, {n_mels}, {nf}]: got {tuple(cot_mel.shape)}")
+    if nf == 0:
+        return torch.zeros_like(wav)
+    cot = cot_mel.detach().float().permute(1, 0, 2).reshape(n_mels, B * Cn * nf).contiguous()
+    g = rows_mel_vjp(wav.reshape(-1, T), cot, nf, n_fft, hop_length, 0.0, False, n_mels, sampling_rate, fmin, fmax)
+    return g.view(B, Cn, T).to(dtype=wav.dtype)

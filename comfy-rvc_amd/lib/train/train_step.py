@@ -1,8 +1,14 @@
 """The discriminator half of one trainer iteration on the device (reference training_cli.py:549-563): forward, discriminator_loss, backward,
 clip_grad_value_, optim_d.step().  fp32 only: the reference's GradScaler with fp16_run off is the identity, and autocast is not implemented.  The gradient
-penalty's parameter gradient is not built: c_gp > 0 raises (losses.discriminator_grads)."""
+penalty's parameter gradient is not built: c_gp > 0 raises (losses.discriminator_grads).
+
+Of the generator half (:565-601) the loss and its cotangents at the generator's outputs: generator_loss_cotangents.  The generator's own backward, its
+optimizer step and the gradients of the HPSS / TSI / TEFS terms are not built."""
+import torch
+
 from ..infer_pack.commons import clip_grad_value_
-from .losses import discriminator_grads
+from .evaluate import _train_get, multiscale_state
+from .losses import adversarial_input_grads, discriminator_grads, kl_loss, kl_loss_grads, mel_loss_grad
 
 
 def train_discriminator_step(net_d, optim_d, y, y_hat, clip_value=None, batch_size=1, c_gp=0.0):
@@ -15,3 +21,42 @@ def train_discriminator_step(net_d, optim_d, y, y_hat, clip_value=None, batch_si
     grad_norm_d = clip_grad_value_(grads.values(), None, batch_size=batch_size)
     optim_d.step(grads, clip_value)
     return loss_disc, grad_norm_d
+
+
+GEN_LOSS_KEYS = ("loss_gen", "loss_fm", "loss_mel", "loss_kl", "harmonic_loss", "tsi_loss", "tefs_loss")      # the order the trainer hands them to balancer_g
+
+
+def generator_loss_cotangents(net_d, balancer_g, wave, y_hat, y_mel, kl_taps, z_mask, hps, msml=None):
+    """The generator's loss of one iteration and what its backward pass starts from (reference training_cli.py:567-595 and the first step of :598).
+    wave, y_hat [B,1,T] device tensors (the sliced real waves and the generated segments), y_mel [B, n_mels, frames] the sliced target log-mel, kl_taps =
+    (z_p, logs_q, m_p, logs_p) [B,C,T'] with their mask z_mask [B,1,T'], balancer_g a losses.LossBalancer.  ONE net_d(wave, y_hat) gives loss_gen, loss_fm
+    and their gradients at y_hat (losses.adversarial_input_grads); loss_mel is l1_loss on the log-mels or, with hps.train.use_multiscale, msml(y_hat, wave)
+    (msml None: evaluate.multiscale_state(hps)), each with its gradient; loss_kl has none at y_hat.  The balancer reads the losses and those gradients
+    (use_norm) and weighs the terms.  Returns
+      loss_gen_all   the balanced sum, 0-dim float32 device tensor;
+      terms          key -> loss in the trainer's order (GEN_LOSS_KEYS; the three auxiliary terms are the Python 0);
+      d_y_hat        d loss_gen_all / d y_hat = sum_k w_k d loss_k / d y_hat over the terms the balancer kept, [B,1,T] float32 (summed in float64, rounded once);
+      kl_cotangents  losses.kl_loss_grads scaled by loss_kl's weight: d loss_gen_all / d (z_p, logs_q, m_p, logs_p).
+    The weights are balancer_g.last_weights and are constants of the backward pass, as in the reference (they are floats there).
+    The gradients of the auxiliary terms are not built: hps.train.c_hd, c_tsi or c_tefs > 0 raises NotImplementedError."""
+    for name in ("c_hd", "c_tsi", "c_tefs"):
+        if _train_get(hps, name, 0.) > 0:
+            raise NotImplementedError(f"generator_loss_cotangents: hps.train.{name} > 0: the backward of the auxiliary losses is not implemented")
+    d = hps.data
+    grads, _, adv = adversarial_input_grads(net_d, wave, y_hat, return_losses=True)
+    if bool(_train_get(hps, "use_multiscale", False)):
+        loss_mel, grads["loss_mel"] = (msml if msml is not None else multiscale_state(hps)).forward_and_grad(y_hat, wave)
+    else:
+        loss_mel, grads["loss_mel"] = mel_loss_grad(y_mel, y_hat, d.filter_length, d.n_mel_channels, d.sampling_rate, d.hop_length, d.win_length, d.mel_fmin,
+                                                    d.mel_fmax)
+    z_p, logs_q, m_p, logs_p = kl_taps
+    terms = dict(loss_gen=adv["loss_gen"], loss_fm=adv["loss_fm"], loss_mel=loss_mel, loss_kl=kl_loss(z_p, logs_q, m_p, logs_p, z_mask), harmonic_loss=0,
+                 tsi_loss=0, tefs_loss=0)
+    loss_gen_all = balancer_g.on_train_batch_start(terms, input_grads={**grads, "loss_kl": None})
+    w = balancer_g.last_weights
+    d_y_hat = torch.zeros(y_hat.shape, dtype=torch.float64, device=y_hat.device)
+    for k, g in grads.items():
+        if k in w:
+            d_y_hat += w[k] * g.view(y_hat.shape).double()
+    kl_cot = kl_loss_grads(z_p, logs_q, m_p, logs_p, z_mask, scale=w.get("loss_kl", 0.0))
+    return loss_gen_all, terms, d_y_hat.to(torch.float32), kl_cot

@@ -11,6 +11,9 @@
  *   rvc_synth_forward    <- SynthesizerTrnMs{256,768}NSFsid.forward      lib/infer_pack/models.py:665-680,:781-796 (PosteriorEncoder :199-238)
  *   rvc_kl_loss          <- kl_loss                                      lib/train/losses.py:596-611
  *   rvc_l1_sum           <- F.l1_loss(y_mel, y_hat_mel)                  training_cli.py:570
+ *   rvc_kl_loss_grad     <- loss_kl's share of loss_gen_all.backward()   training_cli.py:571,:598
+ *   rvc_mel_spectrogram_vjp <- torch.autograd.grad(loss_mel, [y_hat]) through mel_spectrogram_torch   lib/train/mel_processing.py:117-150, lib/train/losses.py:76-92
+ *   rvc_mel_loss_cotangents <- the backward of F.l1_loss(y_mel, y_hat_mel) / MultiScaleMelSpectrogramLoss's loss_fn   training_cli.py:569-570, lib/train/losses.py:530-561
  *   rvc_disc_forward     <- MultiPeriodDiscriminator[V2].forward         lib/infer_pack/models.py:1024-1145 (net_d: training_cli.py:549,:567)
  *   rvc_sqerr_sums       <- discriminator_loss / generator_loss          lib/train/losses.py:571-593
  *   rvc_l1_sums          <- feature_loss                                 lib/train/losses.py:564-569
@@ -240,6 +243,11 @@ int rvc_synth_forward(rvc_synth* s, void* stream, const float* phone_dev, int ph
  * (float64 accumulation, fixed order: two calls give the same bits), sum_dev[1] = len (the mask's sum); rows have pitch T_pitch >= len. */
 int rvc_kl_loss(void* stream, const float* z_p_dev, const float* logs_q_dev, const float* m_p_dev, const float* logs_p_dev, int C, int64_t T_pitch,
                 int64_t len, double* sum_dev);
+/* The cotangents of rvc_kl_loss's sum for one item, each times scale (the caller passes weight / sum(mask)): rows c < C of pitch T_pitch, and for t < len
+ *   dz_p = scale (z_p - m_p) exp(-2 logs_p), dm_p = -dz_p, dlogs_q = -scale, dlogs_p = scale (1 - (z_p - m_p)^2 exp(-2 logs_p));
+ * exactly 0 for len <= t < T_pitch.  Formed in float64 from the float32 inputs and rounded once.  One launch. */
+int rvc_kl_loss_grad(void* stream, const float* z_p_dev, const float* m_p_dev, const float* logs_p_dev, int C, int64_t T_pitch, int64_t len, float scale,
+                     float* dz_p_dev, float* dlogs_q_dev, float* dm_p_dev, float* dlogs_p_dev);
 /* sum_dev[0] = sum_i |a[i] - b[i]| over n elements, float64 accumulation in a fixed order (F.l1_loss = that / n, training_cli.py:570) */
 int rvc_l1_sum(void* stream, const float* a_dev, const float* b_dev, int64_t n, double* sum_dev);
 
@@ -506,6 +514,24 @@ int rvc_spec_to_mel_batch(rvc_ctx* ctx, void* stream, const float* spec_dev, int
  * owns 16 frames (8 at n_fft 4096, where 16 would not fit the LDS); at 256 and 512 a wave transforms four frames. */
 int rvc_spectrogram_batch_ms(rvc_ctx* ctx, void* stream, const float* audio_dev, int64_t n_audio, const int64_t* clips_host, int n_clips, int n_fft, int hop,
                              float eps, int clamp, float* out_dev, int64_t pitch);
+/* The vector-Jacobian product of the log-mel spectrogram: the adjoint of rvc_spectrogram_batch_ms followed by rvc_spec_to_mel_batch through the filterbank
+ * set for (n_fft, n_mels).  Same clip table (HOST, [n_clips][3] = (sample offset, samples N, first column)), same geometries, same eps and clamp switches;
+ * cot_mel_dev [n_mels][pitch] is the cotangent on the log-mel, clip c's frames in columns [column, column + N / hop).  d_audio_dev [n_audio]: EVERY sample
+ * of every listed clip is written (the caller need not zero it; samples of no clip are not touched): the reflect padding is folded back onto the samples
+ * it mirrors, samples between the frames of a hop > n_fft geometry and samples the clamp cut off (|x| > 1.05) get exactly 0, and a mel value at or above
+ * the 1e-5 floor passes its cotangent (torch's clamp backward).  A workgroup redoes the forward FFT of a few frames in LDS (16 at n_fft 256 / 512, 8 at
+ * 1024 / 2048, 4 at 4096), back-projects through the banded filterbank, runs the inverse transform with the uploaded twiddles and leaves the windowed
+ * frame gradients in the stream's scratch; a gather kernel overlap-adds them per sample, frames in index order.  No atomics: two calls give the same
+ * bits.  rvc_mel_spectrogram_vjp_launch_count() = 2 launches, whatever the number and the lengths of the clips. */
+int rvc_mel_spectrogram_vjp(rvc_ctx* ctx, void* stream, const float* audio_dev, int64_t n_audio, const int64_t* clips_host, int n_clips, int n_fft, int hop,
+                            float eps, int clamp, int n_mels, const float* cot_mel_dev, int64_t pitch, float* d_audio_dev);
+int rvc_mel_spectrogram_vjp_launch_count(void);
+/* Cotangents of the mel losses for K <= 8 pairs of log-mels in one launch; a_dev (generated) / b_dev (target) / out_dev, n, scale: HOST arrays of K device
+ * pointers, lengths, factors.  out = scale d(log_weight sum loss(a, b) + mag_weight sum loss(exp a, exp b)) / da: the caller folds the means' 1 / numel
+ * into scale.  loss 0 l1 (sign(0) = 0, as rvc_loss_cotangents kind 2), 1 l2, 2 smoothl1 with beta 1.  A weight <= 0 drops its term.  Every element is
+ * formed in float64 from the float32 log-mels and rounded once. */
+int rvc_mel_loss_cotangents(void* stream, int K, const float* const* a_dev, const float* const* b_dev, const int64_t* n, int loss, float log_weight,
+                            float mag_weight, const float* scale, float* const* out_dev);
 /* The K <= 8 per-scale terms of MultiScaleMelSpectrogramLoss.forward(x, y).  spec_dev[k] (HOST array of device pointers) is the magnitude spectrogram
  * [n_fft[k] / 2 + 1][pitch[k]] of the 2 B signals x_0 .. x_{B-1}, y_0 .. y_{B-1}: signal r fills columns [r row_stride[k], r row_stride[k] + nf).  Per
  * scale ONE launch projects both through the filterbank set for (n_fft[k], n_mels[k]) (log(max(., 1e-5)) as rvc_spec_to_mel_batch), forms the pointwise
