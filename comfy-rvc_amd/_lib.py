@@ -119,6 +119,16 @@ SIGNATURES = {
     "rvc_synth_has_posterior": (c_int, [c_void_p]),
     "rvc_synth_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64,
                                   c_void_p, P(SynthForwardTaps)]),
+    "rvc_gen_tape_create": (c_int, [c_void_p, P(c_void_p)]),
+    "rvc_gen_tape_release": (c_int, [c_void_p]),
+    "rvc_gen_tape_bytes": (c_int64, [c_void_p]),
+    "rvc_gen_tape_tensor": (c_int, [c_void_p, c_char_p, P(c_void_p), P(c_int), P(c_int64)]),
+    "rvc_gen_tape_timing": (c_int, [c_void_p, c_int]),
+    "rvc_gen_tape_times": (c_int, [c_void_p, P(c_float), c_int]),
+    "rvc_synth_forward_tape": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64,
+                                       c_void_p, P(SynthForwardTaps), c_void_p]),
+    "rvc_synth_dec_input_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rvc_synth_dec_input_grad_launch_count": (c_int, [c_void_p]),
     "rvc_kl_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "rvc_kl_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rvc_l1_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -293,6 +303,20 @@ def ptr(t):
     if hasattr(t, "data_ptr"):
         return c_void_p(t.data_ptr())
     return c_void_p(t.ctypes.data)
+
+
+class _DeviceSpan:
+    """float32 device memory owned by the library, described through __cuda_array_interface__ (version 2) so that torch can read it."""
+
+    def __init__(self, address, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(int(v) for v in shape), "typestr": "<f4", "data": (int(address), False), "version": 2, "strides": None}
+
+
+def device_view(address, shape, device):
+    """A torch tensor holding a COPY (made on the current stream) of `shape` float32 values at a device address the library owns: the result outlives the owner."""
+    import torch
+    with torch.cuda.device(device):
+        return torch.as_tensor(_DeviceSpan(address, shape), device=device).clone()
 
 
 def current_stream():

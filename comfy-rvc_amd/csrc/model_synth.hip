@@ -9,7 +9,7 @@
 namespace rvc {
 
 static OwnedConvLayer make_conv1d(const TensorStore& ts, const std::string& p, int stride, int pad, int dil, bool wn, bool bias = true,
-                             float wscale = 1.f, int row0 = 0, int rows = -1) {
+                             float wscale = 1.f, int row0 = 0, int rows = -1, std::vector<float>* keep = nullptr) {
   std::vector<float> w; std::vector<long long> shape;
   if (wn) { const HostTensor& v = ts.get(p + ".weight_v"); w = weight_norm0(v, ts.get(p + ".weight_g")); shape = v.shape; }
   else { const HostTensor& v = ts.get(p + ".weight"); w = v.data; shape = v.shape; }
@@ -25,6 +25,7 @@ static OwnedConvLayer make_conv1d(const TensorStore& ts, const std::string& p, i
   if (bias) { bs.assign(b.begin() + row0, b.begin() + row0 + rows); if (wscale != 1.f) for (auto& x : bs) x *= wscale; }
   OwnedConvLayer L;
   conv1d_layer_init(L, ws.data(), bias ? bs.data() : nullptr, rows, Ci, k, stride, pad, dil, 1);
+  if (keep) *keep = std::move(ws);
   return L;
 }
 
@@ -51,6 +52,15 @@ struct Posterior {
 struct ResBlock { OwnedConvLayer c1[3], c2[3]; };
 struct GenStage { OwnedConvLayer up, noise; DevVec noise_w, noise_b; int u = 1, k = 1, noise_k = 1, noise_s = 1; ResBlock rb[3]; };   // noise_w / _b: raw [C][k] / [C] for the streaming kernel (k <= 8)
 
+// The decoder's backward data pass (synth_dec_input_grad).  GenHostWeights: the folded decoder weights on the HOST, kept by a finalize that loaded a posterior
+// (a training checkpoint) until the first tape is created; GenBwdImages: what that creation builds from them on the device - the transposed, tap-flipped
+// x3_weight_image of every ResBlock convolution and of conv_pre, the up-samplers' images, the raw noise weights.  An inference handle holds neither.
+struct GenHostWeights { std::vector<float> pre; std::vector<std::vector<float>> up, noise, c1, c2; };   // c1 / c2: index (i * 3 + j) * 3 + m
+struct GenBwdImages {
+  bool built = false;
+  DevBuf<uint16_t> pre; std::vector<DevBuf<uint16_t>> up, c1, c2; std::vector<DevVec> noise;
+  size_t bytes = 0;
+};
 struct SynthWeights {    // what synth_finalize builds, and what the graph has learnt about it
   DevVec emb_phone_wT, emb_phone_b, emb_pitch, emb_g;
   std::vector<EncoderLayer> enc;
@@ -61,6 +71,7 @@ struct SynthWeights {    // what synth_finalize builds, and what the graph has l
   DevVec dec_cond_w, dec_cond_b, conv_post_w;   // conv_post_w: raw [Ci][7] weights of the 1-channel output conv (ops.hip::conv_to1)
   std::vector<GenStage> stages;
   float lin_w = 1.f, lin_b = 0.f;
+  GenHostWeights gen_host; GenBwdImages gen_bwd;
   ZeroedBlock imgs;      // split-resident image block whose margins are known to be zero (split_imgs_alloc; keys: T, and the columns of the z image = the generator's window)
 };
 struct Synth : SynthWeights {
@@ -234,7 +245,9 @@ void synth_finalize(Synth* S) {
     RVC_REQUIRE(Q.proj.Co == 2 * S->inter && Q.proj.Ci == C, "enc_q.proj: expected [2 inter][hidden][1]");
     Q.built = true;
   }
-  S->conv_pre = make_conv1d(ts, "dec.conv_pre", 1, 3, 1, false);
+  const bool keep = Q.built;   // a training checkpoint: the folded decoder weights stay on the host for the backward pass's images (gen_bwd_build)
+  GenHostWeights& GH = S->gen_host;
+  S->conv_pre = make_conv1d(ts, "dec.conv_pre", 1, 3, 1, false, true, 1.f, 0, -1, keep ? &GH.pre : nullptr);
   S->conv_post_w.upload(ts.get("dec.conv_post.weight").data);
   S->dec_cond_w.upload(ts.get("dec.cond.weight").data);
   S->dec_cond_b.upload(ts.get("dec.cond.bias").data);
@@ -244,6 +257,7 @@ void synth_finalize(Synth* S) {
   }
   const int nu = (int)S->up_rates.size();
   S->stages.resize(nu);
+  if (keep) { GH.up.resize(nu); GH.noise.resize(nu); GH.c1.resize((size_t)nu * 9); GH.c2.resize((size_t)nu * 9); }
   for (int i = 0; i < nu; ++i) {
     GenStage& st = S->stages[i];
     const int cin = S->up_init >> i, cout = S->up_init >> (i + 1);
@@ -252,6 +266,7 @@ void synth_finalize(Synth* S) {
     const HostTensor& v = ts.get(up + ".weight_v", {cin, cout, st.k});
     std::vector<float> w = weight_norm0(v, ts.get(up + ".weight_g"));
     tconv1d_layer_init(st.up, w.data(), ts.get(up + ".bias", {cout}).data.data(), cin, cout, st.k, st.u, (st.k - st.u) / 2);
+    if (keep) GH.up[i] = w;
     int sf0 = 1;
     for (int j = i + 1; j < nu; ++j) sf0 *= S->up_rates[j];
     const std::string nc = "dec.noise_convs." + std::to_string(i);
@@ -260,6 +275,7 @@ void synth_finalize(Synth* S) {
       const HostTensor& nw = ts.get(nc + ".weight", {cout, 1, st.noise_k});
       // Conv1d(1, C, k, stride) == Linear(k -> C) on the im2col frames of the source
       conv1d_layer_init(st.noise, nw.data.data(), ts.get(nc + ".bias", {cout}).data.data(), cout, st.noise_k, 1, 1, 0, 1, 1);
+      if (keep) GH.noise[i] = nw.data;
       if (st.noise_k <= 8) { st.noise_w.upload(nw.data); st.noise_b.upload(ts.get(nc + ".bias", {cout}).data); }
     }
     for (int j = 0; j < 3; ++j) {
@@ -267,8 +283,9 @@ void synth_finalize(Synth* S) {
       const int k = S->rb_k[j];
       for (int m = 0; m < 3; ++m) {
         const int d = S->rb_d[j][m];
-        st.rb[j].c1[m] = make_conv1d(ts, rb + "convs1." + std::to_string(m), 1, (k * d - d) / 2, d, true);
-        st.rb[j].c2[m] = make_conv1d(ts, rb + "convs2." + std::to_string(m), 1, (k - 1) / 2, 1, true);
+        const size_t q = (size_t)(i * 3 + j) * 3 + m;
+        st.rb[j].c1[m] = make_conv1d(ts, rb + "convs1." + std::to_string(m), 1, (k * d - d) / 2, d, true, true, 1.f, 0, -1, keep ? &GH.c1[q] : nullptr);
+        st.rb[j].c2[m] = make_conv1d(ts, rb + "convs2." + std::to_string(m), 1, (k - 1) / 2, 1, true, true, 1.f, 0, -1, keep ? &GH.c2[q] : nullptr);
       }
     }
   }
@@ -559,6 +576,284 @@ static void gen_tail(Synth* S, hipStream_t s, Arena& A, bool gs, unsigned char* 
   if (!dry) conv_to1(s, cur, Tc, S->conv_post_w.p, S->up_init >> nu, 7, 3, Tc, 0.01f, 1, out + (size_t)g0 * S->upp);
 }
 
+// ------------------------------------------------------------------------------------------------ the recorded decoder pass
+// One item's decoder pass at the net's segment, every tensor fp32 [rows][cols] in one allocation and found by name:
+//   z [inter][seg], har [1][seg upp] (f0 family), pre [up_init][seg] (conv_pre + cond(g), before the leaky ReLU), y_hat [1][seg upp]; per stage i: up{i} (the
+//   up-sampled sum after the noise branch), rb{i}.{j}.y{m} (m = 1, 2: the input of pair m; y0 is up{i}), rb{i}.{j}.t{m} (c1(lrelu(y_m)) + b1), out{i} (xs / 3)
+// and the deltas of synth_dec_input_grad, the cotangent at each convolution's output:
+//   d.post [1][seg upp] (conv_post's), d.out{i} (at EACH ResBlock's output of stage i: the stage output's cotangent / 3), d.rb{i}.{j}.t{m}, d.rb{i}.{j}.y{m}
+//   (m = 1, 2), d.up{i} (the stage sum: the up-sampler's and the noise convolution's), d.pre (conv_pre's), d.cond [1][up_init], d.g [1][gin], d.har
+struct GenTape {
+  struct Tensor { size_t off; int rows; long long cols; };
+  const Synth* S = nullptr; int seg = 0; bool recorded = false;
+  std::map<std::string, Tensor> t;
+  DevVec mem; float* fr = nullptr;      // fr: the im2col frames of a wide noise convolution (scratch)
+  // timing (gen_tape_timing; off: no event is ever created or recorded): events around the taped decoder and at the backward's stage boundaries
+  bool timing = false; std::vector<hipEvent_t> ev; int fwd_marks = 0, bwd_marks = 0;
+  GenTape() = default;
+  GenTape(const GenTape&) = delete; GenTape& operator=(const GenTape&) = delete;
+  ~GenTape() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+  void mark(hipStream_t s, int slot) {
+    if (!timing) return;
+    while ((int)ev.size() <= slot) { hipEvent_t e; RVC_HIP_CHECK(hipEventCreate(&e)); ev.push_back(e); }
+    RVC_HIP_CHECK(hipEventRecord(ev[slot], s));
+  }
+  float* ptr(const std::string& name) const {
+    auto it = t.find(name);
+    RVC_REQUIRE(it != t.end(), "the tape holds no tensor '" + name + "'");
+    return mem.p + it->second.off;
+  }
+};
+static std::string rb_name(int i, int j, const char* what, int m) { return "rb" + std::to_string(i) + "." + std::to_string(j) + "." + what + std::to_string(m); }
+static void tape_check(const Synth* S, const GenTape* tape) {
+  RVC_REQUIRE(tape->S == S, "the tape was created from another synthesizer handle");
+  RVC_REQUIRE(tape->seg == S->segment && S->gen_bwd.built, "the tape was created for another segment_size (the handle was finalized again)");
+}
+
+// the backward pass's weight images, built when the first tape is created (a handle that only infers never gets here)
+static void gen_bwd_build(Synth* S) {
+  GenBwdImages& B = S->gen_bwd; GenHostWeights& H = S->gen_host;
+  if (B.built) return;
+  const int nu = (int)S->stages.size();
+  RVC_REQUIRE(!H.pre.empty() && (int)H.up.size() == nu, "the decoder's folded weights were not kept (no posterior was loaded at finalize)");
+  GenBwdImages N;
+  // Conv1d W [Co][Ci][k] -> W' [Ci][Co][t] = W[co][ci][k - 1 - t]: tap t of the data gradient reads D at t_out + pad - (k - 1) dil + t dil
+  auto conv_image = [&](const std::vector<float>& w, int Co, int Ci, int k, DevBuf<uint16_t>& img) {
+    RVC_REQUIRE(w.size() == (size_t)Co * Ci * k && Co % 16 == 0 && k <= 16, "decoder convolution does not fit the data-gradient kernel");
+    std::vector<float> wt(w.size());
+    for (int co = 0; co < Co; ++co)
+      for (int ci = 0; ci < Ci; ++ci)
+        for (int t = 0; t < k; ++t) wt[((size_t)ci * Co + co) * k + t] = w[((size_t)co * Ci + ci) * k + (k - 1 - t)];
+    std::vector<uint16_t> P;
+    x3_weight_image(wt.data(), Ci, Co, k, (Ci + 127) & ~127, P);
+    img.upload(P); N.bytes += P.size() * sizeof(uint16_t);
+  };
+  conv_image(H.pre, S->up_init, S->inter, 7, N.pre);
+  N.up.resize(nu); N.noise.resize(nu); N.c1.resize((size_t)nu * 9); N.c2.resize((size_t)nu * 9);
+  for (int i = 0; i < nu; ++i) {
+    const GenStage& st = S->stages[i];
+    const int cin = S->up_init >> i, cout = S->up_init >> (i + 1);
+    RVC_REQUIRE(H.up[i].size() == (size_t)cin * cout * st.k && cout % 16 == 0 && st.k <= 16, "up-sampler does not fit the data-gradient kernel");
+    std::vector<uint16_t> P;      // ConvTranspose1d W [Ci][Co][k] is its own data gradient's image: tap t reads D at u t_in - pad + t
+    x3_weight_image(H.up[i].data(), cin, cout, st.k, (cin + 127) & ~127, P);
+    N.up[i].upload(P); N.bytes += P.size() * sizeof(uint16_t);
+    if (S->f0) { N.noise[i].upload(H.noise[i]); N.bytes += H.noise[i].size() * sizeof(float); }
+    for (int j = 0; j < 3; ++j)
+      for (int m = 0; m < 3; ++m) {
+        const size_t q = (size_t)(i * 3 + j) * 3 + m;
+        conv_image(H.c1[q], cout, cout, S->rb_k[j], N.c1[q]);
+        conv_image(H.c2[q], cout, cout, S->rb_k[j], N.c2[q]);
+      }
+  }
+  N.built = true;
+  B = std::move(N);
+  H = {};
+}
+
+GenTape* gen_tape_create(Synth* S) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  RVC_REQUIRE(S->post_enc.built, "no posterior encoder loaded: a tape belongs to the training forward");
+  RVC_REQUIRE(S->segment > 0, "segment_size is not set in the configuration");
+  gen_bwd_build(S);
+  std::unique_ptr<GenTape> T(new GenTape());
+  T->S = S; T->seg = S->segment;
+  size_t off = 0;
+  auto add = [&](const std::string& name, int rows, long long cols) {
+    T->t[name] = {off, rows, cols};
+    off += ((size_t)rows * (size_t)cols + 63) & ~size_t(63);
+  };
+  const int seg = S->segment, nu = (int)S->stages.size();
+  const long long N = (long long)seg * S->upp;
+  auto layout = [&](bool deltas) {      // the activations, then the deltas under the same names behind "d."
+    const std::string d = deltas ? "d." : "";
+    if (!deltas) { add("z", S->inter, seg); if (S->f0) add("har", 1, N); }
+    add(d + "pre", S->up_init, seg);
+    long long Tn = seg;
+    for (int i = 0; i < nu; ++i) {
+      const int Cc = S->up_init >> (i + 1);
+      Tn *= S->stages[i].u;
+      add(d + "up" + std::to_string(i), Cc, Tn);
+      for (int j = 0; j < 3; ++j) {
+        for (int m = 1; m < 3; ++m) add(d + rb_name(i, j, "y", m), Cc, Tn);
+        for (int m = 0; m < 3; ++m) add(d + rb_name(i, j, "t", m), Cc, Tn);
+      }
+      add(d + "out" + std::to_string(i), Cc, Tn);
+    }
+    add(deltas ? "d.post" : "y_hat", 1, N);
+  };
+  layout(false); layout(true);
+  add("d.cond", 1, S->up_init); add("d.g", 1, S->gin);
+  if (S->f0) add("d.har", 1, N);
+  size_t fr = 0;
+  {
+    long long Tn = seg;
+    for (int i = 0; i < nu; ++i) { Tn *= S->stages[i].u; if (S->f0 && S->stages[i].noise_k > 1) fr = std::max(fr, (size_t)S->stages[i].noise_k * (size_t)Tn); }
+  }
+  const size_t fr_off = off; off += fr;
+  T->mem.alloc(off);
+  T->fr = T->mem.p + fr_off;
+  return T.release();
+}
+void gen_tape_destroy(GenTape* T) { delete T; }
+size_t gen_tape_bytes(const GenTape* T) { return T->mem.n * sizeof(float); }
+size_t synth_gen_bwd_bytes(const Synth* S) { return S->gen_bwd.bytes; }
+bool gen_tape_tensor(const GenTape* T, const char* name, float** p, int* rows, long long* cols) {
+  auto it = T->t.find(name);
+  if (it == T->t.end()) return false;
+  *p = T->mem.p + it->second.off; *rows = it->second.rows; *cols = it->second.cols;
+  return true;
+}
+
+// gen_tail on the slice, layer by layer on the unfused conv1d_run path (one launch per convolution), every tensor the backward pass reads written into the tape
+static void gen_tail_tape(Synth* S, hipStream_t s, GenTape& tape, const float* pre_bias, float* out) {
+  const int seg = S->segment, nu = (int)S->stages.size();
+  const long long N = (long long)seg * S->upp;
+  tape.mark(s, 0);
+  const float* har = S->f0 ? tape.ptr("har") : nullptr;
+  float* cur = tape.ptr("pre");
+  ConvEpilogue Eb; Eb.bias_override = pre_bias;
+  conv1d_run(S->conv_pre, s, tape.ptr("z"), seg, seg, cur, seg, Eb);
+  int Tc = seg;
+  for (int i = 0; i < nu; ++i) {
+    GenStage& st = S->stages[i];
+    const int Cc = S->up_init >> (i + 1), Tn = Tc * st.u;
+    float* up = tape.ptr("up" + std::to_string(i));
+    float* xs = tape.ptr("out" + std::to_string(i));
+    RVC_REQUIRE(conv1d_out_len(st.up, Tc) == Tn, "ConvTranspose1d geometry must give T_out = u * T_in");
+    ConvEpilogue Eu; Eu.pre_act = ACT_LRELU; Eu.pre_slope = 0.1f;
+    conv1d_run(st.up, s, cur, Tc, Tc, up, Tn, Eu);
+    ConvEpilogue En; En.accumulate = 1;
+    if (!S->f0) {
+      // plain Generator: nothing is added to the up-sampled signal
+    } else if (st.noise_w.p && noise_add(s, up, Tn, Cc, Tn, har, N, st.noise_k, st.noise_s, st.noise_k > 1 ? st.noise_s / 2 : 0, st.noise_w.p, st.noise_b.p)) {
+    } else if (st.noise_k > 1) {
+      frames(s, har, tape.fr, (int)N, st.noise_k, st.noise_s, st.noise_s / 2, Tn, 0);
+      conv1d_run(st.noise, s, tape.fr, Tn, Tn, up, Tn, En);
+    } else {
+      conv1d_run(st.noise, s, har, Tn, Tn, up, Tn, En);
+    }
+    for (int j = 0; j < 3; ++j) {
+      const float* in = up;
+      for (int m = 0; m < 3; ++m) {
+        float* t = tape.ptr(rb_name(i, j, "t", m));
+        float* dst = m < 2 ? tape.ptr(rb_name(i, j, "y", m + 1)) : xs;
+        ConvEpilogue E1; E1.pre_act = ACT_LRELU; E1.pre_slope = 0.1f;
+        conv1d_run(st.rb[j].c1[m], s, in, Tn, Tn, t, Tn, E1);
+        ConvEpilogue E2; E2.pre_act = ACT_LRELU; E2.pre_slope = 0.1f; E2.R = in; E2.ldR = Tn;
+        if (m == 2) { E2.out_scale = 1.f / 3.f; E2.accumulate = (j > 0); }      // out{i} = sum_j (pair 2's output) / 3, added in the order j = 0, 1, 2
+        conv1d_run(st.rb[j].c2[m], s, t, Tn, Tn, dst, Tn, E2);
+        in = dst;
+      }
+    }
+    cur = xs; Tc = Tn;
+  }
+  float* y_hat = tape.ptr("y_hat");
+  conv_to1(s, cur, Tc, S->conv_post_w.p, S->up_init >> nu, 7, 3, Tc, 0.01f, 1, y_hat);
+  RVC_HIP_CHECK(hipMemcpyAsync(out, y_hat, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));
+  tape.mark(s, 1); tape.fwd_marks = 2;
+}
+
+// The vector-Jacobian product of that pass (GeneratorNSF / Generator, reference models.py:542-564 read backwards): d y_hat -> d z, d cond, d g, d har, every delta
+// left in the tape.  Masks come from the tape, so this is the exact gradient of what the taped forward computed.  tape null: nothing is launched, the return
+// value is the number of launches of the plan (a constant of the net: it does not depend on the segment).  No atomics: two calls give the same bits.
+static int dec_backward(const Synth* S, hipStream_t s, GenTape* tape, const float* dy, float* dz, float* dcond, float* dg, float* dhar) {
+  const GenBwdImages& B = S->gen_bwd;
+  const int seg = S->segment, nu = (int)S->stages.size();
+  const long long N = (long long)seg * S->upp;
+  int launches = 0;
+  auto P = [&](const std::string& name) -> float* { return tape ? tape->ptr(name) : nullptr; };
+  auto gemm = [&](const DevBuf<uint16_t>* img, const float* D, int Ck, int Td, const float* A, const float* Res, float* Y, int R, int Ncols, int nt, int cstride,
+                  int tstep, int off0, float slope, float scale, int accumulate) {
+    ++launches;
+    if (!tape) return;
+    ConvGenBwdArgs a{D, Td, Td, reinterpret_cast<const unsigned char*>(img->p), A, Res, Y, Ncols, R, (R + 127) & ~127, Ck, Ncols, nt, cstride, tstep, off0, slope, scale,
+                     accumulate};
+    ConvGenBwdPlan p;
+    RVC_REQUIRE(conv_gen_bwd_plan(a, p), "decoder layer does not fit the data-gradient kernel");
+    conv_gen_bwd_launch(p, s);
+  };
+  int marks = 0;
+  auto mark = [&] { if (tape) { tape->mark(s, 2 + marks); tape->bwd_marks = ++marks; } };      // intervals: tanh + conv_post, stage nu - 1 .. 0, conv_pre + cond + noise
+  mark();
+  // tanh and conv_post (k = 7, no bias; F.leaky_relu's default slope 0.01 in front of it), the stage mean's 1 / 3 folded into the same store
+  const int Clast = S->up_init >> nu;
+  ++launches; if (tape) gen_tanh_bwd(s, dy, P("y_hat"), P("d.post"), N);
+  ++launches; if (tape) gen_post_bwd(s, P("d.post"), S->conv_post_w.p, P("out" + std::to_string(nu - 1)), P("d.out" + std::to_string(nu - 1)), Clast, 7, 3, N, 0.01f, 1.f / 3.f);
+  long long Tn = N;
+  for (int i = nu - 1; i >= 0; --i) {
+    mark();
+    const GenStage& st = S->stages[i];
+    const int Cc = S->up_init >> (i + 1), Cin = S->up_init >> i;
+    const int Tni = (int)Tn, Tc = Tni / st.u;
+    const std::string si = std::to_string(i);
+    float* dup = P("d.up" + si);
+    for (int j = 0; j < 3; ++j) {
+      const int k = S->rb_k[j];
+      const float* D = P("d.out" + si);
+      for (int m = 2; m >= 0; --m) {
+        const size_t q = (size_t)(i * 3 + j) * 3 + m;
+        const int dil = S->rb_d[j][m];
+        float* dt = P("d." + rb_name(i, j, "t", m));
+        // d_t = c2^T(D) lrelu'(t_m);  d_y = D + c1^T(d_t) lrelu'(y_m), the three ResBlocks' d_y0 added into d.up{i} in the order j = 0, 1, 2
+        gemm(tape ? &B.c2[q] : nullptr, D, Cc, Tni, P(rb_name(i, j, "t", m)), nullptr, dt, Cc, Tni, k, 1, 1, (k - 1) / 2 - (k - 1), 0.1f, 1.f, 0);
+        float* dyv = m > 0 ? P("d." + rb_name(i, j, "y", m)) : dup;
+        gemm(tape ? &B.c1[q] : nullptr, dt, Cc, Tni, m > 0 ? P(rb_name(i, j, "y", m)) : P("up" + si), D, dyv, Cc, Tni, k, 1, dil, (k * dil - dil) / 2 - (k - 1) * dil, 0.1f, 1.f,
+             m == 0 && j > 0);
+        D = dyv;
+      }
+    }
+    // the up-sampler's data gradient, a stride-u convolution, times the mask (slope 0.1) of what it read: the previous stage's output (whose three ResBlocks each
+    // receive a third) or conv_pre's
+    gemm(tape ? &B.up[i] : nullptr, dup, Cc, Tni, i > 0 ? P("out" + std::to_string(i - 1)) : P("pre"), nullptr, i > 0 ? P("d.out" + std::to_string(i - 1)) : P("d.pre"),
+         Cin, Tc, st.k, st.u, 1, -((st.k - st.u) / 2), 0.1f, i > 0 ? 1.f / 3.f : 1.f, 0);
+    Tn = Tc;
+  }
+  mark();
+  // conv_pre (k = 7, pad 3, no activation in front of it) and the conditioning: dcond = row sums of conv_pre's output cotangent, dg = cond_w^T dcond
+  gemm(tape ? &B.pre : nullptr, P("d.pre"), S->up_init, seg, nullptr, nullptr, dz, S->inter, seg, 7, 1, 1, -3, 1.f, 1.f, 0);
+  ++launches; if (tape) gen_row_sums(s, P("d.pre"), S->up_init, seg, P("d.cond"), dcond);
+  ++launches; if (tape) gen_cond_bwd(s, S->dec_cond_w.p, P("d.cond"), S->up_init, S->gin, P("d.g"), dg);
+  // the noise branch onto the harmonic source, stage by stage in index order
+  if (S->f0) {
+    float* dh = P("d.har");      // the sum runs in the tape (d.har is always written); the caller's dhar receives a copy of it, like dcond and dg
+    long long Ti = seg;
+    for (int i = 0; i < nu; ++i) {
+      const GenStage& st = S->stages[i];
+      Ti *= st.u;
+      ++launches;
+      if (tape) gen_noise_bwd(s, P("d.up" + std::to_string(i)), B.noise[i].p, dh, dhar, S->up_init >> (i + 1), st.noise_k, st.noise_s, st.noise_k > 1 ? st.noise_s / 2 : 0, Ti, N, i > 0);
+    }
+  }
+  mark();
+  return launches;
+}
+void gen_tape_timing(GenTape* T, bool on) { T->timing = on; if (!on) T->fwd_marks = T->bwd_marks = 0; }
+// waits for the recorded events.  ms[0]: the taped decoder (conv_pre .. y_hat) of the last taped forward; then the last backward's intervals in execution order:
+// tanh + conv_post, stage n - 1 .. stage 0, conv_pre + conditioning + noise branch.  Returns the number of values (0: timing off or nothing recorded yet).
+int gen_tape_times(GenTape* T, float* ms, int cap) {
+  if (!T->timing || T->fwd_marks < 2) return 0;
+  int n = 0;
+  auto put = [&](int a, int b) {
+    if (n >= cap) return;
+    RVC_HIP_CHECK(hipEventSynchronize(T->ev[b]));
+    RVC_HIP_CHECK(hipEventElapsedTime(&ms[n++], T->ev[a], T->ev[b]));
+  };
+  put(0, 1);
+  for (int k = 1; k < T->bwd_marks; ++k) put(2 + k - 1, 2 + k);
+  return n;
+}
+int synth_dec_input_grad_launch_count(const Synth* S) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  return dec_backward(S, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+void synth_dec_input_grad(Synth* S, hipStream_t s, GenTape* tape, const float* dy, float* dz, float* dcond, float* dg, float* dhar) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  tape_check(S, tape);
+  RVC_REQUIRE(tape->recorded, "the tape holds no forward pass: call synth_forward_tape first");
+  RVC_REQUIRE(S->f0 || !dhar, "no-f0 model: there is no harmonic source, dhar must be NULL");
+  dec_backward(S, s, tape, dy, dz, dcond, dg, dhar);
+}
+
 // the phone features channel-major [feat_dim][T]: the caller's own tensor, or its transpose as the graph's first temporary
 static const float* feat_cm_of(const Synth* S, hipStream_t s, Arena& A, const float* feat, int feat_channel_major, int T) {
   if (feat_channel_major) return feat;
@@ -631,7 +926,7 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
 
 // SynthesizerTrnMs{256,768}NSFsid[_nono].forward for one item at its own length (reference models.py:781-796,:894-903): every mask is all ones.
 static void synth_forward_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm, const long long* pitch, const float* pitchf, const float* spec, int sid,
-                                const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps) {
+                                const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps, GenTape* tape) {
   const int C = S->hidden, IC = S->inter, seg = S->segment;
   Posterior& Q = S->post_enc;
   const bool dry = A.dry;
@@ -697,9 +992,10 @@ static void synth_forward_graph(Synth* S, hipStream_t s, Arena& A, const float* 
     A.off = mark;
   }
   // ---- the slice as a sequence of its own through the generator
-  float* zs = A.alloc<float>((size_t)IC * seg);
+  // (with a tape the slice and the source are its first two tensors)
   const long long N = (long long)seg * S->upp;
-  float* har = S->f0 ? A.alloc<float>((size_t)N) : nullptr;
+  float* zs = tape ? tape->ptr("z") : A.alloc<float>((size_t)IC * seg);
+  float* har = !S->f0 ? nullptr : (tape ? tape->ptr("har") : A.alloc<float>((size_t)N));
   if (!dry) segment_gather(s, z, IC, T, ids, seg, zs);
   if (S->f0) {
     float* pfs = A.alloc<float>((size_t)seg);
@@ -711,7 +1007,8 @@ static void synth_forward_graph(Synth* S, hipStream_t s, Arena& A, const float* 
       sine_source(s, pfs, noise_src, har, nullptr, rad, tmp, bsum, seg, S->upp, (float)S->sr, S->lin_w, S->lin_b);
     }
   }
-  gen_tail(S, s, A, gs, im.z_s, zs, har, pre_bias, seg, 0, seg, h2, out, nullptr);
+  if (tape) { if (!dry) gen_tail_tape(S, s, *tape, pre_bias, out); }
+  else gen_tail(S, s, A, gs, im.z_s, zs, har, pre_bias, seg, 0, seg, h2, out, nullptr);
 }
 
 // [keep0, keep1): the frames whose samples the caller keeps.  out[keep0 upp, keep1 upp) is defined, nothing else is promised: the generator (conv_pre on) runs on the
@@ -757,16 +1054,23 @@ void synth_infer(Synth* S, hipStream_t s, const float* feat, int feat_channel_ma
   synth_infer_window(S, s, feat, feat_channel_major, pitch, pitchf, sid, noise_z, noise_src, T, out, taps, 0, T, -1);
 }
 
-void synth_forward(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, const float* spec, int sid,
-                   const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps) {
+void synth_forward_tape(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, const float* spec,
+                        int sid, const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps, GenTape* tape) {
   RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  if (tape) { tape_check(S, tape); tape->recorded = false; }
   RVC_REQUIRE(S->post_enc.built, "no posterior encoder loaded: the checkpoint had no enc_q.* tensors (an inference checkpoint)");
   RVC_REQUIRE(S->segment > 0, "segment_size is not set in the configuration");
   RVC_REQUIRE(T >= S->segment && T >= 11, "the sequence is shorter than the segment");
   RVC_REQUIRE(ids >= 0 && ids <= T - S->segment, "slice start outside [0, T - segment]");
   RVC_REQUIRE(sid >= 0 && sid < S->n_spk, "speaker id out of range");
   Arena& A = S->arena;
-  arena_passes(A, [&] { synth_forward_graph(S, s, A, feat_cm_of(S, s, A, feat, feat_channel_major, T), pitch, pitchf, spec, sid, noise_q, noise_src, T, ids, out, taps); });
+  arena_passes(A, [&] { synth_forward_graph(S, s, A, feat_cm_of(S, s, A, feat, feat_channel_major, T), pitch, pitchf, spec, sid, noise_q, noise_src, T, ids, out, taps, tape); });
+  if (tape) tape->recorded = true;
+}
+
+void synth_forward(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, const float* spec, int sid,
+                   const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps) {
+  synth_forward_tape(S, s, feat, feat_channel_major, pitch, pitchf, spec, sid, noise_q, noise_src, T, ids, out, taps, nullptr);
 }
 
 size_t synth_workspace(const Synth* M) { return M->arena.cap; }

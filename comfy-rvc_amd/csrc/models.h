@@ -31,6 +31,22 @@ bool synth_has_posterior(const Synth* S); // enc_q.* were present at finalize
 // the training forward of one item (reference models.py:781-796; model_synth.hip): spec [spec_channels][T], noise_q [inter][T], noise_src [seg upp], out [seg upp]
 void synth_forward(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, const float* spec, int sid,
                    const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps);
+// The recorded decoder pass and its backward data pass (model_synth.hip).  A tape belongs to one handle at its segment and holds one item's decoder activations
+// and deltas by name; the first creation builds the backward pass's weight images.  synth_forward_tape: synth_forward with the decoder run layer by layer into
+// the tape (tape null: synth_forward itself).  synth_dec_input_grad: d y_hat [seg upp] -> dz [inter][seg], dcond [up_init], dg [gin], dhar [seg upp] (the last three
+// may be null; dhar must be for a no-f0 net)
+struct GenTape;
+GenTape* gen_tape_create(Synth* S);
+void gen_tape_destroy(GenTape* T);
+size_t gen_tape_bytes(const GenTape* T);
+size_t synth_gen_bwd_bytes(const Synth* S);   // device bytes of the backward pass's weight images (0 before the first tape)
+void gen_tape_timing(GenTape* T, bool on);             // events around the taped decoder and at the backward's stage boundaries (off: none is created)
+int gen_tape_times(GenTape* T, float* ms, int cap);    // ms[0] the taped decoder, then the backward's intervals in execution order; waits for the events
+bool gen_tape_tensor(const GenTape* T, const char* name, float** p, int* rows, long long* cols);   // false: no such tensor
+void synth_forward_tape(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, const float* spec,
+                        int sid, const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps, GenTape* tape);
+void synth_dec_input_grad(Synth* S, hipStream_t s, GenTape* tape, const float* dy, float* dz, float* dcond, float* dg, float* dhar);
+int synth_dec_input_grad_launch_count(const Synth* S);   // pure: the size of the plan, independent of the segment
 // train_forward.hip: z = m + noise exp(logs) from stats [m | logs] (2 C rows); columns [ids, ids + seg) of x [C][T] -> y [C][seg]; the two loss reductions
 void posterior_sample(hipStream_t s, const float* stats, const float* noise, float* z, int C, int T);
 void segment_gather(hipStream_t s, const float* x, int C, int T, int ids, int seg, float* y);

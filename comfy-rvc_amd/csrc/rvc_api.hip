@@ -293,6 +293,56 @@ int rvc_synth_forward(rvc_synth* s, void* stream, const float* phone, int phone_
   check_launch();
   RVC_CATCH
 }
+struct rvc_gen_tape { rvc_synth* s; GenTape* t; };
+int rvc_gen_tape_create(rvc_synth* s, rvc_gen_tape** out) {
+  RVC_TRY
+  RVC_REQUIRE(s && out, "null argument");
+  RVC_HIP_CHECK(hipSetDevice(s->ctx->c.device));
+  std::unique_ptr<rvc_gen_tape> t(new rvc_gen_tape{s, nullptr});
+  t->t = gen_tape_create(s->m);
+  *out = t.release();
+  RVC_CATCH
+}
+int rvc_gen_tape_release(rvc_gen_tape* t) { if (t) { gen_tape_destroy(t->t); delete t; } return 0; }
+int64_t rvc_gen_tape_bytes(rvc_gen_tape* t) { return t ? (int64_t)gen_tape_bytes(t->t) : 0; }
+int rvc_gen_tape_timing(rvc_gen_tape* t, int on) { RVC_TRY RVC_REQUIRE(t, "null argument"); gen_tape_timing(t->t, on != 0); RVC_CATCH }
+int rvc_gen_tape_times(rvc_gen_tape* t, float* ms_host, int cap) {
+  try { RVC_REQUIRE(t && ms_host && cap > 0, "bad argument"); return gen_tape_times(t->t, ms_host, cap); }
+  catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_gen_tape_tensor(rvc_gen_tape* t, const char* name, float** ptr, int* rows, int64_t* cols) {
+  RVC_TRY
+  RVC_REQUIRE(t && name && ptr && rows && cols, "null argument");
+  long long c = 0;
+  RVC_REQUIRE(gen_tape_tensor(t->t, name, ptr, rows, &c), std::string("the tape holds no tensor '") + name + "'");
+  *cols = c;
+  RVC_CATCH
+}
+int rvc_synth_forward_tape(rvc_synth* s, void* stream, const float* phone, int phone_cm, const int64_t* pitch, const float* pitchf, const float* spec, int sid,
+                           const float* noise_q, const float* noise_src, int64_t T, int64_t ids, float* out, const rvc_synth_forward_taps* taps,
+                           rvc_gen_tape* tape) {
+  RVC_TRY
+  RVC_REQUIRE(s && phone && spec && noise_q && out && tape, "null argument");
+  RVC_REQUIRE(T > 0 && T < (1LL << 24), "bad sequence length");
+  check_pitch_args(s, pitch, pitchf, noise_src, 0);
+  RVC_HIP_CHECK(hipSetDevice(s->ctx->c.device));
+  synth_forward_tape(s->m, (hipStream_t)stream, phone, phone_cm, (const long long*)pitch, pitchf, spec, sid, noise_q, noise_src, (int)T,
+                     (int)std::max<int64_t>(-1, std::min<int64_t>(ids, T)), out, taps, tape->t);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_synth_dec_input_grad(rvc_synth* s, void* stream, rvc_gen_tape* tape, const float* dy_hat, float* dz, float* dcond, float* dg, float* dhar) {
+  RVC_TRY
+  RVC_REQUIRE(s && tape && dy_hat && dz, "null argument");
+  RVC_HIP_CHECK(hipSetDevice(s->ctx->c.device));
+  synth_dec_input_grad(s->m, (hipStream_t)stream, tape->t, dy_hat, dz, dcond, dg, dhar);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_synth_dec_input_grad_launch_count(rvc_synth* s) {
+  try { return s ? synth_dec_input_grad_launch_count(s->m) : -1; }
+  catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
 int rvc_kl_loss_grad(void* stream, const float* z_p, const float* m_p, const float* logs_p, int C, int64_t T_pitch, int64_t len, float scale, float* dz_p,
                      float* dlogs_q, float* dm_p, float* dlogs_p) {
   RVC_TRY

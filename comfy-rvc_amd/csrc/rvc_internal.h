@@ -243,7 +243,25 @@ struct ConvX3dBwdArgs {
 struct ConvX3dBwdPlan { ConvX3dBwdArgs a; dim3 grid; int units = 1; size_t lds = 0; double flops = 0.0; };
 bool conv_x3d_bwd_plan(const ConvX3dBwdArgs& a, ConvX3dBwdPlan& p);   // false: the layer does not fit the kernel
 void conv_x3d_bwd_launch(const ConvX3dBwdPlan& p, hipStream_t s);
-// The weight gradient of that convolution (conv_x3d_wgrad.hip):  dW[m][c][j] = sum_s sum_n D[s][m][n] X[s][c][stride n - (stride - 1) w + (j - pad) p], both
+// The data gradient of the generator's 1-D convolutions with the backward chain's epilogue (conv_gen_bwd.hip):
+//   Y[r][n] = (sum_c sum_t W'[r][c][t] D[c][cstride n + off0 + tstep t]) * (A[r][n] > 0 ? scale : scale slope) + Res[r][n] (+ Y[r][n]),   r < R, n < N
+// D [Ck][ldD] with Td valid columns (zero outside), Wx = x3_weight_image of W' [R][Ck][nt] with its rows padded to RPx (a multiple of 128); A (null: no mask),
+// Res (null) and Y share the pitch ldY.  One launch; planned, then launched, like the split-MFMA family.
+struct ConvGenBwdArgs {
+  const float* D; long long ldD; int Td; const unsigned char* Wx; const float* A; const float* Res; float* Y; long long ldY;
+  int R, RPx, Ck, N, nt, cstride, tstep, off0; float slope, scale; int accumulate;
+};
+struct ConvGenBwdPlan { ConvGenBwdArgs a; dim3 grid; int bm = 128, units = 1; size_t lds = 0; double flops = 0.0; };   // bm: rows per workgroup (128, 64, 32)
+bool conv_gen_bwd_plan(const ConvGenBwdArgs& a, ConvGenBwdPlan& p);   // false: the layer does not fit the kernel (Ck % 16, k <= 16, 32-bit offsets)
+void conv_gen_bwd_launch(const ConvGenBwdPlan& p, hipStream_t s);
+// the direct kernels of that pass: d = dy (1 - y^2); conv_post transposed with its input's mask; a noise convolution transposed onto the source (accumulate: added
+// to dhar; out2: a second copy of the sum so far, or null); float64 row sums and the conditioning's transposed product (out2: a second copy or null)
+void gen_tanh_bwd(hipStream_t s, const float* dy, const float* y, float* d, long long n);
+void gen_post_bwd(hipStream_t s, const float* d, const float* w, const float* x, float* dx, int C, int k, int pad, long long T, float slope, float scale);
+void gen_noise_bwd(hipStream_t s, const float* D, const float* w, float* dhar, float* out2, int C, int k, int stride, int pad, long long T, long long N, int accumulate);
+void gen_row_sums(hipStream_t s, const float* D, int C, long long T, float* out, float* out2);
+void gen_cond_bwd(hipStream_t s, const float* W, const float* dcond, int C, int G, float* out, float* out2);
+// The weight gradient of that convolution (conv_x3d_wgrad.hip): dW[m][c][j] = sum_s sum_n D[s][m][n] X[s][c][stride n - (stride - 1) w + (j - pad) p], both
 // operands fp32 and split in the kernel, the reduction over (signal, n) cut into `splits` runs of stages (one signal, 128 columns each): split z writes the
 // partial image part[z][Co][Ci k]; the caller provides part_floats floats and adds the partials in index order.  cps / per / total: filled by the planner.
 struct ConvX3dWgradArgs {

@@ -36,6 +36,7 @@ class _SynthesizerNSFsid:
         self.inter_channels, self.hidden_channels, self.sr = inter_channels, hidden_channels, sr
         self.spec_channels, self.segment_size, self.p_dropout = int(spec_channels), int(segment_size), float(p_dropout)
         self.upsample_rates = list(upsample_rates)
+        self.gin_channels = int(gin_channels)
         self.upp = int(np.prod(upsample_rates))
         self.device = torch.device(device)
         cfg = _lib.SynthConfig()
@@ -139,7 +140,7 @@ class _SynthesizerNSFsid:
         return out, x_mask, (tbuf.get("z"), tbuf.get("z_p"), tbuf.get("m_p"), tbuf.get("logs_p"))
 
     # ------------------------------------------------------------------------------------------- training forward
-    def _forward(self, phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise, ids_slice):
+    def _forward(self, phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise, ids_slice, with_tape=False):
         """SynthesizerTrnMs{256,768}NSFsid[_nono].forward (reference :781-796,:894-903).  noise=(noise_q [B,inter,T], noise_src [B,seg*upp,1]);
         without it the draws are made on the host in the reference's order and shapes: enc_q's randn_like [B,inter,T] (:237), torch.rand([B]) of
         rand_slice_segments (commons.py:173), SineGen's rand_ini torch.rand(B, 1) (:378-381, zeroed) and its randn_like [B,seg*upp,1] (:409)."""
@@ -182,6 +183,14 @@ class _SynthesizerNSFsid:
             ns = torch.as_tensor(noise_src).to(dev, torch.float32).reshape(B, seg * upp)
         o = torch.zeros(B, 1, seg * upp, dtype=torch.float32, device=dev)
         taps = [torch.zeros(B, IC, Ty, dtype=torch.float32, device=dev) for _ in range(6)]       # z, z_p, m_p, logs_p, m_q, logs_q
+        tape = None
+        if isinstance(with_tape, GeneratorTape):      # record again into the caller's tape: nothing is allocated
+            tape = with_tape
+            if tape.net is not self or tape.B != B:
+                raise ValueError("the tape belongs to another net or another batch size")
+            tape.ids, tape.Ty = [int(i) for i in ids], Ty
+        elif with_tape:
+            tape = GeneratorTape(self, B, ids, Ty)
         with torch.cuda.device(dev):
             st = _lib.current_stream()
             for b in range(B):
@@ -193,20 +202,131 @@ class _SynthesizerNSFsid:
                 pf_b = pf[b, :L].contiguous() if f0 else None
                 ns_b = ns[b].contiguous() if f0 else None
                 o_b = torch.empty(seg * upp, dtype=torch.float32, device=dev)
-                _lib.check(_lib.lib.rvc_synth_forward(self._h, st, _lib.ptr(ph_b), 0, _lib.ptr(pc_b), _lib.ptr(pf_b), _lib.ptr(y_b), int(sid[b]),
-                                                      _lib.ptr(nq_b), _lib.ptr(ns_b), L, int(ids[b]), _lib.ptr(o_b), C.byref(tp)))
+                if tape is not None:      # the decoder layer by layer, recorded: y_hat is the taped wave
+                    _lib.check(_lib.lib.rvc_synth_forward_tape(self._h, st, _lib.ptr(ph_b), 0, _lib.ptr(pc_b), _lib.ptr(pf_b), _lib.ptr(y_b), int(sid[b]),
+                                                               _lib.ptr(nq_b), _lib.ptr(ns_b), L, int(ids[b]), _lib.ptr(o_b), C.byref(tp), tape._h[b]))
+                else:
+                    _lib.check(_lib.lib.rvc_synth_forward(self._h, st, _lib.ptr(ph_b), 0, _lib.ptr(pc_b), _lib.ptr(pf_b), _lib.ptr(y_b), int(sid[b]),
+                                                          _lib.ptr(nq_b), _lib.ptr(ns_b), L, int(ids[b]), _lib.ptr(o_b), C.byref(tp)))
                 o[b, 0] = o_b
                 for dst, src in zip(taps, item):
                     dst[b, :, :L] = src
         x_mask = (torch.arange(Tx)[None, :] < pl[:, None]).to(torch.float32).unsqueeze(1).to(dev)
         y_mask = (torch.arange(Ty)[None, :] < yl[:, None]).to(torch.float32).unsqueeze(1).to(dev)
-        return o, ids.to(dev), x_mask, y_mask, tuple(taps)
+        res = (o, ids.to(dev), x_mask, y_mask, tuple(taps))
+        return (res, tape) if with_tape else res
 
     def forward(self, phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise=None, ids_slice=None):
         return self._forward(phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise, ids_slice)
 
+    # ------------------------------------------------------------------------------------------- the decoder's backward data pass
+    def forward_with_tape(self, phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise=None, ids_slice=None, tape=None):
+        """forward's arguments -> (forward's 5-tuple, GeneratorTape).  The decoder runs layer by layer and records what its backward reads
+        (rvc_synth_forward_tape); `o` is the taped wave, inside the 1e-3 gate of forward's but not bit-equal to it (forward keeps its fused ResBlock kernels).
+        tape: a GeneratorTape of an earlier call with the same batch size to record into again (a trainer keeps one), instead of a new one."""
+        return self._forward(phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise, ids_slice, with_tape=tape if tape is not None else True)
+
+    def dec_input_grad(self, tape, d_y_hat, return_deltas=False):
+        """d_y_hat [B,1,seg*upp] -> (dz [B,inter,Ty], dg [B,gin], dhar [B,seg*upp] or None for a no-f0 net): the decoder's vector-Jacobian product
+        (rvc_synth_dec_input_grad).  dz holds the slice's gradient at frames [ids, ids + seg) and zero elsewhere: what autograd leaves in z.grad from the decoder
+        branch.  dg flows into emb_g's row; dhar stops at the harmonic source.  return_deltas: also a list of B dicts name -> copy of the tape's delta."""
+        if not isinstance(tape, GeneratorTape) or tape.net is not self:
+            raise ValueError("dec_input_grad: the tape belongs to another net")
+        dev, seg, IC, upp, B = self.device, self.segment_size, self.inter_channels, self.upp, tape.B
+        d = torch.as_tensor(d_y_hat).to(dev, torch.float32).reshape(B, seg * upp).contiguous()
+        dz = torch.zeros(B, IC, tape.Ty, dtype=torch.float32, device=dev)
+        dg = torch.empty(B, self.gin_channels, dtype=torch.float32, device=dev)
+        dhar = torch.empty(B, seg * upp, dtype=torch.float32, device=dev) if self.HAS_F0 else None
+        with torch.cuda.device(dev):
+            st = _lib.current_stream()
+            for b in range(B):
+                dz_b = torch.empty(IC, seg, dtype=torch.float32, device=dev)
+                _lib.check(_lib.lib.rvc_synth_dec_input_grad(self._h, st, tape._h[b], _lib.ptr(d[b]), _lib.ptr(dz_b), None, _lib.ptr(dg[b]),
+                                                             _lib.ptr(dhar[b]) if dhar is not None else None))
+                i0 = int(tape.ids[b])
+                dz[b, :, i0:i0 + seg] = dz_b
+        if return_deltas:
+            return dz, dg, dhar, [{n: tape.tensor(b, n) for n in tape.delta_names()} for b in range(B)]
+        return dz, dg, dhar
+
+    def dec_backward_launch_count(self):
+        n = int(_lib.lib.rvc_synth_dec_input_grad_launch_count(self._h))
+        if n < 0:
+            _lib.check(1)
+        return n
+
     def __call__(self, *args, **kwargs):
         return self.forward(*args, **kwargs)
+
+
+class GeneratorTape:
+    """The recorded decoder passes of one batch (forward_with_tape): B rvc_gen_tape handles, one per item, and the slice starts `ids`.  `tensor(b, name)` is a
+    copy of item b's tensor - activations z, har, pre, up{i}, rb{i}.{j}.y{m}, rb{i}.{j}.t{m}, out{i}, y_hat and, after dec_input_grad, the deltas
+    d.post, d.out{i}, d.rb{i}.{j}.t{m}, d.rb{i}.{j}.y{m}, d.up{i}, d.pre, d.cond, d.g, d.har (include/rvc_hip.h).  `nbytes`: device bytes of the B tapes."""
+
+    def __init__(self, net, B, ids, Ty):
+        self.net, self.B, self.ids, self.Ty = net, int(B), [int(i) for i in ids], int(Ty)
+        self._h = []
+        with torch.cuda.device(net.device):
+            for _ in range(self.B):
+                h = C.c_void_p()
+                _lib.check(_lib.lib.rvc_gen_tape_create(net._h, C.byref(h)))
+                self._h.append(h)
+
+    def __del__(self):
+        if _lib is not None and getattr(_lib, 'lib', None) is not None:
+            for h in getattr(self, "_h", []):
+                _lib.lib.rvc_gen_tape_release(h)
+            self._h = []
+
+    @property
+    def nbytes(self):
+        return sum(int(_lib.lib.rvc_gen_tape_bytes(h)) for h in self._h)
+
+    def tensor(self, b, name):
+        p, rows, cols = C.c_void_p(), C.c_int(), C.c_int64()
+        _lib.check(_lib.lib.rvc_gen_tape_tensor(self._h[b], name.encode(), C.byref(p), C.byref(rows), C.byref(cols)))
+        return _lib.device_view(p.value, (rows.value, cols.value), self.net.device)
+
+    def set_timing(self, on=True):
+        """HIP events around the taped decoder and at the backward's stage boundaries of every item (rvc_gen_tape_timing); off by default."""
+        for h in self._h:
+            _lib.check(_lib.lib.rvc_gen_tape_timing(h, 1 if on else 0))
+
+    def times(self, b):
+        """Milliseconds of item b's last passes (waits for them): {"decoder_forward": .., "backward": {"post": .., "stage3": .., .., "stage0": .., "pre": ..}};
+        {} when nothing was recorded."""
+        buf = (C.c_float * 16)()
+        n = int(_lib.lib.rvc_gen_tape_times(self._h[b], buf, 16))
+        if n < 0:
+            _lib.check(1)
+        if n == 0:
+            return {}
+        nu = len(self.net.upsample_rates)
+        names = ["post"] + [f"stage{i}" for i in range(nu - 1, -1, -1)] + ["pre"]
+        return {"decoder_forward": float(buf[0]), "backward": {k: float(buf[1 + i]) for i, k in enumerate(names[:n - 1])}}
+
+    def _names(self, deltas):
+        net, out = self.net, []
+        d = "d." if deltas else ""
+        if not deltas:
+            out += ["z"] + (["har"] if net.HAS_F0 else [])
+        out.append(d + "pre")
+        for i in range(len(net.upsample_rates)):
+            out.append(f"{d}up{i}")
+            for j in range(3):
+                out += [f"{d}rb{i}.{j}.y{m}" for m in (1, 2)] + [f"{d}rb{i}.{j}.t{m}" for m in range(3)]
+            out.append(f"{d}out{i}")
+        out.append("d.post" if deltas else "y_hat")
+        if deltas:
+            out += ["d.cond", "d.g"] + (["d.har"] if net.HAS_F0 else [])
+        return out
+
+    def activation_names(self):
+        return self._names(False)
+
+    def delta_names(self):
+        return self._names(True)
 
 
 class _SynthesizerNSFsid_nono(_SynthesizerNSFsid):
@@ -250,6 +370,11 @@ class _SynthesizerNSFsid_nono(_SynthesizerNSFsid):
         if extra:
             raise ValueError("no-f0 model: forward(phone, phone_lengths, y, y_lengths, ds) takes no pitch arguments")
         return self._forward(phone, phone_lengths, None, None, y, y_lengths, ds, noise, ids_slice)
+
+    def forward_with_tape(self, phone, phone_lengths, y, y_lengths, ds, *extra, noise=None, ids_slice=None, tape=None):
+        if extra:
+            raise ValueError("no-f0 model: forward_with_tape(phone, phone_lengths, y, y_lengths, ds) takes no pitch arguments")
+        return self._forward(phone, phone_lengths, None, None, y, y_lengths, ds, noise, ids_slice, with_tape=tape if tape is not None else True)
 
 
 class SynthesizerTrnMs768NSFsid_nono(_SynthesizerNSFsid_nono):

@@ -2,8 +2,10 @@
 clip_grad_value_, optim_d.step().  fp32 only: the reference's GradScaler with fp16_run off is the identity, and autocast is not implemented.  The gradient
 penalty's parameter gradient is not built: c_gp > 0 raises (losses.discriminator_grads).
 
-Of the generator half (:565-601) the loss and its cotangents at the generator's outputs: generator_loss_cotangents.  The generator's own backward, its
-optimizer step and the gradients of the HPSS / TSI / TEFS terms are not built."""
+Of the generator half (:565-601) the loss and its cotangents at the generator's outputs: generator_loss_cotangents; and the first step of the generator's own
+backward, the decoder's data pass from d_y_hat to the sliced latent's, the speaker conditioning's and the harmonic source's cotangents:
+generator_decoder_backward over a net_g.forward_with_tape(...) pass.  The generator's weight and bias gradients, the backward of enc_q, the flow, enc_p and
+m_source, its optimizer step and the gradients of the HPSS / TSI / TEFS terms are not built."""
 import torch
 
 from ..infer_pack.commons import clip_grad_value_
@@ -60,3 +62,10 @@ def generator_loss_cotangents(net_d, balancer_g, wave, y_hat, y_mel, kl_taps, z_
             d_y_hat += w[k] * g.view(y_hat.shape).double()
     kl_cot = kl_loss_grads(z_p, logs_q, m_p, logs_p, z_mask, scale=w.get("loss_kl", 0.0))
     return loss_gen_all, terms, d_y_hat.to(torch.float32), kl_cot
+
+
+def generator_decoder_backward(net_g, tape, d_y_hat):
+    """(dz [B,inter,Ty], dg [B,gin], dhar [B,seg*upp] or None) from d_y_hat [B,1,seg*upp] (generator_loss_cotangents' third result) and the GeneratorTape of
+    `net_g.forward_with_tape(...)`: the decoder's vector-Jacobian product (net_g.dec_input_grad), every per-layer delta left in the tape for the weight-gradient
+    pass.  dz is what autograd leaves in z.grad from the decoder branch; the KL cotangents join it in the passes that are not built yet."""
+    return net_g.dec_input_grad(tape, d_y_hat)

@@ -239,6 +239,41 @@ typedef struct rvc_synth_forward_taps {   /* all [inter][T]; NULL = skip */
 int rvc_synth_forward(rvc_synth* s, void* stream, const float* phone_dev, int phone_channel_major, const int64_t* pitch_dev, const float* pitchf_dev,
                       const float* spec_dev, int sid, const float* noise_q_dev, const float* noise_src_dev, int64_t T, int64_t ids, float* out_dev,
                       const rvc_synth_forward_taps* taps);
+/* ---- the generator's backward, first step: the decoder's data pass (GeneratorNSF / Generator, reference lib/infer_pack/models.py:542-564 read backwards).
+ * A tape is one item's recorded decoder pass at the handle's segment_size: created from a finalized handle with its posterior loaded, it owns the device memory of
+ * every activation the backward reads and of every delta it leaves (rvc_gen_tape_bytes; 40k v2 at 32 frames: see INTEGRATION.md).  The first creation on a
+ * handle also builds the backward's weight images (transposed, tap-flipped bf16 hi / lo images of the decoder's folded weights, about the decoder's weights
+ * again); a handle that never creates a tape allocates nothing for any of this.  Destroy a handle's tapes before the handle.
+ * Tensors are fp32 [rows][cols], read by name through rvc_gen_tape_tensor: z, har (f0 family), pre (conv_pre + cond(g), before the leaky ReLU), up{i} (stage i's
+ * up-sampled sum after the noise branch), rb{i}.{j}.y{m} (m = 1, 2: the input of ResBlock j's pair m; y0 is up{i}), rb{i}.{j}.t{m} (c1(lrelu(y_m)) + b1),
+ * out{i} (the stage output xs / 3), y_hat; and the deltas, the cotangent at each convolution's output: d.post (conv_post's), d.out{i} (at each ResBlock's output
+ * of stage i: the stage output's cotangent / 3), d.rb{i}.{j}.t{m}, d.rb{i}.{j}.y{m}, d.up{i}, d.pre, d.cond, d.g, d.har.  An unknown name is an error. */
+typedef struct rvc_gen_tape rvc_gen_tape;
+int rvc_gen_tape_create(rvc_synth* s, rvc_gen_tape** out);
+int rvc_gen_tape_release(rvc_gen_tape* t);
+int64_t rvc_gen_tape_bytes(rvc_gen_tape* t);
+int rvc_gen_tape_tensor(rvc_gen_tape* t, const char* name, float** ptr_dev, int* rows, int64_t* cols);
+/* Measurement (tools/bench_gen_grad.py).  rvc_gen_tape_timing(t, 1): the passes on this tape record HIP events around the taped decoder and at the backward's stage
+ * boundaries (off, the default: no event exists).  rvc_gen_tape_times waits for them and writes up to cap milliseconds to ms_host: [0] the taped decoder
+ * (conv_pre .. y_hat) of the last taped forward, then the last backward's intervals in execution order - tanh + conv_post, stage n - 1 .. stage 0, conv_pre +
+ * conditioning + noise branch.  Returns the number of values, 0 when nothing was recorded, -1 on error. */
+int rvc_gen_tape_timing(rvc_gen_tape* t, int on);
+int rvc_gen_tape_times(rvc_gen_tape* t, float* ms_host, int cap);
+/* rvc_synth_forward with the decoder recorded: same arguments, same taps, but the decoder runs layer by layer (one launch per convolution, no fused ResBlock
+ * kernels) and writes the tape.  out_dev is the taped y_hat: it may differ from rvc_synth_forward's by the fused kernels' rounding (both inside the 1e-3 gate);
+ * a trainer uses this wave throughout, so the gradient below is exact for the wave it scored.  rvc_synth_forward itself is untouched. */
+int rvc_synth_forward_tape(rvc_synth* s, void* stream, const float* phone_dev, int phone_channel_major, const int64_t* pitch_dev, const float* pitchf_dev,
+                           const float* spec_dev, int sid, const float* noise_q_dev, const float* noise_src_dev, int64_t T, int64_t ids, float* out_dev,
+                           const rvc_synth_forward_taps* taps, rvc_gen_tape* tape);
+/* The vector-Jacobian product of the taped decoder pass: dy_hat_dev [seg * upp] -> dz_dev [inter][seg] (the sliced latent's cotangent), dcond_dev [up_init]
+ * (into dec.cond's output: the float64 row sums of conv_pre's output cotangent), dg_dev [gin] (= cond_w^T dcond, into emb_g's row), dhar_dev [seg * upp] (the
+ * harmonic source's; the chain through m_source belongs to the weight gradients); the last three may be NULL (the tape's d.cond, d.g and d.har are written on every call; the pointers receive copies), dhar_dev must be for a no-f0 net.  Leaky-ReLU
+ * masks are read from the tape.  The ResBlock and up-sampler data gradients run on a bf16x3 MFMA kernel (conv_gen_bwd.hip); no floating-point atomics: two
+ * calls give the same bits.  Not here: weight and bias gradients, enc_q / flow / enc_p / m_source, the optimizer.  Errors: a tape of another handle or another
+ * segment, no taped forward before it, dhar from a no-f0 net.  _launch_count: the size of the plan (independent of the segment; touches no stream), -1 on error. */
+int rvc_synth_dec_input_grad(rvc_synth* s, void* stream, rvc_gen_tape* tape, const float* dy_hat_dev, float* dz_dev, float* dcond_dev, float* dg_dev,
+                             float* dhar_dev);
+int rvc_synth_dec_input_grad_launch_count(rvc_synth* s);
 /* kl_loss of one item (reference lib/train/losses.py:596-611): sum_dev[0] = sum over c < C, t < len of logs_p - logs_q - 0.5 + 0.5 (z_p - m_p)^2 exp(-2 logs_p)
  * (float64 accumulation, fixed order: two calls give the same bits), sum_dev[1] = len (the mask's sum); rows have pitch T_pitch >= len. */
 int rvc_kl_loss(void* stream, const float* z_p_dev, const float* logs_q_dev, const float* m_p_dev, const float* logs_p_dev, int C, int64_t T_pitch,
