@@ -61,6 +61,10 @@ struct GenBwdImages {
   DevBuf<uint16_t> pre; std::vector<DevBuf<uint16_t>> up, c1, c2; std::vector<DevVec> noise;
   size_t bytes = 0;
 };
+// The decoder's weight-gradient pass (synth_dec_weight_grad), opt-in through synth_keep_parameters: weight_v / weight_g of the weight-normed decoder layers on the
+// device for the chain through weight norm (c1 / c2: index (i * 3 + j) * 3 + m).  DecParam: the dec.* parameter tensors in the reference module's state-dict order.
+struct GenKept { bool on = false; std::vector<DevVec> up_v, up_g, c1_v, c1_g, c2_v, c2_g; size_t bytes = 0; };
+struct DecParam { std::string name; std::vector<long long> shape; };
 struct SynthWeights {    // what synth_finalize builds, and what the graph has learnt about it
   DevVec emb_phone_wT, emb_phone_b, emb_pitch, emb_g;
   std::vector<EncoderLayer> enc;
@@ -72,6 +76,7 @@ struct SynthWeights {    // what synth_finalize builds, and what the graph has l
   std::vector<GenStage> stages;
   float lin_w = 1.f, lin_b = 0.f;
   GenHostWeights gen_host; GenBwdImages gen_bwd;
+  GenKept kept; std::vector<DecParam> dec_params; std::map<std::string, int> dec_index;
   ZeroedBlock imgs;      // split-resident image block whose margins are known to be zero (split_imgs_alloc; keys: T, and the columns of the z image = the generator's window)
 };
 struct Synth : SynthWeights {
@@ -84,6 +89,8 @@ struct Synth : SynthWeights {
   int up_init = 512; std::vector<int> rb_k, up_rates, up_k; std::vector<std::vector<int>> rb_d;
   int upp = 1;
   int spec_channels = 0, segment = 0;   // training forward: rows of the posterior's spectrogram, frames of the generator's slice
+  bool keep_params = false;   // synth_keep_parameters: the next finalize keeps what the weight-gradient pass needs
+  DevVec wgrad_part;     // the weight-gradient GEMM's partial images, every layer's in turn (at most kGenWgradPartFloats floats; grown on demand)
   bool f0 = true;        // false: the *_nono family (no pitch embedding, plain Generator: reference models.py:244-311,:812-1022)
 };
 
@@ -109,6 +116,10 @@ int synth_upp(const Synth* S) { return S->upp; }
 int synth_feat_dim(const Synth* S) { return S->feat_dim; }
 bool synth_has_f0(const Synth* S) { return S->f0; }
 bool synth_has_posterior(const Synth* S) { return S->ready && S->post_enc.built; }
+void synth_keep_parameters(Synth* S, bool on) {
+  RVC_REQUIRE(!S->ready, "synth_keep_parameters: set the switch before finalize");
+  S->keep_params = on;
+}
 
 // Frames of z on either side of a kept output window that the generator's result inside the window depends on (GeneratorNSF / Generator, reference
 // lib/infer_pack/models.py:460-566,:244-311): the layer table walked backwards from the waveform.  h = reach in samples at the current rate.
@@ -288,6 +299,35 @@ void synth_finalize(Synth* S) {
         st.rb[j].c2[m] = make_conv1d(ts, rb + "convs2." + std::to_string(m), 1, (k - 1) / 2, 1, true, true, 1.f, 0, -1, keep ? &GH.c2[q] : nullptr);
       }
     }
+  }
+  // the dec.* parameter tensors in the reference module's state-dict order; with keep_params: weight_v / weight_g of the weight-normed layers stay on the device
+  {
+    GenKept& K = S->kept;
+    K.on = S->keep_params;
+    auto add = [&](const std::string& name) {
+      const HostTensor& t = ts.get(name);
+      S->dec_index[name] = (int)S->dec_params.size();
+      S->dec_params.push_back({name, t.shape});
+    };
+    auto add_wn = [&](const std::string& p, DevVec* v, DevVec* g) {
+      add(p + ".bias"); add(p + ".weight_g"); add(p + ".weight_v");
+      if (K.on) { v->upload(ts.get(p + ".weight_v").data); g->upload(ts.get(p + ".weight_g").data); K.bytes += (v->n + g->n) * sizeof(float); }
+    };
+    if (K.on) { K.up_v.resize(nu); K.up_g.resize(nu); K.c1_v.resize((size_t)nu * 9); K.c1_g.resize((size_t)nu * 9); K.c2_v.resize((size_t)nu * 9); K.c2_g.resize((size_t)nu * 9); }
+    if (S->f0) {
+      add("dec.m_source.l_linear.weight"); add("dec.m_source.l_linear.bias");
+      for (int i = 0; i < nu; ++i) { add("dec.noise_convs." + std::to_string(i) + ".weight"); add("dec.noise_convs." + std::to_string(i) + ".bias"); }
+    }
+    add("dec.conv_pre.weight"); add("dec.conv_pre.bias");
+    for (int i = 0; i < nu; ++i) add_wn("dec.ups." + std::to_string(i), K.on ? &K.up_v[i] : nullptr, K.on ? &K.up_g[i] : nullptr);
+    for (int n = 0; n < nu * 3; ++n)
+      for (int c = 1; c <= 2; ++c)
+        for (int m = 0; m < 3; ++m) {
+          const size_t q = (size_t)n * 3 + m;
+          add_wn("dec.resblocks." + std::to_string(n) + ".convs" + std::to_string(c) + "." + std::to_string(m),
+                 !K.on ? nullptr : (c == 1 ? &K.c1_v[q] : &K.c2_v[q]), !K.on ? nullptr : (c == 1 ? &K.c1_g[q] : &K.c2_g[q]));
+        }
+    add("dec.conv_post.weight"); add("dec.cond.weight"); add("dec.cond.bias");
   }
   S->ts.clear();
   S->ready = true;
@@ -583,13 +623,16 @@ static void gen_tail(Synth* S, hipStream_t s, Arena& A, bool gs, unsigned char* 
 // and the deltas of synth_dec_input_grad, the cotangent at each convolution's output:
 //   d.post [1][seg upp] (conv_post's), d.out{i} (at EACH ResBlock's output of stage i: the stage output's cotangent / 3), d.rb{i}.{j}.t{m}, d.rb{i}.{j}.y{m}
 //   (m = 1, 2), d.up{i} (the stage sum: the up-sampler's and the noise convolution's), d.pre (conv_pre's), d.cond [1][up_init], d.g [1][gin], d.har
+// and, on a handle with kept parameters (synth_keep_parameters), what the weight-gradient pass reads beside them: sine [1][seg upp] (the source before
+// m_source.l_linear; f0 family), g [1][gin] (the item's emb_g row)
 struct GenTape {
   struct Tensor { size_t off; int rows; long long cols; };
   const Synth* S = nullptr; int seg = 0; bool recorded = false;
+  bool backward_done = false;      // a backward data pass has run since the last taped forward: the deltas belong to the recorded activations
   std::map<std::string, Tensor> t;
   DevVec mem; float* fr = nullptr;      // fr: the im2col frames of a wide noise convolution (scratch)
   // timing (gen_tape_timing; off: no event is ever created or recorded): events around the taped decoder and at the backward's stage boundaries
-  bool timing = false; std::vector<hipEvent_t> ev; int fwd_marks = 0, bwd_marks = 0;
+  bool timing = false; std::vector<hipEvent_t> ev; int fwd_marks = 0, bwd_marks = 0, wgrad_marks = 0;
   GenTape() = default;
   GenTape(const GenTape&) = delete; GenTape& operator=(const GenTape&) = delete;
   ~GenTape() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
@@ -604,6 +647,7 @@ struct GenTape {
     return mem.p + it->second.off;
   }
 };
+constexpr int kWgradMark0 = 16;      // the weight-gradient pass's events: slots 16 .. (the forward's are 0, 1; the backward's 2 .. n + 4)
 static std::string rb_name(int i, int j, const char* what, int m) { return "rb" + std::to_string(i) + "." + std::to_string(j) + "." + what + std::to_string(m); }
 static void tape_check(const Synth* S, const GenTape* tape) {
   RVC_REQUIRE(tape->S == S, "the tape was created from another synthesizer handle");
@@ -684,6 +728,8 @@ GenTape* gen_tape_create(Synth* S) {
   layout(false); layout(true);
   add("d.cond", 1, S->up_init); add("d.g", 1, S->gin);
   if (S->f0) add("d.har", 1, N);
+  // what the weight-gradient pass reads beside the activations and deltas (a handle with kept parameters only): the source before m_source.l_linear, emb_g's row
+  if (S->kept.on) { if (S->f0) add("sine", 1, N); add("g", 1, S->gin); }
   size_t fr = 0;
   {
     long long Tn = seg;
@@ -827,7 +873,7 @@ static int dec_backward(const Synth* S, hipStream_t s, GenTape* tape, const floa
   mark();
   return launches;
 }
-void gen_tape_timing(GenTape* T, bool on) { T->timing = on; if (!on) T->fwd_marks = T->bwd_marks = 0; }
+void gen_tape_timing(GenTape* T, bool on) { T->timing = on; if (!on) T->fwd_marks = T->bwd_marks = T->wgrad_marks = 0; }
 // waits for the recorded events.  ms[0]: the taped decoder (conv_pre .. y_hat) of the last taped forward; then the last backward's intervals in execution order:
 // tanh + conv_post, stage n - 1 .. stage 0, conv_pre + conditioning + noise branch.  Returns the number of values (0: timing off or nothing recorded yet).
 int gen_tape_times(GenTape* T, float* ms, int cap) {
@@ -852,6 +898,153 @@ void synth_dec_input_grad(Synth* S, hipStream_t s, GenTape* tape, const float* d
   RVC_REQUIRE(tape->recorded, "the tape holds no forward pass: call synth_forward_tape first");
   RVC_REQUIRE(S->f0 || !dhar, "no-f0 model: there is no harmonic source, dhar must be NULL");
   dec_backward(S, s, tape, dy, dz, dcond, dg, dhar);
+  tape->backward_done = true;
+}
+
+// ------------------------------------------------------------------------------------------------ the decoder's weight-gradient pass
+// d loss / d(parameter) for every dec.* tensor, summed over the B items, from the tapes' activations and deltas (GeneratorNSF / Generator, reference models.py:460-566,
+// ResBlock1 modules.py:295-308).  With lr the leaky ReLU (slope 0.1; 0.01 in front of conv_post) and every sum also over the items:
+//   convs1.m of (i, j), dilation d:  dW[co][ci][t] = sum_n d.rb.t{m}[co][n] lr(y_m)[ci][n + t d - pad]          db = row sums of d.rb.t{m}
+//   convs2.m:                        dW[co][ci][t] = sum_n Dy[co][n] lr(t_m)[ci][n + t - pad], Dy = d.rb.y{m+1} (m < 2) or d.out{i}     db = row sums of Dy
+//   ups.i [Cin][Cout][k]:            dW[ci][co][t] = sum_n lr(prev)[ci][n] d.up{i}[co][u n + t - pad]            db = row sums of d.up{i}
+//   noise_convs.i, conv_pre, cond, conv_post, m_source.l_linear: the direct kernels of conv_gen_wgrad.hip
+// and the chain through weight norm in the finishing step.  Every dense convolution is one launch of conv_gen_wgrad_kernel plus one finishing launch whatever B and
+// the segment; tapes null: nothing is launched, the return value is the number of launches of the plan.  No atomics: two calls give the same bits.
+struct GenWgradLayer { ConvGenWgradPlan x; GenWgradFinishArgs f; int stage; };
+static int dec_wgrad(Synth* S, hipStream_t s, GenTape* const* tapes, int B, float* const* grads) {
+  const GenKept& K = S->kept;
+  const int seg = S->segment, nu = (int)S->stages.size();
+  const long long N = (long long)seg * S->upp;
+  const bool run = tapes != nullptr;
+  int launches = 0;
+  auto items = [&](const std::string& name) { GenItems it{}; if (run) for (int b = 0; b < B; ++b) it.p[b] = tapes[b]->ptr(name); return it; };
+  auto grad = [&](const std::string& name) -> float* {
+    if (!run) return nullptr;
+    auto it = S->dec_index.find(name);
+    RVC_REQUIRE(it != S->dec_index.end(), "no parameter tensor '" + name + "'");
+    return grads[it->second];
+  };
+  std::vector<GenWgradLayer> plan;
+  // one dense layer: P / G the tape names of the two operands; prefix: the layer's state-dict prefix; v / g: the kept weight_v / weight_g (null: a plain weight
+  // and no bias here); bias: the tape name of the delta whose row sums are the bias gradient (brows rows of bn columns)
+  auto gemm = [&](int stage, const std::string& Pn, const std::string& Gn, int R, int C, int k, long long n, long long Tg, int cstride, int tstep, int off0, float sp, float sg,
+                  const std::string& prefix, const DevVec* v, const DevVec* g, const std::string& bias, int brows, long long bn) {
+    launches += 2;
+    if (!run) return;
+    GenWgradLayer L{};
+    ConvGenWgradArgs a{};
+    const GenItems Pi = items(Pn), Gi = items(Gn);
+    for (int b = 0; b < B; ++b) { a.P[b] = Pi.p[b]; a.G[b] = Gi.p[b]; }
+    a.B = B; a.R = R; a.C = C; a.k = k; a.N = (int)n; a.ldP = n; a.ldG = Tg; a.Tg = (int)Tg; a.cstride = cstride; a.tstep = tstep; a.off0 = off0; a.slopeP = sp; a.slopeG = sg;
+    RVC_REQUIRE(n < (1LL << 31) && Tg < (1LL << 31) && conv_gen_wgrad_plan(a, L.x), "decoder layer does not fit the weight-gradient kernel: " + prefix);
+    GenWgradFinishArgs& f = L.f;
+    f.pstride = (long long)R * C * k; f.splits = L.x.splits; f.R = R; f.L = C * k;
+    if (v) {
+      RVC_REQUIRE(v->n == (size_t)R * C * k && g->n == (size_t)R, "kept weight_v / weight_g do not have the layer's shape: " + prefix);
+      f.v = v->p; f.g = g->p; f.gw = grad(prefix + ".weight_v"); f.gg = grad(prefix + ".weight_g"); f.gb = grad(prefix + ".bias");
+      f.D = items(bias); f.B = B; f.brows = brows; f.N = bn;
+    } else {
+      f.gw = grad(prefix + ".weight");
+    }
+    L.stage = stage;
+    plan.push_back(L);
+  };
+  long long Tn = seg;
+  for (int i = 0; i < nu; ++i) {
+    const GenStage& st = S->stages[i];
+    const int Cc = S->up_init >> (i + 1), Cin = S->up_init >> i;
+    const long long Tc = Tn;
+    Tn *= st.u;
+    const std::string si = std::to_string(i);
+    gemm(i, i > 0 ? "out" + std::to_string(i - 1) : "pre", "d.up" + si, Cin, Cc, st.k, Tc, Tn, st.u, 1, -((st.k - st.u) / 2), 0.1f, 1.f, "dec.ups." + si,
+         run ? &K.up_v[i] : nullptr, run ? &K.up_g[i] : nullptr, "d.up" + si, Cc, Tn);
+    for (int j = 0; j < 3; ++j) {
+      const int k = S->rb_k[j];
+      const std::string rb = "dec.resblocks." + std::to_string(i * 3 + j);
+      for (int m = 0; m < 3; ++m) {
+        const size_t q = (size_t)(i * 3 + j) * 3 + m;
+        const int dil = S->rb_d[j][m];
+        const std::string dt = "d." + rb_name(i, j, "t", m), dy = m < 2 ? "d." + rb_name(i, j, "y", m + 1) : "d.out" + si;
+        gemm(i, dt, m > 0 ? rb_name(i, j, "y", m) : "up" + si, Cc, Cc, k, Tn, Tn, 1, dil, -((k * dil - dil) / 2), 1.f, 0.1f, rb + ".convs1." + std::to_string(m),
+             run ? &K.c1_v[q] : nullptr, run ? &K.c1_g[q] : nullptr, dt, Cc, Tn);
+        gemm(i, dy, rb_name(i, j, "t", m), Cc, Cc, k, Tn, Tn, 1, 1, -((k - 1) / 2), 1.f, 0.1f, rb + ".convs2." + std::to_string(m),
+             run ? &K.c2_v[q] : nullptr, run ? &K.c2_g[q] : nullptr, dy, Cc, Tn);
+      }
+    }
+  }
+  gemm(nu, "d.pre", "z", S->up_init, S->inter, 7, seg, seg, 1, 1, -3, 1.f, 1.f, "dec.conv_pre", nullptr, nullptr, "", 0, 0);
+  if (run) {
+    size_t most = 0;
+    for (const GenWgradLayer& L : plan) most = std::max(most, L.x.part_floats);
+    if (S->wgrad_part.n < most) { RVC_HIP_CHECK(hipStreamSynchronize(s)); S->wgrad_part.alloc(most); }      // (an earlier pass on this stream may still read the old block)
+    tapes[0]->mark(s, kWgradMark0);
+    int stage = 0;
+    for (GenWgradLayer& L : plan) {
+      if (L.stage != stage) { stage = L.stage; tapes[0]->mark(s, kWgradMark0 + stage); }
+      L.x.a.part = S->wgrad_part.p; L.f.part = S->wgrad_part.p;
+      conv_gen_wgrad_launch(L.x, s);
+      gen_wgrad_finish(s, L.f);
+    }
+  }
+  // the direct kernels: conv_post, the conditioning (its bias sum is conv_pre's too), the noise convolutions, m_source
+  const int Clast = S->up_init >> nu;
+  ++launches; if (run) gen_wgrad_post(s, items("d.post"), items("out" + std::to_string(nu - 1)), B, Clast, N, 7, 3, 0.01f, grad("dec.conv_post.weight"));
+  ++launches; if (run) gen_wgrad_cond(s, items("d.cond"), items("g"), B, S->up_init, S->gin, grad("dec.cond.weight"), grad("dec.cond.bias"), grad("dec.conv_pre.bias"));
+  if (S->f0) {
+    long long Ti = seg;
+    for (int i = 0; i < nu; ++i) {
+      const GenStage& st = S->stages[i];
+      Ti *= st.u;
+      const std::string nc = "dec.noise_convs." + std::to_string(i);
+      ++launches;
+      if (run) gen_wgrad_noise(s, items("d.up" + std::to_string(i)), items("har"), B, S->up_init >> (i + 1), Ti, N, st.noise_k, st.noise_s, st.noise_k > 1 ? st.noise_s / 2 : 0,
+                               grad(nc + ".weight"), grad(nc + ".bias"));
+    }
+    ++launches; if (run) gen_wgrad_msource(s, items("d.har"), items("har"), items("sine"), B, N, grad("dec.m_source.l_linear.weight"), grad("dec.m_source.l_linear.bias"));
+  }
+  if (run) { tapes[0]->mark(s, kWgradMark0 + nu + 1); tapes[0]->wgrad_marks = nu + 2; }
+  return launches;
+}
+int synth_dec_param_count(const Synth* S) { RVC_REQUIRE(S->ready, "synth_finalize has not been called"); return (int)S->dec_params.size(); }
+void synth_dec_param_info(const Synth* S, int k, std::string& name, std::vector<long long>& shape) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  RVC_REQUIRE(k >= 0 && k < (int)S->dec_params.size(), "parameter index out of range");
+  name = S->dec_params[k].name; shape = S->dec_params[k].shape;
+}
+long long synth_dec_param_total(const Synth* S) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  long long n = 0;
+  for (const DecParam& p : S->dec_params) { long long e = 1; for (long long d : p.shape) e *= d; n += e; }
+  return n;
+}
+size_t synth_kept_bytes(const Synth* S) { return S->kept.bytes; }
+int synth_dec_weight_grad_launch_count(const Synth* S) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  return dec_wgrad(const_cast<Synth*>(S), nullptr, nullptr, 1, nullptr);
+}
+void synth_dec_weight_grad(Synth* S, hipStream_t s, GenTape* const* tapes, int B, float* const* grads) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  RVC_REQUIRE(S->kept.on, "dec_weight_grad needs the parameters on the device: call rvc_synth_keep_parameters(s, 1) before finalize (trainable=True)");
+  RVC_REQUIRE(B >= 1 && B <= kGenWgradMaxItems, "1 <= B <= " + std::to_string(kGenWgradMaxItems) + " tapes per weight-gradient pass");
+  RVC_REQUIRE(tapes && grads, "null argument");
+  for (int b = 0; b < B; ++b) {
+    RVC_REQUIRE(tapes[b], "null tape");
+    tape_check(S, tapes[b]);
+    RVC_REQUIRE(tapes[b]->recorded, "the tape holds no forward pass: call synth_forward_tape first");
+    RVC_REQUIRE(tapes[b]->backward_done, "the tape holds no backward pass after its last taped forward: call synth_dec_input_grad first");
+  }
+  for (size_t k = 0; k < S->dec_params.size(); ++k) RVC_REQUIRE(grads[k], "null gradient pointer");
+  dec_wgrad(S, s, tapes, B, grads);
+}
+// the last weight-gradient pass's intervals on its first tape (timing on): stage 0 .. n - 1 (up-sampler and ResBlocks), then conv_pre and the direct kernels
+int gen_tape_wgrad_times(GenTape* T, float* ms, int cap) {
+  if (!T->timing || T->wgrad_marks < 2) return 0;
+  int n = 0;
+  for (int k = 1; k < T->wgrad_marks && n < cap; ++k) {
+    RVC_HIP_CHECK(hipEventSynchronize(T->ev[kWgradMark0 + k]));
+    RVC_HIP_CHECK(hipEventElapsedTime(&ms[n++], T->ev[kWgradMark0 + k - 1], T->ev[kWgradMark0 + k]));
+  }
+  return n;
 }
 
 // the phone features channel-major [feat_dim][T]: the caller's own tensor, or its transpose as the graph's first temporary
@@ -1004,9 +1197,10 @@ static void synth_forward_graph(Synth* S, hipStream_t s, Arena& A, const float* 
     double* bsum = A.alloc<double>((size_t)((N + 1023) / 1024));
     if (!dry) {
       segment_gather(s, pitchf, 1, T, ids, seg, pfs);
-      sine_source(s, pfs, noise_src, har, nullptr, rad, tmp, bsum, seg, S->upp, (float)S->sr, S->lin_w, S->lin_b);
+      sine_source(s, pfs, noise_src, har, tape && S->kept.on ? tape->ptr("sine") : nullptr, rad, tmp, bsum, seg, S->upp, (float)S->sr, S->lin_w, S->lin_b);
     }
   }
+  if (tape && S->kept.on && !dry) RVC_HIP_CHECK(hipMemcpyAsync(tape->ptr("g"), g, (size_t)S->gin * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (tape) { if (!dry) gen_tail_tape(S, s, *tape, pre_bias, out); }
   else gen_tail(S, s, A, gs, im.z_s, zs, har, pre_bias, seg, 0, seg, h2, out, nullptr);
 }
@@ -1057,7 +1251,7 @@ void synth_infer(Synth* S, hipStream_t s, const float* feat, int feat_channel_ma
 void synth_forward_tape(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, const float* spec,
                         int sid, const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps, GenTape* tape) {
   RVC_REQUIRE(S->ready, "synth_finalize has not been called");
-  if (tape) { tape_check(S, tape); tape->recorded = false; }
+  if (tape) { tape_check(S, tape); tape->recorded = false; tape->backward_done = false; }
   RVC_REQUIRE(S->post_enc.built, "no posterior encoder loaded: the checkpoint had no enc_q.* tensors (an inference checkpoint)");
   RVC_REQUIRE(S->segment > 0, "segment_size is not set in the configuration");
   RVC_REQUIRE(T >= S->segment && T >= 11, "the sequence is shorter than the segment");

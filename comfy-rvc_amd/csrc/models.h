@@ -47,6 +47,18 @@ void synth_forward_tape(Synth* S, hipStream_t s, const float* feat, int feat_cha
                         int sid, const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps, GenTape* tape);
 void synth_dec_input_grad(Synth* S, hipStream_t s, GenTape* tape, const float* dy, float* dz, float* dcond, float* dg, float* dhar);
 int synth_dec_input_grad_launch_count(const Synth* S);   // pure: the size of the plan, independent of the segment
+// The decoder's weight-gradient pass (model_synth.hip, conv_gen_wgrad.hip): d loss / d(parameter) of every dec.* tensor summed over the B items whose tapes are
+// given (each recorded, and through synth_dec_input_grad since), grads one device pointer per parameter tensor in synth_dec_param_info's order (the reference
+// module's state-dict order, names with their "dec." prefix), each fully written.  Needs synth_keep_parameters(S, true) before finalize: weight_v / weight_g of
+// the weight-normed layers stay on the device and a tape also records `sine` and `g` (without it nothing of a handle changes).  B <= kGenWgradMaxItems.
+void synth_keep_parameters(Synth* S, bool on);
+int synth_dec_param_count(const Synth* S);
+void synth_dec_param_info(const Synth* S, int k, std::string& name, std::vector<long long>& shape);
+long long synth_dec_param_total(const Synth* S);
+size_t synth_kept_bytes(const Synth* S);
+int synth_dec_weight_grad_launch_count(const Synth* S);   // pure: the size of the plan, independent of B and of the segment
+void synth_dec_weight_grad(Synth* S, hipStream_t s, GenTape* const* tapes, int B, float* const* grads);
+int gen_tape_wgrad_times(GenTape* T, float* ms, int cap);   // the last weight-gradient pass's intervals (its first tape, timing on): stage 0 .. n - 1, the rest
 // train_forward.hip: z = m + noise exp(logs) from stats [m | logs] (2 C rows); columns [ids, ids + seg) of x [C][T] -> y [C][seg]; the two loss reductions
 void posterior_sample(hipStream_t s, const float* stats, const float* noise, float* z, int C, int T);
 void segment_gather(hipStream_t s, const float* x, int C, int T, int ids, int seg, float* y);

@@ -343,6 +343,75 @@ int rvc_synth_dec_input_grad_launch_count(rvc_synth* s) {
   try { return s ? synth_dec_input_grad_launch_count(s->m) : -1; }
   catch (const std::exception& e) { set_error(e.what()); return -1; }
 }
+int rvc_synth_keep_parameters(rvc_synth* s, int on) { RVC_TRY RVC_REQUIRE(s, "null argument"); synth_keep_parameters(s->m, on != 0); RVC_CATCH }
+int rvc_synth_dec_param_count(rvc_synth* s) {
+  try { return s ? synth_dec_param_count(s->m) : -1; }
+  catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_synth_dec_param_info(rvc_synth* s, int k, char* name, int name_cap, int64_t* shape, int* ndim) {
+  RVC_TRY
+  RVC_REQUIRE(s && name && name_cap > 0 && shape && ndim, "null argument");
+  std::string n; std::vector<long long> sh;
+  synth_dec_param_info(s->m, k, n, sh);
+  RVC_REQUIRE((int)n.size() < name_cap && sh.size() <= 8, "name buffer too small");
+  std::copy(n.begin(), n.end(), name); name[n.size()] = 0;
+  for (size_t i = 0; i < sh.size(); ++i) shape[i] = sh[i];
+  *ndim = (int)sh.size();
+  RVC_CATCH
+}
+int64_t rvc_synth_dec_param_total(rvc_synth* s) {
+  try { return s ? (int64_t)synth_dec_param_total(s->m) : -1; }
+  catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_synth_dec_weight_grad(rvc_synth* s, void* stream, rvc_gen_tape* const* tapes, int B, float* const* grads_dev) {
+  RVC_TRY
+  RVC_REQUIRE(s && tapes && grads_dev, "null argument");
+  RVC_REQUIRE(B >= 1 && B <= kGenWgradMaxItems, "1 <= B <= " + std::to_string(kGenWgradMaxItems) + " tapes per weight-gradient pass");
+  GenTape* t[kGenWgradMaxItems];
+  for (int b = 0; b < B; ++b) { RVC_REQUIRE(tapes[b], "null tape"); t[b] = tapes[b]->t; }
+  RVC_HIP_CHECK(hipSetDevice(s->ctx->c.device));
+  synth_dec_weight_grad(s->m, (hipStream_t)stream, t, B, grads_dev);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_synth_dec_weight_grad_launch_count(rvc_synth* s) {
+  try { return s ? synth_dec_weight_grad_launch_count(s->m) : -1; }
+  catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_gen_tape_wgrad_times(rvc_gen_tape* t, float* ms_host, int cap) {
+  try { RVC_REQUIRE(t && ms_host && cap > 0, "bad argument"); return gen_tape_wgrad_times(t->t, ms_host, cap); }
+  catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+static ConvGenWgradArgs conv1d_wgrad_args(int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride, int tstep, int off0, float slope_p, float slope_g) {
+  RVC_REQUIRE(N >= 1 && N < (1LL << 31) && Tg >= 1 && Tg < (1LL << 31), "bad length");
+  ConvGenWgradArgs a{};
+  a.B = B; a.R = R; a.C = C; a.k = k; a.N = (int)N; a.ldP = N; a.ldG = Tg; a.Tg = (int)Tg; a.cstride = cstride; a.tstep = tstep; a.off0 = off0; a.slopeP = slope_p; a.slopeG = slope_g;
+  return a;
+}
+int rvc_conv1d_weight_grad_splits(int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride, int tstep, int off0) {
+  try {
+    ConvGenWgradPlan p;
+    RVC_REQUIRE(conv_gen_wgrad_plan(conv1d_wgrad_args(B, R, C, k, N, Tg, cstride, tstep, off0, 1.f, 1.f), p), "the shape does not fit the weight-gradient kernel");
+    return p.splits;
+  } catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_conv1d_weight_grad(void* stream, const float* const* p_dev, const float* const* g_dev, int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride,
+                           int tstep, int off0, float slope_p, float slope_g, float* out_dev) {
+  RVC_TRY
+  RVC_REQUIRE(p_dev && g_dev && out_dev, "null argument");
+  ConvGenWgradArgs a = conv1d_wgrad_args(B, R, C, k, N, Tg, cstride, tstep, off0, slope_p, slope_g);
+  ConvGenWgradPlan p;
+  RVC_REQUIRE(conv_gen_wgrad_plan(a, p), "the shape does not fit the weight-gradient kernel");
+  for (int b = 0; b < B; ++b) { RVC_REQUIRE(p_dev[b] && g_dev[b], "null operand pointer"); p.a.P[b] = p_dev[b]; p.a.G[b] = g_dev[b]; }
+  hipStream_t st = (hipStream_t)stream;
+  p.a.part = (float*)stream_scratch(st, 25, p.part_floats * sizeof(float));
+  conv_gen_wgrad_launch(p, st);
+  GenWgradFinishArgs f{};
+  f.part = p.a.part; f.pstride = (long long)R * C * k; f.splits = p.splits; f.R = R; f.L = C * k; f.gw = out_dev;
+  gen_wgrad_finish(st, f);
+  check_launch();
+  RVC_CATCH
+}
 int rvc_kl_loss_grad(void* stream, const float* z_p, const float* m_p, const float* logs_p, int C, int64_t T_pitch, int64_t len, float scale, float* dz_p,
                      float* dlogs_q, float* dm_p, float* dlogs_p) {
   RVC_TRY

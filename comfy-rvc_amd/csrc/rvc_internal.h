@@ -271,6 +271,32 @@ struct ConvX3dWgradArgs {
 struct ConvX3dWgradPlan { ConvX3dWgradArgs a; dim3 grid; int splits = 1; size_t lds = 0, part_floats = 0; double flops = 0.0; };
 bool conv_x3d_wgrad_plan(const ConvX3dWgradArgs& a, ConvX3dWgradPlan& p);   // false: the layer does not fit the kernel (Co % 128, k <= 16, 32-bit offsets)
 void conv_x3d_wgrad_launch(const ConvX3dWgradPlan& p, hipStream_t s);
+// The weight gradient of the generator's dense 1-D convolutions over the B items of a batch (conv_gen_wgrad.hip):
+//   out[r][c k + t] = sum_item sum_n a_P(P[item][r][n]) a_G(G[item][c][cstride n + tstep t + off0]),  r < R, c < C, t < k, n < N;  a_X(v) = max(v, slope_X v), slope 1: none
+// P [R][ldP] with N valid columns and G [C][ldG] with Tg valid columns (zero outside) per item, each item its own allocation: one base pointer per item.  Both
+// operands fp32 and split in the kernel.  The reduction over (item, n) is cut into `splits` runs of stages (one item, 128 columns each): split z writes the partial
+// image part[z][R][C k]; the caller provides part_floats (<= kGenWgradPartFloats) floats and adds the partials in index order (gen_wgrad_finish).  cps / per /
+// total: filled by the planner.  R % 16 == 0.
+constexpr int kGenWgradMaxItems = 16;                          // items of one pass (the kernels receive their base pointers as arguments)
+constexpr size_t kGenWgradPartFloats = (size_t)16 << 20;       // bound on the partial images of one launch: 64 MiB
+struct GenItems { const float* p[kGenWgradMaxItems]; };
+struct ConvGenWgradArgs {
+  const float* P[kGenWgradMaxItems]; const float* G[kGenWgradMaxItems]; float* part;
+  int B, R, C, k, N; long long ldP, ldG; int Tg, cstride, tstep, off0; float slopeP, slopeG; int cps, per, total;
+};
+struct ConvGenWgradPlan { ConvGenWgradArgs a; dim3 grid; int bm = 128, splits = 1; size_t lds = 0, part_floats = 0; double flops = 0.0; };   // bm: rows per workgroup (128, 64, 32)
+bool conv_gen_wgrad_plan(const ConvGenWgradArgs& a, ConvGenWgradPlan& p);   // false: the layer does not fit the kernel (R % 16, k <= 16, B <= 16, 32-bit offsets, the partial bound)
+void conv_gen_wgrad_launch(const ConvGenWgradPlan& p, hipStream_t s);
+// The finishing step, one workgroup per row: gw[m] = the `splits` partials (pstride floats apart) added in index order, through the weight-norm chain where v / g
+// are given (gg receives grad_g); rows m < brows also write gb[m] = the float64 sum of row m (N columns) of D over the B items (gb null: no bias)
+struct GenWgradFinishArgs { const float* part; long long pstride; int splits, R, L; const float* v; const float* g; float* gw; float* gg; float* gb; GenItems D; int B, brows; long long N; };
+void gen_wgrad_finish(hipStream_t s, const GenWgradFinishArgs& a);
+// the direct kernels of the pass (float64 sums in a fixed order): a noise convolution's weight and bias from d.up [C][T] and the source [Nh]; conv_post's weight
+// from d.post [T] and lrelu_slope(x [C][T]); cond's weight [C][G] and the bias sum (written to gb and gb2) from d.cond [C] and the items' g [G]; m_source.l_linear
+void gen_wgrad_noise(hipStream_t s, const GenItems& D, const GenItems& H, int B, int C, long long T, long long Nh, int k, int stride, int pad, float* gw, float* gb);
+void gen_wgrad_post(hipStream_t s, const GenItems& D, const GenItems& X, int B, int C, long long T, int k, int pad, float slope, float* gw);
+void gen_wgrad_cond(hipStream_t s, const GenItems& DC, const GenItems& Gv, int B, int C, int G, float* gw, float* gb, float* gb2);
+void gen_wgrad_msource(hipStream_t s, const GenItems& DH, const GenItems& H, const GenItems& Sn, int B, long long N, float* gw, float* gb);
 // one ConvBlockRes of 16 or 32 channels (3 x 3, 3 x 3, + x) in one launch (conv_cbr2.hip): x, out fp32 [C][H W], distinct
 bool cbr2_small_eligible(const ConvLayer& c1, const ConvLayer& c2);
 void cbr2_small_run(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, const float* x, int H, int W, float* out);

@@ -27,7 +27,7 @@ class _SynthesizerNSFsid:
 
     def __init__(self, spec_channels, segment_size, inter_channels, hidden_channels, filter_channels, n_heads, n_layers,
                  kernel_size, p_dropout, resblock, resblock_kernel_sizes, resblock_dilation_sizes, upsample_rates,
-                 upsample_initial_channel, upsample_kernel_sizes, spk_embed_dim, gin_channels, sr, device="cuda:0", **kwargs):
+                 upsample_initial_channel, upsample_kernel_sizes, spk_embed_dim, gin_channels, sr, device="cuda:0", trainable=False, **kwargs):
         if isinstance(sr, str):
             sr = {"32k": 32000, "40k": 40000, "48k": 48000}[sr]
         assert str(resblock) == "1", "only ResBlock1 generators are on the RVC inference path"
@@ -57,6 +57,9 @@ class _SynthesizerNSFsid:
         h = C.c_void_p()
         _lib.check(_lib.lib.rvc_synth_create(self._ctx, C.byref(cfg), C.byref(h)))
         self._h = h
+        self.trainable = bool(trainable)
+        if self.trainable:                     # weight_v / weight_g of the decoder stay on the device, tapes record `sine` and `g`: what dec_weight_grad needs
+            _lib.check(_lib.lib.rvc_synth_keep_parameters(self._h, 1))
         self._loaded = False
         self.enc_q = None   # `del net_g.enc_q` in get_vc (reference vc_infer_pipeline.py:219) must keep working
 
@@ -255,8 +258,85 @@ class _SynthesizerNSFsid:
             _lib.check(1)
         return n
 
+    # ------------------------------------------------------------------------------------------- the decoder's weight-gradient pass
+    MAX_WGRAD_ITEMS = 16
+
+    def dec_parameter_shapes(self):
+        """OrderedDict name -> shape of the dec.* parameter tensors in the reference module's state-dict order (rvc_synth_dec_param_info)."""
+        assert self._loaded, "load_state_dict first"
+        out = OrderedDict()
+        name, shape, ndim = C.create_string_buffer(128), (_lib.c_int64 * 8)(), C.c_int()
+        n = _lib.lib.rvc_synth_dec_param_count(self._h)
+        if n < 0:
+            _lib.check(1)
+        for k in range(n):
+            _lib.check(_lib.lib.rvc_synth_dec_param_info(self._h, k, name, 128, shape, C.byref(ndim)))
+            out[name.value.decode()] = tuple(int(shape[i]) for i in range(ndim.value))
+        return out
+
+    def dec_weight_grad(self, tape):
+        """The gradient with respect to every dec.* parameter, summed over the tape's items (rvc_synth_dec_weight_grad): an OrderedDict from state-dict name to a
+        float32 device tensor in the parameter's shape, views of ONE contiguous buffer in dec_parameter_shapes() order (`.flat` of the result holds it).  The tape
+        must have been through dec_input_grad since its last forward_with_tape: the deltas it reads are that pass's.  Needs trainable=True."""
+        assert self._loaded, "load_state_dict first"
+        if not self.trainable:
+            raise ValueError("dec_weight_grad: the net was built without trainable=True (weight_v / weight_g are not kept on the device)")
+        if not isinstance(tape, GeneratorTape) or tape.net is not self:
+            raise ValueError("dec_weight_grad: the tape belongs to another net")
+        return self._dec_weight_grad(tape._h)
+
+    def _dec_weight_grad(self, handles):
+        dev = self.device
+        params = self.dec_parameter_shapes()
+        sizes = [int(np.prod(s)) for s in params.values()]
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        out, o = _GradDict(), 0
+        for (name, shape), n in zip(params.items(), sizes):
+            out[name] = flat[o:o + n].view(shape)
+            o += n
+        out.flat = flat
+        pt = (C.c_void_p * max(1, len(handles)))(*[h.value if isinstance(h, C.c_void_p) else h for h in handles])
+        pg = (C.c_void_p * len(out))(*[t.data_ptr() for t in out.values()])
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.rvc_synth_dec_weight_grad(self._h, _lib.current_stream(), pt, len(handles), pg))
+        return out
+
+    def dec_weight_grad_launch_count(self):
+        """Kernel launches of one dec_weight_grad (rvc_synth_dec_weight_grad_launch_count): a constant of the net, whatever the batch and the segment."""
+        n = int(_lib.lib.rvc_synth_dec_weight_grad_launch_count(self._h))
+        if n < 0:
+            _lib.check(1)
+        return n
+
     def __call__(self, *args, **kwargs):
         return self.forward(*args, **kwargs)
+
+
+def dec_parameter_spec(config, f0=True):
+    """OrderedDict name -> shape of the decoder's parameter tensors (GeneratorNSF / Generator, reference lib/infer_pack/models.py:460-566,:244-311) for a
+    constructor argument list, in the reference module's state-dict order: what dec_parameter_shapes() reports for a loaded net, computed on the host."""
+    inter, rb_k, up_rates, up_init, up_k, gin = config[2], config[10], config[12], config[13], config[14], config[16]
+    nu, s = len(up_rates), OrderedDict()
+    if f0:
+        s["dec.m_source.l_linear.weight"], s["dec.m_source.l_linear.bias"] = (1, 1), (1,)
+        for i in range(nu):
+            s[f"dec.noise_convs.{i}.weight"] = (up_init >> (i + 1), 1, 2 * int(np.prod(up_rates[i + 1:])) if i + 1 < nu else 1)
+            s[f"dec.noise_convs.{i}.bias"] = (up_init >> (i + 1),)
+    s["dec.conv_pre.weight"], s["dec.conv_pre.bias"] = (up_init, inter, 7), (up_init,)
+
+    def wn(p, shape):
+        s[p + ".bias"] = (shape[1],) if ".ups." in p else (shape[0],)
+        s[p + ".weight_g"], s[p + ".weight_v"] = (shape[0], 1, 1), shape
+    for i in range(nu):
+        wn(f"dec.ups.{i}", (up_init >> i, up_init >> (i + 1), up_k[i]))
+    for i in range(nu):
+        for j, k in enumerate(rb_k):
+            for cs in ("convs1", "convs2"):
+                for m in range(3):
+                    wn(f"dec.resblocks.{i * len(rb_k) + j}.{cs}.{m}", (up_init >> (i + 1), up_init >> (i + 1), k))
+    s["dec.conv_post.weight"] = (1, up_init >> nu, 7)
+    s["dec.cond.weight"], s["dec.cond.bias"] = (up_init, gin, 1), (up_init,)
+    return s
 
 
 class GeneratorTape:
@@ -305,6 +385,16 @@ class GeneratorTape:
         nu = len(self.net.upsample_rates)
         names = ["post"] + [f"stage{i}" for i in range(nu - 1, -1, -1)] + ["pre"]
         return {"decoder_forward": float(buf[0]), "backward": {k: float(buf[1 + i]) for i, k in enumerate(names[:n - 1])}}
+
+    def wgrad_times(self):
+        """Milliseconds of the last dec_weight_grad on this tape (timing on; waits for it): {"stage0": .., .., "rest": ..} - per stage the up-sampler and its
+        ResBlocks, then conv_pre and the direct kernels; {} when nothing was recorded."""
+        buf = (C.c_float * 16)()
+        n = int(_lib.lib.rvc_gen_tape_wgrad_times(self._h[0], buf, 16))
+        if n < 0:
+            _lib.check(1)
+        names = [f"stage{i}" for i in range(len(self.net.upsample_rates))] + ["rest"]
+        return {k: float(buf[i]) for i, k in enumerate(names[:n])}
 
     def _names(self, deltas):
         net, out = self.net, []

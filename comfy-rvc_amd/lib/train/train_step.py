@@ -4,8 +4,9 @@ penalty's parameter gradient is not built: c_gp > 0 raises (losses.discriminator
 
 Of the generator half (:565-601) the loss and its cotangents at the generator's outputs: generator_loss_cotangents; and the first step of the generator's own
 backward, the decoder's data pass from d_y_hat to the sliced latent's, the speaker conditioning's and the harmonic source's cotangents:
-generator_decoder_backward over a net_g.forward_with_tape(...) pass.  The generator's weight and bias gradients, the backward of enc_q, the flow, enc_p and
-m_source, its optimizer step and the gradients of the HPSS / TSI / TEFS terms are not built."""
+generator_decoder_backward over a net_g.forward_with_tape(...) pass; and its second step, the gradient of every dec.* parameter (weight norm included) from the
+deltas that pass leaves: generator_decoder_grads.  The backward of enc_q, the flow, enc_p and emb_g, grad_norm_g, the generator's optimizer step and the
+gradients of the HPSS / TSI / TEFS terms are not built."""
 import torch
 
 from ..infer_pack.commons import clip_grad_value_
@@ -69,3 +70,11 @@ def generator_decoder_backward(net_g, tape, d_y_hat):
     `net_g.forward_with_tape(...)`: the decoder's vector-Jacobian product (net_g.dec_input_grad), every per-layer delta left in the tape for the weight-gradient
     pass.  dz is what autograd leaves in z.grad from the decoder branch; the KL cotangents join it in the passes that are not built yet."""
     return net_g.dec_input_grad(tape, d_y_hat)
+
+
+def generator_decoder_grads(net_g, tape, d_y_hat):
+    """(dz, dg, dhar, grads): generator_decoder_backward's three results and the gradient of every dec.* parameter, summed over the batch - the second step of the
+    generator's backward (net_g.dec_weight_grad on the deltas the data pass has just left in the tape).  grads is an OrderedDict from state-dict name to a float32
+    device tensor, views of one flat buffer (`grads.flat`) in net_g.dec_parameter_shapes() order; net_g must have been built with trainable=True."""
+    dz, dg, dhar = net_g.dec_input_grad(tape, d_y_hat)
+    return dz, dg, dhar, net_g.dec_weight_grad(tape)

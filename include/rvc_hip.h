@@ -269,11 +269,40 @@ int rvc_synth_forward_tape(rvc_synth* s, void* stream, const float* phone_dev, i
  * (into dec.cond's output: the float64 row sums of conv_pre's output cotangent), dg_dev [gin] (= cond_w^T dcond, into emb_g's row), dhar_dev [seg * upp] (the
  * harmonic source's; the chain through m_source belongs to the weight gradients); the last three may be NULL (the tape's d.cond, d.g and d.har are written on every call; the pointers receive copies), dhar_dev must be for a no-f0 net.  Leaky-ReLU
  * masks are read from the tape.  The ResBlock and up-sampler data gradients run on a bf16x3 MFMA kernel (conv_gen_bwd.hip); no floating-point atomics: two
- * calls give the same bits.  Not here: weight and bias gradients, enc_q / flow / enc_p / m_source, the optimizer.  Errors: a tape of another handle or another
+ * calls give the same bits.  The weight and bias gradients are rvc_synth_dec_weight_grad's (below).  Not here: enc_q / flow / enc_p, the optimizer.  Errors: a tape of another handle or another
  * segment, no taped forward before it, dhar from a no-f0 net.  _launch_count: the size of the plan (independent of the segment; touches no stream), -1 on error. */
 int rvc_synth_dec_input_grad(rvc_synth* s, void* stream, rvc_gen_tape* tape, const float* dy_hat_dev, float* dz_dev, float* dcond_dev, float* dg_dev,
                              float* dhar_dev);
 int rvc_synth_dec_input_grad_launch_count(rvc_synth* s);
+/* ---- the generator's backward, second step: the decoder's weight and bias gradients.  rvc_synth_keep_parameters(s, 1) BEFORE rvc_synth_finalize makes the handle
+ * keep weight_v / weight_g of dec.ups.* and dec.resblocks.* on the device (about the decoder's weights again) and makes its tapes record two more tensors, `sine`
+ * [1][seg upp] (the source before m_source.l_linear; f0 family) and `g` [1][gin] (the item's emb_g row), both reached by rvc_gen_tape_tensor; every other tape
+ * tensor and the taped wave keep their bits.  Without it a handle allocates and launches exactly what it did, and rvc_synth_dec_weight_grad is an error.
+ * rvc_synth_dec_param_count / _param_info / _param_total list the dec.* parameter tensors, names with their "dec." prefix, in the reference module's state-dict
+ * order: m_source.l_linear, noise_convs (f0 family), conv_pre, ups (bias, weight_g, weight_v), resblocks, conv_post, cond.
+ * rvc_synth_dec_weight_grad: d loss / d(parameter) of every such tensor, summed over the B <= 16 items whose tapes are given (host array; each recorded by
+ * rvc_synth_forward_tape and run through rvc_synth_dec_input_grad since) -> grads_dev, a HOST array of one device pointer per parameter tensor in that order,
+ * each fully written.  The chain through weight norm (dim 0) is included.  Every ResBlock convolution, every up-sampler and conv_pre run on one bf16x3 MFMA GEMM
+ * over all items (conv_gen_wgrad.hip: both operands split in the kernel, the leaky ReLU applied where an operand is loaded) plus one finishing launch; the
+ * reduction's partial images live in a block the handle owns, at most 64 MiB.  No floating-point atomics: two calls give the same bits.  The launch count is a
+ * constant of the net (_launch_count; -1 on error): it does not depend on B or on the segment.  Errors: no kept parameters, B < 1 or B > 16, a tape of another
+ * handle or another segment, a tape without a taped forward or without a backward data pass after its last taped forward.
+ * rvc_gen_tape_wgrad_times (timing on, the pass's FIRST tape): the last pass's intervals in milliseconds - stage 0 .. n - 1, then conv_pre and the direct kernels. */
+int rvc_synth_keep_parameters(rvc_synth* s, int on);
+int rvc_synth_dec_param_count(rvc_synth* s);
+int rvc_synth_dec_param_info(rvc_synth* s, int k, char* name, int name_cap, int64_t* shape, int* ndim);
+int64_t rvc_synth_dec_param_total(rvc_synth* s);
+int rvc_synth_dec_weight_grad(rvc_synth* s, void* stream, rvc_gen_tape* const* tapes, int B, float* const* grads_dev);
+int rvc_synth_dec_weight_grad_launch_count(rvc_synth* s);
+int rvc_gen_tape_wgrad_times(rvc_gen_tape* t, float* ms_host, int cap);
+/* The GEMM of that pass at any small shape, gradient launch plus finish, no weight norm:
+ *   out_dev[r][c k + t] = sum_item sum_n a_p(P[item][r][n]) a_g(G[item][c][cstride n + tstep t + off0]),  a_x(v) = max(v, slope_x v) (slope 1: none; 0 <= slope <= 1)
+ * p_dev / g_dev: HOST arrays of B <= 16 device pointers, P [R][N] and G [C][Tg] dense; elements of G outside [0, Tg) read as zero.  R % 16 == 0, k <= 16.
+ * A Conv1d's weight gradient is P = delta, G = input, (cstride, tstep, off0) = (1, dilation, -pad); a ConvTranspose1d's is P = input, G = delta, (stride, 1, -pad).
+ * _splits: the number of partial images the planner cuts the reduction into for the shape, -1 when the shape does not fit. */
+int rvc_conv1d_weight_grad(void* stream, const float* const* p_dev, const float* const* g_dev, int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride,
+                           int tstep, int off0, float slope_p, float slope_g, float* out_dev);
+int rvc_conv1d_weight_grad_splits(int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride, int tstep, int off0);
 /* kl_loss of one item (reference lib/train/losses.py:596-611): sum_dev[0] = sum over c < C, t < len of logs_p - logs_q - 0.5 + 0.5 (z_p - m_p)^2 exp(-2 logs_p)
  * (float64 accumulation, fixed order: two calls give the same bits), sum_dev[1] = len (the mask's sum); rows have pitch T_pitch >= len. */
 int rvc_kl_loss(void* stream, const float* z_p_dev, const float* logs_q_dev, const float* m_p_dev, const float* logs_p_dev, int C, int64_t T_pitch,
