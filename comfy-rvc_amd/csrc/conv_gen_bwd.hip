@@ -7,11 +7,13 @@
 //   columns  n: the positions of the forward's input, (4 / WM) * 32 per workgroup
 //   K        units of (16-channel chunk of the forward's OUTPUT channels, tap), tap fastest; the weight image (x3_weight_image of W', rows padded to RPx) comes by
 //            LDS-DMA, the gradient operand is gathered through one descriptor per channel row (out of range reads as zero), split in the kernel and stored to LDS;
-//            two slots of U units, conv_x3d_bwd.hip's pipeline
+//            two slots of U units
 // A stride-1 dilated Conv1d(C, C, k) is cstride 1, tstep dil, off0 = pad - (k - 1) dil over the transposed, tap-flipped image W'[ci][co][t] = W[co][ci][k - 1 - t];
 // a ConvTranspose1d(Cin, Cout, k, u, pad) is cstride u, tstep 1, off0 = -pad over its own weight [ci][co][t].  A: the recorded pre-activation (null: no mask),
 // R: the residual cotangent (null: none), accumulate: the output's previous value is added last (the three ResBlocks' sum, in launch order).
-#include "conv_x3_dev.h"
+// The kernel writes the image loop of conv_x3gather_dev.h out: through the shared loop the compiler orders the address arithmetic differently and the 32-channel stage of the decoder's backward pass measured 1.2 % slower
+// (profiles/x3g_dedup_timing.txt), so it keeps its own copy; the planner and the launcher share the header's arithmetic.
+#include "conv_x3gather_dev.h"
 
 namespace rvc {
 
@@ -89,26 +91,7 @@ __global__ __launch_bounds__(256) void conv_gen_bwd_kernel(const ConvGenBwdArgs 
     const bool more = st + 1 < nstages;
     if (more) issue(cur ^ 1);                    // slot cur ^ 1 was last read before the barrier that ended stage st - 1
 #pragma unroll
-    for (int q = 0; q < U; ++q) {
-      const unsigned char* wa = smem_gb + cur * kSlot + q * kUSlot + aoff;
-      const unsigned char* xa = smem_gb + cur * kSlot + q * kUSlot + boff;
-      u32x4 ah[AM], al[AM];
-#pragma unroll
-      for (int am = 0; am < AM; ++am) {
-        ah[am] = *reinterpret_cast<const u32x4*>(wa + am * 512);
-        al[am] = *reinterpret_cast<const u32x4*>(wa + AR * 32 + am * 512);
-      }
-      const u32x4 bh = *reinterpret_cast<const u32x4*>(xa), bl = *reinterpret_cast<const u32x4*>(xa + BN * 32);
-#pragma unroll
-      for (int am = 0; am < AM; ++am)
-        acc[am] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[am]), __builtin_bit_cast(bf16x8, bl), acc[am], 0, 0, 0);
-#pragma unroll
-      for (int am = 0; am < AM; ++am)
-        acc[am] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[am]), __builtin_bit_cast(bf16x8, bh), acc[am], 0, 0, 0);
-#pragma unroll
-      for (int am = 0; am < AM; ++am)
-        acc[am] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[am]), __builtin_bit_cast(bf16x8, bh), acc[am], 0, 0, 0);
-    }
+    for (int q = 0; q < U; ++q) gather_mfma3_unit<AM>(acc, smem_gb + cur * kSlot + q * kUSlot + aoff, AR * 32, smem_gb + cur * kSlot + q * kUSlot + boff, BN * 32);
     if (more) {
       wait_vmcnt<0>();                           // this wave's weight pieces have landed in LDS, its gradient values in registers
       store_b(cur ^ 1);
@@ -116,7 +99,6 @@ __global__ __launch_bounds__(256) void conv_gen_bwd_kernel(const ConvGenBwdArgs 
     __syncthreads();
   }
 
-  // 32 x 32 accumulator layout: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
   const int nn = n0 + wn * 32 + li;
   if (nn < p.N) {
     const int row0 = r0 + wm * (AM * 32) + 4 * lh;
@@ -125,7 +107,7 @@ __global__ __launch_bounds__(256) void conv_gen_bwd_kernel(const ConvGenBwdArgs 
     for (int am = 0; am < AM; ++am)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = row0 + am * 32 + (r & 3) + 8 * (r >> 2);
+        const int row = row0 + am * 32 + (r & 3) + 8 * (r >> 2);      // acc_row32(r, 0) written out: with the helper's parentheses the compiler folds the sum another way and the kernel changes
         if (row < p.R) {
           const long long idx = (long long)row * p.ldY + nn;
           float v = acc[am][r];
@@ -138,14 +120,12 @@ __global__ __launch_bounds__(256) void conv_gen_bwd_kernel(const ConvGenBwdArgs 
   }
 }
 
-template <int WM, int AM, int U> void gen_bwd_launch_t(const ConvGenBwdPlan& p, hipStream_t s) {
-  RVC_ALLOW_BIG_LDS((conv_gen_bwd_kernel<WM, AM, U>));
-  hipLaunchKernelGGL((conv_gen_bwd_kernel<WM, AM, U>), p.grid, dim3(256), p.lds, s, p.a);
-}
 template <int WM, int AM> void gen_bwd_launch_u(const ConvGenBwdPlan& p, hipStream_t s) {
-  if (p.units == 4) gen_bwd_launch_t<WM, AM, 4>(p, s);
-  else if (p.units == 2) gen_bwd_launch_t<WM, AM, 2>(p, s);
-  else gen_bwd_launch_t<WM, AM, 1>(p, s);
+  gather_dispatch_units(p.units, [&](auto u) {
+    constexpr int U = decltype(u)::value;
+    RVC_ALLOW_BIG_LDS((conv_gen_bwd_kernel<WM, AM, U>));
+    hipLaunchKernelGGL((conv_gen_bwd_kernel<WM, AM, U>), p.grid, dim3(256), p.lds, s, p.a);
+  });
 }
 }  // namespace
 
@@ -159,12 +139,10 @@ bool conv_gen_bwd_plan(const ConvGenBwdArgs& a, ConvGenBwdPlan& p) {
   if ((ncols * a.cstride + (long long)a.nt * a.tstep) * 4 >= (1LL << 31) || (long long)a.Td * 4 >= (1LL << 31)) return false;
   const long long nunits = (long long)(a.Ck / 16) * a.nt;
   if (nunits * a.RPx * 64 >= (1LL << 31)) return false;
-  int units = 4;
-  while (nunits % units) units >>= 1;
   p.a = a;
   p.bm = bm;
-  p.units = units;
-  p.lds = (size_t)2 * units * ((size_t)std::max(bm, 64) * 64 + (size_t)bn * 64);
+  p.units = gather_units(nunits);
+  p.lds = gather_image_lds(std::max(bm, 64), bn, p.units);
   p.grid = dim3((unsigned)(ncols / bn), (unsigned)((a.R + bm - 1) / bm), 1);
   p.flops = 2.0 * a.N * a.R * a.Ck * a.nt;
   return true;

@@ -1,6 +1,6 @@
 // The decoder's weight-gradient pass (model_synth.hip::synth_dec_weight_grad): the weight gradient of its dense 1-D convolutions - every ResBlock convolution,
 // every up-sampler, conv_pre - as ONE bf16x3 GEMM kernel over the items of a batch, and the direct kernels around it (finish with the weight-norm chain, the
-// noise convolutions, conv_post, the conditioning's outer product, m_source).  Modelled on conv_x3d_wgrad.hip.
+// noise convolutions, conv_post, the conditioning's outer product, m_source).
 //
 // conv_gen_wgrad_kernel:  out[r][c k + t] = sum_item sum_n a_P(P[item][r][n]) a_G(G[item][c][cstride n + tstep t + off0]),  a_X(v) = max(v, slope_X v) (slope 1: none)
 //   Conv1d(C, R, k, dilation d, pad): P = the layer's delta [R][N], G = the layer's input [C][N] (a pre-activation: the leaky ReLU is applied here, no activated
@@ -8,28 +8,25 @@
 //   ConvTranspose1d(R, C, k, u, pad): P = the layer's input [R][N], G = the layer's delta [C][u N], (u, 1, -pad): the output is the weight [R][C][k]
 //   rows     r: WM * AM * 32 per workgroup (128, 64 or 32; the 32-row tile runs over 128 columns, as in conv_gen_bwd.hip)
 //   columns  q = c k + t in the weight's own order, (4 / WM) * 32 per workgroup; a last tile may be ragged
-//   K        the reduction over (item, n): stages of ONE item and 128 consecutive n, 8 units of three v_mfma_f32_32x32x16_bf16 per accumulator (hi lo, lo hi,
-//            hi hi).  An item's last stage is ragged (n >= N reads as zero): a stage never straddles two items.
+//   K        the reduction over (item, n): stages of ONE item and 128 consecutive n, the pair loop of conv_x3gather_dev.h.  An item's last stage is ragged
+//            (n >= N reads as zero): a stage never straddles two items.
 // Every item is its own allocation with the same layout (a tape): the kernel receives one base pointer per item and operand.  A load instruction fetches ONE
 // row of P or ONE column (c, t) of G for 64 lanes through a descriptor of exactly that (item, channel) row; an element outside [0, Tg) and every n >= N is given
-// kOOB and reads as zero.  BOTH operands are fp32 and are split (split2) in the kernel after the activation.
+// kOOB and reads as zero.  BOTH operands are fp32 and are split in the loop after the activation.
 // The reduction is SPLIT without atomics: blockIdx.z owns a contiguous run of stages and writes its own partial image [R][C k]; gen_wgrad_finish_kernel adds the
-// partials in index order, so two calls give the same bits.  Registers hold the next stage's loads while the current one is multiplied.
-#include "conv_x3_dev.h"
+// partials in index order, so two calls give the same bits.
+#include "conv_x3gather_dev.h"
 #include "signal_dev.h"
 
 namespace rvc {
 
 namespace {
-constexpr int kKB = 128, kKU = kKB / 16;
+constexpr int kKB = kGatherKB;
 
 template <int WM, int AM>
 __global__ __launch_bounds__(256) void conv_gen_wgrad_kernel(const ConvGenWgradArgs p) {
   constexpr int WN = 4 / WM, BM = WM * AM * 32, BN = WN * 32;
   constexpr int kARows = BM / 4, kBCols = BN / 4;          // rows of P and columns of G one wave fetches per stage
-  // one (unit, half) block of rows is padded by one 16-B row: the 16 groups of 4 lanes of a store land in 16 different bank quads
-  constexpr int kABlock = BM * 16 + 16, kBBlock = BN * 16 + 16;
-  constexpr int kAPlane = 2 * kKU * kABlock, kBPlane = 2 * kKU * kBBlock;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem_gw[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -40,8 +37,7 @@ __global__ __launch_bounds__(256) void conv_gen_wgrad_kernel(const ConvGenWgradA
   // this wave's first column of G: (channel, tap); the following ones by counting
   const int q0 = c0 + wave * kBCols, qc0 = q0 / p.k, qt0 = q0 - qc0 * p.k;
 
-  float ar[kARows][2], br[kBCols][2];
-  auto load = [&](int g) {
+  auto load = [&](int g, float (&ar)[kARows][2], float (&br)[kBCols][2]) {
     const int s = g / p.cps, nc = (g - s * p.cps) * kKB;
     const int n = nc + 2 * lane;
     const bool ok0 = n < p.N, ok1 = n + 1 < p.N;
@@ -66,75 +62,19 @@ __global__ __launch_bounds__(256) void conv_gen_wgrad_kernel(const ConvGenWgradA
       if (++t == p.k) { t = 0; ++c; }
     }
   };
-  // lane l's pair is k = 2 l, 2 l + 1 of the stage: unit l >> 3, half (l >> 2) & 1, bytes 4 (l & 3) .. of the row's 16
-  const int soff = (lane & 3) * 4;
-  const float sp = p.slopeP, sg = p.slopeG;
-  auto store = [&]() {
-    unsigned char* a = smem_gw + (lane >> 2) * kABlock + (wave * kARows) * 16 + soff;
-#pragma unroll
-    for (int i = 0; i < kARows; ++i) {
-      unsigned hi, lo;
-      split2(fmaxf(ar[i][0], ar[i][0] * sp), fmaxf(ar[i][1], ar[i][1] * sp), hi, lo);
-      *reinterpret_cast<unsigned*>(a + i * 16) = hi;
-      *reinterpret_cast<unsigned*>(a + i * 16 + kAPlane) = lo;
-    }
-    unsigned char* b = smem_gw + 2 * kAPlane + (lane >> 2) * kBBlock + (wave * kBCols) * 16 + soff;
-#pragma unroll
-    for (int i = 0; i < kBCols; ++i) {
-      unsigned hi, lo;
-      split2(fmaxf(br[i][0], br[i][0] * sg), fmaxf(br[i][1], br[i][1] * sg), hi, lo);
-      *reinterpret_cast<unsigned*>(b + i * 16) = hi;
-      *reinterpret_cast<unsigned*>(b + i * 16 + kBPlane) = lo;
-    }
-  };
-
   f32x16 acc[AM];
-#pragma unroll
-  for (int am = 0; am < AM; ++am)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[am][r] = 0.f;
+  gather_pair_loop<BM, BN, AM>(smem_gw, g0, g1, wave, lane, wm, wn, acc, load, GatherLrelu{p.slopeP}, GatherLrelu{p.slopeG});
 
-  const int aoff = lh * kABlock + (wm * (AM * 32) + li) * 16;
-  const int boff = 2 * kAPlane + lh * kBBlock + (wn * 32 + li) * 16;
-  if (g0 < g1) load(g0);
-  for (int g = g0; g < g1; ++g) {
-    __syncthreads();                               // the previous stage's operands have been read
-    store();
-    __syncthreads();
-    if (g + 1 < g1) load(g + 1);                   // in flight while this stage is multiplied
-#pragma unroll
-    for (int ku = 0; ku < kKU; ++ku) {
-      const unsigned char* wa = smem_gw + aoff + ku * 2 * kABlock;
-      const unsigned char* xa = smem_gw + boff + ku * 2 * kBBlock;
-      u32x4 ah[AM], al[AM];
-#pragma unroll
-      for (int am = 0; am < AM; ++am) {
-        ah[am] = *reinterpret_cast<const u32x4*>(wa + am * 512);
-        al[am] = *reinterpret_cast<const u32x4*>(wa + kAPlane + am * 512);
-      }
-      const u32x4 bh = *reinterpret_cast<const u32x4*>(xa), bl = *reinterpret_cast<const u32x4*>(xa + kBPlane);
-#pragma unroll
-      for (int am = 0; am < AM; ++am)
-        acc[am] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[am]), __builtin_bit_cast(bf16x8, bl), acc[am], 0, 0, 0);
-#pragma unroll
-      for (int am = 0; am < AM; ++am)
-        acc[am] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[am]), __builtin_bit_cast(bf16x8, bh), acc[am], 0, 0, 0);
-#pragma unroll
-      for (int am = 0; am < AM; ++am)
-        acc[am] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[am]), __builtin_bit_cast(bf16x8, bh), acc[am], 0, 0, 0);
-    }
-  }
-
-  // the split's partial image, in the weight's layout; 32 x 32 accumulator layout: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  // the split's partial image, in the weight's layout
   const int q = c0 + wn * 32 + li;
   if (q < ncols) {
-    const int row0 = r0 + wm * (AM * 32) + 4 * lh;
+    const int row0 = r0 + wm * (AM * 32) + acc_row32(0, lh);
     float* O = p.part + ((long long)split * p.R + row0) * ncols + q;
 #pragma unroll
     for (int am = 0; am < AM; ++am)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int dr = am * 32 + (r & 3) + 8 * (r >> 2);
+        const int dr = am * 32 + acc_row32(r, 0);
         if (row0 + dr < p.R) O[(long long)dr * ncols] = acc[am][r];
       }
   }
@@ -166,14 +106,12 @@ bool conv_gen_wgrad_plan(const ConvGenWgradArgs& a0, ConvGenWgradPlan& p) {
   const int rtiles = (a.R + bm - 1) / bm;                     // (a 16- or 48-row layer leaves the last 32-row tile half empty)
   const long long tiles = ((ncols + bn - 1) / bn) * rtiles;
   constexpr long long kTarget = 1024, kMaxSplits = 32;       // about four workgroups per compute unit; a bound on the finishing pass's reads
-  long long splits = std::min<long long>(std::min<long long>((kTarget + tiles - 1) / tiles, kMaxSplits), a.total);
-  splits = std::max<long long>(1, std::min<long long>(splits, (long long)kGenWgradPartFloats / ((long long)a.R * ncols)));
-  a.per = (int)((a.total + splits - 1) / splits);
-  splits = (a.total + a.per - 1) / a.per;                     // no split without a stage
+  const long long fit = (long long)kGenWgradPartFloats / ((long long)a.R * ncols);      // partial images the buffer holds: >= 1 (checked above)
+  const int splits = gather_splits(tiles, a.total, kTarget, std::min(kMaxSplits, fit), a.per);
   p.a = a;
   p.bm = bm;
-  p.splits = (int)splits;
-  p.lds = (size_t)4 * kKU * ((size_t)(bm * 16 + 16) + (size_t)(bn * 16 + 16));
+  p.splits = splits;
+  p.lds = gather_pair_lds(bm, bn);
   p.part_floats = (size_t)splits * a.R * ncols;
   p.grid = dim3((unsigned)((ncols + bn - 1) / bn), (unsigned)rtiles, (unsigned)splits);
   p.flops = 2.0 * a.B * (double)a.N * a.R * (double)ncols;

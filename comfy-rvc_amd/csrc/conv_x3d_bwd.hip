@@ -11,7 +11,9 @@
 // r = h mod 3, of the rows h = 3 j + r:  r = 0: W[2] D[j];  r = 1: W[3] D[j], W[0] D[j + 1];  r = 2: W[4] D[j], W[1] D[j + 1]  - off0 = 0, one or
 // two taps, and the store goes to row 3 j + r (element 3 n - 2 w + r p).  The host regroups the weights per product (discriminator.hip) and
 // x3_weight_image makes the image, so the kernel is conv_x3d_kernel's pipeline with another gather and another epilogue.
-#include "conv_x3_dev.h"
+// The kernel writes the image loop of conv_x3gather_dev.h out: through the shared loop the compiler orders the address arithmetic differently and the input-gradient pass measured 0.6 % slower
+// (profiles/x3g_dedup_timing.txt), so it keeps its own copy; the planner and the launcher share the header's arithmetic.
+#include "conv_x3gather_dev.h"
 
 namespace rvc {
 
@@ -89,26 +91,7 @@ __global__ __launch_bounds__(256) void conv_x3d_bwd_kernel(const ConvX3dBwdArgs 
     const bool more = st + 1 < nstages;
     if (more) issue(cur ^ 1);                    // slot cur ^ 1 was last read before the barrier that ended stage st - 1
 #pragma unroll
-    for (int q = 0; q < U; ++q) {
-      const unsigned char* wa = smem_x3b + cur * kSlot + q * kUSlot + aoff;
-      const unsigned char* xa = smem_x3b + cur * kSlot + q * kUSlot + boff;
-      u32x4 ah[2], al[2];
-#pragma unroll
-      for (int am = 0; am < 2; ++am) {
-        ah[am] = *reinterpret_cast<const u32x4*>(wa + am * 512);
-        al[am] = *reinterpret_cast<const u32x4*>(wa + kBM * 32 + am * 512);
-      }
-      const u32x4 bh = *reinterpret_cast<const u32x4*>(xa), bl = *reinterpret_cast<const u32x4*>(xa + kBN * 32);
-#pragma unroll
-      for (int am = 0; am < 2; ++am)
-        acc[am] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[am]), __builtin_bit_cast(bf16x8, bl), acc[am], 0, 0, 0);
-#pragma unroll
-      for (int am = 0; am < 2; ++am)
-        acc[am] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[am]), __builtin_bit_cast(bf16x8, bh), acc[am], 0, 0, 0);
-#pragma unroll
-      for (int am = 0; am < 2; ++am)
-        acc[am] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[am]), __builtin_bit_cast(bf16x8, bh), acc[am], 0, 0, 0);
-    }
+    for (int q = 0; q < U; ++q) gather_mfma3_unit<2>(acc, smem_x3b + cur * kSlot + q * kUSlot + aoff, kBM * 32, smem_x3b + cur * kSlot + q * kUSlot + boff, kBN * 32);
     if (more) {
       wait_vmcnt<0>();                           // this wave's 2 U weight pieces have landed in LDS, its 4 U gradient values in registers
       store_b(cur ^ 1);
@@ -117,18 +100,17 @@ __global__ __launch_bounds__(256) void conv_x3d_bwd_kernel(const ConvX3dBwdArgs 
   }
 
   // epilogue: column nn of phase ph is element ostride nn - (ostride - 1) w + ph p of the output plane (row ostride j + ph); cotangent, mask.
-  // 32 x 32 accumulator layout: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
   const int nn = n0 + wn * 32 + li;
   if (nn < N) {
     const int w = nn % p.p;
     const long long e = (long long)p.ostride * nn - (long long)(p.ostride - 1) * w + (long long)ph * p.p;
-    const int row0 = r0 + wm * 64 + 4 * lh;
+    const int row0 = r0 + wm * 64 + acc_row32(0, lh);
     const long long base = ((long long)sig * p.R + row0) * HP + e;
 #pragma unroll
     for (int am = 0; am < 2; ++am)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int dr = am * 32 + (r & 3) + 8 * (r >> 2);
+        const int dr = am * 32 + acc_row32(r, 0);
         if (row0 + dr < p.R) {
           const long long idx = base + (long long)dr * HP;
           float v = acc[am][r];
@@ -156,8 +138,7 @@ bool conv_x3d_bwd_plan(const ConvX3dBwdArgs& a0, ConvX3dBwdPlan& p) {
     if ((long long)(a.Ck / 16) * a.nt[ph] * a.RPx * 64 >= (1LL << 31)) return false;
     a.Hj[ph] = a.H > ph ? (a.H - ph + a.ostride - 1) / a.ostride : 0;                    // rows h = ostride j + ph below H
     if (a.Hj[ph] > a.Hd) return false;                                                  // tap 0 of every column lies in the plane of D
-    const int nunits = (a.Ck / 16) * a.nt[ph];
-    while (nunits % units) units >>= 1;
+    units = std::min(units, gather_units((a.Ck / 16) * a.nt[ph]));
     a.tile0[ph] = tiles;
     tiles += (int)(((long long)a.Hj[ph] * a.p + kBN - 1) / kBN);
     p.flops += 2.0 * a.S * (double)a.Hj[ph] * a.p * a.R * a.Ck * a.nt[ph];
@@ -166,18 +147,16 @@ bool conv_x3d_bwd_plan(const ConvX3dBwdArgs& a0, ConvX3dBwdPlan& p) {
   if (tiles < 1) return false;
   p.a = a;
   p.units = units;
-  p.lds = (size_t)2 * p.units * kUSlot;
+  p.lds = gather_image_lds(kBM, kBN, p.units);
   p.grid = dim3((unsigned)tiles, (unsigned)(a.RPx / kBM), (unsigned)a.S);
   return true;
 }
-template <int U> static void conv_x3d_bwd_launch_u(const ConvX3dBwdPlan& p, hipStream_t s) {
-  RVC_ALLOW_BIG_LDS(conv_x3d_bwd_kernel<U>);
-  hipLaunchKernelGGL(conv_x3d_bwd_kernel<U>, p.grid, dim3(256), p.lds, s, p.a);
-}
 void conv_x3d_bwd_launch(const ConvX3dBwdPlan& p, hipStream_t s) {
-  if (p.units == 4) conv_x3d_bwd_launch_u<4>(p, s);
-  else if (p.units == 2) conv_x3d_bwd_launch_u<2>(p, s);
-  else conv_x3d_bwd_launch_u<1>(p, s);
+  gather_dispatch_units(p.units, [&](auto u) {
+    constexpr int U = decltype(u)::value;
+    RVC_ALLOW_BIG_LDS(conv_x3d_bwd_kernel<U>);
+    hipLaunchKernelGGL(conv_x3d_bwd_kernel<U>, p.grid, dim3(256), p.lds, s, p.a);
+  });
 }
 
 }  // namespace rvc

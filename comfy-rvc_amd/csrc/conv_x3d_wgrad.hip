@@ -12,7 +12,9 @@
 // The reduction is SPLIT without atomics: blockIdx.z = split owns a contiguous run of stages and writes its own partial image [Co][Ci k]; the
 // finishing kernel (discriminator.hip) adds the partials in index order, so two calls give the same bits.  Registers hold the next stage's loads
 // while the current one is multiplied.
-#include "conv_x3_dev.h"
+// This is the pair loop of conv_x3gather_dev.h written out: through the shared loop the compiler schedules the 160 loads of a stage differently and the pass
+// measured 1.8 % slower (profiles/x3g_dedup_timing.txt), so the kernel keeps its own copy; the planner shares the header's arithmetic.
+#include "conv_x3gather_dev.h"
 
 namespace rvc {
 
@@ -95,36 +97,17 @@ __global__ __launch_bounds__(256) void conv_x3d_wgrad_kernel(const ConvX3dWgradA
     __syncthreads();
     if (g + 1 < g1) load(g + 1);                   // in flight while this stage is multiplied
 #pragma unroll
-    for (int ku = 0; ku < kKU; ++ku) {
-      const unsigned char* wa = smem_x3w + aoff + ku * 2 * kABlock;
-      const unsigned char* xa = smem_x3w + boff + ku * 2 * kBBlock;
-      u32x4 ah[2], al[2];
-#pragma unroll
-      for (int am = 0; am < 2; ++am) {
-        ah[am] = *reinterpret_cast<const u32x4*>(wa + am * 512);
-        al[am] = *reinterpret_cast<const u32x4*>(wa + kAPlane + am * 512);
-      }
-      const u32x4 bh = *reinterpret_cast<const u32x4*>(xa), bl = *reinterpret_cast<const u32x4*>(xa + kBPlane);
-#pragma unroll
-      for (int am = 0; am < 2; ++am)
-        acc[am] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[am]), __builtin_bit_cast(bf16x8, bl), acc[am], 0, 0, 0);
-#pragma unroll
-      for (int am = 0; am < 2; ++am)
-        acc[am] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[am]), __builtin_bit_cast(bf16x8, bh), acc[am], 0, 0, 0);
-#pragma unroll
-      for (int am = 0; am < 2; ++am)
-        acc[am] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[am]), __builtin_bit_cast(bf16x8, bh), acc[am], 0, 0, 0);
-    }
+    for (int ku = 0; ku < kKU; ++ku) gather_mfma3_unit<2>(acc, smem_x3w + aoff + ku * 2 * kABlock, kAPlane, smem_x3w + boff + ku * 2 * kBBlock, kBPlane);
   }
 
-  // the split's partial image, in the weight's layout; 32 x 32 accumulator layout: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  // the split's partial image, in the weight's layout
   const int q = c0 + wn * 32 + li;
   if (q < ncols) {
-    float* P = p.part + ((long long)split * p.Co + r0 + wm * 64 + 4 * lh) * ncols + q;
+    float* P = p.part + ((long long)split * p.Co + r0 + wm * 64 + acc_row32(0, lh)) * ncols + q;
 #pragma unroll
     for (int am = 0; am < 2; ++am)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) P[(long long)(am * 32 + (r & 3) + 8 * (r >> 2)) * ncols] = acc[am][r];
+      for (int r = 0; r < 16; ++r) P[(long long)(am * 32 + acc_row32(r, 0)) * ncols] = acc[am][r];
   }
 }
 }  // namespace
@@ -143,12 +126,11 @@ bool conv_x3d_wgrad_plan(const ConvX3dWgradArgs& a0, ConvX3dWgradPlan& p) {
   a.total = a.S * a.cps;
   const long long tiles = ((ncols + kBN - 1) / kBN) * (a.Co / kBM);
   constexpr long long kTarget = 1024, kMaxSplits = 64;       // about four workgroups per compute unit; a bound on the partial images
-  long long splits = std::min<long long>(std::min<long long>((kTarget + tiles - 1) / tiles, kMaxSplits), a.total);
-  a.per = (int)((a.total + splits - 1) / splits);
-  splits = (a.total + a.per - 1) / a.per;                     // no split without a stage
+  const int splits = gather_splits(tiles, a.total, kTarget, kMaxSplits, a.per);
   p.a = a;
-  p.splits = (int)splits;
+  p.splits = splits;
   p.lds = kLds;
+  static_assert(kLds == gather_pair_lds(kBM, kBN), "the kernel's tiles are the pair loop's");
   p.part_floats = (size_t)splits * a.Co * ncols;
   p.grid = dim3((unsigned)((ncols + kBN - 1) / kBN), (unsigned)(a.Co / kBM), (unsigned)splits);
   p.flops = 2.0 * a.S * (double)N * a.Co * a.Ci * a.k;
