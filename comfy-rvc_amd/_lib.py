@@ -139,6 +139,7 @@ SIGNATURES = {
     "rvc_conv1d_weight_grad": (c_int, [c_void_p, P(c_void_p), P(c_void_p), c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, c_float, c_float,
                                        c_void_p]),
     "rvc_conv1d_weight_grad_splits": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int]),
+    "rvc_conv1d_weight_grad_plan": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, P(c_int)]),
     "rvc_kl_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "rvc_kl_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rvc_l1_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -258,6 +259,14 @@ SIGNATURES = {
     "rvc_prof_collect": (c_int, [P(C.c_double), P(C.c_double), P(c_int64)]),
     "rvc_prof_collect_ex": (c_int, [P(C.c_double), C.c_double, C.c_double]),
     "rvc_prof_cfg_name": (c_char_p, [c_int]),
+    "rvc_op_disc_conv": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_float, P(c_int)]),
+    "rvc_op_disc_conv_plan": (c_int, [c_int] * 8 + [P(c_int)]),
+    "rvc_op_disc_conv_input_grad": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_float, P(c_int)]),
+    "rvc_op_disc_conv_input_grad_plan": (c_int, [c_int] * 7 + [P(c_int)]),
+    "rvc_op_disc_conv_weight_grad": (c_int, [c_void_p] * 4 + [c_int] * 8 + [P(c_int)]),
+    "rvc_op_disc_conv_weight_grad_plan": (c_int, [c_int] * 8 + [P(c_int)]),
+    "rvc_op_conv1d_input_grad": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_int64] * 4 + [c_float, c_float, c_int, P(c_int), P(c_int)]),
+    "rvc_op_conv1d_input_grad_plan": (c_int, [c_int] * 6 + [c_int64, c_int64, P(c_int)]),
     "rvc_op_sine_source": (c_int, [c_void_p] * 5 + [c_int, c_int, c_float, c_float, c_float] + [c_void_p] * 3),
     "rvc_op_hubert_conv0": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64]),
     "rvc_op_conv_to1": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, P(c_int)]),

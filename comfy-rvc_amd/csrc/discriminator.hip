@@ -132,23 +132,37 @@ static std::vector<int> disc_periods(int version) {
 // The transposed, phase-grouped images of a dense layer's data gradient (conv_x3d_bwd.hip).  Input row h = stride h' + j - pad: stride 1 is one product,
 // tap t (row h + t - pad of the gradient) carrying W[.][.][k - 1 - t]; stride 3 (k 5, pad 2) is one product per phase r = h mod 3, tap 0 (row j) carrying
 // W[.][.][r + 2] and - r > 0 - tap 1 (row j + 1) carrying W[.][.][r - 1].
-static void disc_bwd_images(DiscLayer& L, const std::vector<float>& w) {
-  RVC_REQUIRE(L.k == 5 && L.pad == 2 && (L.stride == 1 || L.stride == 3), "dense discriminator layer: k 5, pad 2, stride 1 or 3");
-  L.CiPx = (L.Ci + 127) & ~127;
-  for (int r = 0; r < L.stride; ++r) {
+// Returns the number of phases (= stride) and fills img[r] and nt[r], the taps of phase r; rows Ci padded to a multiple of 128.
+int disc_bwd_weight_images(const float* w, int Co, int Ci, int k, int stride, int pad, std::vector<uint16_t> (&img)[3], int (&nt)[3]) {
+  RVC_REQUIRE(k == 5 && pad == 2 && (stride == 1 || stride == 3), "dense discriminator layer: k 5, pad 2, stride 1 or 3");
+  RVC_REQUIRE(Ci >= 1 && Co >= 16 && Co % 16 == 0, "dense discriminator layer: output channels a multiple of 16");
+  const int CiPx = (Ci + 127) & ~127;
+  for (int r = 0; r < stride; ++r) {
     std::vector<int> taps;
-    if (L.stride == 1) taps = {4, 3, 2, 1, 0};
+    if (stride == 1) taps = {4, 3, 2, 1, 0};
     else if (r == 0) taps = {2};
     else taps = {r + 2, r - 1};
-    const int nt = (int)taps.size();
-    std::vector<float> wt((size_t)L.Ci * L.Co * nt);
-    for (int co = 0; co < L.Co; ++co)
-      for (int ci = 0; ci < L.Ci; ++ci)
-        for (int t = 0; t < nt; ++t) wt[((size_t)ci * L.Co + co) * nt + t] = w[((size_t)co * L.Ci + ci) * L.k + taps[t]];
-    std::vector<uint16_t> img;
-    x3_weight_image(wt.data(), L.Ci, L.Co, nt, L.CiPx, img);
-    L.wxb[r].upload(img);
+    nt[r] = (int)taps.size();
+    std::vector<float> wt((size_t)Ci * Co * nt[r]);
+    for (int co = 0; co < Co; ++co)
+      for (int ci = 0; ci < Ci; ++ci)
+        for (int t = 0; t < nt[r]; ++t) wt[((size_t)ci * Co + co) * nt[r] + t] = w[((size_t)co * Ci + ci) * k + taps[t]];
+    x3_weight_image(wt.data(), Ci, Co, nt[r], CiPx, img[r]);
   }
+  return stride;
+}
+// the geometry of that launch for a layer (Ci -> Co, k 5, pad 2, stride 1 or 3) whose input has H rows and whose output gradient has Hd: everything of the
+// arguments but the pointers
+void disc_bwd_geometry(ConvX3dBwdArgs& a, int Ci, int Co, int k, int stride, int pad, int H, int Hd, int p, int S, float slope) {
+  a.R = Ci; a.RPx = (Ci + 127) & ~127; a.Ck = Co; a.Hd = Hd; a.H = H; a.p = p; a.ostride = stride; a.off0 = stride == 1 ? -pad : 0; a.nph = stride;
+  for (int r = 0; r < stride && r < 3; ++r) a.nt[r] = stride == 1 ? k : (r == 0 ? 1 : 2);
+  a.S = S; a.slope = slope;
+}
+static void disc_bwd_images(DiscLayer& L, const std::vector<float>& w) {
+  std::vector<uint16_t> img[3]; int nt[3];
+  const int nph = disc_bwd_weight_images(w.data(), L.Co, L.Ci, L.k, L.stride, L.pad, img, nt);
+  L.CiPx = (L.Ci + 127) & ~127;
+  for (int r = 0; r < nph; ++r) L.wxb[r].upload(img[r]);
 }
 
 void disc_keep_parameters(Disc* D, bool on) {
@@ -493,9 +507,8 @@ static void disc_bwd_plan(const Disc* D, int S, long long T, const float* const*
         d.kind = 2;
         ConvX3dBwdArgs a{};
         a.D = delta; a.Cot = cot; a.A = act; a.Y = y;
-        for (int r = 0; r < L.stride; ++r) { a.Wx[r] = reinterpret_cast<const unsigned char*>(L.wxb[r].p); a.nt[r] = L.stride == 1 ? L.k : (r == 0 ? 1 : 2); }
-        a.R = L.Ci; a.RPx = L.CiPx; a.Ck = L.Co; a.Hd = Ho; a.H = H; a.p = per; a.ostride = L.stride; a.off0 = L.stride == 1 ? -L.pad : 0; a.nph = L.stride;
-        a.S = S; a.slope = kDiscSlope;
+        for (int r = 0; r < L.stride; ++r) a.Wx[r] = reinterpret_cast<const unsigned char*>(L.wxb[r].p);
+        disc_bwd_geometry(a, L.Ci, L.Co, L.k, L.stride, L.pad, H, Ho, per, S, kDiscSlope);
         RVC_REQUIRE(conv_x3d_bwd_plan(a, d.x), "discriminator layer does not fit the data-gradient kernel");
       } else {
         RVC_REQUIRE(L.k == kGrpK && L.stride == kGrpStride && L.pad == kGrpPad && L.Ci / L.groups == kGrpCin && per == 1, "grouped layer geometry");
@@ -622,7 +635,6 @@ __global__ __launch_bounds__(256) void disc_wgrad_direct_kernel(const DiscWgradD
 // One workgroup per output channel m: db[m] (float64, thread-strided then block_sum: a fixed order), dW[m] = the partials added in index order, and the
 // weight-norm chain where v is given (gw receives dW itself otherwise).  gw doubles as the row's store between the two passes: a thread re-reads only what
 // it wrote itself.
-struct DiscWgradFinishArgs { const float* part; const float* D; const float* v; const float* g; float* gw; float* gg; float* gb; long long pstride; int splits, S, Co, N, L; };
 __global__ __launch_bounds__(256) void disc_wgrad_finish_kernel(const DiscWgradFinishArgs a) {
   __shared__ double red[4];
   const int m = blockIdx.x;
@@ -652,6 +664,9 @@ __global__ __launch_bounds__(256) void disc_wgrad_finish_kernel(const DiscWgradF
   const double nrm = sqrt(vv), coef = d / vv, sc = (double)a.g[m] / nrm;
   if (threadIdx.x == 0) a.gg[m] = (float)(d / nrm);
   for (int q = threadIdx.x; q < a.L; q += 256) gw[q] = (float)(sc * ((double)gw[q] - coef * (double)v[q]));
+}
+void disc_wgrad_finish(hipStream_t s, const DiscWgradFinishArgs& a) {
+  hipLaunchKernelGGL(disc_wgrad_finish_kernel, dim3((unsigned)a.Co), dim3(256), 0, s, a);
 }
 
 struct DiscWgradLaunch {
@@ -725,7 +740,7 @@ void disc_weight_grad(Disc* D, hipStream_t s, const float* signals, int S, long 
     d.f.part = part;
     if (d.gemm) { d.x.a.part = part; conv_x3d_wgrad_launch(d.x, s); }
     else { d.d.part = part; hipLaunchKernelGGL(disc_wgrad_direct_kernel, d.dgrid, dim3(256), 0, s, d.d); }
-    hipLaunchKernelGGL(disc_wgrad_finish_kernel, dim3((unsigned)d.f.Co), dim3(256), 0, s, d.f);
+    disc_wgrad_finish(s, d.f);
   }
 }
 

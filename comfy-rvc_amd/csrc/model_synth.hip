@@ -654,6 +654,22 @@ static void tape_check(const Synth* S, const GenTape* tape) {
   RVC_REQUIRE(tape->seg == S->segment && S->gen_bwd.built, "the tape was created for another segment_size (the handle was finalized again)");
 }
 
+// The data-gradient images (conv_gen_bwd.hip), rows = the forward's input channels padded to a multiple of 128.
+// Conv1d W [Co][Ci][k] -> W' [Ci][Co][t] = W[co][ci][k - 1 - t]: tap t of the data gradient reads D at t_out + pad - (k - 1) dil + t dil
+void gen_bwd_conv_image(const float* w, int Co, int Ci, int k, std::vector<uint16_t>& P) {
+  RVC_REQUIRE(Co >= 16 && Co % 16 == 0 && Ci >= 1 && k >= 1 && k <= 16, "decoder convolution does not fit the data-gradient kernel");
+  std::vector<float> wt((size_t)Co * Ci * k);
+  for (int co = 0; co < Co; ++co)
+    for (int ci = 0; ci < Ci; ++ci)
+      for (int t = 0; t < k; ++t) wt[((size_t)ci * Co + co) * k + t] = w[((size_t)co * Ci + ci) * k + (k - 1 - t)];
+  x3_weight_image(wt.data(), Ci, Co, k, (Ci + 127) & ~127, P);
+}
+// ConvTranspose1d W [Cin][Cout][k] is its own data gradient's image: tap t reads D at u t_in - pad + t
+void gen_bwd_up_image(const float* w, int Cin, int Cout, int k, std::vector<uint16_t>& P) {
+  RVC_REQUIRE(Cout >= 16 && Cout % 16 == 0 && Cin >= 1 && k >= 1 && k <= 16, "up-sampler does not fit the data-gradient kernel");
+  x3_weight_image(w, Cin, Cout, k, (Cin + 127) & ~127, P);
+}
+
 // the backward pass's weight images, built when the first tape is created (a handle that only infers never gets here)
 static void gen_bwd_build(Synth* S) {
   GenBwdImages& B = S->gen_bwd; GenHostWeights& H = S->gen_host;
@@ -661,15 +677,10 @@ static void gen_bwd_build(Synth* S) {
   const int nu = (int)S->stages.size();
   RVC_REQUIRE(!H.pre.empty() && (int)H.up.size() == nu, "the decoder's folded weights were not kept (no posterior was loaded at finalize)");
   GenBwdImages N;
-  // Conv1d W [Co][Ci][k] -> W' [Ci][Co][t] = W[co][ci][k - 1 - t]: tap t of the data gradient reads D at t_out + pad - (k - 1) dil + t dil
   auto conv_image = [&](const std::vector<float>& w, int Co, int Ci, int k, DevBuf<uint16_t>& img) {
-    RVC_REQUIRE(w.size() == (size_t)Co * Ci * k && Co % 16 == 0 && k <= 16, "decoder convolution does not fit the data-gradient kernel");
-    std::vector<float> wt(w.size());
-    for (int co = 0; co < Co; ++co)
-      for (int ci = 0; ci < Ci; ++ci)
-        for (int t = 0; t < k; ++t) wt[((size_t)ci * Co + co) * k + t] = w[((size_t)co * Ci + ci) * k + (k - 1 - t)];
+    RVC_REQUIRE(w.size() == (size_t)Co * Ci * k, "decoder convolution: weight size");
     std::vector<uint16_t> P;
-    x3_weight_image(wt.data(), Ci, Co, k, (Ci + 127) & ~127, P);
+    gen_bwd_conv_image(w.data(), Co, Ci, k, P);
     img.upload(P); N.bytes += P.size() * sizeof(uint16_t);
   };
   conv_image(H.pre, S->up_init, S->inter, 7, N.pre);
@@ -677,9 +688,9 @@ static void gen_bwd_build(Synth* S) {
   for (int i = 0; i < nu; ++i) {
     const GenStage& st = S->stages[i];
     const int cin = S->up_init >> i, cout = S->up_init >> (i + 1);
-    RVC_REQUIRE(H.up[i].size() == (size_t)cin * cout * st.k && cout % 16 == 0 && st.k <= 16, "up-sampler does not fit the data-gradient kernel");
-    std::vector<uint16_t> P;      // ConvTranspose1d W [Ci][Co][k] is its own data gradient's image: tap t reads D at u t_in - pad + t
-    x3_weight_image(H.up[i].data(), cin, cout, st.k, (cin + 127) & ~127, P);
+    RVC_REQUIRE(H.up[i].size() == (size_t)cin * cout * st.k, "up-sampler: weight size");
+    std::vector<uint16_t> P;
+    gen_bwd_up_image(H.up[i].data(), cin, cout, st.k, P);
     N.up[i].upload(P); N.bytes += P.size() * sizeof(uint16_t);
     if (S->f0) { N.noise[i].upload(H.noise[i]); N.bytes += H.noise[i].size() * sizeof(float); }
     for (int j = 0; j < 3; ++j)

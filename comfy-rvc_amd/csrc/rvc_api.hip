@@ -382,18 +382,28 @@ int rvc_gen_tape_wgrad_times(rvc_gen_tape* t, float* ms_host, int cap) {
   try { RVC_REQUIRE(t && ms_host && cap > 0, "bad argument"); return gen_tape_wgrad_times(t->t, ms_host, cap); }
   catch (const std::exception& e) { set_error(e.what()); return -1; }
 }
+// what the pure *_plan queries report (include/rvc_hip.h, single ops): units, rows per workgroup, splits, the grid, stages, stages per split
+static void plan_info(int* info, int units, int bm, int splits, dim3 grid, int stages, int per) {
+  if (!info) return;
+  const int v[8] = {units, bm, splits, (int)grid.x, (int)grid.y, (int)grid.z, stages, per};
+  std::copy(v, v + 8, info);
+}
 static ConvGenWgradArgs conv1d_wgrad_args(int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride, int tstep, int off0, float slope_p, float slope_g) {
   RVC_REQUIRE(N >= 1 && N < (1LL << 31) && Tg >= 1 && Tg < (1LL << 31), "bad length");
   ConvGenWgradArgs a{};
   a.B = B; a.R = R; a.C = C; a.k = k; a.N = (int)N; a.ldP = N; a.ldG = Tg; a.Tg = (int)Tg; a.cstride = cstride; a.tstep = tstep; a.off0 = off0; a.slopeP = slope_p; a.slopeG = slope_g;
   return a;
 }
-int rvc_conv1d_weight_grad_splits(int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride, int tstep, int off0) {
+int rvc_conv1d_weight_grad_plan(int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride, int tstep, int off0, int* info) {
   try {
     ConvGenWgradPlan p;
     RVC_REQUIRE(conv_gen_wgrad_plan(conv1d_wgrad_args(B, R, C, k, N, Tg, cstride, tstep, off0, 1.f, 1.f), p), "the shape does not fit the weight-gradient kernel");
+    plan_info(info, 8, p.bm, p.splits, p.grid, p.a.total, p.a.per);
     return p.splits;
   } catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_conv1d_weight_grad_splits(int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride, int tstep, int off0) {
+  return rvc_conv1d_weight_grad_plan(B, R, C, k, N, Tg, cstride, tstep, off0, nullptr);
 }
 int rvc_conv1d_weight_grad(void* stream, const float* const* p_dev, const float* const* g_dev, int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride,
                            int tstep, int off0, float slope_p, float slope_g, float* out_dev) {
@@ -410,6 +420,153 @@ int rvc_conv1d_weight_grad(void* stream, const float* const* p_dev, const float*
   f.part = p.a.part; f.pstride = (long long)R * C * k; f.splits = p.splits; f.R = R; f.L = C * k; f.gw = out_dev;
   gen_wgrad_finish(st, f);
   check_launch();
+  RVC_CATCH
+}
+// ---- raw entries of the other four bf16x3 gather GEMMs (conv_x3d*.hip, conv_gen_bwd.hip), stated as the forward operation: the weights come from the host in
+// the module's layout and go through the regrouping the nets use.  info (8 ints, may be null): units, bm, splits, grid x / y / z, stages, stages per split
+static const float kNoDevice = 0.f;      // a non-null pointer for the planners' pure queries: nothing dereferences it
+static ConvX3dArgs disc_conv_args(int S, int Ci, int Co, int H, int p, int k, int stride, int pad, float slope) {
+  RVC_REQUIRE(H >= 1 && k >= 1 && stride >= 1 && pad >= 0 && H + 2 * pad >= k, "bad geometry");
+  ConvX3dArgs a{};
+  a.X = &kNoDevice; a.Wx = reinterpret_cast<const unsigned char*>(&kNoDevice); a.bias = &kNoDevice;
+  a.Ci = Ci; a.Co = Co; a.CoPx = Co; a.H = H; a.Hout = (H + 2 * pad - k) / stride + 1; a.p = p; a.k = k; a.stride = stride; a.pad = pad; a.S = S; a.slope = slope;
+  return a;
+}
+int rvc_op_disc_conv_plan(int S, int Ci, int Co, int H, int p, int k, int stride, int pad, int* info) {
+  try {
+    ConvX3dPlan pl;
+    RVC_REQUIRE(conv_x3d_plan(disc_conv_args(S, Ci, Co, H, p, k, stride, pad, 1.f), pl), "the shape does not fit the GEMM kernel");
+    plan_info(info, pl.units, 128, 1, pl.grid, (Ci / 16) * k / pl.units, 0);
+    return pl.units;
+  } catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_op_disc_conv(void* stream, const float* x, const float* w, const float* bias, float* y, int S, int Ci, int Co, int H, int p, int k, int stride, int pad,
+                     float slope, int* units) {
+  RVC_TRY
+  RVC_REQUIRE(x && w && bias && y, "null argument");
+  RVC_REQUIRE(slope >= 0.f && slope <= 1.f, "0 <= slope <= 1");
+  ConvX3dArgs a = disc_conv_args(S, Ci, Co, H, p, k, stride, pad, slope);
+  ConvX3dPlan pl;
+  RVC_REQUIRE(conv_x3d_plan(a, pl), "the shape does not fit the GEMM kernel");
+  std::vector<uint16_t> img;
+  x3_weight_image(w, Co, Ci, k, Co, img);
+  DevBuf<uint16_t> wx; wx.upload(img);
+  DevBuf<float> b; b.upload(bias, (size_t)Co);
+  pl.a.X = x; pl.a.Wx = reinterpret_cast<const unsigned char*>(wx.p); pl.a.bias = b.p; pl.a.Y = y;
+  hipStream_t st = (hipStream_t)stream;
+  conv_x3d_launch(pl, st);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(st));
+  if (units) *units = pl.units;
+  RVC_CATCH
+}
+static ConvX3dBwdArgs disc_conv_bwd_args(int S, int Ci, int Co, int H, int Hd, int p, int stride, float slope) {
+  RVC_REQUIRE(stride == 1 || stride == 3, "stride 1 or 3");
+  RVC_REQUIRE(Ci >= 1 && Co >= 16 && Co % 16 == 0, "output channels a multiple of 16");
+  ConvX3dBwdArgs a{};
+  for (int r = 0; r < stride; ++r) a.Wx[r] = reinterpret_cast<const unsigned char*>(&kNoDevice);
+  disc_bwd_geometry(a, Ci, Co, 5, stride, 2, H, Hd, p, S, slope);
+  return a;
+}
+static int bwd_min_stages(const ConvX3dBwdPlan& pl) {
+  int stages = 1 << 30;
+  for (int r = 0; r < pl.a.nph; ++r) if (pl.a.Hj[r] > 0) stages = std::min(stages, (pl.a.Ck / 16) * pl.a.nt[r] / pl.units);
+  return stages;
+}
+int rvc_op_disc_conv_input_grad_plan(int S, int Ci, int Co, int H, int Hd, int p, int stride, int* info) {
+  try {
+    ConvX3dBwdPlan pl;
+    RVC_REQUIRE(conv_x3d_bwd_plan(disc_conv_bwd_args(S, Ci, Co, H, Hd, p, stride, 1.f), pl), "the shape does not fit the data-gradient kernel");
+    plan_info(info, pl.units, 128, 1, pl.grid, bwd_min_stages(pl), 0);
+    return pl.units;
+  } catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_op_disc_conv_input_grad(void* stream, const float* d, const float* w, const float* cot, const float* act, float* y, int S, int Ci, int Co, int H, int Hd,
+                                int p, int stride, float slope, int* units) {
+  RVC_TRY
+  RVC_REQUIRE(d && w && act && y, "null argument");
+  ConvX3dBwdArgs a = disc_conv_bwd_args(S, Ci, Co, H, Hd, p, stride, slope);
+  std::vector<uint16_t> img[3]; int nt[3];
+  const int nph = disc_bwd_weight_images(w, Co, Ci, 5, stride, 2, img, nt);
+  DevBuf<uint16_t> wx[3];
+  for (int r = 0; r < nph; ++r) { RVC_REQUIRE(nt[r] == a.nt[r], "phase taps"); wx[r].upload(img[r]); a.Wx[r] = reinterpret_cast<const unsigned char*>(wx[r].p); }
+  a.D = d; a.Cot = cot; a.A = act; a.Y = y;
+  ConvX3dBwdPlan pl;
+  RVC_REQUIRE(conv_x3d_bwd_plan(a, pl), "the shape does not fit the data-gradient kernel");
+  hipStream_t st = (hipStream_t)stream;
+  conv_x3d_bwd_launch(pl, st);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(st));
+  if (units) *units = pl.units;
+  RVC_CATCH
+}
+static ConvX3dWgradArgs disc_conv_wgrad_args(int S, int Ci, int Co, int H, int p, int k, int stride, int pad) {
+  RVC_REQUIRE(H >= 1 && k >= 1 && stride >= 1 && pad >= 0 && H + 2 * pad >= k, "bad geometry");
+  return ConvX3dWgradArgs{nullptr, nullptr, nullptr, Ci, Co, H, (H + 2 * pad - k) / stride + 1, p, k, stride, pad, S, 0, 0, 0};
+}
+int rvc_op_disc_conv_weight_grad_plan(int S, int Ci, int Co, int H, int p, int k, int stride, int pad, int* info) {
+  try {
+    ConvX3dWgradPlan pl;
+    RVC_REQUIRE(conv_x3d_wgrad_plan(disc_conv_wgrad_args(S, Ci, Co, H, p, k, stride, pad), pl), "the shape does not fit the weight-gradient kernel");
+    plan_info(info, 8, 128, pl.splits, pl.grid, pl.a.total, pl.a.per);
+    return pl.splits;
+  } catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_op_disc_conv_weight_grad(void* stream, const float* d, const float* x, float* dw, int S, int Ci, int Co, int H, int p, int k, int stride, int pad, int* splits) {
+  RVC_TRY
+  RVC_REQUIRE(d && x && dw, "null argument");
+  ConvX3dWgradPlan pl;
+  RVC_REQUIRE(conv_x3d_wgrad_plan(disc_conv_wgrad_args(S, Ci, Co, H, p, k, stride, pad), pl), "the shape does not fit the weight-gradient kernel");
+  RVC_REQUIRE((long long)Co * Ci * k < (1LL << 31) && (long long)pl.a.Hout * p < (1LL << 31), "layer too large");
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf<float> part, gb;
+  part.alloc(pl.part_floats); gb.alloc((size_t)Co);
+  pl.a.D = d; pl.a.X = x; pl.a.part = part.p;
+  conv_x3d_wgrad_launch(pl, st);
+  DiscWgradFinishArgs f{};
+  f.part = part.p; f.D = d; f.gw = dw; f.gb = gb.p; f.pstride = (long long)Co * Ci * k; f.splits = pl.splits; f.S = S; f.Co = Co; f.N = pl.a.Hout * p; f.L = Ci * k;
+  disc_wgrad_finish(st, f);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(st));
+  if (splits) *splits = pl.splits;
+  RVC_CATCH
+}
+static ConvGenBwdArgs conv1d_bwd_args(int transposed, int Ci, int Co, int k, int step, int pad, int64_t N, int64_t Td, int64_t ldD, int64_t ldY, float slope,
+                                      float scale, int accumulate) {
+  RVC_REQUIRE(N >= 1 && N < (1LL << 31) && Td >= 1 && Td < (1LL << 31) && k >= 1 && step >= 1 && pad >= 0, "bad geometry");
+  ConvGenBwdArgs a{};
+  a.D = &kNoDevice; a.Wx = reinterpret_cast<const unsigned char*>(&kNoDevice); a.Y = const_cast<float*>(&kNoDevice);
+  a.ldD = ldD; a.Td = (int)Td; a.ldY = ldY; a.R = Ci; a.RPx = (Ci + 127) & ~127; a.Ck = Co; a.N = (int)N; a.nt = k;
+  if (transposed) { a.cstride = step; a.tstep = 1; a.off0 = -pad; }                       // ConvTranspose1d(Ci, Co, k, stride = step, pad)
+  else { a.cstride = 1; a.tstep = step; a.off0 = pad - (k - 1) * step; }                    // Conv1d(Ci, Co, k, dilation = step, pad)
+  a.slope = slope; a.scale = scale; a.accumulate = accumulate;
+  return a;
+}
+int rvc_op_conv1d_input_grad_plan(int transposed, int Ci, int Co, int k, int step, int pad, int64_t N, int64_t Td, int* info) {
+  try {
+    ConvGenBwdPlan pl;
+    RVC_REQUIRE(conv_gen_bwd_plan(conv1d_bwd_args(transposed, Ci, Co, k, step, pad, N, Td, Td, N, 1.f, 1.f, 0), pl), "the shape does not fit the data-gradient kernel");
+    plan_info(info, pl.units, pl.bm, 1, pl.grid, (Co / 16) * k / pl.units, 0);
+    return pl.units;
+  } catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_op_conv1d_input_grad(void* stream, const float* d, const float* w, const float* act, const float* res, float* y, int transposed, int Ci, int Co, int k,
+                             int step, int pad, int64_t N, int64_t Td, int64_t ldD, int64_t ldY, float slope, float scale, int accumulate, int* bm, int* units) {
+  RVC_TRY
+  RVC_REQUIRE(d && w && y, "null argument");
+  ConvGenBwdArgs a = conv1d_bwd_args(transposed, Ci, Co, k, step, pad, N, Td, ldD, ldY, slope, scale, accumulate);
+  std::vector<uint16_t> img;
+  if (transposed) gen_bwd_up_image(w, Ci, Co, k, img); else gen_bwd_conv_image(w, Co, Ci, k, img);
+  DevBuf<uint16_t> wx; wx.upload(img);
+  a.D = d; a.Wx = reinterpret_cast<const unsigned char*>(wx.p); a.A = act; a.Res = res; a.Y = y;
+  ConvGenBwdPlan pl;
+  RVC_REQUIRE(conv_gen_bwd_plan(a, pl), "the shape does not fit the data-gradient kernel");
+  hipStream_t st = (hipStream_t)stream;
+  conv_gen_bwd_launch(pl, st);
+  check_launch();
+  RVC_HIP_CHECK(hipStreamSynchronize(st));
+  if (bm) *bm = pl.bm;
+  if (units) *units = pl.units;
   RVC_CATCH
 }
 int rvc_kl_loss_grad(void* stream, const float* z_p, const float* m_p, const float* logs_p, int C, int64_t T_pitch, int64_t len, float scale, float* dz_p,

@@ -243,6 +243,10 @@ struct ConvX3dBwdArgs {
 struct ConvX3dBwdPlan { ConvX3dBwdArgs a; dim3 grid; int units = 1; size_t lds = 0; double flops = 0.0; };
 bool conv_x3d_bwd_plan(const ConvX3dBwdArgs& a, ConvX3dBwdPlan& p);   // false: the layer does not fit the kernel
 void conv_x3d_bwd_launch(const ConvX3dBwdPlan& p, hipStream_t s);
+// the host side of that launch for a dense layer w [Co][Ci][5] (pad 2, stride 1 or 3), shared by the net and the raw entry (discriminator.hip): the transposed,
+// phase-grouped images (returns the number of phases) and every field of the arguments but the pointers
+int disc_bwd_weight_images(const float* w, int Co, int Ci, int k, int stride, int pad, std::vector<uint16_t> (&img)[3], int (&nt)[3]);
+void disc_bwd_geometry(ConvX3dBwdArgs& a, int Ci, int Co, int k, int stride, int pad, int H, int Hd, int p, int S, float slope);
 // The data gradient of the generator's 1-D convolutions with the backward chain's epilogue (conv_gen_bwd.hip):
 //   Y[r][n] = (sum_c sum_t W'[r][c][t] D[c][cstride n + off0 + tstep t]) * (A[r][n] > 0 ? scale : scale slope) + Res[r][n] (+ Y[r][n]),   r < R, n < N
 // D [Ck][ldD] with Td valid columns (zero outside), Wx = x3_weight_image of W' [R][Ck][nt] with its rows padded to RPx (a multiple of 128); A (null: no mask),
@@ -254,6 +258,10 @@ struct ConvGenBwdArgs {
 struct ConvGenBwdPlan { ConvGenBwdArgs a; dim3 grid; int bm = 128, units = 1; size_t lds = 0; double flops = 0.0; };   // bm: rows per workgroup (128, 64, 32)
 bool conv_gen_bwd_plan(const ConvGenBwdArgs& a, ConvGenBwdPlan& p);   // false: the layer does not fit the kernel (Ck % 16, k <= 16, 32-bit offsets)
 void conv_gen_bwd_launch(const ConvGenBwdPlan& p, hipStream_t s);
+// the images of that launch, shared by the net and the raw entry (model_synth.hip): of a Conv1d w [Co][Ci][k] (transposed, taps flipped) and of a
+// ConvTranspose1d w [Cin][Cout][k] (its own weight); rows padded to a multiple of 128
+void gen_bwd_conv_image(const float* w, int Co, int Ci, int k, std::vector<uint16_t>& P);
+void gen_bwd_up_image(const float* w, int Cin, int Cout, int k, std::vector<uint16_t>& P);
 // the direct kernels of that pass: d = dy (1 - y^2); conv_post transposed with its input's mask; a noise convolution transposed onto the source (accumulate: added
 // to dhar; out2: a second copy of the sum so far, or null); float64 row sums and the conditioning's transposed product (out2: a second copy or null)
 void gen_tanh_bwd(hipStream_t s, const float* dy, const float* y, float* d, long long n);
@@ -271,6 +279,10 @@ struct ConvX3dWgradArgs {
 struct ConvX3dWgradPlan { ConvX3dWgradArgs a; dim3 grid; int splits = 1; size_t lds = 0, part_floats = 0; double flops = 0.0; };
 bool conv_x3d_wgrad_plan(const ConvX3dWgradArgs& a, ConvX3dWgradPlan& p);   // false: the layer does not fit the kernel (Co % 128, k <= 16, 32-bit offsets)
 void conv_x3d_wgrad_launch(const ConvX3dWgradPlan& p, hipStream_t s);
+// The finishing step (discriminator.hip), one workgroup per output channel m: gb[m] = the float64 sum of row m of D [S][Co][N], gw[m] (L floats) = the `splits`
+// partials (pstride floats apart) added in index order, through the weight-norm chain where v / g are given (gg receives grad_g)
+struct DiscWgradFinishArgs { const float* part; const float* D; const float* v; const float* g; float* gw; float* gg; float* gb; long long pstride; int splits, S, Co, N, L; };
+void disc_wgrad_finish(hipStream_t s, const DiscWgradFinishArgs& a);
 // The weight gradient of the generator's dense 1-D convolutions over the B items of a batch (conv_gen_wgrad.hip):
 //   out[r][c k + t] = sum_item sum_n a_P(P[item][r][n]) a_G(G[item][c][cstride n + tstep t + off0]),  r < R, c < C, t < k, n < N;  a_X(v) = max(v, slope_X v), slope 1: none
 // P [R][ldP] with N valid columns and G [C][ldG] with Tg valid columns (zero outside) per item, each item its own allocation: one base pointer per item.  Both

@@ -303,6 +303,8 @@ int rvc_gen_tape_wgrad_times(rvc_gen_tape* t, float* ms_host, int cap);
 int rvc_conv1d_weight_grad(void* stream, const float* const* p_dev, const float* const* g_dev, int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride,
                            int tstep, int off0, float slope_p, float slope_g, float* out_dev);
 int rvc_conv1d_weight_grad_splits(int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride, int tstep, int off0);
+/* _plan: the same query with the plan's figures in info (8 ints, or NULL), laid out as for the rvc_op_*_plan queries of the single-ops section. */
+int rvc_conv1d_weight_grad_plan(int B, int R, int C, int k, int64_t N, int64_t Tg, int cstride, int tstep, int off0, int* info);
 /* kl_loss of one item (reference lib/train/losses.py:596-611): sum_dev[0] = sum over c < C, t < len of logs_p - logs_q - 0.5 + 0.5 (z_p - m_p)^2 exp(-2 logs_p)
  * (float64 accumulation, fixed order: two calls give the same bits), sum_dev[1] = len (the mask's sum); rows have pitch T_pitch >= len. */
 int rvc_kl_loss(void* stream, const float* z_p_dev, const float* logs_q_dev, const float* m_p_dev, const float* logs_p_dev, int C, int64_t T_pitch,
@@ -624,6 +626,36 @@ int rvc_tsi_terms(void* stream, const float* org_dev, const float* gen_dev, int 
 int rvc_op_conv1d(void* stream, const float* x_dev, const float* w_host, const float* bias_host, const float* res_dev, float* y_dev,
                   int Ci, int Co, int Tin, int k, int stride, int pad, int dil, int groups, int pre_act, float pre_slope, int act,
                   float act_slope, int act_before_res, float out_scale, int accumulate);
+/* The trainer's bf16x3 gather GEMMs at any small shape, each stated as the FORWARD operation it belongs to: weights come from the host in the module's own
+ * layout and pass through the regrouping the nets use (tests/test_hip_gather_gemms.py).  Device tensors are dense fp32; the stream is synchronised on return.
+ * Every entry has a pure query *_plan that needs no device: it returns what the entry reports (units per pipeline stage, or splits), -1 when the planner
+ * declines the shape, and fills info (8 ints, or NULL): units, rows per workgroup, splits, grid x / y / z, pipeline stages (the fewest of any phase; for a
+ * weight gradient the stages of the whole reduction), stages per split.
+ *
+ * rvc_op_disc_conv: y [S][Co][Hout][p] = lrelu_slope(b + conv along H of x [S][Ci][H][p]) with w_host [Co][Ci][k], stride, pad; Hout = (H + 2 pad - k) / stride + 1.
+ * Ci % 16 == 0, Co % 128 == 0, k <= 16, 0 <= slope <= 1. */
+int rvc_op_disc_conv(void* stream, const float* x_dev, const float* w_host, const float* bias_host, float* y_dev, int S, int Ci, int Co, int H, int p, int k,
+                     int stride, int pad, float slope, int* units_out);
+int rvc_op_disc_conv_plan(int S, int Ci, int Co, int H, int p, int k, int stride, int pad, int* info);
+/* The data gradient of that layer for k = 5, pad = 2, stride 1 or 3, with the backward chain's epilogue: y [S][Ci][H][p] = (convT(d) + cot) * (a > 0 ? 1 : slope),
+ * d_dev [S][Co][Hd][p] (Hd: the forward's output rows for H), cot_dev (or NULL) and a_dev laid out like y; w_host [Co][Ci][5], Co % 16 == 0. */
+int rvc_op_disc_conv_input_grad(void* stream, const float* d_dev, const float* w_host, const float* cot_dev, const float* a_dev, float* y_dev, int S, int Ci, int Co,
+                                int H, int Hd, int p, int stride, float slope, int* units_out);
+int rvc_op_disc_conv_input_grad_plan(int S, int Ci, int Co, int H, int Hd, int p, int stride, int* info);
+/* The weight gradient of that layer: dw_dev [Co][Ci][k] = sum over signals and outputs of d [S][Co][Hout][p] times the input x [S][Ci][H][p] the tap read (zero
+ * outside the rows); gradient launch plus the nets' finishing kernel, no weight norm.  Co % 128 == 0, k <= 16. */
+int rvc_op_disc_conv_weight_grad(void* stream, const float* d_dev, const float* x_dev, float* dw_dev, int S, int Ci, int Co, int H, int p, int k, int stride, int pad,
+                                 int* splits_out);
+int rvc_op_disc_conv_weight_grad_plan(int S, int Ci, int Co, int H, int p, int k, int stride, int pad, int* info);
+/* The data gradient of the generator's 1-D convolutions with the backward chain's epilogue, y [Ci][ldY] (N columns written):
+ *   y = g * (a > 0 ? scale : scale slope) + res (+ y when accumulate),  a_dev / res_dev (either may be NULL: no mask / nothing added) laid out like y,
+ * g the gradient at the input of, transposed = 0: Conv1d(Ci, Co, k, dilation = step, padding = pad), w_host [Co][Ci][k], d_dev [Co][ldD] with Td = N + 2 pad -
+ * (k - 1) step valid columns; transposed = 1: ConvTranspose1d(Ci, Co, k, stride = step, padding = pad), w_host [Ci][Co][k], Td = (N - 1) step - 2 pad + k.
+ * Co % 16 == 0, k <= 16, pad <= (k - 1) step for a Conv1d. */
+int rvc_op_conv1d_input_grad(void* stream, const float* d_dev, const float* w_host, const float* a_dev, const float* res_dev, float* y_dev, int transposed, int Ci,
+                             int Co, int k, int step, int pad, int64_t N, int64_t Td, int64_t ldD, int64_t ldY, float slope, float scale, int accumulate,
+                             int* bm_out, int* units_out);
+int rvc_op_conv1d_input_grad_plan(int transposed, int Ci, int Co, int k, int step, int pad, int64_t N, int64_t Td, int* info);
 /* k = 1 projection (torch.nn.Linear over [T, Ci] rows, reference transformers/models/hubert/modeling_hubert.py:291-477 via
  * lib/infer_pack/loaders.py:55-61) on the split-resident GEMM kernel (csrc/conv_x3s.hip): x_dev [Ci][T] fp32 is first written as the bf16
  * hi / lo image the kernel stages, y = act(W x + b [+ res]) (act_before_res: act(W x + b) + res).  y_dev fp32 [Co][T] or null;

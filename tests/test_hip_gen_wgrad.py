@@ -1,5 +1,5 @@
 """GPU: the decoder's weight-gradient pass (rvc_synth_dec_weight_grad, conv_gen_wgrad.hip) and its raw GEMM entry (rvc_conv1d_weight_grad) against float64:
-the raw GEMM against float64 torch autograd, the whole pass against the float64 restatement (tests/gen_wgrad_ref.py) on the device's own taped activations and
+the raw GEMM against float64 torch autograd (gate 2e-5, the bf16x3 product's), the whole pass against the float64 restatement (tests/gen_wgrad_ref.py) on the device's own taped activations and
 deltas - given the tape the pass is a bilinear form of what it reads, so the restatement on those tensors is the exact map.  Gate: conftest.rel_err < 1e-3,
 the project's fp32 gate.  Every measured value is kept by conftest.record_parity under gen_wgrad.*; profiles/gen_wgrad_parity.json is a copy of those entries.
 
@@ -19,10 +19,12 @@ from conftest import golden, record_parity, rel_err
 from comfy_rvc_amd import synthetic as S
 from oracle import nets as N
 import gen_wgrad_ref as W
+import gather_gemm_ref as G
 import test_hip_gen_grad as H
 
 pytestmark = pytest.mark.gpu
 GATE = 1e-3
+RAW_GATE = G.GATE      # the raw GEMM: the bf16x3 product's own gate (tests/test_gather_gemms_host.py calibrates it on these cases' shapes)
 DEV = H.DEV
 SEG13 = H.SEG13
 TAGS = ["40k_v2", "32k_v1", "40k_v2_nono", SEG13]
@@ -65,12 +67,11 @@ def run_raw(name, shapes_p, shapes_g, R, Cc, k, cstride, tstep, off0, sp, sg, wa
     want = want_fn([h.double() for h in host[:B]], [h.double() for h in host[B:]])
     e = rel_err(got.numpy().reshape(want.shape), want.numpy())
     print(name, e)
-    record(f"raw.{name}", e, GATE)
-    assert e < GATE, (name, e)
+    record(f"raw.{name}", e, RAW_GATE)
+    assert e < RAW_GATE, (name, e)
 
 
-CONV_CASES = [(32, 32, 11, 5, 1, 1, 0.1), (32, 32, 3, 1, 127, 1, 0.1), (32, 32, 3, 1, 128, 1, 0.1), (32, 32, 3, 1, 129, 1, 0.1), (64, 64, 7, 3, 130, 3, 0.1),
-              (128, 128, 3, 1, 200, 2, 0.1), (256, 256, 11, 5, 130, 2, 0.1), (512, 192, 7, 1, 13, 2, 1.0), (32, 32, 3, 1, 5200, 2, 0.1)]
+CONV_CASES = G.GEN_WGRAD_CONV_CASES      # with R = 16 and R = 48: the last 32-row tile half empty
 
 
 @pytest.mark.parametrize("R,Cc,k,dil,n,B,slope", CONV_CASES)
