@@ -127,6 +127,11 @@ SIGNATURES = {
     "rvc_gen_tape_times": (c_int, [c_void_p, P(c_float), c_int]),
     "rvc_synth_forward_tape": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64,
                                        c_void_p, P(SynthForwardTaps), c_void_p]),
+    "rvc_synth_forward_tape_flow": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64,
+                                            c_void_p, P(SynthForwardTaps), c_void_p, c_int]),
+    "rvc_synth_flow_input_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rvc_synth_flow_input_grad_launch_count": (c_int, [c_void_p]),
+    "rvc_gen_tape_flow_times": (c_int, [c_void_p, P(c_float), c_int]),
     "rvc_synth_dec_input_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rvc_synth_dec_input_grad_launch_count": (c_int, [c_void_p]),
     "rvc_synth_keep_parameters": (c_int, [c_void_p, c_int]),

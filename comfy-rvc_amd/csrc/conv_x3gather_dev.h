@@ -1,14 +1,15 @@
 // The two main loops of the bf16x3 gather GEMMs: the kernels whose fp32 operand is gathered through per-row buffer descriptors and split (split2) in the
 // kernel.  A kernel keeps its tile coordinates, its gather or load closure and its epilogue; the loop, the operand layout in LDS and the product live here, and so
 // does what the planners and launchers share.  (Not conv_x3p.hip's conv_x3g_kernel, the pipelined k = 1 GEMM.)  Private to csrc/.
-// conv_x3d_kernel runs the image loop and conv_gen_wgrad_kernel the pair loop.  conv_x3d_bwd_kernel, conv_gen_bwd_kernel (image) and conv_x3d_wgrad_kernel (pair)
+// conv_x3d_kernel and conv_flow_bwd_kernel (whose operand element is a function of three fetched values: gather_image_loop_act) run the image loop and
+// conv_gen_wgrad_kernel the pair loop.  conv_x3d_bwd_kernel, conv_gen_bwd_kernel (image) and conv_x3d_wgrad_kernel (pair)
 // still write their loop out around gather_mfma3_unit: called through the loops below they compute the same bits, but the compiler emits the address arithmetic
 // in another order and they measured 0.6 - 1.8 % slower (profiles/x3g_dedup_isa.txt, x3g_dedup_timing.txt).  A change to a loop here is made there as well.
 //
 // The product of one 16-deep unit and accumulator is three v_mfma_f32_32x32x16_bf16 in the order hi lo, lo hi, hi hi; a 32 x 32 accumulator holds column
 // lane & 31 and rows acc_row32(r, lane >> 5).
 //
-// "image" (conv_x3d.hip, conv_x3d_bwd.hip, conv_gen_bwd.hip): A is a weight image [unit][hi | lo][half][rows][8 ch] (x3_weight_image) and comes by LDS-DMA,
+// "image" (conv_x3d.hip, conv_x3d_bwd.hip, conv_gen_bwd.hip, conv_flow_bwd.hip): A is a weight image [unit][hi | lo][half][rows][8 ch] (x3_weight_image) and comes by LDS-DMA,
 //   wave w fetching block (plane, half) = w of the unit in AR / 64 pieces of 1 KiB; B is gathered as fp32, wave w holding channels 4 w .. 4 w + 3 of the unit's
 //   16-channel chunk at columns lane (+ 64), and is stored as [hi | lo][half][BN columns][8 ch].  LDS holds two slots of U units, a unit being its A block
 //   (AR x 64 bytes) followed by its B block (BN x 64 bytes): stage st + 1 is fetched while stage st is multiplied, and a stage is what one barrier publishes,
@@ -49,18 +50,20 @@ __device__ __forceinline__ void gather_mfma3_unit(f32x16 (&acc)[AM], const unsig
 
 // The image loop.  AR: rows of the A block (>= 64), BN: columns of the tile (CN = BN / 64 column groups), AM: accumulators per wave (rows 32 AM wm .. of the A
 // block, columns 32 wn .. of the B block), U: units per stage.  ars / avoff / astep: the image's descriptor, this lane's byte offset in unit 0 and the bytes of
-// one unit.  gather(c, x): called once per issued unit and column group c, in issue order; fills x with this wave's four channel values of column 64 c + lane
-// (out of range: zero, by the descriptor) and advances the closure's own (chunk, tap) after the unit's last group.  Zeroes and fills acc.
-template <int AR, int BN, int AM, int U, class G>
-__device__ __forceinline__ void gather_image_loop(unsigned char* smem, __amdgpu_buffer_rsrc_t ars, int avoff, int astep, int nstages, int wave, int lane, int wm,
-                                                  int wn, f32x16 (&acc)[AM], G gather) {
+// one unit.  NV: fp32 values fetched per operand element.  gather(c, raw): called once per issued unit and column group c, in issue order; fills raw[v][i] with
+// value v of this wave's four channels i at column 64 c + lane (out of range: zero, by the descriptor) and advances the closure's own (chunk, tap) after the
+// unit's last group.  finish(c, raw, x): called in the same order when the stage's loads have landed, just before the split; x[i] = the operand element (a
+// function of its NV fetched values: conv_flow_bwd.hip's gate derivative).  Zeroes and fills acc.
+template <int AR, int BN, int AM, int U, int NV, class G, class F>
+__device__ __forceinline__ void gather_image_loop_act(unsigned char* smem, __amdgpu_buffer_rsrc_t ars, int avoff, int astep, int nstages, int wave, int lane, int wm,
+                                                      int wn, f32x16 (&acc)[AM], G gather, F finish) {
   constexpr int CN = BN / 64;
   constexpr int kASlot = AR * 64;              // bytes of [hi | lo][half][AR rows][16 B]
   constexpr int kBSlot = BN * 64;              // bytes of [hi | lo][half][BN columns][16 B]
   constexpr int kUSlot = kASlot + kBSlot, kSlot = U * kUSlot;
   const int li = lane & 31, lh = lane >> 5;
 
-  float xr[U][CN][4];
+  float xr[U][CN][NV][4];
   int asoff = 0;                                                    // image offset of the next unit to be issued
   auto issue = [&](int slot) {
 #pragma unroll
@@ -79,9 +82,11 @@ __device__ __forceinline__ void gather_image_loop(unsigned char* smem, __amdgpu_
     for (int q = 0; q < U; ++q)
 #pragma unroll
       for (int c = 0; c < CN; ++c) {
+        float x[4];
+        finish(c, xr[q][c], x);
         unsigned h0, l0, h1, l1;
-        split2(xr[q][c][0], xr[q][c][1], h0, l0);
-        split2(xr[q][c][2], xr[q][c][3], h1, l1);
+        split2(x[0], x[1], h0, l0);
+        split2(x[2], x[3], h1, l1);
         const u32x2_t hi = {h0, h1}, lo = {l0, l1};
         unsigned char* b = smem + slot * kSlot + q * kUSlot + kASlot + ((wave >> 1) * BN + c * 64 + lane) * 16 + (wave & 1) * 8;
         *reinterpret_cast<u32x2_t*>(b) = hi;
@@ -113,6 +118,17 @@ __device__ __forceinline__ void gather_image_loop(unsigned char* smem, __amdgpu_
     }
     __syncthreads();
   }
+}
+// the plain operand: one value per element, gather(c, x) fills this wave's four channel values
+template <int AR, int BN, int AM, int U, class G>
+__device__ __forceinline__ void gather_image_loop(unsigned char* smem, __amdgpu_buffer_rsrc_t ars, int avoff, int astep, int nstages, int wave, int lane, int wm,
+                                                  int wn, f32x16 (&acc)[AM], G gather) {
+  gather_image_loop_act<AR, BN, AM, U, 1>(smem, ars, avoff, astep, nstages, wave, lane, wm, wn, acc,
+                                          [&](int c, float (&raw)[1][4]) { gather(c, raw[0]); },
+                                          [](int, const float (&raw)[1][4], float (&x)[4]) {
+#pragma unroll
+                                            for (int i = 0; i < 4; ++i) x[i] = raw[0][i];
+                                          });
 }
 
 // The pair loop.  BM x BN: the tile; a wave fetches BM / 4 rows of A and BN / 4 columns of B per stage and multiplies AM accumulators (rows 32 AM wm .., columns

@@ -63,6 +63,11 @@ struct GenBwdImages {
 };
 // The decoder's weight-gradient pass (synth_dec_weight_grad), opt-in through synth_keep_parameters: weight_v / weight_g of the weight-normed decoder layers on the
 // device for the chain through weight norm (c1 / c2: index (i * 3 + j) * 3 + m).  DecParam: the dec.* parameter tensors in the reference module's state-dict order.
+// The flow's backward data pass (synth_flow_input_grad).  FlowHostWeights: the folded weights of one coupling on the HOST, kept by a finalize that loaded a posterior
+// until the first recording forward; FlowBwdImages: what that forward builds from them on the device - the transposed, tap-flipped x3_weight_image of pre, post,
+// the in_layers and the res_skip layers (whole: 2 H rows, the last H).  An inference handle holds neither.
+struct FlowHostWeights { std::vector<float> pre, post, in[3], rs[3]; };
+struct FlowBwdImages { bool built = false; DevBuf<uint16_t> pre[4], post[4], in[4][3], rs[4][3]; size_t bytes = 0; };
 struct GenKept { bool on = false; std::vector<DevVec> up_v, up_g, c1_v, c1_g, c2_v, c2_g; size_t bytes = 0; };
 struct DecParam { std::string name; std::vector<long long> shape; };
 struct SynthWeights {    // what synth_finalize builds, and what the graph has learnt about it
@@ -76,6 +81,7 @@ struct SynthWeights {    // what synth_finalize builds, and what the graph has l
   std::vector<GenStage> stages;
   float lin_w = 1.f, lin_b = 0.f;
   GenHostWeights gen_host; GenBwdImages gen_bwd;
+  FlowHostWeights flow_host[4]; FlowBwdImages flow_bwd;
   GenKept kept; std::vector<DecParam> dec_params; std::map<std::string, int> dec_index;
   ZeroedBlock imgs;      // split-resident image block whose margins are known to be zero (split_imgs_alloc; keys: T, and the columns of the z image = the generator's window)
 };
@@ -146,11 +152,11 @@ int synth_dec_halo_frames(const Synth* S) {
 }
 
 // the weight-normed layers of one modules.WN under prefix p ("flow.flows.0.enc." / "enc_q.enc."), kernel 5, dilation 1
-static void make_wn(const TensorStore& ts, const std::string& p, int n, int C, WNStack& W) {
+static void make_wn(const TensorStore& ts, const std::string& p, int n, int C, WNStack& W, FlowHostWeights* keep = nullptr) {
   W.n = n;
   W.in.resize(n); W.in_gate.resize(n); W.skip.resize(n); W.res.resize(n - 1); W.rs.resize(n - 1);
   for (int i = 0; i < n; ++i) {
-    W.in[i] = make_conv1d(ts, p + "in_layers." + std::to_string(i), 1, 2, 1, true);
+    W.in[i] = make_conv1d(ts, p + "in_layers." + std::to_string(i), 1, 2, 1, true, true, 1.f, 0, -1, keep ? &keep->in[i] : nullptr);
     if ((C & 15) == 0) {
       const std::string q = p + "in_layers." + std::to_string(i);
       const HostTensor& v = ts.get(q + ".weight_v");
@@ -170,9 +176,9 @@ static void make_wn(const TensorStore& ts, const std::string& p, int n, int C, W
     if (i < n - 1) {
       W.res[i] = make_conv1d(ts, rs, 1, 0, 1, true, true, 1.f, 0, C);
       W.skip[i] = make_conv1d(ts, rs, 1, 0, 1, true, true, 1.f, C, C);
-      W.rs[i] = make_conv1d(ts, rs, 1, 0, 1, true);
+      W.rs[i] = make_conv1d(ts, rs, 1, 0, 1, true, true, 1.f, 0, -1, keep ? &keep->rs[i] : nullptr);
     } else {
-      W.skip[i] = make_conv1d(ts, rs, 1, 0, 1, true);
+      W.skip[i] = make_conv1d(ts, rs, 1, 0, 1, true, true, 1.f, 0, -1, keep ? &keep->rs[i] : nullptr);
     }
   }
   W.cond_w.upload(weight_norm0(ts.get(p + "cond_layer.weight_v"), ts.get(p + "cond_layer.weight_g")));
@@ -231,13 +237,15 @@ void synth_finalize(Synth* S) {
     e.b2.upload(ts.get("enc_p.encoder.norm_layers_2." + std::to_string(l) + ".beta", {C}).data);
   }
   S->proj = make_conv1d(ts, "enc_p.proj", 1, 0, 1, false);
+  const bool keep = ts.has("enc_q.pre.weight");   // a training checkpoint: the folded flow and decoder weights stay on the host for the backward passes' images
   for (int f = 0; f < 4; ++f) {
     FlowLayer& F = S->flow[f];
+    FlowHostWeights* FH = keep ? &S->flow_host[f] : nullptr;
     const std::string p = "flow.flows." + std::to_string(2 * f) + ".";
-    F.pre = make_conv1d(ts, p + "pre", 1, 0, 1, false);
-    F.post = make_conv1d(ts, p + "post", 1, 0, 1, false);
+    F.pre = make_conv1d(ts, p + "pre", 1, 0, 1, false, true, 1.f, 0, -1, keep ? &FH->pre : nullptr);
+    F.post = make_conv1d(ts, p + "post", 1, 0, 1, false, true, 1.f, 0, -1, keep ? &FH->post : nullptr);
     F.post_neg = make_conv1d(ts, p + "post", 1, 0, 1, false, true, -1.f);
-    make_wn(ts, p + "enc.", 3, C, F.wn);
+    make_wn(ts, p + "enc.", 3, C, F.wn, FH);
   }
   Posterior& Q = S->post_enc;
   if (ts.has("enc_q.pre.weight")) {
@@ -256,7 +264,7 @@ void synth_finalize(Synth* S) {
     RVC_REQUIRE(Q.proj.Co == 2 * S->inter && Q.proj.Ci == C, "enc_q.proj: expected [2 inter][hidden][1]");
     Q.built = true;
   }
-  const bool keep = Q.built;   // a training checkpoint: the folded decoder weights stay on the host for the backward pass's images (gen_bwd_build)
+  RVC_REQUIRE(keep == Q.built, "enc_q.pre.weight decides whether a posterior is built");   // (gen_bwd_build, flow_bwd_build)
   GenHostWeights& GH = S->gen_host;
   S->conv_pre = make_conv1d(ts, "dec.conv_pre", 1, 3, 1, false, true, 1.f, 0, -1, keep ? &GH.pre : nullptr);
   S->conv_post_w.upload(ts.get("dec.conv_post.weight").data);
@@ -445,7 +453,33 @@ static float* enc_p_stats(Synth* S, hipStream_t s, Arena& A, bool gs, const Spli
 // posterior encoder (n = 16).  In: the residual stream h = hw rows [0, H) (split-resident path: also its image, the first H channels of hw_s); out: the skip sum
 // wo = hw rows [H, 2 H) (and its image behind h's).  gcond: cond_layer(g), 2 H n values.
 struct WnBufs { float* hw; float* xin; float* acts; unsigned char* hw_s; unsigned char* acts_s; };
-static void wn_run(hipStream_t s, const WNStack& W, const float* gcond, bool gs, const WnBufs& b, int C, int T) {
+// what a recording pass keeps of a 3-layer stack (the flow's): x[i] receives layer i's input, a[i] its pre-gate activation in_layers[i](x) + gc slice (2 H rows)
+struct WnRecord { float* x[3]; float* a[3]; };
+// The recording variant: in_layers[i] writes its 2 H rows into the tape (the gate cannot run in the launch's epilogue, which never stores them), the gate is
+// wn_gate_record - the arithmetic of wn_gate / wn_gate_split, the summed pre-gate activation stored back - and the residual stream is copied out per layer.
+static void wn_run_record(hipStream_t s, const WNStack& W, const float* gcond, bool gs, const WnBufs& b, int C, int T, const WnRecord& rec) {
+  const long long tp = split_image_tp(T);
+  float* h = b.hw; float* wo = b.hw + (size_t)C * T;
+  unsigned char* wo_s = gs ? b.hw_s + split_image_bytes(C, T) : nullptr;
+  ConvEpilogue E0;
+  RVC_REQUIRE(W.n == 3, "a recorded WaveNet stack has 3 layers");
+  if (gs) fill(s, wo, 0.f, (long long)C * T);
+  for (int i = 0; i < W.n; ++i) {
+    RVC_HIP_CHECK(hipMemcpyAsync(rec.x[i], h, (size_t)C * T * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (gs) conv_x3s_run(W.in[i], s, b.hw_s, tp, T, rec.a[i], T, E0); else conv1d_run(W.in[i], s, h, T, T, rec.a[i], T, E0);
+    wn_gate_record(s, rec.a[i], gcond + (size_t)i * 2 * C, gs ? nullptr : b.acts, gs ? b.acts_s : nullptr, tp, kSplitMargin, C, T);
+    if (gs) {
+      if (i < W.n - 1) { ConvEpilogue Ea; Ea.R = b.hw; Ea.ldR = T; Ea.ys_out = b.hw_s; Ea.ys_tp = tp; conv_x3s_run(W.rs[i], s, b.acts_s, tp, T, b.hw, T, Ea); }
+      else { ConvEpilogue Ea; Ea.R = wo; Ea.ldR = T; Ea.ys_out = wo_s; Ea.ys_tp = tp; conv_x3s_run(W.skip[i], s, b.acts_s, tp, T, wo, T, Ea); }
+    } else {
+      ConvEpilogue Es; Es.accumulate = (i > 0);
+      conv1d_run(W.skip[i], s, b.acts, T, T, wo, T, Es);
+      if (i < W.n - 1) { ConvEpilogue Er; Er.R = h; Er.ldR = T; conv1d_run(W.res[i], s, b.acts, T, T, h, T, Er); }
+    }
+  }
+}
+static void wn_run(hipStream_t s, const WNStack& W, const float* gcond, bool gs, const WnBufs& b, int C, int T, const WnRecord* rec = nullptr) {
+  if (rec) return wn_run_record(s, W, gcond, gs, b, C, T, *rec);
   const long long tp = split_image_tp(T);
   float* h = b.hw; float* wo = b.hw + (size_t)C * T;
   ConvEpilogue E0;
@@ -479,7 +513,8 @@ static void wn_run(hipStream_t s, const WNStack& W, const float* gcond, bool gs,
 
 // One ResidualCouplingLayer (reference lib/infer_pack/modules.py:436-455, mean_only) on cur [inter][T] in place: x1 -= m (reverse, infer) or x1 += m (forward,
 // training).  The split-resident path packs post with both signs (post_neg / post): either direction is a plain residual add in the GEMM's epilogue.
-static void coupling_run(Synth* S, hipStream_t s, FlowLayer& F, const float* gcond, bool gs, const SplitImgs& im, const WnBufs& b, float* cur, int T, bool reverse) {
+static void coupling_run(Synth* S, hipStream_t s, FlowLayer& F, const float* gcond, bool gs, const SplitImgs& im, const WnBufs& b, float* cur, int T, bool reverse,
+                         const WnRecord* rec = nullptr) {
   const int C = S->hidden, half = S->inter / 2;
   const long long tp = split_image_tp(T);
   float* h = b.hw; float* wo = b.hw + (size_t)C * T;
@@ -490,13 +525,13 @@ static void coupling_run(Synth* S, hipStream_t s, FlowLayer& F, const float* gco
     unsigned char* wo_s = b.hw_s + split_image_bytes(C, T);
     ConvEpilogue Eh; Eh.ys_out = b.hw_s; Eh.ys_tp = tp;
     conv_x3s_run(F.pre, s, im.x0_s, tp, T, h, T, Eh);
-    wn_run(s, F.wn, gcond, gs, b, C, T);
+    wn_run(s, F.wn, gcond, gs, b, C, T, rec);
     ConvEpilogue Ep; Ep.R = x1; Ep.ldR = T;
     conv_x3s_run(reverse ? F.post_neg : F.post, s, wo_s, tp, T, x1, T, Ep);    // x1 = x1 -+ m
     return;
   }
   conv1d_run(F.pre, s, cur, T, T, h, T, E0);
-  wn_run(s, F.wn, gcond, gs, b, C, T);
+  wn_run(s, F.wn, gcond, gs, b, C, T, rec);
   ConvEpilogue Ep; Ep.out_scale = reverse ? -1.f : 1.f; Ep.accumulate = 1;
   conv1d_run(F.post, s, wo, T, T, x1, T, Ep);     // x1 = x1 -+ m
 }
@@ -626,11 +661,14 @@ static void gen_tail(Synth* S, hipStream_t s, Arena& A, bool gs, unsigned char* 
 // and, on a handle with kept parameters (synth_keep_parameters), what the weight-gradient pass reads beside them: sine [1][seg upp] (the source before
 // m_source.l_linear; f0 family), g [1][gin] (the item's emb_g row)
 struct GenTape {
-  struct Tensor { size_t off; int rows; long long cols; };
+  struct Tensor { size_t off; int rows; long long cols; bool flow = false; };      // flow: an offset into flow_mem
   const Synth* S = nullptr; int seg = 0; bool recorded = false;
   bool backward_done = false;      // a backward data pass has run since the last taped forward: the deltas belong to the recorded activations
   std::map<std::string, Tensor> t;
   DevVec mem; float* fr = nullptr;      // fr: the im2col frames of a wide noise convolution (scratch)
+  // the flow's recording (synth_forward_tape with record_flow): its tensors live in a block of their own, laid out for the item's length when a recording
+  // forward first meets that length - a tape that never records the flow holds none of it
+  DevVec flow_mem; int flow_T = 0; bool flow_recorded = false; int flow_fwd_marks = 0, flow_bwd_marks = 0;
   // timing (gen_tape_timing; off: no event is ever created or recorded): events around the taped decoder and at the backward's stage boundaries
   bool timing = false; std::vector<hipEvent_t> ev; int fwd_marks = 0, bwd_marks = 0, wgrad_marks = 0;
   GenTape() = default;
@@ -644,9 +682,10 @@ struct GenTape {
   float* ptr(const std::string& name) const {
     auto it = t.find(name);
     RVC_REQUIRE(it != t.end(), "the tape holds no tensor '" + name + "'");
-    return mem.p + it->second.off;
+    return (it->second.flow ? flow_mem.p : mem.p) + it->second.off;
   }
 };
+constexpr int kFlowMark0 = 32;       // the flow's events: 32, 33 around the recorded flow forward, 34, 35 around its backward
 constexpr int kWgradMark0 = 16;      // the weight-gradient pass's events: slots 16 .. (the forward's are 0, 1; the backward's 2 .. n + 4)
 static std::string rb_name(int i, int j, const char* what, int m) { return "rb" + std::to_string(i) + "." + std::to_string(j) + "." + what + std::to_string(m); }
 static void tape_check(const Synth* S, const GenTape* tape) {
@@ -752,12 +791,12 @@ GenTape* gen_tape_create(Synth* S) {
   return T.release();
 }
 void gen_tape_destroy(GenTape* T) { delete T; }
-size_t gen_tape_bytes(const GenTape* T) { return T->mem.n * sizeof(float); }
+size_t gen_tape_bytes(const GenTape* T) { return (T->mem.n + T->flow_mem.n) * sizeof(float); }
 size_t synth_gen_bwd_bytes(const Synth* S) { return S->gen_bwd.bytes; }
 bool gen_tape_tensor(const GenTape* T, const char* name, float** p, int* rows, long long* cols) {
   auto it = T->t.find(name);
   if (it == T->t.end()) return false;
-  *p = T->mem.p + it->second.off; *rows = it->second.rows; *cols = it->second.cols;
+  *p = (it->second.flow ? T->flow_mem.p : T->mem.p) + it->second.off; *rows = it->second.rows; *cols = it->second.cols;
   return true;
 }
 
@@ -884,7 +923,7 @@ static int dec_backward(const Synth* S, hipStream_t s, GenTape* tape, const floa
   mark();
   return launches;
 }
-void gen_tape_timing(GenTape* T, bool on) { T->timing = on; if (!on) T->fwd_marks = T->bwd_marks = T->wgrad_marks = 0; }
+void gen_tape_timing(GenTape* T, bool on) { T->timing = on; if (!on) T->fwd_marks = T->bwd_marks = T->wgrad_marks = T->flow_fwd_marks = T->flow_bwd_marks = 0; }
 // waits for the recorded events.  ms[0]: the taped decoder (conv_pre .. y_hat) of the last taped forward; then the last backward's intervals in execution order:
 // tanh + conv_post, stage n - 1 .. stage 0, conv_pre + conditioning + noise branch.  Returns the number of values (0: timing off or nothing recorded yet).
 int gen_tape_times(GenTape* T, float* ms, int cap) {
@@ -910,6 +949,146 @@ void synth_dec_input_grad(Synth* S, hipStream_t s, GenTape* tape, const float* d
   RVC_REQUIRE(S->f0 || !dhar, "no-f0 model: there is no harmonic source, dhar must be NULL");
   dec_backward(S, s, tape, dy, dz, dcond, dg, dhar);
   tape->backward_done = true;
+}
+
+// ------------------------------------------------------------------------------------------------ the flow's backward data pass
+// ResidualCouplingBlock (reference models.py:150-196; modules.py ResidualCouplingLayer, WN, Flip) read backwards on ONE item at its own length T: d z_p -> d z and
+// the flow's share of d g.  The recording forward (synth_forward_tape, record_flow) leaves per coupling f in the tape's flow block, fp32 [rows][T]:
+//   flow{f}.h0 [H] (pre(x0), = flow{f}.x0), flow{f}.x{i} [H] (the input of WN layer i), flow{f}.a{i} [2 H] (in_layers[i](x{i}) + its slice of cond_layer(g))
+// and the backward leaves its deltas beside them:
+//   d.flow{f}.m [inter / 2] (post's output cotangent), d.flow{f}.a{i} [2 H], d.flow{f}.h0 [H] (pre's output cotangent), d.flow{f}.gc [1][6 H], d.flow.g [1][gin]
+// The item runs at its own length, so its mask is all ones inside the tape; the kernels still take the length and write zero behind it.
+static std::string flow_name(int f, const std::string& what) { return "flow" + std::to_string(f) + "." + what; }
+
+// the weight images of the pass, built by the first recording forward (a handle that never records the flow never gets here)
+static void flow_bwd_build(Synth* S) {
+  FlowBwdImages& B = S->flow_bwd;
+  if (B.built) return;
+  const int H = S->hidden, half = S->inter / 2;
+  RVC_REQUIRE(!S->flow_host[0].pre.empty(), "the flow's folded weights were not kept (no posterior was loaded at finalize)");
+  RVC_REQUIRE(S->inter % 2 == 0 && half % 16 == 0 && H % 16 == 0, "the flow's backward kernels need inter_channels / 2 and hidden_channels to be multiples of 16");
+  FlowBwdImages N;
+  auto image = [&](const std::vector<float>& w, int Co, int Ci, int k, DevBuf<uint16_t>& img) {
+    RVC_REQUIRE(w.size() == (size_t)Co * Ci * k, "flow convolution: weight size");
+    std::vector<uint16_t> P;
+    gen_bwd_conv_image(w.data(), Co, Ci, k, P);
+    img.upload(P); N.bytes += P.size() * sizeof(uint16_t);
+  };
+  for (int f = 0; f < 4; ++f) {
+    const FlowHostWeights& W = S->flow_host[f];
+    image(W.pre, H, half, 1, N.pre[f]);
+    image(W.post, half, H, 1, N.post[f]);
+    for (int i = 0; i < 3; ++i) {
+      image(W.in[i], 2 * H, H, 5, N.in[f][i]);
+      image(W.rs[i], i < 2 ? 2 * H : H, H, 1, N.rs[f][i]);
+    }
+  }
+  N.built = true;
+  B = std::move(N);
+  for (FlowHostWeights& W : S->flow_host) W = {};
+}
+size_t synth_flow_bwd_bytes(const Synth* S) { return S->flow_bwd.bytes; }
+
+// the flow block's layout for an item of T frames: the recorded activations, the deltas, the backward's scratch (the [dx | dh] pair that a res_skip layer's
+// transposed product reads as one 2 H-row operand, d acts, one ping-pong cotangent)
+static void flow_tape_layout(GenTape& tape, const Synth* S, int T, hipStream_t s) {
+  if (tape.flow_T == T && tape.flow_mem.p) return;
+  for (auto it = tape.t.begin(); it != tape.t.end();) it = it->second.flow ? tape.t.erase(it) : std::next(it);
+  const int H = S->hidden, IC = S->inter;
+  size_t off = 0;
+  auto add = [&](const std::string& name, int rows, long long cols) {
+    tape.t[name] = {off, rows, cols, true};
+    off += ((size_t)rows * (size_t)cols + 63) & ~size_t(63);
+  };
+  for (int f = 0; f < 4; ++f) {
+    add(flow_name(f, "h0"), H, T);
+    tape.t[flow_name(f, "x0")] = tape.t[flow_name(f, "h0")];      // WN's first input is pre's output: one tensor under both names
+    for (int i = 1; i < 3; ++i) add(flow_name(f, "x" + std::to_string(i)), H, T);
+    for (int i = 0; i < 3; ++i) add(flow_name(f, "a" + std::to_string(i)), 2 * H, T);
+  }
+  for (int f = 0; f < 4; ++f) {
+    add("d." + flow_name(f, "m"), IC / 2, T);
+    for (int i = 0; i < 3; ++i) add("d." + flow_name(f, "a" + std::to_string(i)), 2 * H, T);
+    add("d." + flow_name(f, "h0"), H, T);
+    add("d." + flow_name(f, "gc"), 1, 6 * H);
+  }
+  add("d.flow.g", 1, S->gin);
+  add("flow.scratch.dxh", 2 * H, T); add("flow.scratch.dacts", H, T); add("flow.scratch.cur", IC, T);
+  if (tape.flow_mem.n < off) { RVC_HIP_CHECK(hipStreamSynchronize(s)); tape.flow_mem.alloc(off); }      // (an earlier pass on this stream may still read the old block)
+  tape.flow_T = T;
+}
+
+// tape null: nothing is launched, the return value is the number of launches of the plan (a constant of the net).  No atomics: two calls give the same bits.
+static int flow_backward(const Synth* S, hipStream_t s, GenTape* tape, const float* dzp, float* dz, float* dg) {
+  const FlowBwdImages& B = S->flow_bwd;
+  const int H = S->hidden, IC = S->inter, half = IC / 2, T = tape ? tape->flow_T : 0, len = T;
+  int launches = 0;
+  auto P = [&](const std::string& name) -> float* { return tape ? tape->ptr(name) : nullptr; };
+  // Y [R][T] = W'(D) (+ Res) under the mask; A: the taped pre-gate activation whose gate derivative the operand is formed with (D = d acts)
+  auto gemm = [&](const DevBuf<uint16_t>* img, const float* D, const float* A, int Ck, int nt, const float* Res, float* Y, int R) {
+    ++launches;
+    if (!tape) return;
+    ConvFlowBwdArgs a{D, T, T, A, H, reinterpret_cast<const unsigned char*>(img->p), Res, Y, T, R, (R + 127) & ~127, Ck, T, nt, -((nt - 1) / 2), len};
+    ConvFlowBwdPlan p;
+    RVC_REQUIRE(conv_flow_bwd_plan(a, p), "flow layer does not fit the data-gradient kernel");
+    conv_flow_bwd_launch(p, s);
+  };
+  if (tape) { tape->mark(s, kFlowMark0 + 2); tape->flow_bwd_marks = 0; }
+  float* dxh = P("flow.scratch.dxh"); float* dh = tape ? dxh + (size_t)H * T : nullptr;      // [dx | dh]: the x-chain cotangent above WN's output cotangent
+  float* dacts = P("flow.scratch.dacts");
+  const float* src = dzp;
+  for (int f = 3; f >= 0; --f) {
+    // Flip, and the coupling's x1 half: d x1 = d m = d x1' under the mask
+    float* cur = (f & 1) ? P("flow.scratch.cur") : dz;
+    float* dm = P("d." + flow_name(f, "m"));
+    ++launches; if (tape) flow_unflip(s, src, cur, dm, IC, T, len);
+    gemm(tape ? &B.post[f] : nullptr, dm, nullptr, half, 1, nullptr, dh, H);                                  // d h = post^T d m, the skip cotangent of every layer
+    float* dgc = P("d." + flow_name(f, "gc"));
+    for (int i = 2; i >= 0; --i) {
+      const std::string si = std::to_string(i);
+      // d acts = res_skip^T [dx | dh] (the last layer's res_skip has the skip rows only); d a = d acts times the gate's derivative, kept with its row sums
+      if (i == 2) gemm(tape ? &B.rs[f][i] : nullptr, dh, nullptr, H, 1, nullptr, dacts, H);
+      else gemm(tape ? &B.rs[f][i] : nullptr, dxh, nullptr, 2 * H, 1, nullptr, dacts, H);
+      const float* a = P(flow_name(f, "a" + si));
+      ++launches; if (tape) flow_gate_bwd(s, dacts, a, P("d." + flow_name(f, "a" + si)), dgc + (size_t)2 * H * i, H, T, len);
+      // dx += in_layers[i]^T (d a): the x-chain cotangent is zero above the last layer; layer 0's is pre's output cotangent d h0
+      gemm(tape ? &B.in[f][i] : nullptr, dacts, a, 2 * H, 5, i < 2 ? dxh : nullptr, i > 0 ? dxh : P("d." + flow_name(f, "h0")), H);
+    }
+    gemm(tape ? &B.pre[f] : nullptr, P("d." + flow_name(f, "h0")), nullptr, H, 1, cur, cur, half);              // d x0 = d x0' + pre^T d h0
+    src = cur;
+  }
+  // d g = sum over the couplings of cond_layer^T d gc
+  ++launches;
+  if (tape) {
+    const float* W[4]; const float* G[4];
+    for (int f = 0; f < 4; ++f) { W[f] = S->flow[f].wn.cond_w.p; G[f] = P("d." + flow_name(f, "gc")); }
+    flow_cond_bwd(s, W, G, 6 * H, S->gin, P("d.flow.g"), dg);
+    tape->mark(s, kFlowMark0 + 3); tape->flow_bwd_marks = tape->timing ? 2 : 0;
+  }
+  return launches;
+}
+int synth_flow_input_grad_launch_count(const Synth* S) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  return flow_backward(S, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+void synth_flow_input_grad(Synth* S, hipStream_t s, GenTape* tape, const float* dzp, long long T, float* dz, float* dg) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  tape_check(S, tape);
+  RVC_REQUIRE(tape->recorded && tape->flow_recorded && S->flow_bwd.built, "the tape holds no recorded flow: run synth_forward_tape with record_flow first");
+  RVC_REQUIRE(T == tape->flow_T, "d z_p does not have the recorded item's length");
+  flow_backward(S, s, tape, dzp, dz, dg);
+}
+// [0]: the recorded flow forward (its four couplings and Flips), [1]: the last flow backward; waits for the events.  Returns the number of values
+int gen_tape_flow_times(GenTape* T, float* ms, int cap) {
+  if (!T->timing) return 0;
+  int n = 0;
+  auto put = [&](int a, int b) {
+    RVC_HIP_CHECK(hipEventSynchronize(T->ev[b]));
+    RVC_HIP_CHECK(hipEventElapsedTime(&ms[n++], T->ev[a], T->ev[b]));
+  };
+  if (T->flow_fwd_marks == 2 && n < cap) put(kFlowMark0, kFlowMark0 + 1); else return 0;
+  if (T->flow_bwd_marks == 2 && n < cap) put(kFlowMark0 + 2, kFlowMark0 + 3);
+  return n;
 }
 
 // ------------------------------------------------------------------------------------------------ the decoder's weight-gradient pass
@@ -1130,7 +1309,8 @@ static void synth_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm,
 
 // SynthesizerTrnMs{256,768}NSFsid[_nono].forward for one item at its own length (reference models.py:781-796,:894-903): every mask is all ones.
 static void synth_forward_graph(Synth* S, hipStream_t s, Arena& A, const float* feat_cm, const long long* pitch, const float* pitchf, const float* spec, int sid,
-                                const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps, GenTape* tape) {
+                                const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps, GenTape* tape,
+                                bool record_flow) {
   const int C = S->hidden, IC = S->inter, seg = S->segment;
   Posterior& Q = S->post_enc;
   const bool dry = A.dry;
@@ -1186,11 +1366,16 @@ static void synth_forward_graph(Synth* S, hipStream_t s, Arena& A, const float* 
       // ---- flow (forward): coupling 0 .. 3, each followed by Flip (reference models.py:185-192)
       RVC_HIP_CHECK(hipMemcpyAsync(zp, z, (size_t)IC * T * sizeof(float), hipMemcpyDeviceToDevice, s));
       float* cur = zp; float* oth = zf;
+      if (record_flow) tape->mark(s, kFlowMark0);
       for (int f = 0; f < 4; ++f) {
-        coupling_run(S, s, S->flow[f], gcond[f], gs, im, wb, cur, T, false);
+        WnRecord rec;
+        if (record_flow)
+          for (int i = 0; i < 3; ++i) { rec.x[i] = tape->ptr(flow_name(f, "x" + std::to_string(i))); rec.a[i] = tape->ptr(flow_name(f, "a" + std::to_string(i))); }
+        coupling_run(S, s, S->flow[f], gcond[f], gs, im, wb, cur, T, false, record_flow ? &rec : nullptr);
         flip_c(s, cur, oth, IC, T);
         std::swap(cur, oth);
       }
+      if (record_flow) { tape->mark(s, kFlowMark0 + 1); tape->flow_fwd_marks = tape->timing ? 2 : 0; }
       if (taps) tap(A, s, taps->z_p, cur, (size_t)IC * T);
     }
     A.off = mark;
@@ -1260,17 +1445,22 @@ void synth_infer(Synth* S, hipStream_t s, const float* feat, int feat_channel_ma
 }
 
 void synth_forward_tape(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, const float* spec,
-                        int sid, const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps, GenTape* tape) {
+                        int sid, const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps, GenTape* tape,
+                        bool record_flow) {
   RVC_REQUIRE(S->ready, "synth_finalize has not been called");
-  if (tape) { tape_check(S, tape); tape->recorded = false; tape->backward_done = false; }
+  RVC_REQUIRE(tape || !record_flow, "record_flow needs a tape");
+  if (tape) { tape_check(S, tape); tape->recorded = false; tape->backward_done = false; tape->flow_recorded = false; }
   RVC_REQUIRE(S->post_enc.built, "no posterior encoder loaded: the checkpoint had no enc_q.* tensors (an inference checkpoint)");
   RVC_REQUIRE(S->segment > 0, "segment_size is not set in the configuration");
   RVC_REQUIRE(T >= S->segment && T >= 11, "the sequence is shorter than the segment");
   RVC_REQUIRE(ids >= 0 && ids <= T - S->segment, "slice start outside [0, T - segment]");
   RVC_REQUIRE(sid >= 0 && sid < S->n_spk, "speaker id out of range");
+  if (record_flow) { flow_bwd_build(S); flow_tape_layout(*tape, S, T, s); }
   Arena& A = S->arena;
-  arena_passes(A, [&] { synth_forward_graph(S, s, A, feat_cm_of(S, s, A, feat, feat_channel_major, T), pitch, pitchf, spec, sid, noise_q, noise_src, T, ids, out, taps, tape); });
-  if (tape) tape->recorded = true;
+  arena_passes(A, [&] {
+    synth_forward_graph(S, s, A, feat_cm_of(S, s, A, feat, feat_channel_major, T), pitch, pitchf, spec, sid, noise_q, noise_src, T, ids, out, taps, tape, record_flow);
+  });
+  if (tape) { tape->recorded = true; tape->flow_recorded = record_flow; }
 }
 
 void synth_forward(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, const float* spec, int sid,

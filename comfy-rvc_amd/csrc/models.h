@@ -44,7 +44,15 @@ void gen_tape_timing(GenTape* T, bool on);             // events around the tape
 int gen_tape_times(GenTape* T, float* ms, int cap);    // ms[0] the taped decoder, then the backward's intervals in execution order; waits for the events
 bool gen_tape_tensor(const GenTape* T, const char* name, float** p, int* rows, long long* cols);   // false: no such tensor
 void synth_forward_tape(Synth* S, hipStream_t s, const float* feat, int feat_channel_major, const long long* pitch, const float* pitchf, const float* spec,
-                        int sid, const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps, GenTape* tape);
+                        int sid, const float* noise_q, const float* noise_src, int T, int ids, float* out, const SynthForwardTaps* taps, GenTape* tape,
+                        bool record_flow = false);
+// The flow's backward data pass on a forward recorded with record_flow (the tape then also holds, for the item's T frames, what the four couplings' backward
+// reads: flow{f}.h0, flow{f}.x{i}, flow{f}.a{i}; the first such forward builds the pass's weight images): d z_p [inter][T] -> dz [inter][T] and dg [gin] (may be
+// null), the flow's share of both; the deltas d.flow{f}.a{i}, d.flow{f}.m, d.flow{f}.h0, d.flow{f}.gc and d.flow.g stay in the tape.
+void synth_flow_input_grad(Synth* S, hipStream_t s, GenTape* tape, const float* dzp, long long T, float* dz, float* dg);
+int synth_flow_input_grad_launch_count(const Synth* S);   // pure: the size of the plan, independent of the item's length
+size_t synth_flow_bwd_bytes(const Synth* S);              // device bytes of that pass's weight images (0 before the first recording forward)
+int gen_tape_flow_times(GenTape* T, float* ms, int cap);  // timing on: [0] the recorded flow forward, [1] the last flow backward; waits for the events
 void synth_dec_input_grad(Synth* S, hipStream_t s, GenTape* tape, const float* dy, float* dz, float* dcond, float* dg, float* dhar);
 int synth_dec_input_grad_launch_count(const Synth* S);   // pure: the size of the plan, independent of the segment
 // The decoder's weight-gradient pass (model_synth.hip, conv_gen_wgrad.hip): d loss / d(parameter) of every dec.* tensor summed over the B items whose tapes are

@@ -331,6 +331,35 @@ int rvc_synth_forward_tape(rvc_synth* s, void* stream, const float* phone, int p
   check_launch();
   RVC_CATCH
 }
+int rvc_synth_forward_tape_flow(rvc_synth* s, void* stream, const float* phone, int phone_cm, const int64_t* pitch, const float* pitchf, const float* spec, int sid,
+                                const float* noise_q, const float* noise_src, int64_t T, int64_t ids, float* out, const rvc_synth_forward_taps* taps,
+                                rvc_gen_tape* tape, int record_flow) {
+  RVC_TRY
+  RVC_REQUIRE(s && phone && spec && noise_q && out && tape, "null argument");
+  RVC_REQUIRE(T > 0 && T < (1LL << 24), "bad sequence length");
+  check_pitch_args(s, pitch, pitchf, noise_src, 0);
+  RVC_HIP_CHECK(hipSetDevice(s->ctx->c.device));
+  synth_forward_tape(s->m, (hipStream_t)stream, phone, phone_cm, (const long long*)pitch, pitchf, spec, sid, noise_q, noise_src, (int)T,
+                     (int)std::max<int64_t>(-1, std::min<int64_t>(ids, T)), out, taps, tape->t, record_flow != 0);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_synth_flow_input_grad(rvc_synth* s, void* stream, rvc_gen_tape* tape, const float* dz_p, int64_t T, float* dz, float* dg) {
+  RVC_TRY
+  RVC_REQUIRE(s && tape && dz_p && dz, "null argument");
+  RVC_HIP_CHECK(hipSetDevice(s->ctx->c.device));
+  synth_flow_input_grad(s->m, (hipStream_t)stream, tape->t, dz_p, T, dz, dg);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_synth_flow_input_grad_launch_count(rvc_synth* s) {
+  try { return s ? synth_flow_input_grad_launch_count(s->m) : -1; }
+  catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_gen_tape_flow_times(rvc_gen_tape* t, float* ms_host, int cap) {
+  try { RVC_REQUIRE(t && ms_host && cap >= 2, "bad argument"); return gen_tape_flow_times(t->t, ms_host, cap); }
+  catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
 int rvc_synth_dec_input_grad(rvc_synth* s, void* stream, rvc_gen_tape* tape, const float* dy_hat, float* dz, float* dcond, float* dg, float* dhar) {
   RVC_TRY
   RVC_REQUIRE(s && tape && dy_hat && dz, "null argument");

@@ -269,6 +269,26 @@ void gen_post_bwd(hipStream_t s, const float* d, const float* w, const float* x,
 void gen_noise_bwd(hipStream_t s, const float* D, const float* w, float* dhar, float* out2, int C, int k, int stride, int pad, long long T, long long N, int accumulate);
 void gen_row_sums(hipStream_t s, const float* D, int C, long long T, float* out, float* out2);
 void gen_cond_bwd(hipStream_t s, const float* W, const float* dcond, int C, int G, float* out, float* out2);
+// The transposed products of the flow's backward data pass (conv_flow_bwd.hip; model_synth.hip::flow_backward), one item per launch:
+//   Y[r][n] = n < len ? sum_c sum_t W'[r][c][t] G[c][n + off0 + t] + Res[r][n] : 0,   r < R, n < N
+// Wx = x3_weight_image of W' [R][Ck][nt] (gen_bwd_conv_image of the forward's layer), rows padded to RPx.  A null: G = D [Ck][ldD] with Td valid columns (zero
+// outside).  A = the taped pre-gate activation [2 H][ldD] (Ck = 2 H): D holds d acts [H][ldD] and G is WN's gate read backwards, formed where the operand is
+// gathered and split:  G[c] = D[c] sigmoid(A[H + c]) (1 - tanh^2(A[c])),  G[H + c] = D[c] tanh(A[c]) sigmoid'(A[H + c]),  c < H.  Res (null: none) and Y share ldY.
+struct ConvFlowBwdArgs {
+  const float* D; long long ldD; int Td; const float* A; int H; const unsigned char* Wx; const float* Res; float* Y; long long ldY;
+  int R, RPx, Ck, N, nt, off0, len;
+};
+struct ConvFlowBwdPlan { ConvFlowBwdArgs a; dim3 grid; int units = 1; size_t lds = 0; };
+bool conv_flow_bwd_plan(const ConvFlowBwdArgs& a, ConvFlowBwdPlan& p);   // pure; false: the layer does not fit the kernel (Ck % 16, H % 16, nt <= 16, 32-bit offsets)
+void conv_flow_bwd_launch(const ConvFlowBwdPlan& p, hipStream_t s);
+// the direct kernels of that pass.  flow_unflip: y[c][t] = t < len ? x[C - 1 - c][t] : 0 (Flip read backwards, with the mask), rows C / 2 .. also to dm.
+// flow_gate_bwd: da = the gate's derivative above as a tensor [2 H][T] (zero behind len) and dgc[r] = its row sums in float64, rounded once.
+// flow_cond_bwd: dg[g] = sum_f sum_c W_f[c][g] dgc_f[c] over the four couplings in float64, rounded once (out2: a second copy or null).
+// wn_gate_record: WN's gate as wn_gate / wn_gate_split compute it (img null: acts as fp32 [H][T] in out), a += g left in place: the recorded pre-gate activation.
+void flow_unflip(hipStream_t s, const float* x, float* y, float* dm, int C, int T, int len);
+void flow_gate_bwd(hipStream_t s, const float* dacts, const float* a, float* da, float* dgc, int H, int T, int len);
+void flow_cond_bwd(hipStream_t s, const float* const (&W)[4], const float* const (&dgc)[4], int C, int G, float* out, float* out2);
+void wn_gate_record(hipStream_t s, float* a, const float* g, float* out, unsigned char* img, long long tp, int margin, int H, int T);
 // The weight gradient of that convolution (conv_x3d_wgrad.hip): dW[m][c][j] = sum_s sum_n D[s][m][n] X[s][c][stride n - (stride - 1) w + (j - pad) p], both
 // operands fp32 and split in the kernel, the reduction over (signal, n) cut into `splits` runs of stages (one signal, 128 columns each): split z writes the
 // partial image part[z][Co][Ci k]; the caller provides part_floats floats and adds the partials in index order.  cps / per / total: filled by the planner.

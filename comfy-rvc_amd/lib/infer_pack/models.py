@@ -143,7 +143,7 @@ class _SynthesizerNSFsid:
         return out, x_mask, (tbuf.get("z"), tbuf.get("z_p"), tbuf.get("m_p"), tbuf.get("logs_p"))
 
     # ------------------------------------------------------------------------------------------- training forward
-    def _forward(self, phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise, ids_slice, with_tape=False):
+    def _forward(self, phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise, ids_slice, with_tape=False, record_flow=False):
         """SynthesizerTrnMs{256,768}NSFsid[_nono].forward (reference :781-796,:894-903).  noise=(noise_q [B,inter,T], noise_src [B,seg*upp,1]);
         without it the draws are made on the host in the reference's order and shapes: enc_q's randn_like [B,inter,T] (:237), torch.rand([B]) of
         rand_slice_segments (commons.py:173), SineGen's rand_ini torch.rand(B, 1) (:378-381, zeroed) and its randn_like [B,seg*upp,1] (:409)."""
@@ -194,6 +194,8 @@ class _SynthesizerNSFsid:
             tape.ids, tape.Ty = [int(i) for i in ids], Ty
         elif with_tape:
             tape = GeneratorTape(self, B, ids, Ty)
+        if tape is not None:
+            tape.lengths, tape.flow_recorded = [int(v) for v in yl], False
         with torch.cuda.device(dev):
             st = _lib.current_stream()
             for b in range(B):
@@ -205,7 +207,10 @@ class _SynthesizerNSFsid:
                 pf_b = pf[b, :L].contiguous() if f0 else None
                 ns_b = ns[b].contiguous() if f0 else None
                 o_b = torch.empty(seg * upp, dtype=torch.float32, device=dev)
-                if tape is not None:      # the decoder layer by layer, recorded: y_hat is the taped wave
+                if tape is not None and record_flow:      # and the flow's four couplings recorded for flow_input_grad
+                    _lib.check(_lib.lib.rvc_synth_forward_tape_flow(self._h, st, _lib.ptr(ph_b), 0, _lib.ptr(pc_b), _lib.ptr(pf_b), _lib.ptr(y_b), int(sid[b]),
+                                                                    _lib.ptr(nq_b), _lib.ptr(ns_b), L, int(ids[b]), _lib.ptr(o_b), C.byref(tp), tape._h[b], 1))
+                elif tape is not None:      # the decoder layer by layer, recorded: y_hat is the taped wave
                     _lib.check(_lib.lib.rvc_synth_forward_tape(self._h, st, _lib.ptr(ph_b), 0, _lib.ptr(pc_b), _lib.ptr(pf_b), _lib.ptr(y_b), int(sid[b]),
                                                                _lib.ptr(nq_b), _lib.ptr(ns_b), L, int(ids[b]), _lib.ptr(o_b), C.byref(tp), tape._h[b]))
                 else:
@@ -217,17 +222,22 @@ class _SynthesizerNSFsid:
         x_mask = (torch.arange(Tx)[None, :] < pl[:, None]).to(torch.float32).unsqueeze(1).to(dev)
         y_mask = (torch.arange(Ty)[None, :] < yl[:, None]).to(torch.float32).unsqueeze(1).to(dev)
         res = (o, ids.to(dev), x_mask, y_mask, tuple(taps))
+        if tape is not None:
+            tape.flow_recorded = bool(record_flow)
         return (res, tape) if with_tape else res
 
     def forward(self, phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise=None, ids_slice=None):
         return self._forward(phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise, ids_slice)
 
     # ------------------------------------------------------------------------------------------- the decoder's backward data pass
-    def forward_with_tape(self, phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise=None, ids_slice=None, tape=None):
+    def forward_with_tape(self, phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise=None, ids_slice=None, tape=None, record_flow=False):
         """forward's arguments -> (forward's 5-tuple, GeneratorTape).  The decoder runs layer by layer and records what its backward reads
         (rvc_synth_forward_tape); `o` is the taped wave, inside the 1e-3 gate of forward's but not bit-equal to it (forward keeps its fused ResBlock kernels).
-        tape: a GeneratorTape of an earlier call with the same batch size to record into again (a trainer keeps one), instead of a new one."""
-        return self._forward(phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise, ids_slice, with_tape=tape if tape is not None else True)
+        tape: a GeneratorTape of an earlier call with the same batch size to record into again (a trainer keeps one), instead of a new one.
+        record_flow: the tape also records, per item at its own length, what flow_input_grad reads (rvc_synth_forward_tape_flow); z_p is then inside the 1e-3
+        gate of a non-recording call's (the recording pass gates the WaveNet layers in a launch of its own), z and `o` keep their bits."""
+        return self._forward(phone, phone_lengths, pitch, pitchf, y, y_lengths, ds, noise, ids_slice, with_tape=tape if tape is not None else True,
+                             record_flow=record_flow)
 
     def dec_input_grad(self, tape, d_y_hat, return_deltas=False):
         """d_y_hat [B,1,seg*upp] -> (dz [B,inter,Ty], dg [B,gin], dhar [B,seg*upp] or None for a no-f0 net): the decoder's vector-Jacobian product
@@ -251,6 +261,41 @@ class _SynthesizerNSFsid:
         if return_deltas:
             return dz, dg, dhar, [{n: tape.tensor(b, n) for n in tape.delta_names()} for b in range(B)]
         return dz, dg, dhar
+
+    # ------------------------------------------------------------------------------------------- the flow's backward data pass
+    def flow_input_grad(self, tape, d_z_p, return_deltas=False):
+        """d_z_p [B,inter,Ty] -> (dz_flow [B,inter,Ty], dg_flow [B,gin]): the vector-Jacobian product of the flow (rvc_synth_flow_input_grad) on a tape recorded
+        with record_flow=True.  Each item runs at its own length; everything behind it is exactly 0 in dz_flow.  dz_flow is added to dec_input_grad's dz, dg_flow
+        to its dg.  return_deltas: also a list of B dicts name -> copy of the tape's flow delta (GeneratorTape.flow_delta_names())."""
+        if not isinstance(tape, GeneratorTape) or tape.net is not self:
+            raise ValueError("flow_input_grad: the tape belongs to another net")
+        if not getattr(tape, "flow_recorded", False):
+            raise ValueError("flow_input_grad: the tape was recorded without record_flow=True")
+        dev, IC, B = self.device, self.inter_channels, tape.B
+        d = torch.as_tensor(d_z_p)
+        if tuple(d.shape) != (B, IC, tape.Ty):
+            raise ValueError(f"flow_input_grad: d_z_p must have the shape {(B, IC, tape.Ty)}, got {tuple(d.shape)}")
+        d = d.to(dev, torch.float32)
+        dz = torch.zeros(B, IC, tape.Ty, dtype=torch.float32, device=dev)
+        dg = torch.empty(B, self.gin_channels, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = _lib.current_stream()
+            for b in range(B):
+                L = tape.lengths[b]
+                d_b = d[b, :, :L].contiguous()
+                dz_b = torch.empty(IC, L, dtype=torch.float32, device=dev)
+                _lib.check(_lib.lib.rvc_synth_flow_input_grad(self._h, st, tape._h[b], _lib.ptr(d_b), L, _lib.ptr(dz_b), _lib.ptr(dg[b])))
+                dz[b, :, :L] = dz_b
+        if return_deltas:
+            return dz, dg, [{n: tape.tensor(b, n) for n in tape.flow_delta_names()} for b in range(B)]
+        return dz, dg
+
+    def flow_backward_launch_count(self):
+        """Kernel launches of one item's flow_input_grad (rvc_synth_flow_input_grad_launch_count): a constant of the net, whatever the batch and the lengths."""
+        n = int(_lib.lib.rvc_synth_flow_input_grad_launch_count(self._h))
+        if n < 0:
+            _lib.check(1)
+        return n
 
     def dec_backward_launch_count(self):
         n = int(_lib.lib.rvc_synth_dec_input_grad_launch_count(self._h))
@@ -418,6 +463,22 @@ class GeneratorTape:
     def delta_names(self):
         return self._names(True)
 
+    def flow_activation_names(self):
+        """what a forward with record_flow=True leaves per item: pre's output, each WaveNet layer's input (x0 is h0) and pre-gate activation, per coupling f"""
+        return [f"flow{f}.{n}" for f in range(4) for n in ["h0"] + [f"x{i}" for i in range(3)] + [f"a{i}" for i in range(3)]]
+
+    def flow_delta_names(self):
+        """what flow_input_grad leaves per item: post's output cotangent, each layer's d a, pre's output cotangent, cond_layer's, and the item's dg"""
+        return [f"d.flow{f}.{n}" for f in range(4) for n in ["m"] + [f"a{i}" for i in range(3)] + ["h0", "gc"]] + ["d.flow.g"]
+
+    def flow_times(self, b):
+        """Milliseconds of item b's recorded flow forward and last flow backward (set_timing on; waits for them): {"flow_forward": .., "flow_backward": ..}."""
+        buf = (C.c_float * 2)()
+        n = int(_lib.lib.rvc_gen_tape_flow_times(self._h[b], buf, 2))
+        if n < 0:
+            _lib.check(1)
+        return {k: float(buf[i]) for i, k in enumerate(["flow_forward", "flow_backward"][:n])}
+
 
 class _SynthesizerNSFsid_nono(_SynthesizerNSFsid):
     """No-f0 family (reference lib/infer_pack/models.py:812-1022): text encoder without pitch embedding, plain HiFi-GAN Generator.
@@ -461,10 +522,11 @@ class _SynthesizerNSFsid_nono(_SynthesizerNSFsid):
             raise ValueError("no-f0 model: forward(phone, phone_lengths, y, y_lengths, ds) takes no pitch arguments")
         return self._forward(phone, phone_lengths, None, None, y, y_lengths, ds, noise, ids_slice)
 
-    def forward_with_tape(self, phone, phone_lengths, y, y_lengths, ds, *extra, noise=None, ids_slice=None, tape=None):
+    def forward_with_tape(self, phone, phone_lengths, y, y_lengths, ds, *extra, noise=None, ids_slice=None, tape=None, record_flow=False):
         if extra:
             raise ValueError("no-f0 model: forward_with_tape(phone, phone_lengths, y, y_lengths, ds) takes no pitch arguments")
-        return self._forward(phone, phone_lengths, None, None, y, y_lengths, ds, noise, ids_slice, with_tape=tape if tape is not None else True)
+        return self._forward(phone, phone_lengths, None, None, y, y_lengths, ds, noise, ids_slice, with_tape=tape if tape is not None else True,
+                             record_flow=record_flow)
 
 
 class SynthesizerTrnMs768NSFsid_nono(_SynthesizerNSFsid_nono):

@@ -78,3 +78,19 @@ def generator_decoder_grads(net_g, tape, d_y_hat):
     device tensor, views of one flat buffer (`grads.flat`) in net_g.dec_parameter_shapes() order; net_g must have been built with trainable=True."""
     dz, dg, dhar = net_g.dec_input_grad(tape, d_y_hat)
     return dz, dg, dhar, net_g.dec_weight_grad(tape)
+
+
+def generator_flow_backward(net_g, tape, kl_cotangents):
+    """(dz_flow [B,inter,Ty], dg_flow [B,gin]) from kl_cotangents["z_p"] (generator_loss_cotangents' fourth result) and a GeneratorTape recorded with
+    `net_g.forward_with_tape(..., record_flow=True)`: the flow's vector-Jacobian product (net_g.flow_input_grad), the third step of the generator's backward.
+    Its per-layer deltas stay in the tape for the flow's weight gradients."""
+    return net_g.flow_input_grad(tape, kl_cotangents["z_p"])
+
+
+def generator_latent_grad(net_g, tape, d_y_hat, kl_cotangents):
+    """(dz_total, dg_total, dhar): the complete z.grad - the decoder's branch (generator_decoder_backward) plus the flow's (generator_flow_backward) - that the
+    posterior encoder's backward starts from, the two branches' gradient at the speaker embedding, and the decoder's dhar.  kl_cotangents["logs_q"] reaches the
+    posterior's statistics directly and is not part of this."""
+    dz, dg, dhar = generator_decoder_backward(net_g, tape, d_y_hat)
+    dz_flow, dg_flow = generator_flow_backward(net_g, tape, kl_cotangents)
+    return dz + dz_flow, dg + dg_flow, dhar

@@ -14,6 +14,7 @@
  *   rvc_kl_loss_grad     <- loss_kl's share of loss_gen_all.backward()   training_cli.py:571,:598
  *   rvc_mel_spectrogram_vjp <- torch.autograd.grad(loss_mel, [y_hat]) through mel_spectrogram_torch   lib/train/mel_processing.py:117-150, lib/train/losses.py:76-92
  *   rvc_mel_loss_cotangents <- the backward of F.l1_loss(y_mel, y_hat_mel) / MultiScaleMelSpectrogramLoss's loss_fn   training_cli.py:569-570, lib/train/losses.py:530-561
+ *   rvc_synth_flow_input_grad <- loss_kl's way through ResidualCouplingBlock in loss_gen_all.backward()   training_cli.py:598, lib/infer_pack/models.py:150-196
  *   rvc_disc_forward     <- MultiPeriodDiscriminator[V2].forward         lib/infer_pack/models.py:1024-1145 (net_d: training_cli.py:549,:567)
  *   rvc_sqerr_sums       <- discriminator_loss / generator_loss          lib/train/losses.py:571-593
  *   rvc_l1_sums          <- feature_loss                                 lib/train/losses.py:564-569
@@ -269,7 +270,7 @@ int rvc_synth_forward_tape(rvc_synth* s, void* stream, const float* phone_dev, i
  * (into dec.cond's output: the float64 row sums of conv_pre's output cotangent), dg_dev [gin] (= cond_w^T dcond, into emb_g's row), dhar_dev [seg * upp] (the
  * harmonic source's; the chain through m_source belongs to the weight gradients); the last three may be NULL (the tape's d.cond, d.g and d.har are written on every call; the pointers receive copies), dhar_dev must be for a no-f0 net.  Leaky-ReLU
  * masks are read from the tape.  The ResBlock and up-sampler data gradients run on a bf16x3 MFMA kernel (conv_gen_bwd.hip); no floating-point atomics: two
- * calls give the same bits.  The weight and bias gradients are rvc_synth_dec_weight_grad's (below).  Not here: enc_q / flow / enc_p, the optimizer.  Errors: a tape of another handle or another
+ * calls give the same bits.  The weight and bias gradients are rvc_synth_dec_weight_grad's (below).  Not here: enc_q / enc_p (the flow's data pass is rvc_synth_flow_input_grad's), the optimizer.  Errors: a tape of another handle or another
  * segment, no taped forward before it, dhar from a no-f0 net.  _launch_count: the size of the plan (independent of the segment; touches no stream), -1 on error. */
 int rvc_synth_dec_input_grad(rvc_synth* s, void* stream, rvc_gen_tape* tape, const float* dy_hat_dev, float* dz_dev, float* dcond_dev, float* dg_dev,
                              float* dhar_dev);
@@ -295,6 +296,30 @@ int64_t rvc_synth_dec_param_total(rvc_synth* s);
 int rvc_synth_dec_weight_grad(rvc_synth* s, void* stream, rvc_gen_tape* const* tapes, int B, float* const* grads_dev);
 int rvc_synth_dec_weight_grad_launch_count(rvc_synth* s);
 int rvc_gen_tape_wgrad_times(rvc_gen_tape* t, float* ms_host, int cap);
+/* ---- the generator's backward, third step: the flow's data pass (ResidualCouplingBlock, reference lib/infer_pack/models.py:150-196; ResidualCouplingLayer, WN and
+ * Flip of lib/infer_pack/modules.py read backwards): the cotangent at z_p - the KL loss's, rvc_kl_loss_grad - carried to z and to the speaker embedding.
+ * rvc_synth_forward_tape_flow is rvc_synth_forward_tape with one more argument: record_flow 0 is that call bit for bit (same tape, same bytes); record_flow 1
+ * also records, for the item's T frames and each coupling f = 0 .. 3, what the backward reads - flow{f}.h0 [hidden][T] (pre(x0); also under flow{f}.x0),
+ * flow{f}.x{i} [hidden][T] (the input of WN layer i = 0 .. 2) and flow{f}.a{i} [2 hidden][T] (in_layers[i](x{i}) plus its slice of cond_layer(g), before the gate) -
+ * in a block the tape allocates when a recording forward first meets that length (rvc_gen_tape_bytes then includes it) and reaches through rvc_gen_tape_tensor.
+ * The recording pass stores the 2 hidden rows that the non-recording pass gates inside the GEMM launch and gates them in a launch of its own: z_p of a recording
+ * call is inside the 1e-3 gate of a non-recording call's, not promised bit-equal; the posterior's z and the taped wave do not depend on the flow and keep their
+ * bits.  The first recording forward on a handle builds the pass's weight images (transposed, tap-flipped bf16 hi / lo images of the flow's folded weights).
+ * rvc_synth_flow_input_grad: dz_p_dev [inter][T] -> dz_dev [inter][T], the flow's share of z's cotangent (to be added to the decoder's), and dg_dev [gin] (may
+ * be NULL), its share of emb_g's row: the four couplings' cond_layer^T of the float64 row sums of d a, summed in float64 and rounded once.  The deltas stay in
+ * the tape for the weight gradients: d.flow{f}.a{i} [2 hidden][T], d.flow{f}.m [inter / 2][T] (post's output cotangent), d.flow{f}.h0 [hidden][T] (pre's),
+ * d.flow{f}.gc [1][6 hidden] (cond_layer's), d.flow.g [1][gin].  The transposed products run on a bf16x3 MFMA kernel (conv_flow_bwd.hip: the gate's derivative is
+ * formed from the taped a where the gradient operand is gathered and split; the epilogue adds the running cotangent and applies the mask).  An item runs at its
+ * own length, so every frame of the tape is inside its mask; the kernels take the length and write zero behind it.  No floating-point atomics: two calls give
+ * the same bits.  _launch_count: the size of the plan, a constant of the net whatever T (touches no stream), -1 on error.  Errors: a tape of another handle, a
+ * tape whose last forward did not record the flow, T other than the recorded length.  Not here: the flow's parameter gradients, enc_q / enc_p / emb_g.
+ * rvc_gen_tape_flow_times (timing on): [0] the recorded flow forward, [1] the last flow backward, in milliseconds; returns the number of values, -1 on error. */
+int rvc_synth_forward_tape_flow(rvc_synth* s, void* stream, const float* phone_dev, int phone_channel_major, const int64_t* pitch_dev, const float* pitchf_dev,
+                                const float* spec_dev, int sid, const float* noise_q_dev, const float* noise_src_dev, int64_t T, int64_t ids, float* out_dev,
+                                const rvc_synth_forward_taps* taps, rvc_gen_tape* tape, int record_flow);
+int rvc_synth_flow_input_grad(rvc_synth* s, void* stream, rvc_gen_tape* tape, const float* dz_p_dev, int64_t T, float* dz_dev, float* dg_dev);
+int rvc_synth_flow_input_grad_launch_count(rvc_synth* s);
+int rvc_gen_tape_flow_times(rvc_gen_tape* t, float* ms_host, int cap);
 /* The GEMM of that pass at any small shape, gradient launch plus finish, no weight norm:
  *   out_dev[r][c k + t] = sum_item sum_n a_p(P[item][r][n]) a_g(G[item][c][cstride n + tstep t + off0]),  a_x(v) = max(v, slope_x v) (slope 1: none; 0 <= slope <= 1)
  * p_dev / g_dev: HOST arrays of B <= 16 device pointers, P [R][N] and G [C][Tg] dense; elements of G outside [0, Tg) read as zero.  R % 16 == 0, k <= 16.
