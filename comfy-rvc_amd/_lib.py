@@ -145,7 +145,14 @@ SIGNATURES = {
                                        c_void_p]),
     "rvc_conv1d_weight_grad_splits": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int]),
     "rvc_conv1d_weight_grad_plan": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, P(c_int)]),
-    "rvc_kl_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
+    "rvc_synth_flow_param_count": (c_int, [c_void_p]),
+    "rvc_synth_flow_param_info": (c_int, [c_void_p, c_int, c_char_p, c_int, P(c_int64), P(c_int)]),
+    "rvc_synth_flow_param_total": (c_int64, [c_void_p]),
+    "rvc_synth_flow_weight_grad": (c_int, [c_void_p, c_void_p, P(c_void_p), c_int, P(c_void_p)]),
+    "rvc_synth_flow_weight_grad_launch_count": (c_int, [c_void_p]),
+    "rvc_gated_conv1d_weight_grad": (c_int, [c_void_p, P(c_void_p), P(c_void_p), c_int, c_int, c_int, c_int, P(c_int64), c_int, c_int, c_void_p]),
+    "rvc_gated_conv1d_weight_grad_plan": (c_int, [c_int, c_int, c_int, c_int, P(c_int64), c_int, c_int, P(c_int)]),
+    "rvc_kl_loss": (c_int,[c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "rvc_kl_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rvc_l1_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "rvc_disc_create": (c_int, [c_void_p, c_int, P(c_void_p)]),

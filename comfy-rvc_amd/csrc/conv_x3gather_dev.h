@@ -5,6 +5,7 @@
 // conv_gen_wgrad_kernel the pair loop.  conv_x3d_bwd_kernel, conv_gen_bwd_kernel (image) and conv_x3d_wgrad_kernel (pair)
 // still write their loop out around gather_mfma3_unit: called through the loops below they compute the same bits, but the compiler emits the address arithmetic
 // in another order and they measured 0.6 - 1.8 % slower (profiles/x3g_dedup_isa.txt, x3g_dedup_timing.txt).  A change to a loop here is made there as well.
+// conv_flow_wgrad_kernel (pair) writes its loop out too: its B operand holds two fetched values per element (WN's gate is formed between the load and the split).
 //
 // The product of one 16-deep unit and accumulator is three v_mfma_f32_32x32x16_bf16 in the order hi lo, lo hi, hi hi; a 32 x 32 accumulator holds column
 // lane & 31 and rows acc_row32(r, lane >> 5).

@@ -70,6 +70,9 @@ struct FlowHostWeights { std::vector<float> pre, post, in[3], rs[3]; };
 struct FlowBwdImages { bool built = false; DevBuf<uint16_t> pre[4], post[4], in[4][3], rs[4][3]; size_t bytes = 0; };
 struct GenKept { bool on = false; std::vector<DevVec> up_v, up_g, c1_v, c1_g, c2_v, c2_g; size_t bytes = 0; };
 struct DecParam { std::string name; std::vector<long long> shape; };
+// The flow's weight-gradient pass (synth_flow_weight_grad), opt-in through synth_keep_parameters as well: weight_v / weight_g of every coupling's in_layers,
+// res_skip_layers and cond_layer on the device.  flow_params: the flow.* parameter tensors in the reference module's state-dict order (25 per coupling).
+struct FlowKept { DevVec in_v[4][3], in_g[4][3], rs_v[4][3], rs_g[4][3], cond_v[4], cond_g[4]; };
 struct SynthWeights {    // what synth_finalize builds, and what the graph has learnt about it
   DevVec emb_phone_wT, emb_phone_b, emb_pitch, emb_g;
   std::vector<EncoderLayer> enc;
@@ -83,6 +86,7 @@ struct SynthWeights {    // what synth_finalize builds, and what the graph has l
   GenHostWeights gen_host; GenBwdImages gen_bwd;
   FlowHostWeights flow_host[4]; FlowBwdImages flow_bwd;
   GenKept kept; std::vector<DecParam> dec_params; std::map<std::string, int> dec_index;
+  FlowKept flow_kept; std::vector<DecParam> flow_params; std::map<std::string, int> flow_index;
   ZeroedBlock imgs;      // split-resident image block whose margins are known to be zero (split_imgs_alloc; keys: T, and the columns of the z image = the generator's window)
 };
 struct Synth : SynthWeights {
@@ -336,6 +340,27 @@ void synth_finalize(Synth* S) {
                  !K.on ? nullptr : (c == 1 ? &K.c1_v[q] : &K.c2_v[q]), !K.on ? nullptr : (c == 1 ? &K.c1_g[q] : &K.c2_g[q]));
         }
     add("dec.conv_post.weight"); add("dec.cond.weight"); add("dec.cond.bias");
+  }
+  // the flow.* parameter tensors likewise: per coupling pre, enc.in_layers.*, enc.res_skip_layers.*, enc.cond_layer, post
+  {
+    GenKept& K = S->kept; FlowKept& FK = S->flow_kept;
+    auto add = [&](const std::string& name) {
+      const HostTensor& t = ts.get(name);
+      S->flow_index[name] = (int)S->flow_params.size();
+      S->flow_params.push_back({name, t.shape});
+    };
+    auto add_wn = [&](const std::string& p, DevVec& v, DevVec& g) {
+      add(p + ".bias"); add(p + ".weight_g"); add(p + ".weight_v");
+      if (K.on) { v.upload(ts.get(p + ".weight_v").data); g.upload(ts.get(p + ".weight_g").data); K.bytes += (v.n + g.n) * sizeof(float); }
+    };
+    for (int f = 0; f < 4; ++f) {
+      const std::string p = "flow.flows." + std::to_string(2 * f) + ".";
+      add(p + "pre.weight"); add(p + "pre.bias");
+      for (int i = 0; i < 3; ++i) add_wn(p + "enc.in_layers." + std::to_string(i), FK.in_v[f][i], FK.in_g[f][i]);
+      for (int i = 0; i < 3; ++i) add_wn(p + "enc.res_skip_layers." + std::to_string(i), FK.rs_v[f][i], FK.rs_g[f][i]);
+      add_wn(p + "enc.cond_layer", FK.cond_v[f], FK.cond_g[f]);
+      add(p + "post.weight"); add(p + "post.bias");
+    }
   }
   S->ts.clear();
   S->ready = true;
@@ -669,6 +694,7 @@ struct GenTape {
   // the flow's recording (synth_forward_tape with record_flow): its tensors live in a block of their own, laid out for the item's length when a recording
   // forward first meets that length - a tape that never records the flow holds none of it
   DevVec flow_mem; int flow_T = 0; bool flow_recorded = false; int flow_fwd_marks = 0, flow_bwd_marks = 0;
+  bool flow_backward_done = false;      // synth_flow_input_grad has run since the last recording forward: the flow's deltas belong to the recorded activations
   // timing (gen_tape_timing; off: no event is ever created or recorded): events around the taped decoder and at the backward's stage boundaries
   bool timing = false; std::vector<hipEvent_t> ev; int fwd_marks = 0, bwd_marks = 0, wgrad_marks = 0;
   GenTape() = default;
@@ -1014,6 +1040,13 @@ static void flow_tape_layout(GenTape& tape, const Synth* S, int T, hipStream_t s
   }
   add("d.flow.g", 1, S->gin);
   add("flow.scratch.dxh", 2 * H, T); add("flow.scratch.dacts", H, T); add("flow.scratch.cur", IC, T);
+  // what the flow's weight-gradient pass reads beside them (a handle with kept parameters only), behind everything a plain tape holds: pre's input and post's
+  // input, the x-chain cotangent at the input of layers 1 and 2 and post^T d m, which flow.scratch.dxh holds only until the next layer overwrites it
+  if (S->kept.on)
+    for (int f = 0; f < 4; ++f) {
+      add(flow_name(f, "xin"), IC / 2, T); add(flow_name(f, "out"), H, T);
+      add("d." + flow_name(f, "x1"), H, T); add("d." + flow_name(f, "x2"), H, T); add("d." + flow_name(f, "skip"), H, T);
+    }
   if (tape.flow_mem.n < off) { RVC_HIP_CHECK(hipStreamSynchronize(s)); tape.flow_mem.alloc(off); }      // (an earlier pass on this stream may still read the old block)
   tape.flow_T = T;
 }
@@ -1043,6 +1076,13 @@ static int flow_backward(const Synth* S, hipStream_t s, GenTape* tape, const flo
     float* dm = P("d." + flow_name(f, "m"));
     ++launches; if (tape) flow_unflip(s, src, cur, dm, IC, T, len);
     gemm(tape ? &B.post[f] : nullptr, dm, nullptr, half, 1, nullptr, dh, H);                                  // d h = post^T d m, the skip cotangent of every layer
+    // a handle with kept parameters keeps what the scratch pair holds only for a while, as copies: no operand of the pass changes
+    auto keep = [&](const std::string& name, const float* src) {
+      if (!S->kept.on) return;
+      ++launches;
+      if (tape) RVC_HIP_CHECK(hipMemcpyAsync(P("d." + flow_name(f, name)), src, (size_t)H * T * sizeof(float), hipMemcpyDeviceToDevice, s));
+    };
+    keep("skip", dh);
     float* dgc = P("d." + flow_name(f, "gc"));
     for (int i = 2; i >= 0; --i) {
       const std::string si = std::to_string(i);
@@ -1053,6 +1093,7 @@ static int flow_backward(const Synth* S, hipStream_t s, GenTape* tape, const flo
       ++launches; if (tape) flow_gate_bwd(s, dacts, a, P("d." + flow_name(f, "a" + si)), dgc + (size_t)2 * H * i, H, T, len);
       // dx += in_layers[i]^T (d a): the x-chain cotangent is zero above the last layer; layer 0's is pre's output cotangent d h0
       gemm(tape ? &B.in[f][i] : nullptr, dacts, a, 2 * H, 5, i < 2 ? dxh : nullptr, i > 0 ? dxh : P("d." + flow_name(f, "h0")), H);
+      if (i > 0) keep("x" + si, dxh);
     }
     gemm(tape ? &B.pre[f] : nullptr, P("d." + flow_name(f, "h0")), nullptr, H, 1, cur, cur, half);              // d x0 = d x0' + pre^T d h0
     src = cur;
@@ -1077,6 +1118,7 @@ void synth_flow_input_grad(Synth* S, hipStream_t s, GenTape* tape, const float* 
   RVC_REQUIRE(tape->recorded && tape->flow_recorded && S->flow_bwd.built, "the tape holds no recorded flow: run synth_forward_tape with record_flow first");
   RVC_REQUIRE(T == tape->flow_T, "d z_p does not have the recorded item's length");
   flow_backward(S, s, tape, dzp, dz, dg);
+  tape->flow_backward_done = true;
 }
 // [0]: the recorded flow forward (its four couplings and Flips), [1]: the last flow backward; waits for the events.  Returns the number of values
 int gen_tape_flow_times(GenTape* T, float* ms, int cap) {
@@ -1089,6 +1131,123 @@ int gen_tape_flow_times(GenTape* T, float* ms, int cap) {
   if (T->flow_fwd_marks == 2 && n < cap) put(kFlowMark0, kFlowMark0 + 1); else return 0;
   if (T->flow_bwd_marks == 2 && n < cap) put(kFlowMark0 + 2, kFlowMark0 + 3);
   return n;
+}
+
+// ------------------------------------------------------------------------------------------------ the flow's weight-gradient pass
+// d loss / d(parameter) for every flow.* tensor, summed over the B items, each at its own length, from the tapes' recorded flow and the deltas of
+// synth_flow_input_grad.  Per coupling f, every sum also over the items and n < the item's length:
+//   pre:               dW[o][c]    = sum_n d.h0[o][n] xin[c][n]                                   db = row sums of d.h0
+//   in_layers.i:       dW[o][c][t] = sum_n d.a{i}[o][n] x{i}[c][n + t - 2]                         db = d.gc[2 H i ..), the row sums the data pass formed
+//   res_skip_layers.i: dW[o][c]    = sum_n [d.x{i+1} | d.skip][o][n] gate(a{i})[c][n]              db = row sums of the pair (i = 2: d.skip alone, H rows)
+//   post:              dW[o][c]    = sum_n d.m[o][n] out[c][n]                                     db = row sums of d.m
+//   cond_layer:        dW[o][j]    = d.gc[o] g[j]                                                  db = d.gc
+// and the chain through weight norm in the finishing step.  Every convolution is one launch of conv_flow_wgrad_kernel (the pair by a second base pointer) plus one
+// finishing launch, cond_layer one finishing launch: 4 (2 + 6 + 6 + 1 + 2) = 68 whatever B and the lengths; tapes null: nothing is launched, the return value
+// is that count.  The partial images live in the block the decoder's pass uses.  No atomics: two calls give the same bits.
+struct FlowWgradLayer { ConvFlowWgradPlan x; FlowWgradFinishArgs f; bool gemm; };
+static int flow_wgrad(Synth* S, hipStream_t s, GenTape* const* tapes, int B, float* const* grads) {
+  const FlowKept& K = S->flow_kept;
+  const int H = S->hidden, half = S->inter / 2;
+  const bool run = tapes != nullptr;
+  int launches = 0;
+  auto items = [&](const std::string& name, size_t off = 0) { GenItems it{}; if (run) for (int b = 0; b < B; ++b) it.p[b] = tapes[b]->ptr(name) + off; return it; };
+  auto grad = [&](const std::string& name) -> float* {
+    if (!run) return nullptr;
+    auto it = S->flow_index.find(name);
+    RVC_REQUIRE(it != S->flow_index.end(), "no parameter tensor '" + name + "'");
+    return grads[it->second];
+  };
+  std::vector<FlowWgradLayer> plan;
+  auto finish_common = [&](FlowWgradFinishArgs& f, int R, int L, const std::string& prefix, const DevVec* v, const DevVec* g) {
+    f.R = R; f.L = L; f.B = B; f.R0 = R;
+    for (int b = 0; b < B; ++b) f.N[b] = tapes[b]->flow_T;
+    if (v) {
+      RVC_REQUIRE(v->n == (size_t)R * L && g->n == (size_t)R, "kept weight_v / weight_g do not have the layer's shape: " + prefix);
+      f.v = v->p; f.g = g->p; f.gw = grad(prefix + ".weight_v"); f.gg = grad(prefix + ".weight_g");
+    } else f.gw = grad(prefix + ".weight");
+    f.gb = grad(prefix + ".bias");
+  };
+  // one convolution: Pn (R0 rows) and P2n (the rows behind them; empty: none) the tape names of the delta, Gn of the input; gc_off >= 0: the bias gradient is the
+  // slice of d.flow{f}.gc there, otherwise the row sums of the delta
+  auto gemm = [&](int f, const std::string& Pn, const std::string& P2n, const std::string& Gn, int R, int R0, int C, int k, int gate, const std::string& prefix,
+                  const DevVec* v, const DevVec* g, long long gc_off) {
+    launches += 2;
+    if (!run) return;
+    FlowWgradLayer L{};
+    L.gemm = true;
+    ConvFlowWgradArgs a{};
+    const GenItems Pi = items(Pn), P2i = P2n.empty() ? Pi : items(P2n), Gi = items(Gn);
+    for (int b = 0; b < B; ++b) { a.P[b] = Pi.p[b]; a.P2[b] = P2i.p[b]; a.G[b] = Gi.p[b]; a.N[b] = tapes[b]->flow_T; }
+    a.B = B; a.R = R; a.R0 = R0; a.C = C; a.k = k; a.off0 = -((k - 1) / 2); a.gate = gate;
+    RVC_REQUIRE(conv_flow_wgrad_plan(a, L.x), "flow layer does not fit the weight-gradient kernel: " + prefix);
+    finish_common(L.f, R, C * k, prefix, v, g);
+    L.f.pstride = (long long)R * C * k; L.f.splits = L.x.splits; L.f.R0 = R0;
+    if (gc_off >= 0) { L.f.bias = 2; L.f.V = items("d." + flow_name(f, "gc"), (size_t)gc_off); }
+    else { L.f.bias = 1; L.f.D = Pi; L.f.D2 = P2i; }
+    plan.push_back(L);
+  };
+  for (int f = 0; f < 4; ++f) {
+    const std::string p = "flow.flows." + std::to_string(2 * f) + ".";
+    gemm(f, "d." + flow_name(f, "h0"), "", flow_name(f, "xin"), H, H, half, 1, 0, p + "pre", nullptr, nullptr, -1);
+    for (int i = 0; i < 3; ++i) {
+      const std::string si = std::to_string(i);
+      gemm(f, "d." + flow_name(f, "a" + si), "", flow_name(f, "x" + si), 2 * H, 2 * H, H, 5, 0, p + "enc.in_layers." + si, &K.in_v[f][i], &K.in_g[f][i], (long long)2 * H * i);
+    }
+    for (int i = 0; i < 3; ++i) {
+      const std::string si = std::to_string(i);
+      if (i < 2) gemm(f, "d." + flow_name(f, "x" + std::to_string(i + 1)), "d." + flow_name(f, "skip"), flow_name(f, "a" + si), 2 * H, H, H, 1, 1,
+                      p + "enc.res_skip_layers." + si, &K.rs_v[f][i], &K.rs_g[f][i], -1);
+      else gemm(f, "d." + flow_name(f, "skip"), "", flow_name(f, "a" + si), H, H, H, 1, 1, p + "enc.res_skip_layers." + si, &K.rs_v[f][i], &K.rs_g[f][i], -1);
+    }
+    ++launches;
+    if (run) {
+      FlowWgradLayer L{};
+      finish_common(L.f, 6 * H, S->gin, p + "enc.cond_layer", &K.cond_v[f], &K.cond_g[f]);
+      L.f.outer = 1; L.f.bias = 2; L.f.V = items("d." + flow_name(f, "gc")); L.f.Gv = items("g");
+      plan.push_back(L);
+    }
+    gemm(f, "d." + flow_name(f, "m"), "", flow_name(f, "out"), half, half, H, 1, 0, p + "post", nullptr, nullptr, -1);
+  }
+  if (run) {
+    size_t most = 0;
+    for (const FlowWgradLayer& L : plan) if (L.gemm) most = std::max(most, L.x.part_floats);
+    if (S->wgrad_part.n < most) { RVC_HIP_CHECK(hipStreamSynchronize(s)); S->wgrad_part.alloc(most); }      // (an earlier pass on this stream may still read the old block)
+    for (FlowWgradLayer& L : plan) {
+      if (L.gemm) { L.x.a.part = S->wgrad_part.p; L.f.part = S->wgrad_part.p; conv_flow_wgrad_launch(L.x, s); }
+      flow_wgrad_finish(s, L.f);
+    }
+  }
+  return launches;
+}
+int synth_flow_param_count(const Synth* S) { RVC_REQUIRE(S->ready, "synth_finalize has not been called"); return (int)S->flow_params.size(); }
+void synth_flow_param_info(const Synth* S, int k, std::string& name, std::vector<long long>& shape) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  RVC_REQUIRE(k >= 0 && k < (int)S->flow_params.size(), "parameter index out of range");
+  name = S->flow_params[k].name; shape = S->flow_params[k].shape;
+}
+long long synth_flow_param_total(const Synth* S) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  long long n = 0;
+  for (const DecParam& p : S->flow_params) { long long e = 1; for (long long d : p.shape) e *= d; n += e; }
+  return n;
+}
+int synth_flow_weight_grad_launch_count(const Synth* S) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  return flow_wgrad(const_cast<Synth*>(S), nullptr, nullptr, 1, nullptr);
+}
+void synth_flow_weight_grad(Synth* S, hipStream_t s, GenTape* const* tapes, int B, float* const* grads) {
+  RVC_REQUIRE(S->ready, "synth_finalize has not been called");
+  RVC_REQUIRE(S->kept.on, "flow_weight_grad needs the parameters on the device: call rvc_synth_keep_parameters(s, 1) before finalize (trainable=True)");
+  RVC_REQUIRE(B >= 1 && B <= kGenWgradMaxItems, "1 <= B <= " + std::to_string(kGenWgradMaxItems) + " tapes per weight-gradient pass");
+  RVC_REQUIRE(tapes && grads, "null argument");
+  for (int b = 0; b < B; ++b) {
+    RVC_REQUIRE(tapes[b], "null tape");
+    tape_check(S, tapes[b]);
+    RVC_REQUIRE(tapes[b]->recorded && tapes[b]->flow_recorded && tapes[b]->flow_T >= 1, "the tape holds no recorded flow: run synth_forward_tape with record_flow first");
+    RVC_REQUIRE(tapes[b]->flow_backward_done, "the tape holds no flow backward pass after its last recording forward: call synth_flow_input_grad first");
+  }
+  for (size_t k = 0; k < S->flow_params.size(); ++k) RVC_REQUIRE(grads[k], "null gradient pointer");
+  flow_wgrad(S, s, tapes, B, grads);
 }
 
 // ------------------------------------------------------------------------------------------------ the decoder's weight-gradient pass
@@ -1372,6 +1531,10 @@ static void synth_forward_graph(Synth* S, hipStream_t s, Arena& A, const float* 
         if (record_flow)
           for (int i = 0; i < 3; ++i) { rec.x[i] = tape->ptr(flow_name(f, "x" + std::to_string(i))); rec.a[i] = tape->ptr(flow_name(f, "a" + std::to_string(i))); }
         coupling_run(S, s, S->flow[f], gcond[f], gs, im, wb, cur, T, false, record_flow ? &rec : nullptr);
+        if (record_flow && S->kept.on) {      // copies only: x0 passes through the coupling unchanged, the skip sum stays in the WaveNet's buffer until the next one
+          RVC_HIP_CHECK(hipMemcpyAsync(tape->ptr(flow_name(f, "xin")), cur, (size_t)(IC / 2) * T * sizeof(float), hipMemcpyDeviceToDevice, s));
+          RVC_HIP_CHECK(hipMemcpyAsync(tape->ptr(flow_name(f, "out")), wb.hw + (size_t)C * T, (size_t)C * T * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
         flip_c(s, cur, oth, IC, T);
         std::swap(cur, oth);
       }
@@ -1449,7 +1612,7 @@ void synth_forward_tape(Synth* S, hipStream_t s, const float* feat, int feat_cha
                         bool record_flow) {
   RVC_REQUIRE(S->ready, "synth_finalize has not been called");
   RVC_REQUIRE(tape || !record_flow, "record_flow needs a tape");
-  if (tape) { tape_check(S, tape); tape->recorded = false; tape->backward_done = false; tape->flow_recorded = false; }
+  if (tape) { tape_check(S, tape); tape->recorded = false; tape->backward_done = false; tape->flow_recorded = false; tape->flow_backward_done = false; }
   RVC_REQUIRE(S->post_enc.built, "no posterior encoder loaded: the checkpoint had no enc_q.* tensors (an inference checkpoint)");
   RVC_REQUIRE(S->segment > 0, "segment_size is not set in the configuration");
   RVC_REQUIRE(T >= S->segment && T >= 11, "the sequence is shorter than the segment");

@@ -67,6 +67,15 @@ size_t synth_kept_bytes(const Synth* S);
 int synth_dec_weight_grad_launch_count(const Synth* S);   // pure: the size of the plan, independent of B and of the segment
 void synth_dec_weight_grad(Synth* S, hipStream_t s, GenTape* const* tapes, int B, float* const* grads);
 int gen_tape_wgrad_times(GenTape* T, float* ms, int cap);   // the last weight-gradient pass's intervals (its first tape, timing on): stage 0 .. n - 1, the rest
+// The flow's weight-gradient pass (model_synth.hip, conv_flow_wgrad.hip): d loss / d(parameter) of every flow.* tensor (100: 25 per coupling) summed over the B
+// items whose tapes are given, each at its own length (each recorded with record_flow on a handle with kept parameters - the tape then also holds flow{f}.xin,
+// flow{f}.out and, after synth_flow_input_grad, d.flow{f}.x1, d.flow{f}.x2, d.flow{f}.skip - and through synth_flow_input_grad since); grads one device pointer
+// per tensor in synth_flow_param_info's order (the reference module's state-dict order), each fully written.  B <= kGenWgradMaxItems.
+int synth_flow_param_count(const Synth* S);
+void synth_flow_param_info(const Synth* S, int k, std::string& name, std::vector<long long>& shape);
+long long synth_flow_param_total(const Synth* S);
+int synth_flow_weight_grad_launch_count(const Synth* S);   // pure: the size of the plan, independent of B and of the lengths
+void synth_flow_weight_grad(Synth* S, hipStream_t s, GenTape* const* tapes, int B, float* const* grads);
 // train_forward.hip: z = m + noise exp(logs) from stats [m | logs] (2 C rows); columns [ids, ids + seg) of x [C][T] -> y [C][seg]; the two loss reductions
 void posterior_sample(hipStream_t s, const float* stats, const float* noise, float* z, int C, int T);
 void segment_gather(hipStream_t s, const float* x, int C, int T, int ids, int seg, float* y);

@@ -451,6 +451,74 @@ int rvc_conv1d_weight_grad(void* stream, const float* const* p_dev, const float*
   check_launch();
   RVC_CATCH
 }
+// ---- the flow's parameter gradients
+int rvc_synth_flow_param_count(rvc_synth* s) {
+  try { return s ? synth_flow_param_count(s->m) : -1; }
+  catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_synth_flow_param_info(rvc_synth* s, int k, char* name, int name_cap, int64_t* shape, int* ndim) {
+  RVC_TRY
+  RVC_REQUIRE(s && name && name_cap > 0 && shape && ndim, "null argument");
+  std::string n; std::vector<long long> sh;
+  synth_flow_param_info(s->m, k, n, sh);
+  RVC_REQUIRE((int)n.size() < name_cap && sh.size() <= 8, "name buffer too small");
+  std::copy(n.begin(), n.end(), name); name[n.size()] = 0;
+  for (size_t i = 0; i < sh.size(); ++i) shape[i] = sh[i];
+  *ndim = (int)sh.size();
+  RVC_CATCH
+}
+int64_t rvc_synth_flow_param_total(rvc_synth* s) {
+  try { return s ? (int64_t)synth_flow_param_total(s->m) : -1; }
+  catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_synth_flow_weight_grad(rvc_synth* s, void* stream, rvc_gen_tape* const* tapes, int B, float* const* grads_dev) {
+  RVC_TRY
+  RVC_REQUIRE(s && tapes && grads_dev, "null argument");
+  RVC_REQUIRE(B >= 1 && B <= kGenWgradMaxItems, "1 <= B <= " + std::to_string(kGenWgradMaxItems) + " tapes per weight-gradient pass");
+  GenTape* t[kGenWgradMaxItems];
+  for (int b = 0; b < B; ++b) { RVC_REQUIRE(tapes[b], "null tape"); t[b] = tapes[b]->t; }
+  RVC_HIP_CHECK(hipSetDevice(s->ctx->c.device));
+  synth_flow_weight_grad(s->m, (hipStream_t)stream, t, B, grads_dev);
+  check_launch();
+  RVC_CATCH
+}
+int rvc_synth_flow_weight_grad_launch_count(rvc_synth* s) {
+  try { return s ? synth_flow_weight_grad_launch_count(s->m) : -1; }
+  catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+// the raw GEMM of that pass: one pointer per item, item b's operands laid out for its own length n_host[b]
+static ConvFlowWgradArgs gated_wgrad_args(int B, int R, int C, int k, const int64_t* n_host, int off0, int gate) {
+  RVC_REQUIRE(n_host, "null argument");
+  RVC_REQUIRE(B >= 1 && B <= kGenWgradMaxItems, "1 <= B <= " + std::to_string(kGenWgradMaxItems) + " items");
+  ConvFlowWgradArgs a{};
+  for (int b = 0; b < B; ++b) { RVC_REQUIRE(n_host[b] >= 1 && n_host[b] < (1LL << 31), "bad length"); a.N[b] = (int)n_host[b]; }
+  a.B = B; a.R = R; a.R0 = R; a.C = C; a.k = k; a.off0 = off0; a.gate = gate;
+  return a;
+}
+int rvc_gated_conv1d_weight_grad_plan(int B, int R, int C, int k, const int64_t* n_host, int off0, int gate, int* info) {
+  try {
+    ConvFlowWgradPlan p;
+    RVC_REQUIRE(conv_flow_wgrad_plan(gated_wgrad_args(B, R, C, k, n_host, off0, gate), p), "the shape does not fit the weight-gradient kernel");
+    plan_info(info, 8, p.bm, p.splits, p.grid, p.a.total, p.a.per);
+    return p.splits;
+  } catch (const std::exception& e) { set_error(e.what()); return -1; }
+}
+int rvc_gated_conv1d_weight_grad(void* stream, const float* const* p_dev, const float* const* g_dev, int B, int R, int C, int k, const int64_t* n_host, int off0,
+                                 int gate, float* out_dev) {
+  RVC_TRY
+  RVC_REQUIRE(p_dev && g_dev && out_dev, "null argument");
+  ConvFlowWgradPlan p;
+  RVC_REQUIRE(conv_flow_wgrad_plan(gated_wgrad_args(B, R, C, k, n_host, off0, gate), p), "the shape does not fit the weight-gradient kernel");
+  for (int b = 0; b < B; ++b) { RVC_REQUIRE(p_dev[b] && g_dev[b], "null operand pointer"); p.a.P[b] = p.a.P2[b] = p_dev[b]; p.a.G[b] = g_dev[b]; }
+  hipStream_t st = (hipStream_t)stream;
+  p.a.part = (float*)stream_scratch(st, 25, p.part_floats * sizeof(float));
+  conv_flow_wgrad_launch(p, st);
+  FlowWgradFinishArgs f{};
+  f.part = p.a.part; f.pstride = (long long)R * C * k; f.splits = p.splits; f.R = R; f.L = C * k; f.gw = out_dev; f.B = B; f.R0 = R;
+  flow_wgrad_finish(st, f);
+  check_launch();
+  RVC_CATCH
+}
 // ---- raw entries of the other four bf16x3 gather GEMMs (conv_x3d*.hip, conv_gen_bwd.hip), stated as the forward operation: the weights come from the host in
 // the module's layout and go through the regrouping the nets use.  info (8 ints, may be null): units, bm, splits, grid x / y / z, stages, stages per split
 static const float kNoDevice = 0.f;      // a non-null pointer for the planners' pure queries: nothing dereferences it

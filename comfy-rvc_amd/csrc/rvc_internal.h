@@ -329,6 +329,29 @@ void gen_wgrad_noise(hipStream_t s, const GenItems& D, const GenItems& H, int B,
 void gen_wgrad_post(hipStream_t s, const GenItems& D, const GenItems& X, int B, int C, long long T, int k, int pad, float slope, float* gw);
 void gen_wgrad_cond(hipStream_t s, const GenItems& DC, const GenItems& Gv, int B, int C, int G, float* gw, float* gb, float* gb2);
 void gen_wgrad_msource(hipStream_t s, const GenItems& DH, const GenItems& H, const GenItems& Sn, int B, long long N, float* gw, float* gb);
+// The weight gradient of the flow's convolutions over the B items of a batch, each at its own length (conv_flow_wgrad.hip):
+//   out[r][c k + t] = sum_item sum_{n < N[item]} P[item][r][n] act(G[item])[c][n + t + off0],  r < R, c < C, t < k
+// P [R0][N[item]] and, for rows [R0, R), P2 [R - R0][N[item]] (R0 == R: no second tensor); gate 0: G [C][N[item]], act = identity; gate 1: G [2 C][N[item]] and
+// act(G)[c] = tanh(G[c]) sigmoid(G[C + c]), formed in the kernel.  Zero outside [0, N[item]).  Both operands fp32 and split in the kernel.  The ragged reduction
+// is cut into stages of one item and 128 columns (first[b]: item b's first stage, filled by the planner with per / total) and into `splits` runs of them: split z
+// writes the partial image part[z][R][C k]; the caller provides part_floats (<= kGenWgradPartFloats) floats and adds them in index order (flow_wgrad_finish).
+struct ConvFlowWgradArgs {
+  const float* P[kGenWgradMaxItems]; const float* P2[kGenWgradMaxItems]; const float* G[kGenWgradMaxItems]; float* part;
+  int N[kGenWgradMaxItems]; int first[kGenWgradMaxItems + 1];
+  int B, R, R0, C, k, off0, gate; int per, total;
+};
+struct ConvFlowWgradPlan { ConvFlowWgradArgs a; dim3 grid; int bm = 128, splits = 1; size_t lds = 0, part_floats = 0; };   // bm: rows per workgroup (128, 64, 32)
+// pure; false: R % 16, k > 16, B outside 1 .. 16, an N[item] < 1, offsets outside 32 bits, a partial image beyond kGenWgradPartFloats
+bool conv_flow_wgrad_plan(const ConvFlowWgradArgs& a, ConvFlowWgradPlan& p);
+void conv_flow_wgrad_launch(const ConvFlowWgradPlan& p, hipStream_t s);
+// The finishing step for ragged items, one workgroup per row m: gw[m] (L floats) = the `splits` partials (pstride floats apart) added in index order - or, outer
+// = 1, sum_item V[item][m] Gv[item][q] in float64 (cond_layer) - through the weight-norm chain where v / g are given (gg receives grad_g).  bias 0: none; 1: gb[m]
+// = the float64 sum of row m of the pair [D (R0 rows) | D2] over every item's N[item] columns; 2: gb[m] = the float64 sum over the items of V[item][m].
+struct FlowWgradFinishArgs {
+  const float* part; long long pstride; int splits, R, L; const float* v; const float* g; float* gw; float* gg; float* gb;
+  int bias, outer, B, R0; GenItems D, D2, V, Gv; int N[kGenWgradMaxItems];
+};
+void flow_wgrad_finish(hipStream_t s, const FlowWgradFinishArgs& a);
 // one ConvBlockRes of 16 or 32 channels (3 x 3, 3 x 3, + x) in one launch (conv_cbr2.hip): x, out fp32 [C][H W], distinct
 bool cbr2_small_eligible(const ConvLayer& c1, const ConvLayer& c2);
 void cbr2_small_run(const ConvLayer& c1, const ConvLayer& c2, hipStream_t s, const float* x, int H, int W, float* out);

@@ -353,8 +353,78 @@ class _SynthesizerNSFsid:
             _lib.check(1)
         return n
 
+    # ------------------------------------------------------------------------------------------- the flow's weight-gradient pass
+    def flow_parameter_shapes(self):
+        """OrderedDict name -> shape of the 100 flow.* parameter tensors in the reference module's state-dict order (rvc_synth_flow_param_info)."""
+        assert self._loaded, "load_state_dict first"
+        out = OrderedDict()
+        name, shape, ndim = C.create_string_buffer(128), (_lib.c_int64 * 8)(), C.c_int()
+        n = _lib.lib.rvc_synth_flow_param_count(self._h)
+        if n < 0:
+            _lib.check(1)
+        for k in range(n):
+            _lib.check(_lib.lib.rvc_synth_flow_param_info(self._h, k, name, 128, shape, C.byref(ndim)))
+            out[name.value.decode()] = tuple(int(shape[i]) for i in range(ndim.value))
+        return out
+
+    def flow_weight_grad(self, tape):
+        """The gradient with respect to every flow.* parameter, summed over the tape's items, each at its own length (rvc_synth_flow_weight_grad): an OrderedDict
+        from state-dict name to a float32 device tensor in the parameter's shape, views of ONE contiguous buffer in flow_parameter_shapes() order (`.flat`).  The
+        tape must have been recorded with record_flow=True and been through flow_input_grad since.  Needs trainable=True."""
+        assert self._loaded, "load_state_dict first"
+        if not self.trainable:
+            raise ValueError("flow_weight_grad: the net was built without trainable=True (weight_v / weight_g are not kept on the device)")
+        if not isinstance(tape, GeneratorTape) or tape.net is not self:
+            raise ValueError("flow_weight_grad: the tape belongs to another net")
+        if not getattr(tape, "flow_recorded", False):
+            raise ValueError("flow_weight_grad: the tape was recorded without record_flow=True")
+        return self._flow_weight_grad(tape._h)
+
+    def _flow_weight_grad(self, handles):
+        dev = self.device
+        params = self.flow_parameter_shapes()
+        sizes = [int(np.prod(s)) for s in params.values()]
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        out, o = _GradDict(), 0
+        for (name, shape), n in zip(params.items(), sizes):
+            out[name] = flat[o:o + n].view(shape)
+            o += n
+        out.flat = flat
+        pt = (C.c_void_p * max(1, len(handles)))(*[h.value if isinstance(h, C.c_void_p) else h for h in handles])
+        pg = (C.c_void_p * len(out))(*[t.data_ptr() for t in out.values()])
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.rvc_synth_flow_weight_grad(self._h, _lib.current_stream(), pt, len(handles), pg))
+        return out
+
+    def flow_weight_grad_launch_count(self):
+        """Kernel launches of one flow_weight_grad (rvc_synth_flow_weight_grad_launch_count): a constant of the net, whatever the batch and the lengths."""
+        n = int(_lib.lib.rvc_synth_flow_weight_grad_launch_count(self._h))
+        if n < 0:
+            _lib.check(1)
+        return n
+
     def __call__(self, *args, **kwargs):
         return self.forward(*args, **kwargs)
+
+
+def flow_parameter_spec(config):
+    """OrderedDict name -> shape of the flow's parameter tensors (ResidualCouplingBlock, reference lib/infer_pack/models.py:150-196; WN modules.py:130-182) for a
+    constructor argument list, in the reference module's state-dict order: what flow_parameter_shapes() reports for a loaded net, computed on the host."""
+    inter, hidden, gin = config[2], config[3], config[16]
+    s, half = OrderedDict(), inter // 2
+
+    def wn(p, shape):
+        s[p + ".bias"], s[p + ".weight_g"], s[p + ".weight_v"] = (shape[0],), (shape[0], 1, 1), shape
+    for f in range(4):
+        p = f"flow.flows.{2 * f}."
+        s[p + "pre.weight"], s[p + "pre.bias"] = (hidden, half, 1), (hidden,)
+        for i in range(3):
+            wn(p + f"enc.in_layers.{i}", (2 * hidden, hidden, 5))
+        for i in range(3):
+            wn(p + f"enc.res_skip_layers.{i}", (2 * hidden if i < 2 else hidden, hidden, 1))
+        wn(p + "enc.cond_layer", (6 * hidden, gin, 1))
+        s[p + "post.weight"], s[p + "post.bias"] = (half, hidden, 1), (half,)
+    return s
 
 
 def dec_parameter_spec(config, f0=True):
@@ -470,6 +540,11 @@ class GeneratorTape:
     def flow_delta_names(self):
         """what flow_input_grad leaves per item: post's output cotangent, each layer's d a, pre's output cotangent, cond_layer's, and the item's dg"""
         return [f"d.flow{f}.{n}" for f in range(4) for n in ["m"] + [f"a{i}" for i in range(3)] + ["h0", "gc"]] + ["d.flow.g"]
+
+    def flow_wgrad_names(self):
+        """what a trainable net's tape additionally holds per item for flow_weight_grad: pre's and post's inputs from the recording forward, and from
+        flow_input_grad the x-chain cotangent at the input of layers 1 and 2 and post^T d m (the skip half of every res_skip layer's output cotangent)"""
+        return [f"flow{f}.{n}" for f in range(4) for n in ("xin", "out")] + [f"d.flow{f}.{n}" for f in range(4) for n in ("x1", "x2", "skip")]
 
     def flow_times(self, b):
         """Milliseconds of item b's recorded flow forward and last flow backward (set_timing on; waits for them): {"flow_forward": .., "flow_backward": ..}."""

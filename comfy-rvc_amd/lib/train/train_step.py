@@ -5,8 +5,9 @@ penalty's parameter gradient is not built: c_gp > 0 raises (losses.discriminator
 Of the generator half (:565-601) the loss and its cotangents at the generator's outputs: generator_loss_cotangents; and the first step of the generator's own
 backward, the decoder's data pass from d_y_hat to the sliced latent's, the speaker conditioning's and the harmonic source's cotangents:
 generator_decoder_backward over a net_g.forward_with_tape(...) pass; and its second step, the gradient of every dec.* parameter (weight norm included) from the
-deltas that pass leaves: generator_decoder_grads.  The backward of enc_q, the flow, enc_p and emb_g, grad_norm_g, the generator's optimizer step and the
-gradients of the HPSS / TSI / TEFS terms are not built."""
+deltas that pass leaves: generator_decoder_grads; its third step, the flow's data pass from the KL loss's cotangent at z_p: generator_flow_backward; and its
+fourth, the gradient of every flow.* parameter from the deltas that pass leaves: generator_flow_grads.  The backward of enc_q, enc_p and emb_g, grad_norm_g, the
+generator's optimizer step and the gradients of the HPSS / TSI / TEFS terms are not built."""
 import torch
 
 from ..infer_pack.commons import clip_grad_value_
@@ -85,6 +86,14 @@ def generator_flow_backward(net_g, tape, kl_cotangents):
     `net_g.forward_with_tape(..., record_flow=True)`: the flow's vector-Jacobian product (net_g.flow_input_grad), the third step of the generator's backward.
     Its per-layer deltas stay in the tape for the flow's weight gradients."""
     return net_g.flow_input_grad(tape, kl_cotangents["z_p"])
+
+
+def generator_flow_grads(net_g, tape, kl_cotangents):
+    """generator_flow_backward's two results and grads: the gradient of every flow.* parameter, weight norm included, summed over the batch - the fourth step of the
+    generator's backward (net_g.flow_weight_grad on the deltas the data pass has just left in the tape).  grads is an OrderedDict from state-dict name to a float32
+    device tensor, views of one flat buffer (`grads.flat`) in net_g.flow_parameter_shapes() order; net_g must have been built with trainable=True."""
+    dz_flow, dg_flow = net_g.flow_input_grad(tape, kl_cotangents["z_p"])
+    return dz_flow, dg_flow, net_g.flow_weight_grad(tape)
 
 
 def generator_latent_grad(net_g, tape, d_y_hat, kl_cotangents):

@@ -15,6 +15,7 @@
  *   rvc_mel_spectrogram_vjp <- torch.autograd.grad(loss_mel, [y_hat]) through mel_spectrogram_torch   lib/train/mel_processing.py:117-150, lib/train/losses.py:76-92
  *   rvc_mel_loss_cotangents <- the backward of F.l1_loss(y_mel, y_hat_mel) / MultiScaleMelSpectrogramLoss's loss_fn   training_cli.py:569-570, lib/train/losses.py:530-561
  *   rvc_synth_flow_input_grad <- loss_kl's way through ResidualCouplingBlock in loss_gen_all.backward()   training_cli.py:598, lib/infer_pack/models.py:150-196
+ *   rvc_synth_flow_weight_grad <- the same backward onto net_g.flow.parameters() (optim_g's gradients)      training_cli.py:598, lib/infer_pack/modules.py:130-209,:436-455
  *   rvc_disc_forward     <- MultiPeriodDiscriminator[V2].forward         lib/infer_pack/models.py:1024-1145 (net_d: training_cli.py:549,:567)
  *   rvc_sqerr_sums       <- discriminator_loss / generator_loss          lib/train/losses.py:571-593
  *   rvc_l1_sums          <- feature_loss                                 lib/train/losses.py:564-569
@@ -312,7 +313,7 @@ int rvc_gen_tape_wgrad_times(rvc_gen_tape* t, float* ms_host, int cap);
  * formed from the taped a where the gradient operand is gathered and split; the epilogue adds the running cotangent and applies the mask).  An item runs at its
  * own length, so every frame of the tape is inside its mask; the kernels take the length and write zero behind it.  No floating-point atomics: two calls give
  * the same bits.  _launch_count: the size of the plan, a constant of the net whatever T (touches no stream), -1 on error.  Errors: a tape of another handle, a
- * tape whose last forward did not record the flow, T other than the recorded length.  Not here: the flow's parameter gradients, enc_q / enc_p / emb_g.
+ * tape whose last forward did not record the flow, T other than the recorded length.  The flow's parameter gradients are rvc_synth_flow_weight_grad's (below).  Not here: enc_q / enc_p / emb_g.
  * rvc_gen_tape_flow_times (timing on): [0] the recorded flow forward, [1] the last flow backward, in milliseconds; returns the number of values, -1 on error. */
 int rvc_synth_forward_tape_flow(rvc_synth* s, void* stream, const float* phone_dev, int phone_channel_major, const int64_t* pitch_dev, const float* pitchf_dev,
                                 const float* spec_dev, int sid, const float* noise_q_dev, const float* noise_src_dev, int64_t T, int64_t ids, float* out_dev,
@@ -320,6 +321,34 @@ int rvc_synth_forward_tape_flow(rvc_synth* s, void* stream, const float* phone_d
 int rvc_synth_flow_input_grad(rvc_synth* s, void* stream, rvc_gen_tape* tape, const float* dz_p_dev, int64_t T, float* dz_dev, float* dg_dev);
 int rvc_synth_flow_input_grad_launch_count(rvc_synth* s);
 int rvc_gen_tape_flow_times(rvc_gen_tape* t, float* ms_host, int cap);
+/* ---- the generator's backward, fourth step: the flow's weight and bias gradients.  On a handle with kept parameters (rvc_synth_keep_parameters, which then also
+ * keeps weight_v / weight_g of flow.flows.{0,2,4,6}.enc.{in_layers.*, res_skip_layers.*, cond_layer} on the device) a forward with record_flow 1 records four more
+ * tensors per coupling: flow{f}.xin [inter / 2][T] (pre's input), flow{f}.out [hidden][T] (the WaveNet's summed skip output, post's input) and, written by
+ * rvc_synth_flow_input_grad, d.flow{f}.x1 / d.flow{f}.x2 [hidden][T] (the x-chain cotangent at the input of layers 1 and 2) and d.flow{f}.skip [hidden][T]
+ * (post^T d m).  They are copies: z_p, dz, dg and every tensor a plain handle's tape holds keep their bits, and a plain handle allocates and launches exactly
+ * what it did (rvc_synth_flow_input_grad_launch_count counts the copies on a handle with kept parameters only).
+ * rvc_synth_flow_param_count / _param_info / _param_total list the 100 flow.* parameter tensors in the reference module's state-dict order: per coupling pre,
+ * enc.in_layers.*, enc.res_skip_layers.*, enc.cond_layer (each bias, weight_g, weight_v), post.
+ * rvc_synth_flow_weight_grad: d loss / d(parameter) of every such tensor, summed over the B <= 16 items whose tapes are given, EACH AT ITS OWN LENGTH -> grads_dev,
+ * a HOST array of one device pointer per tensor in that order, each fully written; the chain through weight norm (dim 0) included.  Every convolution is one
+ * launch of a bf16x3 MFMA GEMM over all items (conv_flow_wgrad.hip: the reduction runs over ragged items, a stage being one item and 128 frames; a res_skip
+ * layer's input tanh(a[:H]) sigmoid(a[H:]) is formed in the kernel from the taped pre-gate rows) plus one finishing launch, cond_layer one float64 launch; the
+ * partial images live in the block the decoder's pass uses.  No floating-point atomics: two calls give the same bits.  _launch_count: a constant of the net (68),
+ * -1 on error.  Errors: no kept parameters, B < 1 or B > 16, a tape of another handle, a tape whose last forward did not record the flow or that has not been
+ * through rvc_synth_flow_input_grad since.  Not here: enc_q / enc_p / emb_g, grad_norm_g, the optimizer. */
+int rvc_synth_flow_param_count(rvc_synth* s);
+int rvc_synth_flow_param_info(rvc_synth* s, int k, char* name, int name_cap, int64_t* shape, int* ndim);
+int64_t rvc_synth_flow_param_total(rvc_synth* s);
+int rvc_synth_flow_weight_grad(rvc_synth* s, void* stream, rvc_gen_tape* const* tapes, int B, float* const* grads_dev);
+int rvc_synth_flow_weight_grad_launch_count(rvc_synth* s);
+/* The GEMM of that pass at any small shape, gradient launch plus finish, no weight norm:
+ *   out_dev[r][c k + t] = sum_item sum_{n < n_host[item]} P[item][r][n] act(G[item])[c][n + t + off0]
+ * p_dev / g_dev: HOST arrays of B <= 16 device pointers, item b dense at its own length: P [R][n_host[b]], G [C][n_host[b]] (gate 0, act = identity) or
+ * [2 C][n_host[b]] (gate 1, act(G)[c] = tanh(G[c]) sigmoid(G[C + c])); elements outside [0, n_host[b]) read as zero.  R % 16 == 0, k <= 16.
+ * _plan: the planner's decisions without a device (info: 8 ints as the other _plan queries, may be NULL); returns the splits, -1 when the shape does not fit. */
+int rvc_gated_conv1d_weight_grad(void* stream, const float* const* p_dev, const float* const* g_dev, int B, int R, int C, int k, const int64_t* n_host, int off0,
+                                 int gate, float* out_dev);
+int rvc_gated_conv1d_weight_grad_plan(int B, int R, int C, int k, const int64_t* n_host, int off0, int gate, int* info);
 /* The GEMM of that pass at any small shape, gradient launch plus finish, no weight norm:
  *   out_dev[r][c k + t] = sum_item sum_n a_p(P[item][r][n]) a_g(G[item][c][cstride n + tstep t + off0]),  a_x(v) = max(v, slope_x v) (slope 1: none; 0 <= slope <= 1)
  * p_dev / g_dev: HOST arrays of B <= 16 device pointers, P [R][N] and G [C][Tg] dense; elements of G outside [0, Tg) read as zero.  R % 16 == 0, k <= 16.
